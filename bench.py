@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- senone-frames/s of the PTM scoring hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step is one pass of the hot path (ssw_score_batch: density/top-N kernel + senone kernel)
 over one batch of synthetic features already resident in HBM: BASELINE.json configs[1],
@@ -12,8 +12,14 @@ touched the GPU) every rank scores its own shard of utterances -- the path parti
 utterance, there is no data-path collective -- and the reported value is the whole-job rate over
 the max-over-ranks time (weak scaling).
 
-Prints ONE JSON line on rank 0, including
-  `roofline`     dominant kernels, HIP-event timed on the launch stream over the timed region;
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0: `value`,
+`ms_per_step` (wall milliseconds of one timed step) and `roofline`, which is derived from the
+timed region itself (two HIP events on the launch stream around it).  --dump-outputs DIR also
+writes what the last timed step computed (rank 0's senone scores) to DIR as float32 .npy files;
+the inputs are seeded, so two builds can be compared output for output.
+
+--full adds what takes runs of its own, each in the same line:
+  `kernels`      the per-kernel split, from a separate pass with HIP events between the launches;
   `cpu_baseline` the CPU oracle timed on a bounded sample of the same workload on the host
                  cores of this box, one core and all cores (N = 1 only);
   `config5`      BASELINE.json configs[4] at every N: 2048 utterances x 1000 frames x 150 phones
@@ -47,6 +53,7 @@ VALU_PEAK_TOPS = 78.6          # vector fp32 peak with an FMA counted once (SURV
 # mul, sub): 864,864 for en-us PTM
 N_SIMD = 1024                   # 256 CUs x 4 SIMDs
 CLOCK_HZ = 2.4e9
+DUMP_BYTES = 60_000_000        # --dump-outputs writes at most this much (under 64 MB)
 PMC_FILE = "r06_pmc.json"      # rocprofv3 --pmc passes of this step (tools/pmc_pass.py); only
                                # quoted when its kernel_src_sha equals this tree's
 
@@ -248,6 +255,21 @@ def spin_up(torch, step, seconds=0.5):
         torch.cuda.synchronize()
 
 
+def dump_outputs(out_dir, scores):
+    """--dump-outputs: the senone scores [frames][senones] the last timed step left in HBM (what a
+    caller of ssw_score_batch receives) as DIR/senone_scores.npy, float32 (int16 converts
+    exactly), and the frame index of each row as DIR/senone_scores_frames.npy.  A whole step of
+    en-us is 80 MB as float32: beyond DUMP_BYTES the rows are a fixed, seeded sample of frames."""
+    n, n_sen = scores.shape
+    rows = np.arange(n)
+    cap = DUMP_BYTES // (4 * n_sen + 8)
+    if n > cap:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=cap, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "senone_scores.npy"), scores[rows].astype(np.float32))
+    np.save(os.path.join(out_dir, "senone_scores_frames.npy"), rows.astype(np.float64))
+
+
 def timed_steps(torch, dist, backend, step, warmup, steps):
     """(host seconds over the K steps, max over ranks; this rank's device milliseconds over the
     same K steps from two HIP events on the launch stream, recorded before the first launch and
@@ -365,6 +387,12 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--model", default="en-us")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel split, the CPU baseline, config5 and (N = 1) the "
+                         "larger batches, real features and configs 3 and 4; the --no-* options "
+                         "below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's senone scores (rank 0) to DIR as .npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-align", action="store_true",
                     help="skip the config-3 / text / config-5 alignment jobs")
@@ -386,7 +414,7 @@ def main():
     import soundswallower_amd as ssw
     mdir = ssw.model_dir(args.model)
     cpu = None
-    if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only; before any GPU call
+    if args.full and not args.no_cpu_baseline and world == 1:   # N = 1 only; before any GPU call
         cpu = cpu_baseline(mdir)
 
     import torch
@@ -429,12 +457,14 @@ def main():
     if not os.environ.get("SSW_BENCH_NO_SPIN"):   # (tools/pmc_pass.py: keep the trace short)
         spin_up(torch, step, float(os.environ.get("SSW_BENCH_SPIN", "0.5")))
     elapsed, region_ms = timed_steps(torch, dist, backend, step, args.warmup, args.steps)
-    k_ms = step.kernel_ms(max(1, min(args.steps, 50)))
     flagged, pairs = model.last_stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step.d_out.cpu().numpy())
+    k_ms = step.kernel_ms(max(1, min(args.steps, 50))) if args.full else None
 
     # BASELINE configs[4] on every rank count (the multi-GPU part of the metric): collective
     c5 = None
-    if not args.no_align and args.model == "en-us":
+    if args.full and not args.no_align and args.model == "en-us":
         # the gather goes through the library's C entry point (ssw_gather_alignments over its own
         # RCCL communicator) when the ranks are on GPUs of their own; SSW_GATHER=torch, a failed
         # communicator set-up, or the gloo shared-GPU test mode use torch.distributed instead
@@ -506,15 +536,6 @@ def main():
         else:
             traffic_source = (f"profiles/{PMC_FILE} was taken on kernel_src_sha "
                               f"{pmc.get('kernel_src_sha')}, this build is {sha}: not quoted")
-    per_kernel = {
-        nm: {"ms": float(k_ms[i]), "algorithmic_bytes_per_frame": ab[nm],
-             "achieved_GBps": ab[nm] * n_frames / (k_ms[i] * 1e-3) / 1e9,
-             "hbm_frac": ab[nm] * n_frames / (k_ms[i] * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        for i, nm in enumerate(names)}
-    per_kernel["senone_kernel"]["note"] = (
-        "hbm_frac > 1 is an accounting artefact, not skipped work: 61.5 of this kernel's "
-        "algorithmic KB/frame are gathers from the 2 MB mixture-weight table, which the L2s "
-        "serve; its real HBM traffic is roofline.traffic")
     out = {
         "metric": "senone-frames/sec (en-us PTM)",
         "value": fps,
@@ -566,9 +587,6 @@ def main():
         "valu_roofline": {"bound": "valu", "achieved": fps / world * REF_OPS_PER_FRAME / 1e12,
                           "peak": VALU_PEAK_TOPS, "unit": "Top/s (non-fused fp32, reference work)",
                           "frac": fps / world * REF_OPS_PER_FRAME / 1e12 / VALU_PEAK_TOPS},
-        "kernels": dict(per_kernel, note="per-kernel split from a separate pass with a HIP event "
-                        "between the two launches (each event adds ~2 us to what it brackets); "
-                        "their sum exceeds roofline.kernel_ms by that overhead"),
         # share of the SIMDs' vector issue slots the step uses at 4 cycles per wave64 instruction
         # (SQ_INSTS_VALU from the PMC file), at the nominal 2.4 GHz (the chip holds less under
         # this load, so the true share is higher)
@@ -581,9 +599,22 @@ def main():
                  "mfma_selftest_worst_u": model.mfma_selftest_worst_u,
                  "mfma_selftest_ms": model.mfma_selftest_ms},
     }
+    if k_ms is not None:
+        per_kernel = {
+            nm: {"ms": float(k_ms[i]), "algorithmic_bytes_per_frame": ab[nm],
+                 "achieved_GBps": ab[nm] * n_frames / (k_ms[i] * 1e-3) / 1e9,
+                 "hbm_frac": ab[nm] * n_frames / (k_ms[i] * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            for i, nm in enumerate(names)}
+        per_kernel["senone_kernel"]["note"] = (
+            "hbm_frac > 1 is an accounting artefact, not skipped work: 61.5 of this kernel's "
+            "algorithmic KB/frame are gathers from the 2 MB mixture-weight table, which the L2s "
+            "serve; its real HBM traffic is roofline.traffic")
+        out["kernels"] = dict(per_kernel, note="per-kernel split from a separate pass with a HIP "
+                              "event between the two launches (each event adds ~2 us to what it "
+                              "brackets); their sum exceeds roofline.kernel_ms by that overhead")
     if c5 is not None:
         out["config5"] = c5
-    if world == 1 and args.model == "en-us" and not args.no_extra:
+    if args.full and world == 1 and args.model == "en-us" and not args.no_extra:
         # north_star says "batch >= 4096 frames": the same step at 16,384 frames per launch (the
         # size at which a frame costs least: DESIGN.md section 5) and at 65,536 (scored in four
         # pieces of 16,384).  roofline_frac: from the wall time of the steps, like the headline's
@@ -608,7 +639,7 @@ def main():
         rf = real_features(ssw, model, torch)
         if rf is not None:
             out["real_features"] = rf
-    if not args.no_align and world == 1 and args.model == "en-us":
+    if args.full and not args.no_align and world == 1 and args.model == "en-us":
         out["align"] = align_config3(ssw, model, means, torch)
         # the same job from TEXT: first pass (which fillers / alternates, word frames) + the
         # rest of decoder_alignment, tools/bench_first_pass.py
@@ -632,7 +663,7 @@ def main():
                                                                            reps=2)
         except Exception as e:      # noqa: BLE001
             out["text_align_default_config"] = {"error": str(e)}
-    if world == 1 and not args.no_extra:
+    if args.full and world == 1 and not args.no_extra:
         # BASELINE configs[3]: the ms scorer (ms_gauden + ms_senone kernels), fr-fr, 8192 frames
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
         import bench_ms

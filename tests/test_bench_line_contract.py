@@ -1,5 +1,5 @@
-"""CPU: the committed bench line of the round (profiles/rNN_bench_line.json, plain `python
-bench.py` on the GPU box) against the contract the driver parses: the fields, the two objects the
+"""CPU: the committed bench line of the round (profiles/rNN_bench_line.json, `python bench.py
+--full` on an MI355X) against the contract the driver parses: the fields, the two objects the
 scope table asks for (`roofline`, `cpu_baseline`), and the arithmetic that ties them together --
 `value` x `ms_per_step` is the step's 4096 frames, `roofline.frac` x peak x `ms_per_step` is the
 step's algorithmic bytes (within 1 %)."""

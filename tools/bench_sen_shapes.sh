@@ -14,7 +14,7 @@ for r, f in (("", ""), ("2", "1"), ("2", "2"), ("3", "1"), ("3", "2"), ("4", "1"
     if r:
         env["SSW_SEN_R"], env["SSW_SEN_FPB"] = r, f
     p = subprocess.run([sys.executable, "bench.py", "--steps", "200", "--warmup", "20",
-                        "--no-cpu-baseline", "--no-align", "--no-extra"],
+                        "--full", "--no-cpu-baseline", "--no-align", "--no-extra"],
                        env=env, capture_output=True, text=True)
     key = f"R={r} FPB={f}" if r else "default (R=3 FPB=2 on en-us)"
     try:

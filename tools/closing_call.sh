@@ -10,9 +10,9 @@ python3 -c "import __graft_entry__ as g; g.build(); g.smoke()" > $O/smoke.log 2>
 tail -1 $O/smoke.log
 bash tools/collect_profiles.sh $tag
 cp gpurun_out/${tag}_pmc.json profiles/${tag}_pmc.json      # (the box's copy of the tree: scratch)
-python3 bench.py > $O/bench_line_with_pmc.json 2> $O/bench_with_pmc.err
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line_driver_style.json 2>> $O/bench_with_pmc.err
-SSW_BENCH_BACKEND=gloo SSW_BENCH_DEVICE=0 python3 bench.py --gpus 2 > $O/bench_line_2ranks_self_launched.json 2>> $O/bench_with_pmc.err
+python3 bench.py --full > $O/bench_line_with_pmc.json 2> $O/bench_with_pmc.err
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_line_driver_style.json 2>> $O/bench_with_pmc.err
+SSW_BENCH_BACKEND=gloo SSW_BENCH_DEVICE=0 python3 bench.py --gpus 2 --full > $O/bench_line_2ranks_self_launched.json 2>> $O/bench_with_pmc.err
 python3 -c "
 import json
 for n in ('bench_line_with_pmc','bench_line_driver_style','bench_line_2ranks_self_launched'):

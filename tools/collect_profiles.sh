@@ -14,7 +14,7 @@ if [ "$2" != "notests" ]; then
   timeout 600 python -m pytest tests -x -q -m gpu > $O/pytest.log 2>&1
   grep -E "passed|failed" $O/pytest.log | tail -2
 fi
-timeout 600 python bench.py > $O/bench_line.json 2> $O/bench.err
+timeout 600 python bench.py --full > $O/bench_line.json 2> $O/bench.err
 cd /tmp
 prof() {  # name, then the program
   local name=$1; shift
@@ -23,7 +23,7 @@ prof() {  # name, then the program
   find $O/prof_$name -name "*kernel_trace.csv" -delete
 }
 prof headline python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-align --no-extra
-prof full python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline
+prof full python3 $R/bench.py --steps 200 --warmup 20 --full --no-cpu-baseline
 prof config4 python3 $R/tools/bench_ms.py
 prof config3_align python3 $R/tools/bench_align.py
 prof config5_align python3 $R/tools/bench_align.py --utts 2048 --reps 2

@@ -1,6 +1,6 @@
 #!/bin/bash
 # short bench line for kernel tuning: value, ms_per_step, per-kernel ms, 65536-frame line
-python bench.py --no-cpu-baseline --no-align "$@" 2>/dev/null | python -c "
+python bench.py --full --no-cpu-baseline --no-align "$@" 2>/dev/null | python -c "
 import sys, json
 b = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = b.get('kernels', {})
