@@ -662,6 +662,67 @@ int ssw_feat_batch(ssw_model_t *m, const float *d_cep, int32_t n_frames,
                    void *stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* MFCC front end on the device: 16-bit PCM -> cepstra for  */
+/* whole utterances, as fe_start + fe_process_int16 over all samples + fe_end compute them */
+/* (src/fe_interface.c:86-330, :560-690; src/fe_sigproc.c:70-738; src/fe_noise.c:111-327). */
+/* Bit-exact float32.  Streaming calls (fe_process_int16 in pieces) are out of scope.      */
+/* ------------------------------------------------------------------------------------ */
+/* the front-end settings of config_defs.h FE_OPTIONS (include/soundswallower/config_defs.h:
+ * 299-412) that ssw_fe_batch reads; defaults are the reference's */
+enum ssw_fe_transform { SSW_FE_LEGACY = 0, SSW_FE_DCT = 1, SSW_FE_HTK = 2 };
+typedef struct ssw_fe_config_s {
+    double samprate;      /* "samprate"      16000 */
+    double wlen;          /* "wlen"          0.025625 */
+    double alpha;         /* "alpha"         0.97 */
+    double lowerf;        /* "lowerf"        133.33334 */
+    double upperf;        /* "upperf"        6855.4976 */
+    int32_t frate;        /* "frate"         100 */
+    int32_t nfft;         /* "nfft"          0 = from the window (512 at 16 kHz) */
+    int32_t ncep;         /* "ncep"          13 */
+    int32_t nfilt;        /* "nfilt"         40 */
+    int32_t lifter;       /* "lifter"        0 */
+    int32_t transform;    /* "transform"     legacy (enum ssw_fe_transform) */
+    int32_t remove_noise; /* "remove_noise"  no */
+    int32_t unit_area;    /* "unit_area"     yes */
+    int32_t round_filters;/* "round_filters" yes */
+    int32_t dither;       /* "dither"        no */
+    int32_t remove_dc;    /* "remove_dc"     no */
+    int32_t doublebw;     /* "doublebw"      no */
+    int32_t smoothspec;   /* "smoothspec"    no */
+    int32_t logspec;      /* "logspec"       no */
+    int32_t warp;         /* 1 when "warp_params" is given (frequency warping) */
+    int32_t from_file;    /* ssw_model_fe_config: 1 when feat_params.json was read */
+} ssw_fe_config_t;
+void ssw_fe_config_defaults(ssw_fe_config_t *cfg);
+/* What ssw_model_load read from feat_params.json beside the `means` file (the model
+ * directory; acmod reads the same file, src/config.c:441-510 parses it), over the defaults;
+ * keys the front end does not use (feat, cmn, svspec, ...) are ignored.  0, or -1 on NULL. */
+int ssw_model_fe_config(const ssw_model_t *m, ssw_fe_config_t *out);
+/* Frames the front end makes of n_samples samples at 16 kHz (fe_process_int16 + fe_end,
+ * src/fe_interface.c:560-690): 0 for 0 samples, 1 below one window (410 samples), else
+ * 2 + (n - 410) / 160 -- the last is fe_end's zero-padded overflow frame.  -1 on error. */
+int64_t ssw_fe_frame_count(const ssw_model_t *m, int64_t n_samples);
+/* The front end for a batch of utterances: d_pcm int16 in HBM, utterance u = samples
+ * samp_off[u] .. samp_off[u + 1] (host int64 [n_utts + 1], samp_off[0] = 0) -> d_cep float32
+ * [total frames][ncep] in HBM, frame_off_out host int32 [n_utts + 1] (ready for
+ * ssw_feat_batch).  Every utterance starts afresh (fe_start_utt: pre-emphasis and noise
+ * tracker reset).  cfg NULL = the model's feat_params.json.  Supported: samprate 16000,
+ * frate 100, wlen 0.025625, nfft 0 or 512, ncep 13, alpha 0.97, transform legacy or dct,
+ * nfilt 1..64 with every filter at least one DFT point wide, 0 <= lowerf < upperf <=
+ * samprate / 2, any lifter >= 0, remove_noise yes / no, unit_area and round_filters yes;
+ * anything else (htk, dither, remove_dc, doublebw, smoothspec, logspec, warping, other
+ * rates) is refused with an error.  Tables (fe_create_hamming, fe_build_melfilters,
+ * fe_compute_melcosine, fe_create_twiddle, the lifter) are built on the host with libm and
+ * uploaded once per configuration.  Synchronous on `stream`; 0, or -1 (ssw_last_error). */
+int ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
+                 const int64_t *samp_off, int32_t n_utts, float *d_cep, int32_t *frame_off_out,
+                 void *stream);
+/* measurement aid: with ssw_set_kernel_timing on, the last ssw_fe_batch call's milliseconds per
+ * kernel -- ms[0] spectrum (framing, FFT, mel), ms[1] noise removal (0 when off), ms[2] log,
+ * DCT and lifter.  0, or -1 when no timed call has been made. */
+int ssw_fe_kernel_timing(ssw_model_t *m, float ms[3]);
+
+/* ------------------------------------------------------------------------------------ */
 /* Multi-GPU (NEW: the reference is single-process).  The path shards by utterance -- one   */
 /* process per GPU, the model replicated, no exchange while scoring and aligning -- and the  */
 /* only collective is ONE gather of the final alignment entries over RCCL (xGMI inside a      */

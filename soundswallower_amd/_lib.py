@@ -34,6 +34,15 @@ class SswModelInfo(C.Structure):
         ("mfma_selftest_worst_u", C.c_float), ("mfma_selftest_ms", C.c_float)]
 
 
+class SswFeConfig(C.Structure):
+    """ssw_fe_config_t: the front end's settings (config_defs.h FE_OPTIONS)"""
+    _fields_ = [(n, C.c_double) for n in ("samprate", "wlen", "alpha", "lowerf", "upperf")] + [
+        (n, C.c_int32) for n in ("frate", "nfft", "ncep", "nfilt", "lifter", "transform",
+                                 "remove_noise", "unit_area", "round_filters", "dither",
+                                 "remove_dc", "doublebw", "smoothspec", "logspec", "warp",
+                                 "from_file")]
+
+
 class SswAlignEntry(C.Structure):
     _fields_ = [("start", C.c_int32), ("duration", C.c_int32), ("score", C.c_int32)]
 
@@ -205,6 +214,13 @@ def lib() -> C.CDLL:
     L.ssw_alignment_populate.restype = i32
     L.ssw_alignment_populate.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.ssw_feat_batch.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
+    L.ssw_fe_config_defaults.argtypes = [C.POINTER(SswFeConfig)]
+    L.ssw_fe_config_defaults.restype = None
+    L.ssw_model_fe_config.argtypes = [vp, C.POINTER(SswFeConfig)]
+    L.ssw_fe_frame_count.argtypes = [vp, C.c_int64]
+    L.ssw_fe_frame_count.restype = C.c_int64
+    L.ssw_fe_batch.argtypes = [vp, C.POINTER(SswFeConfig), vp, vp, i32, vp, vp, vp]
+    L.ssw_fe_kernel_timing.argtypes = [vp, vp]
     L.ssw_comm_unique_id.argtypes = [C.c_char_p]
     L.ssw_comm_init.restype = vp
     L.ssw_comm_init.argtypes = [C.c_char_p, i32, i32, i32]

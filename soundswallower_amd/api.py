@@ -13,10 +13,11 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import SswAlignEntry, SswConfig, SswModelInfo
+from ._lib import SswAlignEntry, SswConfig, SswFeConfig, SswModelInfo
 
 SCORER_PTM = 0
 SCORER_MS = 1
+SSW_DEVICE_NONE = -2
 INT_MAX = 2**31 - 1
 
 _TABLES = {
@@ -32,6 +33,17 @@ _TABLES = {
 
 class SswError(RuntimeError):
     pass
+
+
+FE_TRANSFORMS = {"legacy": 0, "dct": 1, "htk": 2}
+FE_FRAME, FE_SHIFT, FE_NCEP = 410, 160, 13
+
+
+def fe_frame_counts(n_samples) -> np.ndarray:
+    """Frames the front end makes of utterances of n_samples samples (ssw_fe_frame_count):
+    0 for none, 1 below one window, else 2 + (n - 410) // 160 (fe_end's overflow frame last)."""
+    n = np.asarray(n_samples, np.int64)
+    return np.where(n <= 0, 0, np.where(n < FE_FRAME, 1, 2 + (n - FE_FRAME) // FE_SHIFT))
 
 
 class FirstPassConfig(C.Structure):
@@ -394,6 +406,81 @@ class Model:
             self._L.ssw_device_free(d_in)
             self._L.ssw_device_free(d_out)
         return out
+
+    # ---- MFCC front end ----------------------------------------------------------------
+    def fe_config(self, **overrides) -> SswFeConfig:
+        """The front-end settings the model loaded from its feat_params.json (reference defaults
+        for missing keys), with `overrides` applied, e.g. fe_config(transform="legacy")."""
+        c = SswFeConfig()
+        _check(self._L.ssw_model_fe_config(self._m, C.byref(c)), "ssw_model_fe_config")
+        for k, v in overrides.items():
+            if k not in dict(SswFeConfig._fields_):
+                raise SswError(f"unknown front-end setting {k!r}")
+            if k == "transform" and isinstance(v, str):
+                if v not in FE_TRANSFORMS:
+                    raise SswError(f"unknown transform {v!r}")
+                v = FE_TRANSFORMS[v]
+            setattr(c, k, int(v) if isinstance(v, bool) else v)
+        return c
+
+    def _fe_cfg(self, cfg):
+        if cfg is None:
+            return None                               # NULL: the model's feat_params.json
+        return C.byref(cfg if isinstance(cfg, SswFeConfig) else self.fe_config(**cfg))
+
+    def fe_batch_device(self, d_pcm, samp_off, d_cep=None, cfg=None, stream=None):
+        """ssw_fe_batch: int16 PCM in HBM (torch tensor or device pointer), utterance u =
+        samples samp_off[u] .. samp_off[u + 1] -> (d_cep float32 [n_frames][13] in HBM,
+        frame_off int32 [n_utts + 1] on the host, as feat_batch takes them).  d_cep None: a torch
+        tensor is allocated.  cfg: None (feat_params.json), a dict of overrides or an
+        SswFeConfig."""
+        off = np.ascontiguousarray(samp_off, np.int64)
+        n_frames = int(fe_frame_counts(np.diff(off)).sum())
+        if d_cep is None:
+            import torch
+            dev = d_pcm.device if hasattr(d_pcm, "device") else "cuda"
+            d_cep = torch.empty((n_frames, FE_NCEP), dtype=torch.float32, device=dev)
+        fo = np.zeros(len(off), np.int32)
+        _check(self._L.ssw_fe_batch(self._m, self._fe_cfg(cfg), _ptr(d_pcm), _ptr(off),
+                                    len(off) - 1, _ptr(d_cep), _ptr(fo), _ptr(stream)),
+               "ssw_fe_batch")
+        return d_cep, fo
+
+    def fe_batch(self, pcm, samp_off=None, cfg=None):
+        """The MFCC front end on the GPU, host in and host out: int16 PCM (one array, with
+        samp_off for a batch, or a list of arrays) -> (cep float32 [n_frames][13], frame_off)."""
+        if isinstance(pcm, (list, tuple)):
+            samp_off = np.concatenate([[0], np.cumsum([len(p) for p in pcm])])
+            pcm = np.concatenate([np.asarray(p, np.int16).reshape(-1) for p in pcm]) if pcm \
+                else np.zeros(0, np.int16)
+        pcm = np.ascontiguousarray(pcm, np.int16).reshape(-1)
+        off = (np.array([0, len(pcm)], np.int64) if samp_off is None
+               else np.ascontiguousarray(samp_off, np.int64))
+        if len(off) < 1 or off[-1] != len(pcm):
+            raise SswError("fe_batch: samp_off must end at len(pcm)")
+        n_frames = int(fe_frame_counts(np.diff(off)).sum())
+        cep = np.zeros((n_frames, FE_NCEP), np.float32)
+        # (a model without a device gets NULL pointers: ssw_fe_batch checks the configuration,
+        # then refuses the work)
+        on_dev = n_frames > 0 and self.device != SSW_DEVICE_NONE
+        d_pcm = self.to_device(pcm) if on_dev else None
+        d_cep = self.device_malloc(cep.nbytes) if on_dev else None
+        try:
+            _, fo = self.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, cfg)
+            if on_dev:
+                _check(self._L.ssw_memcpy_d2h(_ptr(cep), d_cep, cep.nbytes), "ssw_memcpy_d2h")
+        finally:
+            if d_pcm:
+                self.device_free(d_pcm)
+            if d_cep:
+                self.device_free(d_cep)
+        return cep, fo
+
+    def fe_kernel_timing(self):
+        """ms per front-end kernel of the last timed fe call: (spectrum, noise, cepstrum)."""
+        ms = (C.c_float * 3)()
+        _check(self._L.ssw_fe_kernel_timing(self._m, ms), "ssw_fe_kernel_timing")
+        return tuple(ms)
 
     # ---- device memory (no torch needed) --------------------------------------------
     def to_device(self, arr: np.ndarray) -> int:
@@ -900,6 +987,37 @@ def align_text_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, texts,
     if not h:
         raise SswError("ssw_align_text_batch_active: " + _lib.last_error())
     return AlignmentSet(L, h, lex)
+
+
+def align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, texts, cfg=None, active=False,
+                      fe_cfg=None, scorer=SCORER_PTM, stream=None) -> AlignmentSet:
+    """Audio and text in, alignments out: what decoder_process_int16 over each utterance and
+    decoder_alignment give (src/decoder.c:737-798), for a batch.  int16 PCM (host array or
+    device tensor; utterance u = samples samp_off[u] .. samp_off[u + 1]) -> ssw_fe_batch ->
+    ssw_feat_batch -> ssw_align_text_batch, or ssw_align_text_batch_active when active=True (the
+    reference's default compallsen = no).  cfg: FirstPassConfig; fe_cfg: front-end settings
+    (None = the model's feat_params.json)."""
+    off = np.ascontiguousarray(samp_off, np.int64)
+    on_device = hasattr(pcm, "data_ptr") and getattr(pcm, "is_cuda", False)
+    d_pcm = pcm if on_device else (model.to_device(np.ascontiguousarray(pcm, np.int16))
+                                   if off[-1] > 0 else None)
+    n_frames = int(fe_frame_counts(np.diff(off)).sum())
+    d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
+    d_feat = model.device_malloc(n_frames * 3 * FE_NCEP * 4) if n_frames else None
+    try:
+        _, fo = model.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, fe_cfg, stream)
+        if n_frames:
+            _check(model._L.ssw_feat_batch(model._m, d_cep, n_frames, _ptr(fo), len(fo) - 1,
+                                           FE_NCEP, d_feat, _ptr(stream)), "ssw_feat_batch")
+        fn = align_text_batch_active if active else align_text_batch
+        return fn(model, lex, d_feat if d_feat else 0, fo, texts, cfg=cfg, scorer=scorer,
+                  stream=stream)
+    finally:
+        if d_pcm is not None and not on_device:
+            model.device_free(d_pcm)
+        for p in (d_cep, d_feat):
+            if p:
+                model.device_free(p)
 
 
 def forced_alignment(model: Model, lex: Lexicon, d_senscr, utt_off, texts, cfg=None, stream=None):

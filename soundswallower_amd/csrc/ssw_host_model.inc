@@ -216,6 +216,15 @@ struct ssw_model_s {
     /* utterance offsets of ssw_feat_batch */
     int *d_feat_off;
     size_t feat_off_cap;
+    /* the front end (ssw_host_fe.inc): its tables on the device and the configuration they were
+     * built for; a grow-only workspace (offsets, mel spectra); per-kernel events */
+    ssw_fe_tables_t *d_fe_tab;
+    ssw_fe_config_t fe_tab_cfg;
+    int fe_nfilt, fe_noise;
+    unsigned char *d_fe_ws;
+    size_t fe_ws_cap;
+    hipEvent_t fe_ev[4];
+    int fe_ev_ready, fe_timed;
     /* alignment workspace (ssw_align_batch) */
     unsigned char *d_align_ws;
     unsigned char *d_fp_ws; /* first-pass workspace (grow-only) */
@@ -644,6 +653,11 @@ ssw_model_free(ssw_model_t *m)
     (void)hipFree(m->d_fpa_ws);
     (void)hipFree(m->d_text_scr);
     (void)hipFree(m->d_feat_off);
+    (void)hipFree(m->d_fe_tab);
+    (void)hipFree(m->d_fe_ws);
+    if (m->fe_ev_ready)
+        for (int i = 0; i < 4; ++i)
+            (void)hipEventDestroy(m->fe_ev[i]);
     (void)hipFree(m->d_sen_slot);
     (void)hipFree(m->d_act_ws);
     (void)hipFree(m->d_mixw);

@@ -26,9 +26,43 @@ extern "C" {
 /* matrix-core scan: binary16 values per (codebook, stream) in wfrag */
 #define SSW_WFRAG_PER_CBF (4 * 2 * 2 * 64 * 8)
 
+/* MFCC front end (ssw_model.c, ssw_k8_fe.inc, ssw_host_fe.inc): the one framing supported,
+ * 16 kHz, 100 frames/s, 25.625 ms window, 512-point FFT */
+#define SSW_FE_FRAME 410
+#define SSW_FE_SHIFT 160
+#define SSW_FE_NFFT 512
+#define SSW_FE_MAX_FILT 64
+#define SSW_FE_NCEP 13
+#define SSW_FE_MAX_COEFFS 4096
+
+/* the front end's tables as fe_init builds them (ssw_fe_tables_build) */
+typedef struct ssw_fe_tables_s {
+    int32_t frame_size, frame_shift, fft_size, fft_order, nfilt, ncep, n_coeffs;
+    int32_t transform, remove_noise, lifter_val;
+    float alpha, sqrt_inv_n, sqrt_inv_2n;
+    double hamming[SSW_FE_FRAME / 2];
+    double ccc[SSW_FE_NFFT / 4], sss[SSW_FE_NFFT / 4];
+    int32_t spec_start[SSW_FE_MAX_FILT], filt_width[SSW_FE_MAX_FILT], filt_start[SSW_FE_MAX_FILT];
+    float filt_coeffs[SSW_FE_MAX_COEFFS];
+    float mel_cosine[SSW_FE_NCEP * SSW_FE_MAX_FILT]; /* [ncep][nfilt] */
+    float lifter[SSW_FE_NCEP];
+} ssw_fe_tables_t;
+
+/* feat_params.json over *c (which holds the defaults): 0 read, 1 no such file, -1 unusable
+ * (message in err) */
+int ssw_fe_config_read(const char *path, ssw_fe_config_t *c, char *err, size_t err_len);
+/* 0 when ssw_fe_batch supports the configuration, else -1 and ssw_set_error */
+int ssw_fe_config_check(const ssw_fe_config_t *c);
+int ssw_fe_tables_build(const ssw_fe_config_t *c, ssw_fe_tables_t *t);
+int64_t ssw_fe_frames_of(int64_t n_samples);
+
 /* Host-side model: every table derived exactly as the reference derives it. */
 typedef struct ssw_host_model_s {
     ssw_config_t cfg;
+    /* front end: feat_params.json beside the means file (ssw_model.c); fe_err holds why that file
+     * could not be used ("" when it could, or when there is none) */
+    ssw_fe_config_t fe;
+    char fe_err[256];
     /* Gaussians (gauden_t) */
     int32_t n_cb, n_feat, n_density, veclen_total, n_floored;
     int32_t veclen[SSW_MAX_FEAT], featoff[SSW_MAX_FEAT];

@@ -1,0 +1,280 @@
+/* ssw_k8_fe.inc -- K8: the MFCC front end, whole utterances.
+ * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
+/* ---------------------------------------------------------------------------------- */
+/* K8: PCM -> cepstra (fe_process_int16 + fe_end over whole utterances)                 */
+/* ---------------------------------------------------------------------------------- */
+/* The reference's front end, frame by frame (src/fe_sigproc.c:219-738, src/fe_noise.c:111-327),
+ * in its own types: pre-emphasis, window, FFT, power and mel spectra in double, the noise
+ * tracker in double, log in double, the DCT with float accumulators rounded after every add.
+ * The only operations that are not +, -, *, / or a compare are the log (ocml's, which may sit
+ * one double ulp away from glibc's; the float rounding of the DCT absorbs that, DESIGN K8) and
+ * the conversions.  The tables come from the host (csrc/ssw_model.c), built as fe_init builds them.
+ *
+ * Framing (src/fe_interface.c:560-690): frame f of an utterance of n samples covers samples
+ * 160 f .. 160 f + min(410, n - 160 f) - 1, zero-padded to 512; the last frame is fe_end's
+ * overflow frame.  The pre-emphasis's prior sample is 0 for frame 0 and sample 160 f - 1 after
+ * it (fe_spch_to_frame keeps spch[frame_shift - 1]; the overflow frame starts where the next
+ * full frame would), so frames are independent up to the noise tracker.
+ *
+ *   fe_spectrum_kernel  one wave per frame: samples -> pre-emphasis -> Hamming, stored straight
+ *                       to bit-reversed LDS positions (fe_fft_real's first loop is exactly that
+ *                       permutation), the pair stage and stages k = 1..8 with fe_fft_real's
+ *                       butterflies (those of a stage touch disjoint points: 128 per stage, two
+ *                       per lane), power spectrum, mel sums in the reference's j order
+ *                       -> double mfspec [frame][nfilt]
+ *   fe_noise_kernel     remove_noise: one wave per utterance, lane = filter, frames in order
+ *                       (the tracker is a recurrence); the +-4 gain smoothing by lane shuffles
+ *   fe_cep_kernel       log(mfspec + 1e-4), then DCT-II (transform = dct) or fe_spec2cep
+ *                       (legacy), then the lifter -> float cep [frame][13] */
+struct FeParams {
+    const int16_t *pcm;
+    const long long *samp_off; /* [n_utts + 1] */
+    const int *frame_off;      /* [n_utts + 1] */
+    const ssw_fe_tables_t *tab;
+    double *mfspec;            /* [n_frames][nfilt] */
+    float *cep;                /* [n_frames][13] */
+    int n_utts, n_frames;
+};
+
+constexpr int FE_SPEC_WAVES = 4;  /* frames per workgroup of the spectrum kernel */
+constexpr int FE_CEP_FRAMES = 16; /* frames per workgroup of the cepstrum kernel */
+constexpr int FE_CEP_THREADS = 256;
+static_assert(FE_CEP_FRAMES * SSW_FE_NCEP <= FE_CEP_THREADS, "one thread per cepstrum");
+
+/* the utterance that holds frame f: the last u with frame_off[u] <= f (empty utterances have
+ * frame_off[u] == frame_off[u + 1] and are passed over) */
+__device__ __forceinline__ int
+fe_utt_of(const int *frame_off, int n_utts, int f)
+{
+    int lo = 0, hi = n_utts - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (frame_off[mid] <= f)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(64 * FE_SPEC_WAVES)
+fe_spectrum_kernel(FeParams P)
+{
+    __shared__ double s_x[FE_SPEC_WAVES][SSW_FE_NFFT];
+    __shared__ double s_spec[FE_SPEC_WAVES][SSW_FE_NFFT / 2 + 1];
+    const ssw_fe_tables_t *T = P.tab;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int f = blockIdx.x * FE_SPEC_WAVES + w;
+    const bool live = f < P.n_frames; /* wave-uniform; every wave reaches every barrier */
+    double *x = s_x[w];
+    if (live) {
+        /* fe_spch_to_frame (src/fe_sigproc.c:276-303) into fe_fft_real's bit-reversed order */
+        const int u = fe_utt_of(P.frame_off, P.n_utts, f);
+        const int fl = f - P.frame_off[u];
+        const long long s0 = P.samp_off[u], n = P.samp_off[u + 1] - s0;
+        const long long start = s0 + (long long)SSW_FE_SHIFT * fl;
+        const long long left = n - (long long)SSW_FE_SHIFT * fl;
+        const int len = left < SSW_FE_FRAME ? (int)left : SSW_FE_FRAME;
+        const double alpha = (double)T->alpha;
+        const double prior = fl == 0 ? 0.0 : (double)P.pcm[start - 1];
+#pragma unroll
+        for (int k = 0; k < SSW_FE_NFFT / 64; ++k) {
+            const int i = lane + 64 * k;
+            double v = 0.0;
+            if (i < len) {
+                const double prev = i == 0 ? prior : (double)P.pcm[start + i - 1];
+                v = (double)P.pcm[start + i] - prev * alpha;
+            }
+            if (i < SSW_FE_FRAME / 2)
+                v = v * T->hamming[i];
+            else if (i < SSW_FE_FRAME)
+                v = v * T->hamming[SSW_FE_FRAME - 1 - i];
+            x[__brev((unsigned)i) >> (32 - 9)] = v;
+        }
+    }
+    __syncthreads();
+    if (live) { /* fe_fft_real's first stage: pairs */
+#pragma unroll
+        for (int k = 0; k < SSW_FE_NFFT / 2 / 64; ++k) {
+            const int i = 2 * (lane + 64 * k);
+            const double a = x[i], b = x[i + 1];
+            x[i] = a + b;
+            x[i + 1] = a - b;
+        }
+    }
+    __syncthreads();
+    for (int k = 1; k < 9; ++k) { /* stages 1..8: 128 butterfly groups each */
+        if (live) {
+            const int n2 = 1 << k, n4 = 1 << (k - 1);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int g = lane + 64 * t;
+                const int j = g & (n4 - 1), i = (g >> (k - 1)) << (k + 1);
+                if (j == 0) {
+                    const double a = x[i], b = x[i + n2];
+                    x[i] = a + b;
+                    x[i + n2] = a - b;
+                    x[i + n2 + n4] = -x[i + n2 + n4];
+                } else {
+                    const int i1 = i + j, i2 = i + n2 - j, i3 = i + n2 + j, i4 = i + n2 + n2 - j;
+                    const double cc = T->ccc[j << (8 - k)], ss = T->sss[j << (8 - k)];
+                    const double x1 = x[i1], x2 = x[i2], x3 = x[i3], x4 = x[i4];
+                    const double t1 = x3 * cc + x4 * ss;
+                    const double t2 = x3 * ss - x4 * cc;
+                    x[i4] = x2 - t2;
+                    x[i3] = -x2 - t2;
+                    x[i2] = x1 - t1;
+                    x[i1] = x1 + t1;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    double *spec = s_spec[w];
+    if (live) { /* fe_spec_magnitude, src/fe_sigproc.c:560-585 */
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const int j = lane + 64 * k;
+            if (j == 0)
+                spec[0] = x[0] * x[0];
+            else if (j <= SSW_FE_NFFT / 2)
+                spec[j] = x[j] * x[j] + x[SSW_FE_NFFT - j] * x[SSW_FE_NFFT - j];
+        }
+    }
+    __syncthreads();
+    if (live && lane < T->nfilt) { /* fe_mel_spec, src/fe_sigproc.c:587-607 */
+        const int s0 = T->spec_start[lane], c0 = T->filt_start[lane], wd = T->filt_width[lane];
+        double acc = 0.0;
+        for (int j = 0; j < wd; ++j)
+            acc = acc + spec[s0 + j] * (double)T->filt_coeffs[c0 + j];
+        P.mfspec[(size_t)f * T->nfilt + lane] = acc;
+    }
+}
+
+/* fe_remove_noise, src/fe_noise.c:247-327 with fe_lower_envelope :111-128, fe_temp_masking
+ * :130-149, fe_weight_smooth :151-176 (SMOOTH_WINDOW 4); state reset per utterance
+ * (fe_start_utt -> fe_reset_noise_stats) */
+__global__ void __launch_bounds__(64)
+fe_noise_kernel(FeParams P)
+{
+    const double lambda_power = 0.7, lambda_a = 0.995, lambda_b = 0.5, lambda_t = 0.85,
+                 mu_t = 0.2, max_gain = 20.0, inv_max_gain = 1.0 / 20.0;
+    const double comp_power = 1 - lambda_power, comp_a = 1 - lambda_a, comp_b = 1 - lambda_b;
+    const int u = blockIdx.x, lane = threadIdx.x;
+    const int f0 = P.frame_off[u], nf = P.frame_off[u + 1] - f0;
+    const int n = P.tab->nfilt;
+    const bool act = lane < n;
+    const int l1 = lane - 4 > 0 ? lane - 4 : 0, l2 = lane + 4 < n - 1 ? lane + 4 : n - 1;
+    const double width = (double)(l2 - l1 + 1);
+    double *mf = P.mfspec + (size_t)f0 * n + lane;
+    double power = 0.0, noise = 0.0, floor_ = 0.0, peak = 0.0;
+    /* the recurrence is sequential; the loads are not: CH frames in flight */
+    constexpr int CH = 8;
+    for (int b = 0; b < nf; b += CH) {
+        double v[CH];
+#pragma unroll
+        for (int k = 0; k < CH; ++k)
+            v[k] = act && b + k < nf ? mf[(size_t)(b + k) * n] : 0.0;
+#pragma unroll
+        for (int k = 0; k < CH; ++k) {
+            if (b + k >= nf)
+                break;
+            const double m = v[k];
+            double gain = 0.0;
+            if (act) {
+                if (b + k == 0) { /* noise_stats->undefined */
+                    power = m;
+                    noise = m / max_gain;
+                    floor_ = m / max_gain;
+                    peak = 0.0;
+                }
+                power = lambda_power * power + comp_power * m;
+                if (power >= noise)
+                    noise = lambda_a * noise + comp_a * power;
+                else
+                    noise = lambda_b * noise + comp_b * power;
+                double signal = power - noise;
+                if (signal < 1.0)
+                    signal = 1.0;
+                if (signal >= floor_)
+                    floor_ = lambda_a * floor_ + comp_a * signal;
+                else
+                    floor_ = lambda_b * floor_ + comp_b * signal;
+                const double cur_in = signal;
+                peak *= lambda_t;
+                if (signal < lambda_t * peak)
+                    signal = peak * mu_t;
+                if (cur_in > peak)
+                    peak = cur_in;
+                if (signal < floor_)
+                    signal = floor_;
+                if (signal < max_gain * power)
+                    gain = signal / power;
+                else
+                    gain = max_gain;
+                if (gain < inv_max_gain)
+                    gain = inv_max_gain;
+            }
+            /* coef = gain[l1] + ... + gain[l2], from 0, in that order */
+            double coef = 0.0;
+#pragma unroll
+            for (int d = -4; d <= 4; ++d) {
+                const int src = lane + d;
+                const double gd = __shfl(gain, src < 0 ? 0 : (src > 63 ? 63 : src));
+                if (src >= 0 && src < n)
+                    coef += gd;
+            }
+            if (act)
+                mf[(size_t)(b + k) * n] = m * (coef / width);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(FE_CEP_THREADS)
+fe_cep_kernel(FeParams P)
+{
+    __shared__ double s_lm[FE_CEP_FRAMES][SSW_FE_MAX_FILT];
+    const ssw_fe_tables_t *T = P.tab;
+    const int n = T->nfilt, f0 = blockIdx.x * FE_CEP_FRAMES;
+    /* fe_mel_cep, src/fe_sigproc.c:609-646: LOG_FLOOR 1e-4 */
+    for (int idx = threadIdx.x; idx < FE_CEP_FRAMES * n; idx += FE_CEP_THREADS) {
+        const int r = idx / n, j = idx - r * n;
+        if (f0 + r < P.n_frames)
+            s_lm[r][j] = log(P.mfspec[(size_t)(f0 + r) * n + j] + 1e-4);
+    }
+    __syncthreads();
+    const int r = threadIdx.x / SSW_FE_NCEP, i = threadIdx.x - r * SSW_FE_NCEP, f = f0 + r;
+    if (r >= FE_CEP_FRAMES || f >= P.n_frames)
+        return;
+    const double *lm = s_lm[r];
+    const float *cosrow = T->mel_cosine + i * n;
+    float c;
+    if (T->transform == SSW_FE_DCT) { /* fe_dct2, src/fe_sigproc.c:677-700 */
+        if (i == 0) {
+            c = (float)lm[0];
+            for (int j = 1; j < n; ++j)
+                c = (float)((double)c + lm[j]);
+            c = c * T->sqrt_inv_n;
+        } else {
+            c = 0.0f;
+            for (int j = 0; j < n; ++j)
+                c = (float)((double)c + lm[j] * (double)cosrow[j]);
+            c = c * T->sqrt_inv_2n;
+        }
+    } else { /* fe_spec2cep (transform = legacy), src/fe_sigproc.c:647-676 */
+        if (i == 0) {
+            c = (float)(lm[0] / 2);
+            for (int j = 1; j < n; ++j)
+                c = (float)((double)c + lm[j]);
+            c = (float)((double)c / (double)n);
+        } else {
+            c = 0.0f;
+            for (int j = 0; j < n; ++j)
+                c = (float)((double)c + lm[j] * (double)cosrow[j] * (double)(j == 0 ? 1 : 2));
+            c = (float)((double)c / ((double)n * 2));
+        }
+    }
+    if (T->lifter_val) /* fe_lifter, src/fe_sigproc.c:701-712: after either transform */
+        c = c * T->lifter[i];
+    P.cep[(size_t)f * SSW_FE_NCEP + i] = c;
+}

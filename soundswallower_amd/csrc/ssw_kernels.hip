@@ -33,9 +33,15 @@
  *   ssw_k7_fpactive.inc  the first pass in the default configuration (compallsen = no) as a
  *                        batch: per-frame listed sets from the search's exported HMM sets, the
  *                        senone kernel over them, the comparison that proves a trajectory
+ *   ssw_k8_fe.inc        the MFCC front end for whole utterances: fe_spectrum_kernel (pre-emphasis,
+ *                        window, fe_fft_real, power and mel spectra, one wave per frame),
+ *                        fe_noise_kernel (fe_remove_noise, one wave per utterance),
+ *                        fe_cep_kernel (log, DCT-II or legacy transform, lifter),
+ *                        src/fe_sigproc.c:219-738, src/fe_noise.c:111-327
  *   ssw_host_*.inc       device model and loaders' upload, batched scoring, alignment, the
- *                        mgau_t / search-module shaped objects, features, device-memory helpers,
- *                        the RCCL gather of final alignments (ssw_host_comm.inc)
+ *                        mgau_t / search-module shaped objects, features, the front end
+ *                        (ssw_host_fe.inc; its tables are built in ssw_model.c), device-memory
+ *                        helpers, the RCCL gather of final alignments (ssw_host_comm.inc)
  */
 #pragma clang fp contract(off)
 
@@ -46,6 +52,7 @@
 #include <atomic>
 #include <functional>
 #include <map>
+#include <memory>
 #include <set>
 #include <chrono>
 #include <climits>
@@ -82,6 +89,7 @@ namespace {
 #include "ssw_k5_firstpass.inc"
 #include "ssw_k6_compact.inc"
 #include "ssw_k7_fpactive.inc"
+#include "ssw_k8_fe.inc"
 
 } // namespace
 
@@ -93,6 +101,7 @@ namespace {
 #include "ssw_host_mgau.inc"
 #include "ssw_host_search.inc"
 #include "ssw_host_feat.inc"
+#include "ssw_host_fe.inc"
 #include "ssw_host_firstpass.inc"
 #include "ssw_host_fpactive.inc"
 #include "ssw_host_devmem.inc"

@@ -14,6 +14,7 @@
  */
 #include "ssw_internal.h"
 
+#include <ctype.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -54,6 +55,424 @@ ssw_config_defaults(ssw_config_t *cfg)
     cfg->ds = 1;
     cfg->aw = 1;
     cfg->device = -1;
+}
+
+/* ---------------------------------------------------------------------------------- */
+/* Front-end settings: feat_params.json, read the way config_parse_json reads it         */
+/* (src/config.c:441-510: a flat JSON object, every value a string or a primitive), over */
+/* the defaults of config_defs.h FE_OPTIONS (include/soundswallower/config_defs.h:       */
+/* 299-412).                                                                             */
+/* ---------------------------------------------------------------------------------- */
+void
+ssw_fe_config_defaults(ssw_fe_config_t *c)
+{
+    memset(c, 0, sizeof(*c));
+    c->samprate = 16000;
+    c->wlen = 0.025625;
+    c->alpha = 0.97;
+    c->lowerf = 133.33334;
+    c->upperf = 6855.4976;
+    c->frate = 100;
+    c->nfft = 0;
+    c->ncep = 13;
+    c->nfilt = 40;
+    c->lifter = 0;
+    c->transform = SSW_FE_LEGACY;
+    c->remove_noise = 0;
+    c->unit_area = 1;
+    c->round_filters = 1;
+}
+
+/* ---------------------------------------------------------------------------------- */
+/* feat_params.json                                                                     */
+/* ---------------------------------------------------------------------------------- */
+/* one JSON token: a string (unescaped into out) or a primitive (number, true, false, null);
+ * returns the position after it, NULL on a syntax error */
+static const char *
+json_token(const char *p, char *out, size_t cap, int *is_string)
+{
+    size_t n = 0;
+    while (isspace((unsigned char)*p))
+        ++p;
+    if (*p == '"') {
+        *is_string = 1;
+        for (++p; *p && *p != '"'; ++p) {
+            char ch = *p;
+            if (ch == '\\') {
+                ++p;
+                switch (*p) {
+                case 'n': ch = '\n'; break;
+                case 't': ch = '\t'; break;
+                case 'r': ch = '\r'; break;
+                case 'b': ch = '\b'; break;
+                case 'f': ch = '\f'; break;
+                case '\0': return NULL;
+                default: ch = *p; break; /* \" \\ \/ (\uXXXX is not needed by any key here) */
+                }
+            }
+            if (n + 1 < cap)
+                out[n++] = ch;
+        }
+        if (*p != '"')
+            return NULL;
+        out[n] = '\0';
+        return p + 1;
+    }
+    *is_string = 0;
+    while (*p && *p != ',' && *p != '}' && !isspace((unsigned char)*p)) {
+        if (n + 1 < cap)
+            out[n++] = *p;
+        ++p;
+    }
+    out[n] = '\0';
+    return n ? p : NULL;
+}
+
+static int
+parse_bool(const char *v, int32_t *out)
+{
+    if (!strcmp(v, "true") || !strcmp(v, "yes") || !strcmp(v, "1") || !strcmp(v, "TRUE")
+        || !strcmp(v, "YES"))
+        *out = 1;
+    else if (!strcmp(v, "false") || !strcmp(v, "no") || !strcmp(v, "0") || !strcmp(v, "FALSE")
+             || !strcmp(v, "NO"))
+        *out = 0;
+    else
+        return -1;
+    return 0;
+}
+
+static int
+parse_num(const char *v, double *out)
+{
+    char *end;
+    double x = strtod(v, &end);
+    if (end == v || *end != '\0')
+        return -1;
+    *out = x;
+    return 0;
+}
+
+static int
+parse_int(const char *v, int32_t *out)
+{
+    double x;
+    if (parse_num(v, &x) < 0 || x != (double)(int32_t)x)
+        return -1;
+    *out = (int32_t)x;
+    return 0;
+}
+
+/* one key of the front end's; unknown keys are ignored (they belong to other modules) */
+static int
+fe_set_key(ssw_fe_config_t *c, const char *key, const char *v, int is_string)
+{
+    double d;
+    if (key[0] == '-') /* command-line spelling */
+        ++key;
+#define NUM(name, field)                                                                    \
+    if (!strcmp(key, name))                                                                 \
+        return parse_num(v, &d) < 0 ? -1 : (c->field = d, 0);
+#define INT(name, field)                                                                    \
+    if (!strcmp(key, name))                                                                 \
+        return parse_int(v, &c->field);
+#define BOOL(name, field)                                                                   \
+    if (!strcmp(key, name))                                                                 \
+        return parse_bool(v, &c->field);
+    NUM("samprate", samprate)
+    NUM("wlen", wlen)
+    NUM("alpha", alpha)
+    NUM("lowerf", lowerf)
+    NUM("upperf", upperf)
+    INT("frate", frate)
+    INT("nfft", nfft)
+    INT("ncep", ncep)
+    INT("nfilt", nfilt)
+    INT("lifter", lifter)
+    BOOL("remove_noise", remove_noise)
+    BOOL("unit_area", unit_area)
+    BOOL("round_filters", round_filters)
+    BOOL("dither", dither)
+    BOOL("remove_dc", remove_dc)
+    BOOL("doublebw", doublebw)
+    BOOL("smoothspec", smoothspec)
+    BOOL("logspec", logspec)
+#undef NUM
+#undef INT
+#undef BOOL
+    if (!strcmp(key, "transform")) {
+        if (!strcmp(v, "legacy"))
+            c->transform = SSW_FE_LEGACY;
+        else if (!strcmp(v, "dct"))
+            c->transform = SSW_FE_DCT;
+        else if (!strcmp(v, "htk"))
+            c->transform = SSW_FE_HTK;
+        else
+            return -1;
+        return 0;
+    }
+    if (!strcmp(key, "warp_params")) { /* null or "" = no warping (the default) */
+        c->warp = is_string ? v[0] != '\0' : strcmp(v, "null") != 0;
+        return 0;
+    }
+    return 0;
+}
+
+int
+ssw_fe_config_read(const char *path, ssw_fe_config_t *c, char *err, size_t err_len)
+{
+    FILE *f = fopen(path, "rb");
+    char *buf = NULL, key[128], val[512];
+    const char *p;
+    long len;
+    int is_string, rv = -1;
+
+    err[0] = '\0';
+    if (f == NULL)
+        return 1; /* no file: the defaults */
+    if (fseek(f, 0, SEEK_END) != 0 || (len = ftell(f)) < 0 || len > (1 << 20)
+        || fseek(f, 0, SEEK_SET) != 0 || (buf = (char *)malloc((size_t)len + 1)) == NULL
+        || fread(buf, 1, (size_t)len, f) != (size_t)len) {
+        snprintf(err, err_len, "%s: cannot read", path);
+        goto done;
+    }
+    buf[len] = '\0';
+    p = buf;
+    while (isspace((unsigned char)*p))
+        ++p;
+    if (*p++ != '{') {
+        snprintf(err, err_len, "%s: not a JSON object", path);
+        goto done;
+    }
+    for (;;) {
+        while (isspace((unsigned char)*p))
+            ++p;
+        if (*p == '}')
+            break;
+        if ((p = json_token(p, key, sizeof(key), &is_string)) == NULL || !is_string) {
+            snprintf(err, err_len, "%s: expected a key", path);
+            goto done;
+        }
+        while (isspace((unsigned char)*p))
+            ++p;
+        if (*p++ != ':' || (p = json_token(p, val, sizeof(val), &is_string)) == NULL) {
+            snprintf(err, err_len, "%s: bad value of \"%s\"", path, key);
+            goto done;
+        }
+        if (fe_set_key(c, key, val, is_string) < 0) {
+            snprintf(err, err_len, "%s: cannot use \"%s\" as the value of \"%s\"", path, val, key);
+            goto done;
+        }
+        while (isspace((unsigned char)*p))
+            ++p;
+        if (*p == ',')
+            ++p;
+        else if (*p != '}') {
+            snprintf(err, err_len, "%s: expected ',' or '}' after \"%s\"", path, key);
+            goto done;
+        }
+    }
+    c->from_file = 1;
+    rv = 0;
+done:
+    free(buf);
+    fclose(f);
+    return rv;
+}
+
+/* ---------------------------------------------------------------------------------- */
+/* Front-end checks and tables, built exactly as fe_init builds them                     */
+/* (src/fe_interface.c:86-330, src/fe_sigproc.c:70-252, :447-457): the same float /      */
+/* double types operand by operand, libm for cos, sin, log10, pow and sqrt.  The kernels */
+/* (ssw_k8_fe.inc) only read them.                                                       */
+/* ---------------------------------------------------------------------------------- */
+int
+ssw_fe_config_check(const ssw_fe_config_t *c)
+{
+    if (c->transform == SSW_FE_HTK) {
+        ssw_set_error("front end: transform = htk is not supported (legacy or dct)");
+        return -1;
+    }
+    if (c->transform != SSW_FE_LEGACY && c->transform != SSW_FE_DCT) {
+        ssw_set_error("front end: unknown transform %d", c->transform);
+        return -1;
+    }
+    if (c->dither || c->remove_dc || c->doublebw || c->smoothspec || c->logspec || c->warp) {
+        ssw_set_error("front end: %s is not supported",
+                      c->dither ? "dither" : c->remove_dc ? "remove_dc" : c->doublebw ? "doublebw"
+                      : c->smoothspec ? "smoothspec" : c->logspec ? "logspec"
+                      : "frequency warping (warp_params)");
+        return -1;
+    }
+    if (c->samprate != 16000 || c->frate != 100 || (float)c->wlen != (float)0.025625
+        || (c->nfft != 0 && c->nfft != 512)) {
+        ssw_set_error("front end: only samprate 16000, frate 100, wlen 0.025625 and a 512-point "
+                      "FFT are supported (got %g, %d, %g, %d)", c->samprate, c->frate, c->wlen,
+                      c->nfft);
+        return -1;
+    }
+    if (c->ncep != 13 || (float)c->alpha != (float)0.97) {
+        ssw_set_error("front end: only ncep 13 and alpha 0.97 are supported (got %d, %g)",
+                      c->ncep, c->alpha);
+        return -1;
+    }
+    if (!c->unit_area || !c->round_filters) {
+        ssw_set_error("front end: only unit_area = yes and round_filters = yes are supported");
+        return -1;
+    }
+    if (c->nfilt < 1 || c->nfilt > SSW_FE_MAX_FILT || c->lifter < 0) {
+        ssw_set_error("front end: nfilt must be 1..%d and lifter >= 0 (got %d, %d)",
+                      SSW_FE_MAX_FILT, c->nfilt, c->lifter);
+        return -1;
+    }
+    if (!(c->lowerf >= 0) || !(c->lowerf < c->upperf) || !(c->upperf <= c->samprate / 2)) {
+        ssw_set_error("front end: need 0 <= lowerf < upperf <= samprate / 2 (got %g, %g)",
+                      c->lowerf, c->upperf);
+        return -1;
+    }
+    return 0;
+}
+
+static float
+fe_mel(float x) /* fe_mel, src/fe_sigproc.c:70-76 (no warping) */
+{
+    return (float)(2595.0 * log10(1.0 + x / 700.0));
+}
+
+static float
+fe_melinv(float x) /* fe_melinv, src/fe_sigproc.c:78-83 */
+{
+    return (float)(700.0 * (pow(10.0, x / 2595.0) - 1.0));
+}
+
+/* the three edge frequencies of filter i, src/fe_sigproc.c:111-121 */
+static void
+filter_edges(int i, float melbw, float melmin, float fftfreq, int round_filters, float fr[3])
+{
+    int j;
+    for (j = 0; j < 3; ++j) {
+        fr[j] = fe_melinv((i + j) * melbw + melmin);
+        if (round_filters)
+            fr[j] = ((int)(fr[j] / fftfreq + 0.5)) * fftfreq;
+    }
+}
+
+int
+ssw_fe_tables_build(const ssw_fe_config_t *c, ssw_fe_tables_t *t)
+{
+    const float samprate = (float)c->samprate, wlen = (float)c->wlen;
+    const float lowerf = (float)c->lowerf, upperf = (float)c->upperf;
+    int i, j, n_coeffs = 0;
+
+    if (ssw_fe_config_check(c) < 0)
+        return -1;
+    memset(t, 0, sizeof(*t));
+    /* src/fe_interface.c:129-137, 264-265 */
+    t->frame_shift = (int)(samprate / c->frate + 0.5);
+    t->frame_size = (int)(wlen * samprate + 0.5);
+    t->fft_size = 1;
+    t->fft_order = 0;
+    while (t->fft_size < (int)(wlen * samprate)) {
+        ++t->fft_order;
+        t->fft_size <<= 1;
+    }
+    if (t->frame_shift != SSW_FE_SHIFT || t->frame_size != SSW_FE_FRAME || t->fft_size != SSW_FE_NFFT) {
+        ssw_set_error("front end: framing %d / %d / %d is not 160 / 410 / 512", t->frame_shift,
+                      t->frame_size, t->fft_size);
+        return -1;
+    }
+    t->nfilt = c->nfilt;
+    t->ncep = c->ncep;
+    t->transform = c->transform;
+    t->remove_noise = c->remove_noise;
+    t->lifter_val = c->lifter;
+    t->alpha = (float)c->alpha;
+    /* fe_create_hamming, src/fe_sigproc.c:241-252 */
+    for (i = 0; i < t->frame_size / 2; ++i)
+        t->hamming[i] = 0.54 - 0.46 * cos(2 * M_PI * i / ((double)t->frame_size - 1.0));
+    /* fe_create_twiddle, src/fe_sigproc.c:447-457 */
+    for (i = 0; i < t->fft_size / 4; ++i) {
+        double a = 2 * M_PI * i / t->fft_size;
+        t->ccc[i] = cos(a);
+        t->sss[i] = sin(a);
+    }
+    /* fe_build_melfilters, src/fe_sigproc.c:85-182 */
+    {
+        float melmin = fe_mel(lowerf), melmax = fe_mel(upperf);
+        float melbw = (melmax - melmin) / (t->nfilt + 1);
+        float fftfreq = samprate / (float)t->fft_size;
+        for (i = 0; i < t->nfilt; ++i) {
+            float fr[3];
+            filter_edges(i, melbw, melmin, fftfreq, c->round_filters, fr);
+            t->spec_start[i] = -1;
+            t->filt_width[i] = 0;
+            for (j = 0; j < t->fft_size / 2 + 1; ++j) {
+                float hz = j * fftfreq;
+                if (hz < fr[0])
+                    continue;
+                else if (hz > fr[2] || j == t->fft_size / 2) {
+                    t->filt_width[i] = j - t->spec_start[i];
+                    t->filt_start[i] = n_coeffs;
+                    n_coeffs += t->filt_width[i];
+                    break;
+                }
+                if (t->spec_start[i] == -1)
+                    t->spec_start[i] = j;
+            }
+            if (t->spec_start[i] < 0 || t->filt_width[i] < 1) {
+                ssw_set_error("front end: mel filter %d of %d (lowerf %g, upperf %g) covers no DFT "
+                              "point", i, t->nfilt, c->lowerf, c->upperf);
+                return -1;
+            }
+        }
+        if (n_coeffs > SSW_FE_MAX_COEFFS) {
+            ssw_set_error("front end: %d filter coefficients (at most %d)", n_coeffs,
+                          SSW_FE_MAX_COEFFS);
+            return -1;
+        }
+        n_coeffs = 0;
+        for (i = 0; i < t->nfilt; ++i) {
+            float fr[3];
+            filter_edges(i, melbw, melmin, fftfreq, c->round_filters, fr);
+            for (j = 0; j < t->filt_width[i]; ++j) {
+                float hz = (t->spec_start[i] + j) * fftfreq;
+                float loslope = (hz - fr[0]) / (fr[1] - fr[0]);
+                float hislope = (fr[2] - hz) / (fr[2] - fr[1]);
+                if (c->unit_area) {
+                    loslope *= 2 / (fr[2] - fr[0]);
+                    hislope *= 2 / (fr[2] - fr[0]);
+                }
+                t->filt_coeffs[n_coeffs++] = loslope < hislope ? loslope : hislope;
+            }
+        }
+        t->n_coeffs = n_coeffs;
+    }
+    /* fe_compute_melcosine, src/fe_sigproc.c:184-217 */
+    {
+        double freqstep = M_PI / t->nfilt;
+        for (i = 0; i < t->ncep; ++i)
+            for (j = 0; j < t->nfilt; ++j)
+                t->mel_cosine[i * t->nfilt + j] = (float)cos(freqstep * i * (j + 0.5));
+        t->sqrt_inv_n = (float)sqrt(1.0 / t->nfilt);
+        t->sqrt_inv_2n = (float)sqrt(2.0 / t->nfilt);
+    }
+    /* the lifter, src/fe_sigproc.c:228-232 (integer lifter_val / 2, as there) */
+    for (i = 0; i < t->ncep; ++i)
+        t->lifter[i] = t->lifter_val
+            ? (float)(1 + t->lifter_val / 2 * sin(i * M_PI / t->lifter_val)) : 1.0f;
+    return 0;
+}
+
+int64_t
+ssw_fe_frames_of(int64_t n)
+{
+    if (n < 0)
+        return -1;
+    if (n == 0)
+        return 0;
+    if (n < SSW_FE_FRAME)
+        return 1;
+    return 2 + (n - SSW_FE_FRAME) / SSW_FE_SHIFT;
 }
 
 /* ---------------------------------------------------------------------------------- */
@@ -1332,6 +1751,26 @@ ssw_host_model_load(const char *mdef, const char *means, const char *variances,
         }
     if (h->cfg.topn < 1 || h->cfg.topn > h->n_density)
         h->cfg.topn = h->n_density;
+    /* the front end's settings: feat_params.json in the model directory (the means file's), as
+     * acmod reads it; a file that cannot be used does not fail the load -- ssw_fe_batch
+     * without a configuration of its own refuses with fe_err */
+    ssw_fe_config_defaults(&h->fe);
+    {
+        const char *slash = strrchr(means, '/');
+        size_t dir = slash ? (size_t)(slash - means) + 1 : 0;
+        char *path = (char *)malloc(dir + sizeof("feat_params.json"));
+        if (path == NULL) {
+            ssw_set_error("out of memory");
+            goto bad;
+        }
+        memcpy(path, means, dir);
+        strcpy(path + dir, "feat_params.json");
+        if (ssw_fe_config_read(path, &h->fe, h->fe_err, sizeof(h->fe_err)) < 0) {
+            ssw_fe_config_defaults(&h->fe);
+            h->fe.from_file = 0;
+        }
+        free(path);
+    }
     return h;
 bad:
     ssw_host_model_free(h);
