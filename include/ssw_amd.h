@@ -717,9 +717,41 @@ int64_t ssw_fe_frame_count(const ssw_model_t *m, int64_t n_samples);
 int ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
                  const int64_t *samp_off, int32_t n_utts, float *d_cep, int32_t *frame_off_out,
                  void *stream);
-/* measurement aid: with ssw_set_kernel_timing on, the last ssw_fe_batch call's milliseconds per
- * kernel -- ms[0] spectrum (framing, FFT, mel), ms[1] noise removal (0 when off), ms[2] log,
- * DCT and lifter.  0, or -1 when no timed call has been made. */
+/* ssw_fe_batch at each utterance's own sample rate, as the reference computes cepstra at the
+ * rate the audio has (fe_init, src/fe_interface.c:55-160, 255-301): utterance u is at
+ * samprate[u] Hz (host double [n_utts]; NULL = cfg->samprate for all; cfg NULL = the model's
+ * feat_params.json).  One batch may mix rates.  Per rate, as fe_init derives them:
+ *   samprate     whole hertz (an integer setting, config_defs.h:320-323); 0 = the lowest of
+ *                8000, 11025, 16000, 22050, 32000, 44100, 48000 that is at least
+ *                (int)(2 upperf) (minimum_samprate, src/fe_interface.c:66-81)
+ *   frame shift  (int)(samprate / frate + 0.5), frame size (int)(wlen samprate + 0.5), in float
+ *   nfft         0 = per utterance, the smallest power of 2 >= (int)(wlen samprate); else that
+ *                power of 2 for every utterance, at least every utterance's window
+ * Refused, naming the reason, as fe_init refuses them: frate < 1, > samprate or > 32767; a
+ * frame shift <= 1; a frame size below the shift; an nfft that is not a power of 2 or is below
+ * the window; upperf > samprate / 2 + 1 (src/fe_interface.c:299-301).  This front end's own
+ * limit: FFTs of 64 .. 8192 points (8 kHz at 256 up to 192 kHz at 8192 with the default
+ * window).  Refused as by ssw_fe_batch: a mel filter narrower than one DFT point (the reference
+ * makes NaN cepstra of it), htk, dither, remove_dc, doublebw, smoothspec, logspec, warping,
+ * ncep != 13, alpha != 0.97, unit_area or round_filters off.  A bad entry anywhere in
+ * samprate[] refuses the whole call before any launch, with nothing written.  frame_off_out,
+ * d_cep and the rest as ssw_fe_batch; at 16000 Hz the cepstra are ssw_fe_batch's, byte for
+ * byte.  Tables that depend on the rate are built per distinct (samprate, nfft) and uploaded
+ * once per configuration and rate.  Synchronous on `stream`; 0, or -1 (ssw_last_error). */
+int ssw_fe_batch_ex(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
+                    const int64_t *samp_off, const double *samprate, int32_t n_utts,
+                    float *d_cep, int32_t *frame_off_out, void *stream);
+/* Frames ssw_fe_batch_ex makes of n_samples samples at samprate Hz (one entry of its
+ * samprate[]; cfg NULL = feat_params.json): 0 for 0 samples, 1 below one window, else the full
+ * frames 1 + (n - size) / shift and fe_end's frame of the samples left over (src/fe_interface.c:
+ * 560-712; 2 + (n - size) / shift whenever size > shift).  -1 on error, as ssw_fe_batch_ex
+ * refuses the settings. */
+int64_t ssw_fe_frame_count_ex(const ssw_model_t *m, const ssw_fe_config_t *cfg,
+                              double samprate, int64_t n_samples);
+/* measurement aid: with ssw_set_kernel_timing on, the last ssw_fe_batch(_ex) call's
+ * milliseconds per kernel -- ms[0] spectrum (framing, FFT, mel; every FFT size's launch),
+ * ms[1] noise removal (0 when off), ms[2] log, DCT and lifter.  0, or -1 when no timed call
+ * has been made. */
 int ssw_fe_kernel_timing(ssw_model_t *m, float ms[3]);
 
 /* ------------------------------------------------------------------------------------ */

@@ -220,6 +220,9 @@ def lib() -> C.CDLL:
     L.ssw_fe_frame_count.argtypes = [vp, C.c_int64]
     L.ssw_fe_frame_count.restype = C.c_int64
     L.ssw_fe_batch.argtypes = [vp, C.POINTER(SswFeConfig), vp, vp, i32, vp, vp, vp]
+    L.ssw_fe_frame_count_ex.argtypes = [vp, C.POINTER(SswFeConfig), C.c_double, C.c_int64]
+    L.ssw_fe_frame_count_ex.restype = C.c_int64
+    L.ssw_fe_batch_ex.argtypes = [vp, C.POINTER(SswFeConfig), vp, vp, vp, i32, vp, vp, vp]
     L.ssw_fe_kernel_timing.argtypes = [vp, vp]
     L.ssw_comm_unique_id.argtypes = [C.c_char_p]
     L.ssw_comm_init.restype = vp

@@ -46,6 +46,21 @@ def fe_frame_counts(n_samples) -> np.ndarray:
     return np.where(n <= 0, 0, np.where(n < FE_FRAME, 1, 2 + (n - FE_FRAME) // FE_SHIFT))
 
 
+def fe_frame_counts_at(n_samples, samprate, frate=100, wlen=0.025625) -> np.ndarray:
+    """Frames the front end makes of n_samples samples at samprate Hz (ssw_fe_frame_count_ex;
+    a scalar rate or one per utterance, in whole hertz): shift (int)(samprate / frate + 0.5) and
+    size (int)(wlen samprate + 0.5) in float32 as fe_init computes them; 0 for none, 1 below one
+    window, else the full frames and fe_end's frame of the samples left over."""
+    n = np.asarray(n_samples, np.int64)
+    sr = np.broadcast_to(np.asarray(samprate, np.float32), n.shape)
+    shift = (sr / np.float32(frate)).astype(np.float64) + 0.5
+    size = (sr * np.float32(wlen)).astype(np.float64) + 0.5
+    shift, size = shift.astype(np.int64), size.astype(np.int64)
+    full = 1 + (n - size) // np.maximum(shift, 1)
+    rest = n - full * shift
+    return np.where(n <= 0, 0, np.where(n < size, 1, full + (rest > 0)))
+
+
 class FirstPassConfig(C.Structure):
     """ssw_first_pass_config_t"""
     _fields_ = [("beam", C.c_double), ("pbeam", C.c_double), ("wbeam", C.c_double),
@@ -474,6 +489,74 @@ class Model:
                 self.device_free(d_pcm)
             if d_cep:
                 self.device_free(d_cep)
+        return cep, fo
+
+    def fe_frame_counts_rates(self, n_samples, samprate=None, cfg=None) -> np.ndarray:
+        """ssw_fe_frame_count_ex per utterance: samprate a number, one per utterance, or None
+        for the configuration's samprate.  Raises what ssw_fe_batch_ex would refuse."""
+        n = np.asarray(n_samples, np.int64).reshape(-1)
+        if samprate is None:
+            samprate = (cfg if isinstance(cfg, SswFeConfig) else self.fe_config(**(cfg or {}))).samprate
+        sr = np.broadcast_to(np.asarray(samprate, np.float64), n.shape)
+        c = self._fe_cfg(cfg)
+        out = np.array([self._L.ssw_fe_frame_count_ex(self._m, c, float(r), int(k))
+                        for k, r in zip(n, sr)], np.int64)
+        if (out < 0).any():
+            raise SswError("ssw_fe_frame_count_ex: " + _lib.last_error())
+        return out
+
+    def fe_batch_rates_device(self, d_pcm, samp_off, samprate, d_cep=None, cfg=None, stream=None):
+        """ssw_fe_batch_ex: fe_batch_device with utterance u at samprate[u] Hz (a number for all,
+        one per utterance, or None for the configuration's samprate)."""
+        off = np.ascontiguousarray(samp_off, np.int64)
+        n_utts = len(off) - 1
+        rates = (None if samprate is None else
+                 np.ascontiguousarray(np.broadcast_to(np.asarray(samprate, np.float64), (n_utts,))))
+        if d_cep is None:
+            n_frames = int(self.fe_frame_counts_rates(np.diff(off), rates, cfg).sum())
+            import torch
+            dev = d_pcm.device if hasattr(d_pcm, "device") else "cuda"
+            d_cep = torch.empty((n_frames, FE_NCEP), dtype=torch.float32, device=dev)
+        fo = np.zeros(len(off), np.int32)
+        _check(self._L.ssw_fe_batch_ex(self._m, self._fe_cfg(cfg), _ptr(d_pcm), _ptr(off),
+                                       _ptr(rates), n_utts, _ptr(d_cep), _ptr(fo), _ptr(stream)),
+               "ssw_fe_batch_ex")
+        return d_cep, fo
+
+    def fe_batch_rates(self, pcm, samprate, samp_off=None, cfg=None):
+        """The front end at each utterance's own rate, host in and host out (ssw_fe_batch_ex):
+        int16 PCM as fe_batch takes it, samprate a number or one per utterance (None: the
+        configuration's) -> (cep float32 [n_frames][13], frame_off)."""
+        if isinstance(pcm, (list, tuple)):
+            samp_off = np.concatenate([[0], np.cumsum([len(p) for p in pcm])])
+            pcm = np.concatenate([np.asarray(p, np.int16).reshape(-1) for p in pcm]) if pcm \
+                else np.zeros(0, np.int16)
+        pcm = np.ascontiguousarray(pcm, np.int16).reshape(-1)
+        off = (np.array([0, len(pcm)], np.int64) if samp_off is None
+               else np.ascontiguousarray(samp_off, np.int64))
+        if len(off) < 1 or off[-1] != len(pcm):
+            raise SswError("fe_batch_rates: samp_off must end at len(pcm)")
+        n_utts = len(off) - 1
+        rates = (None if samprate is None else
+                 np.ascontiguousarray(np.broadcast_to(np.asarray(samprate, np.float64), (n_utts,))))
+        # (ssw_fe_batch_ex without a device or frames checks everything, then writes frame_off)
+        fo = np.zeros(len(off), np.int32)
+        if self.device == SSW_DEVICE_NONE or off[-1] == 0:
+            _check(self._L.ssw_fe_batch_ex(self._m, self._fe_cfg(cfg), None, _ptr(off), _ptr(rates),
+                                           n_utts, None, _ptr(fo), None), "ssw_fe_batch_ex")
+        n_frames = int(fo[-1]) if fo[-1] or off[-1] == 0 else \
+            int(self.fe_frame_counts_rates(np.diff(off), rates, cfg).sum())
+        cep = np.zeros((n_frames, FE_NCEP), np.float32)
+        if n_frames == 0:
+            return cep, fo
+        d_pcm = self.to_device(pcm)
+        d_cep = self.device_malloc(cep.nbytes)
+        try:
+            _, fo = self.fe_batch_rates_device(d_pcm, off, rates, d_cep, cfg)
+            _check(self._L.ssw_memcpy_d2h(_ptr(cep), d_cep, cep.nbytes), "ssw_memcpy_d2h")
+        finally:
+            self.device_free(d_pcm)
+            self.device_free(d_cep)
         return cep, fo
 
     def fe_kernel_timing(self):
@@ -990,22 +1073,29 @@ def align_text_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, texts,
 
 
 def align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, texts, cfg=None, active=False,
-                      fe_cfg=None, scorer=SCORER_PTM, stream=None) -> AlignmentSet:
+                      fe_cfg=None, scorer=SCORER_PTM, stream=None, samprate=None) -> AlignmentSet:
     """Audio and text in, alignments out: what decoder_process_int16 over each utterance and
     decoder_alignment give (src/decoder.c:737-798), for a batch.  int16 PCM (host array or
     device tensor; utterance u = samples samp_off[u] .. samp_off[u + 1]) -> ssw_fe_batch ->
     ssw_feat_batch -> ssw_align_text_batch, or ssw_align_text_batch_active when active=True (the
     reference's default compallsen = no).  cfg: FirstPassConfig; fe_cfg: front-end settings
-    (None = the model's feat_params.json)."""
+    (None = the model's feat_params.json).  samprate None: 16 kHz audio through ssw_fe_batch;
+    a number, or one per utterance: the cepstra at that rate through ssw_fe_batch_ex, as the
+    reference computes them at the rate the audio has."""
     off = np.ascontiguousarray(samp_off, np.int64)
+    n_frames = int(fe_frame_counts(np.diff(off)).sum() if samprate is None else
+                   model.fe_frame_counts_rates(np.diff(off), samprate, fe_cfg).sum())
     on_device = hasattr(pcm, "data_ptr") and getattr(pcm, "is_cuda", False)
     d_pcm = pcm if on_device else (model.to_device(np.ascontiguousarray(pcm, np.int16))
                                    if off[-1] > 0 else None)
-    n_frames = int(fe_frame_counts(np.diff(off)).sum())
     d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
     d_feat = model.device_malloc(n_frames * 3 * FE_NCEP * 4) if n_frames else None
     try:
-        _, fo = model.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, fe_cfg, stream)
+        if samprate is None:
+            _, fo = model.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, fe_cfg, stream)
+        else:
+            _, fo = model.fe_batch_rates_device(d_pcm, off, samprate, d_cep if d_cep else 0,
+                                                fe_cfg, stream)
         if n_frames:
             _check(model._L.ssw_feat_batch(model._m, d_cep, n_frames, _ptr(fo), len(fo) - 1,
                                            FE_NCEP, d_feat, _ptr(stream)), "ssw_feat_batch")

@@ -1,4 +1,4 @@
-/* ssw_host_fe.inc -- host: ssw_fe_batch, ssw_fe_frame_count, ssw_model_fe_config.
+/* ssw_host_fe.inc -- host: ssw_fe_batch(_ex), ssw_fe_frame_count(_ex), ssw_model_fe_config.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 /* ---------------------------------------------------------------------------------- */
 /* MFCC front end (SURVEY 2 row 19, 8(f)): PCM -> cepstra for a batch                    */
@@ -24,8 +24,27 @@ ssw_fe_frame_count(const ssw_model_t *m, int64_t n_samples)
     return ssw_fe_frames_of(n_samples);
 }
 
+extern "C" int64_t
+ssw_fe_frame_count_ex(const ssw_model_t *m, const ssw_fe_config_t *cfg, double samprate,
+                      int64_t n_samples)
+{
+    if (m == NULL || n_samples < 0) {
+        ssw_set_error("bad arguments to ssw_fe_frame_count_ex");
+        return -1;
+    }
+    if (cfg == NULL && m->h->fe_err[0]) {
+        ssw_set_error("ssw_fe_frame_count_ex: the model's feat_params.json cannot be used: %s",
+                      m->h->fe_err);
+        return -1;
+    }
+    ssw_fe_framing_t f;
+    if (ssw_fe_framing(cfg != NULL ? cfg : &m->h->fe, samprate, &f) < 0)
+        return -1;
+    return ssw_fe_frames_at(&f, n_samples);
+}
+
 /* the tables for configuration c on the host when the device copy was built for another one
- * (NULL and *ok when it is current; building them is also the last check of c) */
+ * (NULL and *ok when it is current) */
 static std::unique_ptr<ssw_fe_tables_t>
 fe_tables_if_new(const ssw_model_s *m, const ssw_fe_config_t *c, ssw_fe_config_t *key, bool *ok)
 {
@@ -55,13 +74,68 @@ fe_tables_upload(ssw_model_s *m, const ssw_fe_tables_t *t, const ssw_fe_config_t
     return 0;
 }
 
-extern "C" int
-ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
-             const int64_t *samp_off, int32_t n_utts, float *d_cep, int32_t *frame_off_out,
-             void *stream)
+/* one distinct (samprate, nfft) of a batch: its framing, its table block on the host until it
+ * is uploaded (NULL when the model already holds it) and on the device */
+struct FeRate {
+    ssw_fe_framing_t fr;
+    std::string key;
+    std::unique_ptr<ssw_fe_rate_t, void (*)(void *)> host{nullptr, free};
+    ssw_fe_rate_t *dev = nullptr;
+};
+
+static std::string
+fe_rate_key(const ssw_fe_config_t *key, const ssw_fe_framing_t *fr)
+{
+    return std::string((const char *)key, sizeof(*key)) + std::string((const char *)fr, sizeof(*fr));
+}
+
+/* the rate blocks the model does not hold yet, on the device; a model that has gathered more
+ * than 64 first drops those this batch does not use (every front-end call is synchronous: no
+ * launch still reads them) */
+static int
+fe_rates_upload(ssw_model_s *m, std::vector<FeRate> &rates)
+{
+    size_t fresh = 0;
+    for (FeRate &r : rates)
+        fresh += r.host != nullptr;
+    if (fresh && m->fe_rate_tab->size() + fresh > 64) {
+        std::set<std::string> used;
+        for (FeRate &r : rates)
+            used.insert(r.key);
+        for (auto it = m->fe_rate_tab->begin(); it != m->fe_rate_tab->end();) {
+            if (used.count(it->first)) {
+                ++it;
+            } else {
+                (void)hipFree(it->second);
+                it = m->fe_rate_tab->erase(it);
+            }
+        }
+    }
+    for (FeRate &r : rates) {
+        if (r.host == nullptr)
+            continue;
+        ssw_fe_rate_t *d = NULL;
+        HIP_OK(hipMalloc((void **)&d, (size_t)r.host->bytes));
+        if (hipMemcpy(d, r.host.get(), (size_t)r.host->bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            ssw_set_error("front end: cannot upload a rate table");
+            return -1;
+        }
+        (*m->fe_rate_tab)[r.key] = d;
+        r.dev = d;
+    }
+    return 0;
+}
+
+/* ssw_fe_batch and ssw_fe_batch_ex: every utterance at samprate[u] (NULL: c->samprate; ex = 0:
+ * ssw_fe_batch's checks, which allow 16 kHz only) */
+static int
+fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm, const int64_t *samp_off,
+         const double *samprate, int32_t n_utts, float *d_cep, int32_t *frame_off_out,
+         void *stream, bool ex, const char *who)
 {
     if (m == NULL) {
-        ssw_set_error("bad arguments to ssw_fe_batch");
+        ssw_set_error("bad arguments to %s", who);
         return -1;
     }
     ModelBusy busy_(m);
@@ -69,35 +143,68 @@ ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
         return -1;
     hipStream_t st = (hipStream_t)stream;
     if (n_utts < 0 || samp_off == NULL || frame_off_out == NULL || samp_off[0] != 0) {
-        ssw_set_error("bad arguments to ssw_fe_batch");
+        ssw_set_error("bad arguments to %s", who);
         return -1;
     }
     if (cfg == NULL && m->h->fe_err[0]) {
-        ssw_set_error("ssw_fe_batch: the model's feat_params.json cannot be used: %s",
-                      m->h->fe_err);
+        ssw_set_error("%s: the model's feat_params.json cannot be used: %s", who, m->h->fe_err);
         return -1;
     }
     const ssw_fe_config_t *c = cfg != NULL ? cfg : &m->h->fe;
+    if ((ex ? ssw_fe_config_check_ex(c) : ssw_fe_config_check(c)) < 0)
+        return -1;
     ssw_fe_config_t key;
     bool ok;
     std::unique_ptr<ssw_fe_tables_t> fresh = fe_tables_if_new(m, c, &key, &ok);
     if (!ok)
         return -1;
+    /* every utterance's framing, and the distinct (samprate, nfft) of the batch, before anything
+     * is written */
+    if (m->fe_rate_tab == nullptr)
+        m->fe_rate_tab = new std::map<std::string, ssw_fe_rate_t *>();
+    std::vector<FeRate> rates;
+    std::vector<int> rate_of((size_t)n_utts);
+    std::vector<int32_t> foff((size_t)n_utts + 1);
     int64_t total = 0;
-    frame_off_out[0] = 0;
     for (int32_t u = 0; u < n_utts; ++u) {
         const int64_t n = samp_off[u + 1] - samp_off[u];
         if (n < 0) {
-            ssw_set_error("ssw_fe_batch: samp_off decreases at utterance %d", u);
+            ssw_set_error("%s: samp_off decreases at utterance %d", who, u);
             return -1;
         }
-        total += ssw_fe_frames_of(n);
+        ssw_fe_framing_t fr;
+        if (ssw_fe_framing(c, samprate != NULL ? samprate[u] : c->samprate, &fr) < 0) {
+            if (samprate != NULL) {
+                std::string why = ssw_last_error();
+                ssw_set_error("%s: utterance %d: %s", who, u, why.c_str());
+            }
+            return -1;
+        }
+        size_t r = 0;
+        while (r < rates.size() && memcmp(&rates[r].fr, &fr, sizeof(fr)) != 0)
+            ++r;
+        if (r == rates.size()) {
+            rates.emplace_back();
+            rates[r].fr = fr;
+            rates[r].key = fe_rate_key(&key, &fr);
+            auto hit = m->fe_rate_tab->find(rates[r].key);
+            if (hit != m->fe_rate_tab->end()) {
+                rates[r].dev = hit->second;
+            } else {
+                rates[r].host.reset(ssw_fe_rate_build(c, &fr, ex));
+                if (rates[r].host == nullptr)
+                    return -1;
+            }
+        }
+        rate_of[u] = (int)r;
+        total += ssw_fe_frames_at(&fr, n);
         if (total > INT32_MAX) {
-            ssw_set_error("ssw_fe_batch: more than 2^31 - 1 frames in one batch");
+            ssw_set_error("%s: more than 2^31 - 1 frames in one batch", who);
             return -1;
         }
-        frame_off_out[u + 1] = (int32_t)total;
+        foff[u + 1] = (int32_t)total;
     }
+    memcpy(frame_off_out, foff.data(), sizeof(int32_t) * ((size_t)n_utts + 1));
     if (total == 0)
         return 0;
     if (m->device == SSW_DEVICE_NONE) {
@@ -105,15 +212,52 @@ ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
         return -1;
     }
     if (d_pcm == NULL || d_cep == NULL) {
-        ssw_set_error("bad arguments to ssw_fe_batch");
+        ssw_set_error("bad arguments to %s", who);
         return -1;
     }
     HIP_OK(hipSetDevice(m->device));
     if (fresh && fe_tables_upload(m, fresh.get(), &key) < 0)
         return -1;
+    if (fe_rates_upload(m, rates) < 0)
+        return -1;
+    /* the utterance records, the frame offsets, and per FFT size present the group's
+     * utterances and frame prefix (one spectrum launch each) */
+    std::vector<FeUtt> utt((size_t)n_utts);
+    int grp_frames[SSW_FE_MAX_LOG2N + 1] = {0}, grp_n[SSW_FE_MAX_LOG2N + 1] = {0};
+    for (int32_t u = 0; u < n_utts; ++u) {
+        const FeRate &r = rates[(size_t)rate_of[u]];
+        utt[u].start = samp_off[u];
+        utt[u].n = samp_off[u + 1] - samp_off[u];
+        utt[u].rate = r.dev;
+        utt[u].f0 = foff[u];
+        utt[u].shift = r.fr.frame_shift;
+        utt[u].size = r.fr.frame_size;
+        utt[u].pad = 0;
+        ++grp_n[r.fr.fft_order];
+    }
+    std::vector<int> grp_utt((size_t)n_utts), grp_off((size_t)n_utts + SSW_FE_MAX_LOG2N + 1);
+    int grp_at[SSW_FE_MAX_LOG2N + 1], off_at[SSW_FE_MAX_LOG2N + 1];
+    for (int o = 0, a = 0, b = 0; o <= SSW_FE_MAX_LOG2N; ++o) {
+        grp_at[o] = a;
+        off_at[o] = b;
+        a += grp_n[o];
+        b += grp_n[o] ? grp_n[o] + 1 : 0;
+    }
+    {
+        int fill[SSW_FE_MAX_LOG2N + 1] = {0};
+        for (int32_t u = 0; u < n_utts; ++u) {
+            const int o = rates[(size_t)rate_of[u]].fr.fft_order, k = fill[o]++;
+            grp_utt[(size_t)grp_at[o] + k] = u;
+            grp_off[(size_t)off_at[o] + k + 1] = grp_off[(size_t)off_at[o] + k] + (foff[u + 1] - foff[u]);
+        }
+        for (int o = 0; o <= SSW_FE_MAX_LOG2N; ++o)
+            grp_frames[o] = grp_n[o] ? grp_off[(size_t)off_at[o] + grp_n[o]] : 0;
+    }
     const int n_frames = (int)total, nfilt = m->fe_nfilt;
-    /* grow-only workspace: offsets, then the mel spectra */
-    const size_t off_bytes = (((size_t)n_utts + 1) * (sizeof(long long) + sizeof(int)) + 255) & ~(size_t)255;
+    /* grow-only workspace: records, offsets, groups, then the mel spectra */
+    const size_t utt_bytes = sizeof(FeUtt) * (size_t)n_utts;
+    const size_t int_bytes = sizeof(int) * (grp_utt.size() + grp_off.size() + (size_t)n_utts + 1);
+    const size_t off_bytes = (utt_bytes + int_bytes + 255) & ~(size_t)255;
     const size_t ws = off_bytes + (size_t)n_frames * nfilt * sizeof(double);
     if (ws > m->fe_ws_cap) {
         (void)hipFree(m->d_fe_ws);
@@ -122,15 +266,28 @@ ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
         HIP_OK(hipMalloc((void **)&m->d_fe_ws, ws));
         m->fe_ws_cap = ws;
     }
-    long long *d_soff = (long long *)m->d_fe_ws;
-    int *d_foff = (int *)(d_soff + n_utts + 1);
+    std::vector<unsigned char> stage(utt_bytes + int_bytes);
+    {
+        unsigned char *p = stage.data();
+        memcpy(p, utt.data(), utt_bytes);
+        p += utt_bytes;
+        memcpy(p, foff.data(), sizeof(int) * foff.size());
+        p += sizeof(int) * foff.size();
+        memcpy(p, grp_utt.data(), sizeof(int) * grp_utt.size());
+        p += sizeof(int) * grp_utt.size();
+        memcpy(p, grp_off.data(), sizeof(int) * grp_off.size());
+    }
     FeParams F;
     F.pcm = d_pcm;
-    F.samp_off = d_soff;
-    F.frame_off = d_foff;
+    F.utt = (const FeUtt *)m->d_fe_ws;
+    F.frame_off = (const int *)(m->d_fe_ws + utt_bytes);
+    const int *d_grp_utt = F.frame_off + n_utts + 1;
+    const int *d_grp_off = d_grp_utt + n_utts;
     F.tab = m->d_fe_tab;
     F.mfspec = (double *)(m->d_fe_ws + off_bytes);
     F.cep = d_cep;
+    F.grp_utt = F.grp_off = nullptr; /* (set per spectrum launch) */
+    F.n_grp = F.n_grp_frames = 0;
     F.n_utts = n_utts;
     F.n_frames = n_frames;
     if (m->timing && !m->fe_ev_ready) {
@@ -139,16 +296,34 @@ ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
         m->fe_ev_ready = 1;
     }
     const bool timed = m->timing && m->fe_ev_ready;
-    hipError_t e = hipMemcpyAsync(d_soff, samp_off, sizeof(long long) * ((size_t)n_utts + 1),
-                                  hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_foff, frame_off_out, sizeof(int) * ((size_t)n_utts + 1),
-                           hipMemcpyHostToDevice, st);
+    hipError_t e = hipMemcpyAsync(m->d_fe_ws, stage.data(), stage.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && timed)
         e = hipEventRecord(m->fe_ev[0], st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(fe_spectrum_kernel, dim3((n_frames + FE_SPEC_WAVES - 1) / FE_SPEC_WAVES),
-                           dim3(64 * FE_SPEC_WAVES), 0, st, F);
+    for (int o = SSW_FE_MIN_LOG2N; o <= SSW_FE_MAX_LOG2N && e == hipSuccess; ++o) {
+        if (grp_frames[o] == 0)
+            continue;
+        FeParams G = F;
+        G.grp_utt = d_grp_utt + grp_at[o];
+        G.grp_off = d_grp_off + off_at[o];
+        G.n_grp = grp_n[o];
+        G.n_grp_frames = grp_frames[o];
+        switch (o) {
+#define FE_SPEC_LAUNCH(L)                                                                       \
+        case L:                                                                                 \
+            hipLaunchKernelGGL(fe_spectrum_kernel<L>,                                           \
+                               dim3((G.n_grp_frames + fe_spec_waves(L) - 1) / fe_spec_waves(L)), \
+                               dim3(64 * fe_spec_waves(L)), 0, st, G);                          \
+            break;
+        FE_SPEC_LAUNCH(6)
+        FE_SPEC_LAUNCH(7)
+        FE_SPEC_LAUNCH(8)
+        FE_SPEC_LAUNCH(9)
+        FE_SPEC_LAUNCH(10)
+        FE_SPEC_LAUNCH(11)
+        FE_SPEC_LAUNCH(12)
+        FE_SPEC_LAUNCH(13)
+#undef FE_SPEC_LAUNCH
+        }
         e = hipGetLastError();
     }
     if (e == hipSuccess && timed)
@@ -169,7 +344,7 @@ ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
-        ssw_set_error("ssw_fe_batch: %s", hipGetErrorString(e));
+        ssw_set_error("%s: %s", who, hipGetErrorString(e));
         return -1;
     }
     m->fe_timed = timed;
@@ -177,10 +352,28 @@ ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
 }
 
 extern "C" int
+ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
+             const int64_t *samp_off, int32_t n_utts, float *d_cep, int32_t *frame_off_out,
+             void *stream)
+{
+    return fe_batch(m, cfg, d_pcm, samp_off, NULL, n_utts, d_cep, frame_off_out, stream, false,
+                    "ssw_fe_batch");
+}
+
+extern "C" int
+ssw_fe_batch_ex(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
+                const int64_t *samp_off, const double *samprate, int32_t n_utts, float *d_cep,
+                int32_t *frame_off_out, void *stream)
+{
+    return fe_batch(m, cfg, d_pcm, samp_off, samprate, n_utts, d_cep, frame_off_out, stream, true,
+                    "ssw_fe_batch_ex");
+}
+
+extern "C" int
 ssw_fe_kernel_timing(ssw_model_t *m, float ms[3])
 {
     if (m == NULL || ms == NULL || !m->fe_timed) {
-        ssw_set_error("no timed ssw_fe_batch call (ssw_set_kernel_timing first)");
+        ssw_set_error("no timed ssw_fe_batch or ssw_fe_batch_ex call (ssw_set_kernel_timing first)");
         return -1;
     }
     for (int k = 0; k < 3; ++k)

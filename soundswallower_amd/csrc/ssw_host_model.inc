@@ -217,9 +217,11 @@ struct ssw_model_s {
     int *d_feat_off;
     size_t feat_off_cap;
     /* the front end (ssw_host_fe.inc): its tables on the device and the configuration they were
-     * built for; a grow-only workspace (offsets, mel spectra); per-kernel events */
+     * built for; the blocks that depend on the rate, by configuration and framing; a grow-only
+     * workspace (offsets, mel spectra); per-kernel events */
     ssw_fe_tables_t *d_fe_tab;
     ssw_fe_config_t fe_tab_cfg;
+    std::map<std::string, ssw_fe_rate_t *> *fe_rate_tab; /* (a pointer: the struct is memset) */
     int fe_nfilt, fe_noise;
     unsigned char *d_fe_ws;
     size_t fe_ws_cap;
@@ -654,6 +656,10 @@ ssw_model_free(ssw_model_t *m)
     (void)hipFree(m->d_text_scr);
     (void)hipFree(m->d_feat_off);
     (void)hipFree(m->d_fe_tab);
+    if (m->fe_rate_tab)
+        for (auto &kv : *m->fe_rate_tab)
+            (void)hipFree(kv.second);
+    delete m->fe_rate_tab;
     (void)hipFree(m->d_fe_ws);
     if (m->fe_ev_ready)
         for (int i = 0; i < 4; ++i)

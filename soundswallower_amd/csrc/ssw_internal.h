@@ -26,35 +26,59 @@ extern "C" {
 /* matrix-core scan: binary16 values per (codebook, stream) in wfrag */
 #define SSW_WFRAG_PER_CBF (4 * 2 * 2 * 64 * 8)
 
-/* MFCC front end (ssw_model.c, ssw_k8_fe.inc, ssw_host_fe.inc): the one framing supported,
- * 16 kHz, 100 frames/s, 25.625 ms window, 512-point FFT */
+/* MFCC front end (ssw_model.c, ssw_k8_fe.inc, ssw_host_fe.inc): ssw_fe_batch's one framing,
+ * 16 kHz, 100 frames/s, 25.625 ms window, 512-point FFT; ssw_fe_batch_ex frames at any rate
+ * with FFTs of SSW_FE_MIN_NFFT .. SSW_FE_MAX_NFFT points */
 #define SSW_FE_FRAME 410
 #define SSW_FE_SHIFT 160
 #define SSW_FE_NFFT 512
+#define SSW_FE_MIN_LOG2N 6
+#define SSW_FE_MAX_LOG2N 13
+#define SSW_FE_MIN_NFFT (1 << SSW_FE_MIN_LOG2N)
+#define SSW_FE_MAX_NFFT (1 << SSW_FE_MAX_LOG2N)
 #define SSW_FE_MAX_FILT 64
 #define SSW_FE_NCEP 13
-#define SSW_FE_MAX_COEFFS 4096
 
-/* the front end's tables as fe_init builds them (ssw_fe_tables_build) */
+/* the part of the front end's tables that does not depend on the rate (ssw_fe_tables_build) */
 typedef struct ssw_fe_tables_s {
-    int32_t frame_size, frame_shift, fft_size, fft_order, nfilt, ncep, n_coeffs;
-    int32_t transform, remove_noise, lifter_val;
+    int32_t nfilt, ncep, transform, remove_noise, lifter_val;
     float alpha, sqrt_inv_n, sqrt_inv_2n;
-    double hamming[SSW_FE_FRAME / 2];
-    double ccc[SSW_FE_NFFT / 4], sss[SSW_FE_NFFT / 4];
-    int32_t spec_start[SSW_FE_MAX_FILT], filt_width[SSW_FE_MAX_FILT], filt_start[SSW_FE_MAX_FILT];
-    float filt_coeffs[SSW_FE_MAX_COEFFS];
     float mel_cosine[SSW_FE_NCEP * SSW_FE_MAX_FILT]; /* [ncep][nfilt] */
     float lifter[SSW_FE_NCEP];
 } ssw_fe_tables_t;
+
+/* one rate's framing, as fe_parse_general_params and fe_init derive it (ssw_fe_framing) */
+typedef struct ssw_fe_framing_s {
+    int32_t samprate, frame_shift, frame_size, fft_size, fft_order;
+} ssw_fe_framing_t;
+
+/* the part that depends on the rate, one variable-size block per (samprate, nfft)
+ * (ssw_fe_rate_build): this header, then double hamming[frame_size / 2], double
+ * ccc[fft_size / 4], double sss[fft_size / 4] and float filt_coeffs[n_coeffs] at the byte
+ * offsets it records; `bytes` is the whole block */
+typedef struct ssw_fe_rate_s {
+    int32_t samprate, frame_shift, frame_size, fft_size, fft_order, nfilt, n_coeffs, bytes;
+    int32_t hamming_off, ccc_off, sss_off, coeff_off;
+    int32_t spec_start[SSW_FE_MAX_FILT], filt_width[SSW_FE_MAX_FILT], filt_start[SSW_FE_MAX_FILT];
+} ssw_fe_rate_t;
 
 /* feat_params.json over *c (which holds the defaults): 0 read, 1 no such file, -1 unusable
  * (message in err) */
 int ssw_fe_config_read(const char *path, ssw_fe_config_t *c, char *err, size_t err_len);
 /* 0 when ssw_fe_batch supports the configuration, else -1 and ssw_set_error */
 int ssw_fe_config_check(const ssw_fe_config_t *c);
+/* the same for ssw_fe_batch_ex: every setting but the rate and the framing, which
+ * ssw_fe_framing checks per rate */
+int ssw_fe_config_check_ex(const ssw_fe_config_t *c);
+/* samprate (whole hertz; 0 = minimum_samprate of c->upperf) -> *f, or -1 and ssw_set_error */
+int ssw_fe_framing(const ssw_fe_config_t *c, double samprate, ssw_fe_framing_t *f);
 int ssw_fe_tables_build(const ssw_fe_config_t *c, ssw_fe_tables_t *t);
+/* malloc'd block for c at framing f, or NULL and ssw_set_error (a filter that covers no DFT
+ * point; with `finite`, one whose edges round onto one point, which makes NaN coefficients;
+ * out of memory) */
+ssw_fe_rate_t *ssw_fe_rate_build(const ssw_fe_config_t *c, const ssw_fe_framing_t *f, int finite);
 int64_t ssw_fe_frames_of(int64_t n_samples);
+int64_t ssw_fe_frames_at(const ssw_fe_framing_t *f, int64_t n_samples);
 
 /* Host-side model: every table derived exactly as the reference derives it. */
 typedef struct ssw_host_model_s {

@@ -10,46 +10,64 @@
  * one double ulp away from glibc's; the float rounding of the DCT absorbs that, DESIGN K8) and
  * the conversions.  The tables come from the host (csrc/ssw_model.c), built as fe_init builds them.
  *
- * Framing (src/fe_interface.c:560-690): frame f of an utterance of n samples covers samples
- * 160 f .. 160 f + min(410, n - 160 f) - 1, zero-padded to 512; the last frame is fe_end's
- * overflow frame.  The pre-emphasis's prior sample is 0 for frame 0 and sample 160 f - 1 after
- * it (fe_spch_to_frame keeps spch[frame_shift - 1]; the overflow frame starts where the next
- * full frame would), so frames are independent up to the noise tracker.
+ * Framing (src/fe_interface.c:560-712) at any rate: frame f of an utterance of n samples covers
+ * samples shift f .. shift f + min(size, n - shift f) - 1, zero-padded to the FFT size N; the
+ * last frame is fe_end's overflow frame.  The pre-emphasis's prior sample is 0 for frame 0 and
+ * sample shift f - 1 after it (fe_spch_to_frame keeps spch[frame_shift - 1]; the overflow frame
+ * starts where the next full frame would), so frames are independent up to the noise tracker.
+ * Each utterance's shift, size and table block (ssw_fe_rate_t: window, twiddles, filters) come
+ * from its FeUtt record; ssw_fe_batch's are 160, 410 and the 16 kHz block.
  *
- *   fe_spectrum_kernel  one wave per frame: samples -> pre-emphasis -> Hamming, stored straight
- *                       to bit-reversed LDS positions (fe_fft_real's first loop is exactly that
- *                       permutation), the pair stage and stages k = 1..8 with fe_fft_real's
- *                       butterflies (those of a stage touch disjoint points: 128 per stage, two
- *                       per lane), power spectrum, mel sums in the reference's j order
+ *   fe_spectrum_kernel<LOG2N>  one wave per frame, N = 2^LOG2N = 64 .. 8192, one launch per N
+ *                       present in the batch over that group's frames: samples -> pre-emphasis
+ *                       -> Hamming, stored straight to bit-reversed LDS positions (fe_fft_real's
+ *                       first loop is exactly that permutation), the pair stage and stages
+ *                       k = 1..LOG2N-1 with fe_fft_real's butterflies (those of a stage touch
+ *                       disjoint points: N/4 per stage, lanes past N/4 idle at N = 64 and 128),
+ *                       the power spectrum in place, mel sums in the reference's j order
  *                       -> double mfspec [frame][nfilt]
  *   fe_noise_kernel     remove_noise: one wave per utterance, lane = filter, frames in order
  *                       (the tracker is a recurrence); the +-4 gain smoothing by lane shuffles
  *   fe_cep_kernel       log(mfspec + 1e-4), then DCT-II (transform = dct) or fe_spec2cep
  *                       (legacy), then the lifter -> float cep [frame][13] */
+struct FeUtt {
+    long long start, n;         /* first sample in pcm, samples */
+    const ssw_fe_rate_t *rate;  /* the table block of the utterance's (samprate, nfft) */
+    int f0, shift, size, pad;   /* first frame in the batch, frame shift and size in samples */
+};
+
 struct FeParams {
     const int16_t *pcm;
-    const long long *samp_off; /* [n_utts + 1] */
+    const FeUtt *utt;          /* [n_utts] */
     const int *frame_off;      /* [n_utts + 1] */
+    const int *grp_utt;        /* fe_spectrum_kernel: the utterances of the launch's FFT size */
+    const int *grp_off;        /* [n_grp + 1]: their frames' prefix within the launch */
     const ssw_fe_tables_t *tab;
     double *mfspec;            /* [n_frames][nfilt] */
     float *cep;                /* [n_frames][13] */
-    int n_utts, n_frames;
+    int n_utts, n_frames, n_grp, n_grp_frames;
 };
 
-constexpr int FE_SPEC_WAVES = 4;  /* frames per workgroup of the spectrum kernel */
+/* frames per workgroup of the spectrum kernel: N doubles of LDS per wave, so 16 KB at N = 512
+ * (4 waves), 32 KB at 2048 (2 waves), 64 KB at 8192 (1 wave; 160 KiB per CU) */
+__host__ __device__ constexpr int
+fe_spec_waves(int log2n)
+{
+    return log2n <= 10 ? 4 : log2n == 11 ? 2 : 1;
+}
 constexpr int FE_CEP_FRAMES = 16; /* frames per workgroup of the cepstrum kernel */
 constexpr int FE_CEP_THREADS = 256;
 static_assert(FE_CEP_FRAMES * SSW_FE_NCEP <= FE_CEP_THREADS, "one thread per cepstrum");
 
-/* the utterance that holds frame f: the last u with frame_off[u] <= f (empty utterances have
- * frame_off[u] == frame_off[u + 1] and are passed over) */
+/* the entry that holds frame f: the last u with off[u] <= f (empty entries have
+ * off[u] == off[u + 1] and are passed over) */
 __device__ __forceinline__ int
-fe_utt_of(const int *frame_off, int n_utts, int f)
+fe_utt_of(const int *off, int n, int f)
 {
-    int lo = 0, hi = n_utts - 1;
+    int lo = 0, hi = n - 1;
     while (lo < hi) {
         const int mid = (lo + hi + 1) >> 1;
-        if (frame_off[mid] <= f)
+        if (off[mid] <= f)
             lo = mid;
         else
             hi = mid - 1;
@@ -57,59 +75,82 @@ fe_utt_of(const int *frame_off, int n_utts, int f)
     return lo;
 }
 
-__global__ void __launch_bounds__(64 * FE_SPEC_WAVES)
+template <typename T>
+__device__ __forceinline__ const T *
+fe_rate_part(const ssw_fe_rate_t *R, int off)
+{
+    return (const T *)((const char *)R + off);
+}
+
+template <int LOG2N>
+__global__ void __launch_bounds__(64 * fe_spec_waves(LOG2N))
 fe_spectrum_kernel(FeParams P)
 {
-    __shared__ double s_x[FE_SPEC_WAVES][SSW_FE_NFFT];
-    __shared__ double s_spec[FE_SPEC_WAVES][SSW_FE_NFFT / 2 + 1];
-    const ssw_fe_tables_t *T = P.tab;
+    constexpr int N = 1 << LOG2N, W = fe_spec_waves(LOG2N);
+    constexpr int PAIRS = N / 2, GROUPS = N / 4; /* pair-stage and per-stage butterflies */
+    static_assert(N >= 64, "one sample per lane at least");
+    __shared__ double s_x[W][N];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int f = blockIdx.x * FE_SPEC_WAVES + w;
-    const bool live = f < P.n_frames; /* wave-uniform; every wave reaches every barrier */
+    const int g = blockIdx.x * W + w;      /* frame within the launch's group */
+    const bool live = g < P.n_grp_frames;  /* wave-uniform; every wave reaches every barrier */
     double *x = s_x[w];
+    const ssw_fe_rate_t *R = nullptr;
+    int f = 0;
     if (live) {
-        /* fe_spch_to_frame (src/fe_sigproc.c:276-303) into fe_fft_real's bit-reversed order */
-        const int u = fe_utt_of(P.frame_off, P.n_utts, f);
-        const int fl = f - P.frame_off[u];
-        const long long s0 = P.samp_off[u], n = P.samp_off[u + 1] - s0;
-        const long long start = s0 + (long long)SSW_FE_SHIFT * fl;
-        const long long left = n - (long long)SSW_FE_SHIFT * fl;
-        const int len = left < SSW_FE_FRAME ? (int)left : SSW_FE_FRAME;
-        const double alpha = (double)T->alpha;
+        /* fe_spch_to_frame (src/fe_sigproc.c:276-317) into fe_fft_real's bit-reversed order */
+        const int k = fe_utt_of(P.grp_off, P.n_grp, g);
+        const FeUtt U = P.utt[P.grp_utt[k]];
+        const int fl = g - P.grp_off[k];
+        f = U.f0 + fl;
+        R = U.rate;
+        const long long start = U.start + (long long)U.shift * fl;
+        const long long left = U.n - (long long)U.shift * fl;
+        const int size = U.size, half = size / 2;
+        const int len = left < size ? (int)left : size;
+        const double *ham = fe_rate_part<double>(R, R->hamming_off);
+        const double alpha = (double)P.tab->alpha;
         const double prior = fl == 0 ? 0.0 : (double)P.pcm[start - 1];
-#pragma unroll
-        for (int k = 0; k < SSW_FE_NFFT / 64; ++k) {
-            const int i = lane + 64 * k;
+#pragma unroll 8
+        for (int t = 0; t < N / 64; ++t) {
+            const int i = lane + 64 * t;
             double v = 0.0;
             if (i < len) {
                 const double prev = i == 0 ? prior : (double)P.pcm[start + i - 1];
                 v = (double)P.pcm[start + i] - prev * alpha;
             }
-            if (i < SSW_FE_FRAME / 2)
-                v = v * T->hamming[i];
-            else if (i < SSW_FE_FRAME)
-                v = v * T->hamming[SSW_FE_FRAME - 1 - i];
-            x[__brev((unsigned)i) >> (32 - 9)] = v;
+            /* fe_hamming_window: the first and last size / 2 samples (an odd size's middle
+             * sample is not windowed) */
+            if (i < half)
+                v = v * ham[i];
+            else if (i >= size - half && i < size)
+                v = v * ham[size - 1 - i];
+            x[__brev((unsigned)i) >> (32 - LOG2N)] = v;
         }
     }
     __syncthreads();
     if (live) { /* fe_fft_real's first stage: pairs */
-#pragma unroll
-        for (int k = 0; k < SSW_FE_NFFT / 2 / 64; ++k) {
-            const int i = 2 * (lane + 64 * k);
-            const double a = x[i], b = x[i + 1];
-            x[i] = a + b;
-            x[i + 1] = a - b;
+#pragma unroll 8
+        for (int t = 0; t < (PAIRS + 63) / 64; ++t) {
+            const int i = 2 * (lane + 64 * t);
+            if (PAIRS >= 64 || i < N) {
+                const double a = x[i], b = x[i + 1];
+                x[i] = a + b;
+                x[i + 1] = a - b;
+            }
         }
     }
     __syncthreads();
-    for (int k = 1; k < 9; ++k) { /* stages 1..8: 128 butterfly groups each */
+    const double *ccc = live ? fe_rate_part<double>(R, R->ccc_off) : nullptr;
+    const double *sss = live ? fe_rate_part<double>(R, R->sss_off) : nullptr;
+    for (int k = 1; k < LOG2N; ++k) { /* stages 1..LOG2N-1: N/4 butterfly groups each */
         if (live) {
             const int n2 = 1 << k, n4 = 1 << (k - 1);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int g = lane + 64 * t;
-                const int j = g & (n4 - 1), i = (g >> (k - 1)) << (k + 1);
+#pragma unroll 8
+            for (int t = 0; t < (GROUPS + 63) / 64; ++t) {
+                const int gi = lane + 64 * t;
+                if (GROUPS < 64 && gi >= GROUPS)
+                    continue;
+                const int j = gi & (n4 - 1), i = (gi >> (k - 1)) << (k + 1);
                 if (j == 0) {
                     const double a = x[i], b = x[i + n2];
                     x[i] = a + b;
@@ -117,7 +158,7 @@ fe_spectrum_kernel(FeParams P)
                     x[i + n2 + n4] = -x[i + n2 + n4];
                 } else {
                     const int i1 = i + j, i2 = i + n2 - j, i3 = i + n2 + j, i4 = i + n2 + n2 - j;
-                    const double cc = T->ccc[j << (8 - k)], ss = T->sss[j << (8 - k)];
+                    const double cc = ccc[j << (LOG2N - 1 - k)], ss = sss[j << (LOG2N - 1 - k)];
                     const double x1 = x[i1], x2 = x[i2], x3 = x[i3], x4 = x[i4];
                     const double t1 = x3 * cc + x4 * ss;
                     const double t2 = x3 * ss - x4 * cc;
@@ -130,24 +171,27 @@ fe_spectrum_kernel(FeParams P)
         }
         __syncthreads();
     }
-    double *spec = s_spec[w];
-    if (live) { /* fe_spec_magnitude, src/fe_sigproc.c:560-585 */
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int j = lane + 64 * k;
+    if (live) { /* fe_spec_magnitude, src/fe_sigproc.c:560-585, in place: spec[j] -> x[j].
+                 * x[j] (j < N/2) is read only by the lane that computes spec[j], and x[N/2] only
+                 * by spec[N/2]'s; both read before they write, so no lane reads a point that
+                 * another has overwritten */
+#pragma unroll 8
+        for (int t = 0; t < (N / 2 + 1 + 63) / 64; ++t) {
+            const int j = lane + 64 * t;
             if (j == 0)
-                spec[0] = x[0] * x[0];
-            else if (j <= SSW_FE_NFFT / 2)
-                spec[j] = x[j] * x[j] + x[SSW_FE_NFFT - j] * x[SSW_FE_NFFT - j];
+                x[0] = x[0] * x[0];
+            else if (j <= N / 2)
+                x[j] = x[j] * x[j] + x[N - j] * x[N - j];
         }
     }
     __syncthreads();
-    if (live && lane < T->nfilt) { /* fe_mel_spec, src/fe_sigproc.c:587-607 */
-        const int s0 = T->spec_start[lane], c0 = T->filt_start[lane], wd = T->filt_width[lane];
+    if (live && lane < P.tab->nfilt) { /* fe_mel_spec, src/fe_sigproc.c:587-607 */
+        const float *coef = fe_rate_part<float>(R, R->coeff_off);
+        const int s0 = R->spec_start[lane], c0 = R->filt_start[lane], wd = R->filt_width[lane];
         double acc = 0.0;
         for (int j = 0; j < wd; ++j)
-            acc = acc + spec[s0 + j] * (double)T->filt_coeffs[c0 + j];
-        P.mfspec[(size_t)f * T->nfilt + lane] = acc;
+            acc = acc + x[s0 + j] * (double)coef[c0 + j];
+        P.mfspec[(size_t)f * P.tab->nfilt + lane] = acc;
     }
 }
 

@@ -286,8 +286,10 @@ done:
 /* double types operand by operand, libm for cos, sin, log10, pow and sqrt.  The kernels */
 /* (ssw_k8_fe.inc) only read them.                                                       */
 /* ---------------------------------------------------------------------------------- */
-int
-ssw_fe_config_check(const ssw_fe_config_t *c)
+/* the checks of ssw_fe_batch (ex = 0: only its 16 kHz framing) and of ssw_fe_batch_ex (ex = 1:
+ * the framing is ssw_fe_framing's, per rate) */
+static int
+fe_config_check(const ssw_fe_config_t *c, int ex)
 {
     if (c->transform == SSW_FE_HTK) {
         ssw_set_error("front end: transform = htk is not supported (legacy or dct)");
@@ -304,8 +306,8 @@ ssw_fe_config_check(const ssw_fe_config_t *c)
                       : "frequency warping (warp_params)");
         return -1;
     }
-    if (c->samprate != 16000 || c->frate != 100 || (float)c->wlen != (float)0.025625
-        || (c->nfft != 0 && c->nfft != 512)) {
+    if (!ex && (c->samprate != 16000 || c->frate != 100 || (float)c->wlen != (float)0.025625
+                || (c->nfft != 0 && c->nfft != 512))) {
         ssw_set_error("front end: only samprate 16000, frate 100, wlen 0.025625 and a 512-point "
                       "FFT are supported (got %g, %d, %g, %d)", c->samprate, c->frate, c->wlen,
                       c->nfft);
@@ -325,9 +327,113 @@ ssw_fe_config_check(const ssw_fe_config_t *c)
                       SSW_FE_MAX_FILT, c->nfilt, c->lifter);
         return -1;
     }
-    if (!(c->lowerf >= 0) || !(c->lowerf < c->upperf) || !(c->upperf <= c->samprate / 2)) {
+    /* (ssw_fe_framing checks upperf against each rate, with the reference's + 1) */
+    if (!(c->lowerf >= 0) || !(c->lowerf < c->upperf) || (!ex && !(c->upperf <= c->samprate / 2))) {
         ssw_set_error("front end: need 0 <= lowerf < upperf <= samprate / 2 (got %g, %g)",
                       c->lowerf, c->upperf);
+        return -1;
+    }
+    return 0;
+}
+
+int
+ssw_fe_config_check(const ssw_fe_config_t *c)
+{
+    return fe_config_check(c, 0);
+}
+
+int
+ssw_fe_config_check_ex(const ssw_fe_config_t *c)
+{
+    return fe_config_check(c, 1);
+}
+
+/* minimum_samprate, src/fe_interface.c:55-81 */
+static int
+fe_minimum_samprate(double upperf)
+{
+    static const int rates[] = {8000, 11025, 16000, 22050, 32000, 44100, 48000};
+    const int nyquist = (int)(upperf * 2);
+    size_t i;
+    for (i = 0; i < sizeof(rates) / sizeof(rates[0]); ++i)
+        if (rates[i] >= nyquist)
+            return rates[i];
+    return 16000; /* the reference's fallback */
+}
+
+/* fe_parse_general_params and fe_init, src/fe_interface.c:83-160, 255-301: the same float and
+ * int types, the same refusals, and this front end's own FFT limit */
+int
+ssw_fe_framing(const ssw_fe_config_t *c, double samprate, ssw_fe_framing_t *f)
+{
+    float sr, wlen = (float)c->wlen;
+    int window;
+    /* "samprate" is an integer setting (config_defs.h:320-323) */
+    if (!(samprate >= 0) || samprate != floor(samprate) || samprate > 1e7) {
+        ssw_set_error("front end: samprate %g is not a whole number of hertz (0 .. 10^7)", samprate);
+        return -1;
+    }
+    f->samprate = samprate == 0 ? fe_minimum_samprate(c->upperf) : (int32_t)samprate;
+    sr = (float)f->samprate;
+    if (c->frate > 32767 || c->frate > sr || c->frate < 1) {
+        ssw_set_error("front end: frate %d must be 1 .. min(samprate %d, 32767)", c->frate,
+                      f->samprate);
+        return -1;
+    }
+    if (!(wlen * sr < (float)SSW_FE_MAX_NFFT * 2)) {
+        ssw_set_error("front end: a window of %g samples (wlen %g at samprate %d) needs an FFT "
+                      "above the %d points this front end supports", (double)(wlen * sr), c->wlen,
+                      f->samprate, SSW_FE_MAX_NFFT);
+        return -1;
+    }
+    window = (int)(wlen * sr);
+    if (c->nfft == 0) {
+        f->fft_order = 0;
+        f->fft_size = 1;
+        while (f->fft_size < window) {
+            ++f->fft_order;
+            f->fft_size <<= 1;
+        }
+    } else {
+        if (c->nfft < 1 || (c->nfft & (c->nfft - 1)) != 0) {
+            ssw_set_error("front end: nfft %d is not a power of 2", c->nfft);
+            return -1;
+        }
+        if (c->nfft < window) {
+            ssw_set_error("front end: nfft %d is smaller than the window of %d samples at "
+                          "samprate %d", c->nfft, window, f->samprate);
+            return -1;
+        }
+        f->fft_size = c->nfft;
+        for (f->fft_order = 0; (1 << f->fft_order) < c->nfft; ++f->fft_order)
+            ;
+    }
+    f->frame_shift = (int)(sr / c->frate + 0.5);
+    f->frame_size = (int)(wlen * sr + 0.5);
+    if (f->frame_shift <= 1) {
+        ssw_set_error("front end: frame shift %d samples (samprate %d / frate %d) must be above 1",
+                      f->frame_shift, f->samprate, c->frate);
+        return -1;
+    }
+    if (f->frame_size < f->frame_shift) {
+        ssw_set_error("front end: frame size %d (wlen) is smaller than frame shift %d (frate) at "
+                      "samprate %d", f->frame_size, f->frame_shift, f->samprate);
+        return -1;
+    }
+    if (f->frame_size > f->fft_size) {
+        ssw_set_error("front end: nfft %d is smaller than the frame size %d at samprate %d",
+                      f->fft_size, f->frame_size, f->samprate);
+        return -1;
+    }
+    if (f->fft_size < SSW_FE_MIN_NFFT || f->fft_size > SSW_FE_MAX_NFFT) {
+        ssw_set_error("front end: a %d-point FFT at samprate %d is outside the %d .. %d points "
+                      "this front end supports", f->fft_size, f->samprate, SSW_FE_MIN_NFFT,
+                      SSW_FE_MAX_NFFT);
+        return -1;
+    }
+    if ((float)c->upperf > sr / 2 + 1.0) { /* upper_filt_freq is a float32 */
+        ssw_set_error("front end: upperf %g is above samprate / 2 + 1 (samprate %d)", c->upperf,
+                      f->samprate);
         return -1;
     }
     return 0;
@@ -357,96 +463,18 @@ filter_edges(int i, float melbw, float melmin, float fftfreq, int round_filters,
     }
 }
 
+/* the settings are checked (ssw_fe_config_check or _ex) before */
 int
 ssw_fe_tables_build(const ssw_fe_config_t *c, ssw_fe_tables_t *t)
 {
-    const float samprate = (float)c->samprate, wlen = (float)c->wlen;
-    const float lowerf = (float)c->lowerf, upperf = (float)c->upperf;
-    int i, j, n_coeffs = 0;
-
-    if (ssw_fe_config_check(c) < 0)
-        return -1;
+    int i, j;
     memset(t, 0, sizeof(*t));
-    /* src/fe_interface.c:129-137, 264-265 */
-    t->frame_shift = (int)(samprate / c->frate + 0.5);
-    t->frame_size = (int)(wlen * samprate + 0.5);
-    t->fft_size = 1;
-    t->fft_order = 0;
-    while (t->fft_size < (int)(wlen * samprate)) {
-        ++t->fft_order;
-        t->fft_size <<= 1;
-    }
-    if (t->frame_shift != SSW_FE_SHIFT || t->frame_size != SSW_FE_FRAME || t->fft_size != SSW_FE_NFFT) {
-        ssw_set_error("front end: framing %d / %d / %d is not 160 / 410 / 512", t->frame_shift,
-                      t->frame_size, t->fft_size);
-        return -1;
-    }
     t->nfilt = c->nfilt;
     t->ncep = c->ncep;
     t->transform = c->transform;
     t->remove_noise = c->remove_noise;
     t->lifter_val = c->lifter;
     t->alpha = (float)c->alpha;
-    /* fe_create_hamming, src/fe_sigproc.c:241-252 */
-    for (i = 0; i < t->frame_size / 2; ++i)
-        t->hamming[i] = 0.54 - 0.46 * cos(2 * M_PI * i / ((double)t->frame_size - 1.0));
-    /* fe_create_twiddle, src/fe_sigproc.c:447-457 */
-    for (i = 0; i < t->fft_size / 4; ++i) {
-        double a = 2 * M_PI * i / t->fft_size;
-        t->ccc[i] = cos(a);
-        t->sss[i] = sin(a);
-    }
-    /* fe_build_melfilters, src/fe_sigproc.c:85-182 */
-    {
-        float melmin = fe_mel(lowerf), melmax = fe_mel(upperf);
-        float melbw = (melmax - melmin) / (t->nfilt + 1);
-        float fftfreq = samprate / (float)t->fft_size;
-        for (i = 0; i < t->nfilt; ++i) {
-            float fr[3];
-            filter_edges(i, melbw, melmin, fftfreq, c->round_filters, fr);
-            t->spec_start[i] = -1;
-            t->filt_width[i] = 0;
-            for (j = 0; j < t->fft_size / 2 + 1; ++j) {
-                float hz = j * fftfreq;
-                if (hz < fr[0])
-                    continue;
-                else if (hz > fr[2] || j == t->fft_size / 2) {
-                    t->filt_width[i] = j - t->spec_start[i];
-                    t->filt_start[i] = n_coeffs;
-                    n_coeffs += t->filt_width[i];
-                    break;
-                }
-                if (t->spec_start[i] == -1)
-                    t->spec_start[i] = j;
-            }
-            if (t->spec_start[i] < 0 || t->filt_width[i] < 1) {
-                ssw_set_error("front end: mel filter %d of %d (lowerf %g, upperf %g) covers no DFT "
-                              "point", i, t->nfilt, c->lowerf, c->upperf);
-                return -1;
-            }
-        }
-        if (n_coeffs > SSW_FE_MAX_COEFFS) {
-            ssw_set_error("front end: %d filter coefficients (at most %d)", n_coeffs,
-                          SSW_FE_MAX_COEFFS);
-            return -1;
-        }
-        n_coeffs = 0;
-        for (i = 0; i < t->nfilt; ++i) {
-            float fr[3];
-            filter_edges(i, melbw, melmin, fftfreq, c->round_filters, fr);
-            for (j = 0; j < t->filt_width[i]; ++j) {
-                float hz = (t->spec_start[i] + j) * fftfreq;
-                float loslope = (hz - fr[0]) / (fr[1] - fr[0]);
-                float hislope = (fr[2] - hz) / (fr[2] - fr[1]);
-                if (c->unit_area) {
-                    loslope *= 2 / (fr[2] - fr[0]);
-                    hislope *= 2 / (fr[2] - fr[0]);
-                }
-                t->filt_coeffs[n_coeffs++] = loslope < hislope ? loslope : hislope;
-            }
-        }
-        t->n_coeffs = n_coeffs;
-    }
     /* fe_compute_melcosine, src/fe_sigproc.c:184-217 */
     {
         double freqstep = M_PI / t->nfilt;
@@ -463,16 +491,126 @@ ssw_fe_tables_build(const ssw_fe_config_t *c, ssw_fe_tables_t *t)
     return 0;
 }
 
+ssw_fe_rate_t *
+ssw_fe_rate_build(const ssw_fe_config_t *c, const ssw_fe_framing_t *f, int finite)
+{
+    const float samprate = (float)f->samprate;
+    const float lowerf = (float)c->lowerf, upperf = (float)c->upperf;
+    ssw_fe_rate_t h, *t;
+    double *ham, *ccc, *sss;
+    float *coeffs;
+    int i, j, n_coeffs = 0;
+    float melmin = fe_mel(lowerf), melmax = fe_mel(upperf);
+    float melbw = (melmax - melmin) / (c->nfilt + 1);
+    float fftfreq = samprate / (float)f->fft_size;
+
+    memset(&h, 0, sizeof(h));
+    h.samprate = f->samprate;
+    h.frame_shift = f->frame_shift;
+    h.frame_size = f->frame_size;
+    h.fft_size = f->fft_size;
+    h.fft_order = f->fft_order;
+    h.nfilt = c->nfilt;
+    /* fe_build_melfilters, src/fe_sigproc.c:85-182: the widths first */
+    for (i = 0; i < c->nfilt; ++i) {
+        float fr[3];
+        filter_edges(i, melbw, melmin, fftfreq, c->round_filters, fr);
+        h.spec_start[i] = -1;
+        h.filt_width[i] = 0;
+        for (j = 0; j < f->fft_size / 2 + 1; ++j) {
+            float hz = j * fftfreq;
+            if (hz < fr[0])
+                continue;
+            else if (hz > fr[2] || j == f->fft_size / 2) {
+                h.filt_width[i] = j - h.spec_start[i];
+                h.filt_start[i] = n_coeffs;
+                n_coeffs += h.filt_width[i];
+                break;
+            }
+            if (h.spec_start[i] == -1)
+                h.spec_start[i] = j;
+        }
+        if (h.spec_start[i] < 0 || h.filt_width[i] < 1) {
+            ssw_set_error("front end: mel filter %d of %d (lowerf %g, upperf %g) covers no DFT "
+                          "point", i, c->nfilt, c->lowerf, c->upperf);
+            return NULL;
+        }
+    }
+    h.n_coeffs = n_coeffs;
+    h.hamming_off = (int32_t)sizeof(ssw_fe_rate_t);
+    h.ccc_off = h.hamming_off + (int32_t)sizeof(double) * (f->frame_size / 2);
+    h.sss_off = h.ccc_off + (int32_t)sizeof(double) * (f->fft_size / 4);
+    h.coeff_off = h.sss_off + (int32_t)sizeof(double) * (f->fft_size / 4);
+    h.bytes = (h.coeff_off + (int32_t)sizeof(float) * n_coeffs + 7) & ~7;
+    if ((t = (ssw_fe_rate_t *)calloc(1, (size_t)h.bytes)) == NULL) {
+        ssw_set_error("front end: out of host memory");
+        return NULL;
+    }
+    *t = h;
+    ham = (double *)((char *)t + h.hamming_off);
+    ccc = (double *)((char *)t + h.ccc_off);
+    sss = (double *)((char *)t + h.sss_off);
+    coeffs = (float *)((char *)t + h.coeff_off);
+    /* fe_create_hamming, src/fe_sigproc.c:241-252 */
+    for (i = 0; i < f->frame_size / 2; ++i)
+        ham[i] = 0.54 - 0.46 * cos(2 * M_PI * i / ((double)f->frame_size - 1.0));
+    /* fe_create_twiddle, src/fe_sigproc.c:447-457 */
+    for (i = 0; i < f->fft_size / 4; ++i) {
+        double a = 2 * M_PI * i / f->fft_size;
+        ccc[i] = cos(a);
+        sss[i] = sin(a);
+    }
+    /* the coefficients */
+    n_coeffs = 0;
+    for (i = 0; i < c->nfilt; ++i) {
+        float fr[3];
+        filter_edges(i, melbw, melmin, fftfreq, c->round_filters, fr);
+        for (j = 0; j < h.filt_width[i]; ++j) {
+            float hz = (h.spec_start[i] + j) * fftfreq;
+            float loslope = (hz - fr[0]) / (fr[1] - fr[0]);
+            float hislope = (fr[2] - hz) / (fr[2] - fr[1]);
+            if (c->unit_area) {
+                loslope *= 2 / (fr[2] - fr[0]);
+                hislope *= 2 / (fr[2] - fr[0]);
+            }
+            coeffs[n_coeffs++] = loslope < hislope ? loslope : hislope;
+        }
+        /* edges rounded onto one DFT point divide by zero: the reference's cepstra are NaN */
+        for (j = 0; finite && j < h.filt_width[i]; ++j)
+            if (!isfinite(coeffs[h.filt_start[i] + j])) {
+                ssw_set_error("front end: mel filter %d of %d (lowerf %g, upperf %g) is narrower "
+                              "than one DFT point (%g Hz) at samprate %d, nfft %d", i, c->nfilt,
+                              c->lowerf, c->upperf, (double)fftfreq, f->samprate, f->fft_size);
+                free(t);
+                return NULL;
+            }
+    }
+    return t;
+}
+
 int64_t
 ssw_fe_frames_of(int64_t n)
 {
+    ssw_fe_framing_t f;
+    f.frame_size = SSW_FE_FRAME;
+    f.frame_shift = SSW_FE_SHIFT;
+    return ssw_fe_frames_at(&f, n);
+}
+
+/* fe_process_int16 + fe_end over n samples (src/fe_interface.c:560-712): the full frames, then
+ * fe_end's frame of the samples left over, when there are any */
+int64_t
+ssw_fe_frames_at(const ssw_fe_framing_t *f, int64_t n)
+{
+    int64_t full;
     if (n < 0)
         return -1;
     if (n == 0)
         return 0;
-    if (n < SSW_FE_FRAME)
+    if (n < f->frame_size)
         return 1;
-    return 2 + (n - SSW_FE_FRAME) / SSW_FE_SHIFT;
+    full = 1 + (n - f->frame_size) / f->frame_shift;
+    return full + (n - full * f->frame_shift > 0);
 }
 
 /* ---------------------------------------------------------------------------------- */
