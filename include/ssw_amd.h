@@ -651,6 +651,116 @@ int32_t ssw_alignment_json(const ssw_model_t *m, const char *hyp, int32_t hyp_lo
                            const ssw_align_entry_t *state_al, char *out, int32_t out_len);
 
 /* ------------------------------------------------------------------------------------ */
+/* Recognition against a word FSG: decoder_set_fsg + decoder_process_* + decoder_hyp /       */
+/* decoder_seg_iter for a batch, over compallsen = yes scores.  Replaces:                     */
+/*   fsg_model_init / _trans_add / _null_trans_add / _null_trans_closure, fsg_model_read      */
+/*                                                 src/fsg_model.c:62-219, 453-708            */
+/*   fsg_search_init: dictionary check, silences, alternates  src/fsg_search.c:84-253          */
+/*   fsg_lextree_init with null transitions                  src/fsg_lextree.c:85-276, 356-660 */
+/*   fsg_search_start / _null_prop / _word_trans / _step      src/fsg_search.c:543-802          */
+/*   fsg_search_find_exit / _hyp / _seg_iter, fsg_seg_bp2itor src/fsg_search.c:854-1143         */
+/* Not covered: JSGF, the default compallsen = no normalisation, lattices / best path /       */
+/* N-best, tag transitions, grammars beyond what one workgroup holds (4096 phone-tree HMMs).  */
+/* ------------------------------------------------------------------------------------ */
+typedef struct ssw_fsg_s ssw_fsg_t;
+/* fsg_model_init + fsg_model_trans_add / fsg_model_null_trans_add per transition, in the order
+ * given (src/fsg_model.c:62-148, 453-471; the reference's Python create_fsg): word[i] NULL or ""
+ * makes transition i a null transition.  Refused, with the reference's message where it has one:
+ * a state out of range ("Invalid from-state %d" / "Invalid to-state %d", :605-618), a
+ * probability <= 0 or > 1 (:623-628), a word the dictionary lacks ("The word '%s' is missing in
+ * the dictionary", src/fsg_search.c:120-141; d may be NULL: checked by ssw_grammar_prepare
+ * then), a model of more than 64 CI phones.  The log probabilities, the null closure, the
+ * silences and the alternates depend on lw, silprob, ... and are made by ssw_grammar_prepare. */
+ssw_fsg_t *ssw_fsg_create(const ssw_model_t *m, const ssw_dict_t *d, const char *name,
+                          int32_t n_states, int32_t start, int32_t final, int32_t n_trans,
+                          const int32_t *from, const int32_t *to, const float *prob,
+                          const char *const *word);
+/* fsg_model_readfile (src/fsg_model.c:505-708): the .fsg text format -- FSG_BEGIN <name>,
+ * NUM_STATES | N, START_STATE | S, FINAL_STATE | F, TRANSITION | T <from> <to> <prob> [<word>],
+ * FSG_END; lines that start with '#', blank lines and lines with other first words are skipped;
+ * a line's first word may be a prefix of the keyword, as in the reference.  Refusals as above,
+ * plus its "... declaration missing" / "... declaration malformed" / "Line[%d]: ... missing". */
+ssw_fsg_t *ssw_fsg_read(const ssw_model_t *m, const ssw_dict_t *d, const char *path);
+void ssw_fsg_free(ssw_fsg_t *f);
+const char *ssw_fsg_name(const ssw_fsg_t *f);
+int32_t ssw_fsg_n_states(const ssw_fsg_t *f);
+/* fsg_model_write (src/fsg_model.c:764-793) of the grammar as fsg_model_read leaves it
+ * (searched = 0: null transitions closed) or as fsg_search_init does (searched = 1: silence and
+ * filler loops and alternates added, src/fsg_search.c:229-233), the links in fsg_model_arcs
+ * order (:248-302).  cfg NULL = defaults.  snprintf-style return; -1 on error. */
+int32_t ssw_fsg_write(const ssw_fsg_t *f, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
+                      int32_t searched, char *out, int32_t out_len);
+/* ssw_first_pass_graph for a grammar: the phone-tree HMMs fsg_lextree_init makes of it
+ * (src/fsg_lextree.c:85-276, 356-660), host only. */
+int32_t ssw_grammar_graph(const ssw_model_t *m, const ssw_dict_t *d,
+                          const ssw_first_pass_config_t *cfg, const ssw_fsg_t *fsg,
+                          int32_t max_nodes, ssw_fp_node_t *nodes, int32_t *beams);
+
+/* decoder_set_fsg for n_fsgs grammars (src/decoder.c:596-607 -> fsg_search_init / _reinit,
+ * src/fsg_search.c:171-307): the graphs are built once, on the host (no device call), and stay on the device
+ * while the plan is the last one searched.  Refused: an unknown word, a grammar of more than
+ * SSW_GRAMMAR_MAX_HMMS phone-tree HMMs or whose exchange arrays outgrow the workgroup's LDS
+ * (the message names the count and the limit).  cfg NULL = defaults. */
+#define SSW_GRAMMAR_MAX_HMMS 4096
+typedef struct ssw_grammar_plan_s ssw_grammar_plan_t;
+ssw_grammar_plan_t *ssw_grammar_prepare(const ssw_model_t *m, const ssw_dict_t *d,
+                                        const ssw_first_pass_config_t *cfg, int32_t n_fsgs,
+                                        const ssw_fsg_t *const *fsgs);
+void ssw_grammar_plan_free(ssw_grammar_plan_t *plan);
+/* phone-tree HMMs of grammar `fsg` of the plan (fsg_lextree_n_pnode), -1 when out of range */
+int32_t ssw_grammar_plan_hmms(const ssw_grammar_plan_t *plan, int32_t fsg);
+
+/* one history entry of the best path (fsg_seg_bp2itor, src/fsg_search.c:1032-1055) */
+typedef struct ssw_fsg_seg_s {
+    int32_t wid;  /* dictionary word id; -1 for a null transition ("(NULL)") */
+    int32_t sf, ef; /* first and last frame; a null entry has sf = ef (-1 at the start state) */
+    int32_t ascr; /* score - predecessor's score - lscr */
+    int32_t lscr; /* the link's log probability >> 10 */
+} ssw_fsg_seg_t;
+
+/* decoder_start_utt .. decoder_end_utt of fsg_search for a batch (src/fsg_search.c:665-852):
+ * utterance u (score rows utt_off[u] .. utt_off[u+1] of d_senscr, int16 [n_frames][n_sen] in
+ * HBM) is searched against grammar fsg_of_utt[u] of the plan (NULL: grammar 0 for all).  NULL
+ * on a call-level error, which includes a history table beyond SSW_GRAMMAR_HIST_BYTES (or the
+ * environment's SSW_GRAMMAR_HIST_MB).  Per utterance (ssw_recognition_set_status): 0 a
+ * hypothesis; 1 "Final result does not match the grammar in frame N" (fsg_search_find_exit,
+ * :913-917); 2 no history entry at all (find_exit's "No hypothesis (yet)", :876-878).
+ * Synchronous on `stream`. */
+#define SSW_GRAMMAR_HIST_BYTES ((size_t)4 << 30)
+typedef struct ssw_recognition_set_s ssw_recognition_set_t;
+ssw_recognition_set_t *ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d,
+                                                const ssw_grammar_plan_t *plan,
+                                                const int32_t *fsg_of_utt,
+                                                const int16_t *d_senscr, int32_t n_frames,
+                                                const int32_t *utt_off, int32_t n_utts,
+                                                void *stream);
+/* the same from FEATURES (d_feats float32 [n_frames][39]): ssw_score_batch of all senones into
+ * a workspace the model keeps (acmod_score with compallsen = yes), then the search */
+ssw_recognition_set_t *ssw_recognize_batch(ssw_model_t *m, const ssw_dict_t *d,
+                                           const ssw_grammar_plan_t *plan,
+                                           const int32_t *fsg_of_utt, int scorer,
+                                           const float *d_feats, int32_t n_frames,
+                                           const int32_t *utt_off, int32_t n_utts, void *stream);
+int32_t ssw_recognition_set_status(const ssw_recognition_set_t *r, int32_t utt);
+const char *ssw_recognition_set_message(const ssw_recognition_set_t *r, int32_t utt);
+/* decoder_seg_iter (src/fsg_search.c:1084-1142): the path's entries, null transitions
+ * included; returns their number (0 without a hypothesis) and points *seg at the set's array */
+int32_t ssw_recognition_set_segments(const ssw_recognition_set_t *r, int32_t utt,
+                                     const ssw_fsg_seg_t **seg);
+/* decoder_hyp's score (fsg_search_hyp, src/fsg_search.c:935-1030): 0, or -1 without a hypothesis */
+int32_t ssw_recognition_set_score(const ssw_recognition_set_t *r, int32_t utt, int32_t *score);
+/* decoder_hyp's text: base words, fillers and null transitions left out.  snprintf-style;
+ * -1 without a hypothesis (also when every entry is a filler or null: hyp_str NULL, :999-1002) */
+int32_t ssw_recognition_set_hyp(const ssw_recognition_set_t *r, int32_t utt, char *out,
+                                int32_t out_len);
+/* decoder_result_json(d, utt_start, 0) (src/decoder.c:1339-1379, 1502-1593): the line with
+ * its newline; a word's p = logmath_exp(ascr + lscr), top-level p 1.000 (decoder_prob is 0
+ * without bestpath), "(NULL)" entries included, "t":"","w":[] without a hypothesis. */
+int32_t ssw_recognition_set_json(const ssw_recognition_set_t *r, int32_t utt, double utt_start,
+                                 int32_t frate, char *out, int32_t out_len);
+void ssw_recognition_set_free(ssw_recognition_set_t *r);
+
+/* ------------------------------------------------------------------------------------ */
 /* Dynamic features on the device: feat_s2mfc2feat_live for whole    */
 /* utterances with feat = 1s_c_d_dd, cmn = batch ("current"), no varnorm / agc / lda       */
 /* (src/feat.c:977-1008, 589-632; src/cmn.c:168-200).  d_cep [n_frames][ncep] MFCC rows     */

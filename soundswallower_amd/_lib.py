@@ -213,6 +213,44 @@ def lib() -> C.CDLL:
                                      vp, vp, vp, vp, C.c_char_p, i32]
     L.ssw_alignment_populate.restype = i32
     L.ssw_alignment_populate.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.ssw_fsg_create.restype = vp
+    L.ssw_fsg_create.argtypes = [vp, vp, C.c_char_p, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.ssw_fsg_read.restype = vp
+    L.ssw_fsg_read.argtypes = [vp, vp, C.c_char_p]
+    L.ssw_fsg_free.argtypes = [vp]
+    L.ssw_fsg_free.restype = None
+    L.ssw_fsg_name.restype = C.c_char_p
+    L.ssw_fsg_name.argtypes = [vp]
+    L.ssw_fsg_n_states.restype = i32
+    L.ssw_fsg_n_states.argtypes = [vp]
+    L.ssw_fsg_write.restype = i32
+    L.ssw_fsg_write.argtypes = [vp, vp, vp, i32, C.c_char_p, i32]
+    L.ssw_grammar_graph.restype = i32
+    L.ssw_grammar_graph.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+    L.ssw_grammar_prepare.restype = vp
+    L.ssw_grammar_prepare.argtypes = [vp, vp, vp, i32, vp]
+    L.ssw_grammar_plan_free.argtypes = [vp]
+    L.ssw_grammar_plan_free.restype = None
+    L.ssw_grammar_plan_hmms.restype = i32
+    L.ssw_grammar_plan_hmms.argtypes = [vp, i32]
+    L.ssw_grammar_search_batch.restype = vp
+    L.ssw_grammar_search_batch.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, vp]
+    L.ssw_recognize_batch.restype = vp
+    L.ssw_recognize_batch.argtypes = [vp, vp, vp, vp, C.c_int, vp, i32, vp, i32, vp]
+    L.ssw_recognition_set_status.restype = i32
+    L.ssw_recognition_set_status.argtypes = [vp, i32]
+    L.ssw_recognition_set_message.restype = C.c_char_p
+    L.ssw_recognition_set_message.argtypes = [vp, i32]
+    L.ssw_recognition_set_segments.restype = i32
+    L.ssw_recognition_set_segments.argtypes = [vp, i32, C.POINTER(vp)]
+    L.ssw_recognition_set_score.restype = i32
+    L.ssw_recognition_set_score.argtypes = [vp, i32, C.POINTER(i32)]
+    L.ssw_recognition_set_hyp.restype = i32
+    L.ssw_recognition_set_hyp.argtypes = [vp, i32, C.c_char_p, i32]
+    L.ssw_recognition_set_json.restype = i32
+    L.ssw_recognition_set_json.argtypes = [vp, i32, C.c_double, i32, C.c_char_p, i32]
+    L.ssw_recognition_set_free.argtypes = [vp]
+    L.ssw_recognition_set_free.restype = None
     L.ssw_feat_batch.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
     L.ssw_fe_config_defaults.argtypes = [C.POINTER(SswFeConfig)]
     L.ssw_fe_config_defaults.restype = None

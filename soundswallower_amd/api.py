@@ -818,6 +818,22 @@ class Lexicon:
         _check(n, "ssw_first_pass_graph")
         return nodes[:n].copy(), beams
 
+    def grammar_graph(self, fsg, cfg=None, max_nodes=1 << 16):
+        """The phone-tree HMMs the grammar search walks for one Fsg (host only), as
+        first_pass_graph gives them for a text."""
+        nodes = np.zeros(max_nodes, FP_NODE_DTYPE)
+        beams = np.zeros(3, np.int32)
+        n = self._L.ssw_grammar_graph(self.model._m, self._d,
+                                      None if cfg is None else C.byref(cfg), fsg._f, max_nodes,
+                                      _ptr(nodes), _ptr(beams))
+        _check(n, "ssw_grammar_graph")
+        return nodes[:n].copy(), beams
+
+    def grammar_plan(self, fsgs, cfg=None) -> "GrammarPlan":
+        """ssw_grammar_prepare: decoder_set_fsg for a list of Fsg (or one); the graphs are built
+        once on the host and cached on the device while the plan is searched."""
+        return GrammarPlan(self, fsgs, cfg)
+
     def first_pass(self, d_senscr, utt_off, texts, cfg=None, max_seg=None, stream=None):
         """ssw_first_pass_batch: device senone scores of a batch + one word list per utterance
         -> per utterance a list of (word, start, duration, score), or None when the grammar's
@@ -1116,3 +1132,220 @@ def forced_alignment(model: Model, lex: Lexicon, d_senscr, utt_off, texts, cfg=N
     out = [s.utterance(u) for u in range(len(texts))]
     s.free()
     return out
+
+
+FSG_SEG_DTYPE = np.dtype([("wid", "<i4"), ("sf", "<i4"), ("ef", "<i4"), ("ascr", "<i4"),
+                          ("lscr", "<i4")])
+
+
+class Fsg:
+    """ssw_fsg_t: a word finite-state grammar (fsg_model_t), from a transition list or a .fsg
+    file.  lex=None skips the dictionary check until the grammar is planned."""
+
+    def __init__(self, handle):
+        self._L = _lib.lib()
+        self._f = handle
+
+    @classmethod
+    def create(cls, model: Model, lex, name, start, final, transitions, n_states=None):
+        """transitions: (from, to, prob[, word]) tuples; without a word (or with None / "") a
+        null transition.  n_states None: the largest state number + 1, as create_fsg counts."""
+        tr = [(t[0], t[1], t[2], t[3] if len(t) > 3 and t[3] else None) for t in transitions]
+        if n_states is None:
+            n_states = max([start, final] + [max(t[0], t[1]) for t in tr]) + 1
+        n = len(tr)
+        fr = np.array([t[0] for t in tr], np.int32)
+        to = np.array([t[1] for t in tr], np.int32)
+        pr = np.array([t[2] for t in tr], np.float32)
+        words = (C.c_char_p * max(1, n))(*[None if t[3] is None else t[3].encode() for t in tr])
+        L = _lib.lib()
+        h = L.ssw_fsg_create(model._m, None if lex is None else lex._d, name.encode(),
+                             int(n_states), int(start), int(final), n, _ptr(fr), _ptr(to),
+                             _ptr(pr), words)
+        if not h:
+            raise SswError("ssw_fsg_create: " + _lib.last_error())
+        return cls(h)
+
+    @classmethod
+    def read(cls, model: Model, lex, path):
+        L = _lib.lib()
+        h = L.ssw_fsg_read(model._m, None if lex is None else lex._d, os.fsencode(path))
+        if not h:
+            raise SswError("ssw_fsg_read: " + _lib.last_error())
+        return cls(h)
+
+    @property
+    def name(self):
+        return self._L.ssw_fsg_name(self._f).decode()
+
+    @property
+    def n_states(self):
+        return int(self._L.ssw_fsg_n_states(self._f))
+
+    def write(self, lex=None, cfg=None, searched=False) -> str:
+        """fsg_model_write: the grammar as read (null transitions closed) or, with
+        searched=True, as the search sees it (silences and alternates added)."""
+        args = (self._f, None if lex is None else lex._d, None if cfg is None else C.byref(cfg),
+                1 if searched else 0)
+        need = self._L.ssw_fsg_write(*args, None, 0)
+        _check(need, "ssw_fsg_write")
+        buf = C.create_string_buffer(need + 1)
+        _check(self._L.ssw_fsg_write(*args, buf, need + 1), "ssw_fsg_write")
+        return buf.value.decode()
+
+    def free(self):
+        if getattr(self, "_f", None):
+            self._L.ssw_fsg_free(self._f)
+            self._f = None
+
+    __del__ = free
+
+
+class GrammarPlan:
+    """ssw_grammar_plan_t: the phone-tree graphs of one or more grammars."""
+
+    def __init__(self, lex: Lexicon, fsgs, cfg=None):
+        self._L = _lib.lib()
+        fsgs = [fsgs] if isinstance(fsgs, Fsg) else list(fsgs)
+        self.n_fsgs = len(fsgs)
+        arr = (C.c_void_p * max(1, len(fsgs)))(*[f._f for f in fsgs])
+        self._p = self._L.ssw_grammar_prepare(lex.model._m, lex._d,
+                                              None if cfg is None else C.byref(cfg), len(fsgs), arr)
+        if not self._p:
+            raise SswError("ssw_grammar_prepare: " + _lib.last_error())
+
+    def hmms(self, fsg=0) -> int:
+        return int(self._L.ssw_grammar_plan_hmms(self._p, fsg))
+
+    def free(self):
+        if getattr(self, "_p", None):
+            self._L.ssw_grammar_plan_free(self._p)
+            self._p = None
+
+    __del__ = free
+
+
+class RecognitionSet:
+    """ssw_recognition_set_t: per utterance status / message / hyp / score / segments / json."""
+
+    def __init__(self, lib, handle, lex, n_utts):
+        self._L, self._r, self._lex, self.n_utts = lib, handle, lex, n_utts
+
+    def __len__(self):
+        return self.n_utts
+
+    def status(self, u):
+        return int(self._L.ssw_recognition_set_status(self._r, u))
+
+    def message(self, u):
+        return self._L.ssw_recognition_set_message(self._r, u).decode()
+
+    def hyp(self, u):
+        """decoder_hyp's text, or None"""
+        need = self._L.ssw_recognition_set_hyp(self._r, u, None, 0)
+        if need < 0:
+            return None
+        buf = C.create_string_buffer(need + 1)
+        self._L.ssw_recognition_set_hyp(self._r, u, buf, need + 1)
+        return buf.value.decode()
+
+    def score(self, u):
+        v = C.c_int32()
+        return int(v.value) if self._L.ssw_recognition_set_score(self._r, u, C.byref(v)) == 0 else None
+
+    def segments_raw(self, u):
+        p = C.c_void_p()
+        n = self._L.ssw_recognition_set_segments(self._r, u, C.byref(p))
+        return _view(p, n, FSG_SEG_DTYPE)
+
+    def segments(self, u):
+        """[(word or "(NULL)", sf, ef, ascr, lscr)] of the best path"""
+        return [("(NULL)" if s["wid"] < 0 else self._lex.word(int(s["wid"])), int(s["sf"]),
+                 int(s["ef"]), int(s["ascr"]), int(s["lscr"])) for s in self.segments_raw(u)]
+
+    def json(self, u, utt_start=0.0, frate=100):
+        """the line decoder_result_json(d, utt_start, 0) prints"""
+        need = self._L.ssw_recognition_set_json(self._r, u, float(utt_start), frate, None, 0)
+        _check(need, "ssw_recognition_set_json")
+        buf = C.create_string_buffer(need + 1)
+        _check(self._L.ssw_recognition_set_json(self._r, u, float(utt_start), frate, buf, need + 1),
+               "ssw_recognition_set_json")
+        return buf.value.decode()
+
+    def free(self):
+        if getattr(self, "_r", None):
+            self._L.ssw_recognition_set_free(self._r)
+            self._r = None
+
+    __del__ = free
+
+
+def _fsg_of_utt(fsg_of_utt, n_utts):
+    if fsg_of_utt is None:
+        return None
+    a = np.ascontiguousarray(fsg_of_utt, np.int32)
+    assert len(a) == n_utts
+    return a
+
+
+def grammar_search_batch(model: Model, lex: Lexicon, d_senscr, utt_off, plan: GrammarPlan,
+                         fsg_of_utt=None, stream=None) -> RecognitionSet:
+    """ssw_grammar_search_batch: senone scores in HBM (compallsen = yes rows) -> recognition
+    against the plan's grammars, utterance u against grammar fsg_of_utt[u] (None: grammar 0)."""
+    off = np.ascontiguousarray(utt_off, np.int32)
+    n_utts = len(off) - 1
+    g = _fsg_of_utt(fsg_of_utt, n_utts)
+    L = _lib.lib()
+    h = L.ssw_grammar_search_batch(model._m, lex._d, plan._p, _ptr(g), _ptr(d_senscr),
+                                   int(off[-1]), _ptr(off), n_utts, _ptr(stream))
+    if not h:
+        raise SswError("ssw_grammar_search_batch: " + _lib.last_error())
+    return RecognitionSet(L, h, lex, n_utts)
+
+
+def recognize_batch(model: Model, lex: Lexicon, d_feats, utt_off, plan: GrammarPlan,
+                    fsg_of_utt=None, scorer=SCORER_PTM, stream=None) -> RecognitionSet:
+    """ssw_recognize_batch: feature rows in HBM -> all senone scores -> grammar search."""
+    off = np.ascontiguousarray(utt_off, np.int32)
+    n_utts = len(off) - 1
+    g = _fsg_of_utt(fsg_of_utt, n_utts)
+    L = _lib.lib()
+    h = L.ssw_recognize_batch(model._m, lex._d, plan._p, _ptr(g), scorer, _ptr(d_feats),
+                              int(off[-1]), _ptr(off), n_utts, _ptr(stream))
+    if not h:
+        raise SswError("ssw_recognize_batch: " + _lib.last_error())
+    return RecognitionSet(L, h, lex, n_utts)
+
+
+def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: GrammarPlan,
+                          fsg_of_utt=None, samprate=None, fe_cfg=None, scorer=SCORER_PTM,
+                          stream=None) -> RecognitionSet:
+    """Audio in, hypotheses out: decoder_process_int16(full_utt) + decoder_hyp / decoder_seg_iter
+    under decoder_set_fsg with compallsen = yes, for a batch.  int16 PCM (host array or device
+    tensor; utterance u = samples samp_off[u] .. samp_off[u + 1]) -> ssw_fe_batch (samprate None:
+    16 kHz) or ssw_fe_batch_ex -> ssw_feat_batch -> ssw_recognize_batch."""
+    off = np.ascontiguousarray(samp_off, np.int64)
+    n_frames = int(fe_frame_counts(np.diff(off)).sum() if samprate is None else
+                   model.fe_frame_counts_rates(np.diff(off), samprate, fe_cfg).sum())
+    on_device = hasattr(pcm, "data_ptr") and getattr(pcm, "is_cuda", False)
+    d_pcm = pcm if on_device else (model.to_device(np.ascontiguousarray(pcm, np.int16))
+                                   if off[-1] > 0 else None)
+    d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
+    d_feat = model.device_malloc(n_frames * 3 * FE_NCEP * 4) if n_frames else None
+    try:
+        if samprate is None:
+            _, fo = model.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, fe_cfg, stream)
+        else:
+            _, fo = model.fe_batch_rates_device(d_pcm, off, samprate, d_cep if d_cep else 0,
+                                                fe_cfg, stream)
+        if n_frames:
+            _check(model._L.ssw_feat_batch(model._m, d_cep, n_frames, _ptr(fo), len(fo) - 1,
+                                           FE_NCEP, d_feat, _ptr(stream)), "ssw_feat_batch")
+        return recognize_batch(model, lex, d_feat if d_feat else 0, fo, plan, fsg_of_utt,
+                               scorer=scorer, stream=stream)
+    finally:
+        if d_pcm is not None and not on_device:
+            model.device_free(d_pcm)
+        for p in (d_cep, d_feat):
+            if p:
+                model.device_free(p)

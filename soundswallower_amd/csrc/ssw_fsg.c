@@ -18,6 +18,7 @@
  *   - fillers: context-independent, present SIL to their neighbours (:446-468).
  * Orders the reference takes from hash-table iteration only break exact score ties; here
  * links are taken as: the word, its alternates (newest first), <sil>, the other fillers.
+ * Grammars (ssw_fsg_model.inc, build_grammar below) take them in the reference's own order.
  */
 #include "ssw_internal.h"
 
@@ -55,6 +56,8 @@ ilog0(double base, double p)
     return (int32_t)(log(p) * (1.0 / log(base)));
 }
 
+#include "ssw_fsg_model.inc"
+
 static int
 cmp_u64(const void *a, const void *b)
 {
@@ -66,7 +69,8 @@ typedef struct {
     int word;     /* dictionary id */
     int to;       /* destination state */
     int logp;     /* fsg_link_logs2prob */
-    int filler;
+    int filler;   /* fsg_model_is_filler: SIL as context on both sides (fsg_lextree_lc_rc) */
+    int dfiller;  /* dict_filler_word: a context-independent node (psubtree_add_trans) */
 } link_t;
 
 /* growable arrays of the batch */
@@ -200,80 +204,23 @@ alike(const ssw_fp_graphs_t *g, int leaf_base, int i, int j)
         && memcmp(&g->senid[(size_t)j * 4], &g->senid[(size_t)i * 4], 3 * sizeof(uint16_t)) == 0;
 }
 
+/* the phone trees of the states' links (words only; `nulls`: the closed null transitions as
+ * (from, to) pairs in the order fsg_model_arcs walks them state by state, for the context sets) */
 static int
-build_one(builder_t *b, const ssw_model_t *m, const ssw_host_model_t *h, const ssw_dict_t *d,
-          const ssw_first_pass_config_t *cfg, int n_words, const char *const *words, int wip,
-          int pip, int logsil, int logfil)
+build_links(builder_t *b, const ssw_model_t *m, const ssw_host_model_t *h, const ssw_dict_t *d,
+            int n_state, const link_t *links, const int *link_off, int n_nulls, const int *nulls,
+            int wip, int pip)
 {
     ssw_fp_graphs_t *g = b->g;
-    const int n_state = n_words + 1, sil = h->sil;
+    const int sil = h->sil;
     const int base = g->n_nodes, leaf_base = g->n_leaves;
     uint64_t *lcset = (uint64_t *)calloc((size_t)n_state, sizeof(uint64_t));
     uint64_t *rcset = (uint64_t *)calloc((size_t)n_state, sizeof(uint64_t));
-    link_t *links = NULL;
-    int *link_off = (int *)calloc((size_t)n_state + 1, sizeof(int));
-    int n_links = 0, cap_links = 0, s, i, k, rc = -1;
+    int s, i, rc = -1;
 
-    if (!lcset || !rcset || !link_off)
+    if (!lcset || !rcset)
         goto oom;
-    /* links per state: word + alternates to s+1, then the filler loops */
-    for (s = 0; s < n_state; ++s) {
-        link_off[s] = n_links;
-        if (s < n_words) {
-            int w = ssw_dict_find(d, words[s]);
-            if (w < 0) {
-                ssw_set_error("Unknown word %s", words[s]); /* src/decoder.c:699-703 */
-                goto bad;
-            }
-            /* fsg_search_add_altpron walks the dict_nextalt chain from the word and
-             * fsg_model_add_alt PREPENDS every alternate's link (src/fsg_model.c:430-444): the
-             * state's list ends up w(2), w(3), ..., w(k), w.  The order matters: alternates with
-             * identical pronunciations tie for ever and the list order picks the one reported */
-            {
-                int n_alt = 0, j;
-                for (k = cfg->use_altpron ? d->alt[w] : -1; k >= 0; k = d->alt[k])
-                    ++n_alt;
-                if (grow((void **)&links, &cap_links, n_links + n_alt + 1, sizeof(link_t)) < 0)
-                    goto oom;
-                j = n_links + n_alt - 1;
-                for (k = cfg->use_altpron ? d->alt[w] : -1; k >= 0; k = d->alt[k], --j)
-                    links[j].word = k;
-                links[n_links + n_alt].word = w;
-                for (j = n_links; j <= n_links + n_alt; ++j) {
-                    links[j].to = s + 1;
-                    links[j].logp = 0;
-                    links[j].filler = 0;
-                }
-                n_links += n_alt + 1;
-            }
-        }
-        if (cfg->use_filler) {
-            /* fsg_search_add_silences (src/fsg_search.c:84-119): <sil> with silprob, then the
-             * filler words from dict_filler_start up to BUT NOT INCLUDING dict_filler_end
-             * (the loop's `wid < dict_filler_end`), except <s> and </s>, with fillprob;
-             * <sil> met again there keeps its larger probability (fsg_model_trans_add) */
-            const int sw = ssw_dict_find(d, "<sil>"), start = ssw_dict_find(d, "<s>"),
-                      fin = ssw_dict_find(d, "</s>");
-            int f;
-            for (f = -1; f < d->n_words - 1; f = (f < 0 ? d->filler_start : f + 1)) {
-                const int w = f < 0 ? sw : f;
-                if (w < 0 || (f >= 0 && (w == sw || w == start || w == fin)))
-                    continue;
-                for (k = w; k >= 0; k = (cfg->use_altpron ? d->alt[k] : -1)) {
-                    if (grow((void **)&links, &cap_links, n_links + 1, sizeof(link_t)) < 0)
-                        goto oom;
-                    links[n_links].word = k;
-                    links[n_links].to = s;
-                    links[n_links].logp = (w == sw) ? logsil : logfil;
-                    links[n_links].filler = 1;
-                    ++n_links;
-                }
-            }
-        }
-    }
-    link_off[n_state] = n_links;
-
-    /* fsg_lextree_lc_rc: context phone sets per state (no null transitions to propagate) */
+    /* fsg_lextree_lc_rc: context phone sets per state */
     for (s = 0; s < n_state; ++s) {
         lcset[s] |= 1ull << sil;
         rcset[s] |= 1ull << sil;
@@ -286,6 +233,12 @@ build_one(builder_t *b, const ssw_model_t *m, const ssw_host_model_t *h, const s
             rcset[s] |= 1ull << d->pron[l->word][0];
             lcset[l->to] |= 1ull << d->pron[l->word][d->pronlen[l->word] - 1];
         }
+    /* its one pass across the null transitions, in place and in state order
+     * (src/fsg_lextree.c:162-182): what it meets later sees what it changed earlier */
+    for (i = 0; i < n_nulls; ++i) {
+        lcset[nulls[2 * i + 1]] |= lcset[nulls[2 * i]];
+        rcset[nulls[2 * i]] |= rcset[nulls[2 * i + 1]];
+    }
 
     /* the phone trees */
     for (s = 0; s < n_state; ++s) {
@@ -297,7 +250,7 @@ build_one(builder_t *b, const ssw_model_t *m, const ssw_host_model_t *h, const s
             int p, pred = -1;
             if (len == 1) {
                 const int ci = pron[0];
-                if (l->filler) {
+                if (l->dfiller) {
                     int n = add_node(b, h, base, h->phone_ssid[ci], ci, lp + wip + pip, -1,
                                      INFO_ROOT | INFO_LEAF | INFO_ALLRC, sil, s, ~0ull);
                     if (n < 0 || mark_leaf(b, base, leaf_base, n, l->word, l->to) < 0)
@@ -507,8 +460,6 @@ build_one(builder_t *b, const ssw_model_t *m, const ssw_host_model_t *h, const s
     }
     free(lcset);
     free(rcset);
-    free(links);
-    free(link_off);
     return 0;
 bad_phone:
     ssw_set_error("no triphone for a phone of the text (model and dictionary do not match)");
@@ -518,6 +469,85 @@ oom:
 bad:
     free(lcset);
     free(rcset);
+    return -1;
+}
+
+/* the linear grammar of a text: word s leads from state s to state s + 1 */
+static int
+build_one(builder_t *b, const ssw_model_t *m, const ssw_host_model_t *h, const ssw_dict_t *d,
+          const ssw_first_pass_config_t *cfg, int n_words, const char *const *words, int wip,
+          int pip, int logsil, int logfil)
+{
+    const int n_state = n_words + 1;
+    link_t *links = NULL;
+    int *link_off = (int *)calloc((size_t)n_state + 1, sizeof(int));
+    int n_links = 0, cap_links = 0, s, k, rc;
+
+    if (!link_off)
+        goto oom;
+    /* links per state: word + alternates to s+1, then the filler loops */
+    for (s = 0; s < n_state; ++s) {
+        link_off[s] = n_links;
+        if (s < n_words) {
+            int w = ssw_dict_find(d, words[s]);
+            if (w < 0) {
+                ssw_set_error("Unknown word %s", words[s]); /* src/decoder.c:699-703 */
+                goto bad;
+            }
+            /* fsg_search_add_altpron walks the dict_nextalt chain from the word and
+             * fsg_model_add_alt PREPENDS every alternate's link (src/fsg_model.c:430-444): the
+             * state's list ends up w(2), w(3), ..., w(k), w.  The order matters: alternates with
+             * identical pronunciations tie for ever and the list order picks the one reported */
+            {
+                int n_alt = 0, j;
+                for (k = cfg->use_altpron ? d->alt[w] : -1; k >= 0; k = d->alt[k])
+                    ++n_alt;
+                if (grow((void **)&links, &cap_links, n_links + n_alt + 1, sizeof(link_t)) < 0)
+                    goto oom;
+                j = n_links + n_alt - 1;
+                for (k = cfg->use_altpron ? d->alt[w] : -1; k >= 0; k = d->alt[k], --j)
+                    links[j].word = k;
+                links[n_links + n_alt].word = w;
+                for (j = n_links; j <= n_links + n_alt; ++j) {
+                    links[j].to = s + 1;
+                    links[j].logp = 0;
+                    links[j].filler = links[j].dfiller = 0;
+                }
+                n_links += n_alt + 1;
+            }
+        }
+        if (cfg->use_filler) {
+            /* fsg_search_add_silences (src/fsg_search.c:84-119): <sil> with silprob, then the
+             * filler words from dict_filler_start up to BUT NOT INCLUDING dict_filler_end
+             * (the loop's `wid < dict_filler_end`), except <s> and </s>, with fillprob;
+             * <sil> met again there keeps its larger probability (fsg_model_trans_add) */
+            const int sw = ssw_dict_find(d, "<sil>"), start = ssw_dict_find(d, "<s>"),
+                      fin = ssw_dict_find(d, "</s>");
+            int f;
+            for (f = -1; f < d->n_words - 1; f = (f < 0 ? d->filler_start : f + 1)) {
+                const int w = f < 0 ? sw : f;
+                if (w < 0 || (f >= 0 && (w == sw || w == start || w == fin)))
+                    continue;
+                for (k = w; k >= 0; k = (cfg->use_altpron ? d->alt[k] : -1)) {
+                    if (grow((void **)&links, &cap_links, n_links + 1, sizeof(link_t)) < 0)
+                        goto oom;
+                    links[n_links].word = k;
+                    links[n_links].to = s;
+                    links[n_links].logp = (w == sw) ? logsil : logfil;
+                    links[n_links].filler = links[n_links].dfiller = 1;
+                    ++n_links;
+                }
+            }
+        }
+    }
+    link_off[n_state] = n_links;
+    rc = build_links(b, m, h, d, n_state, links, link_off, 0, NULL, wip, pip);
+    free(links);
+    free(link_off);
+    return rc;
+oom:
+    ssw_set_error("out of memory building the first-pass graphs");
+bad:
     free(links);
     free(link_off);
     return -1;
@@ -869,21 +899,28 @@ ssw_fp_graphs_free(ssw_fp_graphs_t *g)
     free(g->tw_off);
     free(g->twin_ref);
     free(g->tw_rk);
+    free(g->g_start);
+    free(g->g_final);
+    free(g->slot_off);
+    free(g->slot_leaf);
+    free(g->slot_pen);
+    free(g->slot_null);
+    free(g->slot_state);
+    free(g->ls_off);
+    free(g->ls_slot);
+    free(g->leaf_lscr);
+    free(g->leaf_filler);
+    free(g->sn_off);
+    free(g->sn_to);
+    free(g->sn_pen);
     free(g);
 }
 
-/* the graph of one text, node by node, for tests and tooling (no device needed) */
-int32_t
-ssw_first_pass_graph(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
-                     int32_t n_words, const char *const *words, int32_t max_nodes,
-                     ssw_fp_node_t *nodes, int32_t *beams)
+static int32_t
+graph_nodes_out(const ssw_fp_graphs_t *g, int32_t max_nodes, ssw_fp_node_t *nodes, int32_t *beams)
 {
-    const int32_t word_off[2] = { 0, n_words };
-    ssw_fp_graphs_t *g = ssw_fp_graphs_build(m, d, cfg, 1, word_off, words);
-    int32_t n, i;
-    if (g == NULL)
-        return -1;
-    n = g->n_nodes;
+    const int32_t n = g->n_nodes;
+    int32_t i;
     if (beams) {
         beams[0] = g->beam;
         beams[1] = g->pbeam;
@@ -906,6 +943,327 @@ ssw_first_pass_graph(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_
         o->wid = lo >= 0 ? g->leaf_wid[lo] : -1;
         o->ctxt = g->ctxt[i];
     }
+    return n;
+}
+
+/* the graph of one text, node by node, for tests and tooling (no device needed) */
+int32_t
+ssw_first_pass_graph(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
+                     int32_t n_words, const char *const *words, int32_t max_nodes,
+                     ssw_fp_node_t *nodes, int32_t *beams)
+{
+    const int32_t word_off[2] = { 0, n_words };
+    ssw_fp_graphs_t *g = ssw_fp_graphs_build(m, d, cfg, 1, word_off, words);
+    int32_t n;
+    if (g == NULL)
+        return -1;
+    n = graph_nodes_out(g, max_nodes, nodes, beams);
+    ssw_fp_graphs_free(g);
+    return n;
+}
+
+/* ---- grammars (ssw_fsg_model.inc) ------------------------------------------------------------- */
+typedef struct {
+    uint64_t key;
+    int leaf, pen;
+} nslot_t;
+
+static int
+cmp_nslot(const void *a, const void *b)
+{
+    const nslot_t *x = (const nslot_t *)a, *y = (const nslot_t *)b;
+    return (x->key > y->key) - (x->key < y->key);
+}
+
+/* one grammar: the links fsg_search_init leaves (ssw_fsg_compile) into phone trees, then the
+ * slots of every state's entering list */
+static int
+build_grammar(builder_t *b, const ssw_model_t *m, const ssw_host_model_t *h, const ssw_dict_t *d,
+              const ssw_first_pass_config_t *cfg, const ssw_fsg_t *f, int gi, int wip, int pip,
+              int *cap_slots, int *cap_ls, int *cap_sn, int *cap_ll)
+{
+    ssw_fp_graphs_t *g = b->g;
+    ssw_fsg_compiled_t *c = ssw_fsg_compile(f, d, cfg, 1);
+    const int leaf_base = g->n_leaves, node_base = g->n_nodes, state_base = g->n_states;
+    link_t *links = NULL;
+    int *link_off = NULL, *nulls = NULL;
+    nslot_t *ns = NULL;
+    int n_links = 0, n_nulls = 0, s, i, rc = -1, nl;
+
+    if (c == NULL)
+        return -1;
+    for (i = 0; i < c->n_word; ++i)
+        if (c->dict_wid[i] < 0) { /* fsg_search_check_dict, src/fsg_search.c:120-141 */
+            ssw_set_error("The word '%s' is missing in the dictionary", c->vocab[i]);
+            goto done;
+        }
+    if (c->n_state > 65535) {
+        ssw_set_error("a grammar of %d states: the grammar search handles at most 65535", c->n_state);
+        goto done;
+    }
+    links = (link_t *)malloc(sizeof(link_t) * (size_t)(c->n_links ? c->n_links : 1));
+    nulls = (int *)malloc(sizeof(int) * 2 * (size_t)(c->n_links ? c->n_links : 1));
+    link_off = (int *)calloc((size_t)c->n_state + 1, sizeof(int));
+    if (!links || !nulls || !link_off)
+        goto oom;
+    for (s = 0; s < c->n_state; ++s) {
+        link_off[s] = n_links;
+        for (i = c->state_off[s]; i < c->state_off[s + 1]; ++i) {
+            const ssw_fsg_link_t *l = &c->links[i];
+            if (l->wid < 0) {
+                nulls[2 * n_nulls] = l->from;
+                nulls[2 * n_nulls + 1] = l->to;
+                ++n_nulls;
+                continue;
+            }
+            links[n_links].word = c->dict_wid[l->wid];
+            links[n_links].to = l->to;
+            links[n_links].logp = l->logp;
+            links[n_links].filler = c->is_sil[l->wid];
+            links[n_links].dfiller = ssw_dict_is_filler(d, c->dict_wid[l->wid]);
+            ++n_links;
+        }
+    }
+    link_off[c->n_state] = n_links;
+    if (build_links(b, m, h, d, c->n_state, links, link_off, n_nulls, nulls, wip, pip) < 0)
+        goto done;
+    nl = g->n_leaves - leaf_base;
+    g->g_start[gi] = c->start;
+    g->g_final[gi] = c->final;
+    /* per leaf: the link's lscr and whether the grammar counts its word as a filler.  A leaf's
+     * link is found again through its state's links: word and destination */
+    if (grow((void **)&g->leaf_lscr, cap_ll, g->n_leaves + 1, sizeof(int32_t)) < 0)
+        goto oom;
+    {
+        int c2 = *cap_ll;
+        /* (leaf_filler grows with leaf_lscr) */
+        int32_t *q = (int32_t *)realloc(g->leaf_filler, sizeof(int32_t) * (size_t)c2);
+        if (q == NULL)
+            goto oom;
+        g->leaf_filler = q;
+    }
+    for (i = 0; i < nl; ++i) {
+        const int node = node_base + g->leaf_node[leaf_base + i];
+        const int st = (int)(g->info[node] >> 16);
+        int k, found = 0;
+        for (k = link_off[st]; k < link_off[st + 1]; ++k)
+            if (links[k].word == g->leaf_wid[leaf_base + i] && links[k].to == g->leaf_to[leaf_base + i]) {
+                g->leaf_lscr[leaf_base + i] = links[k].logp >> SSW_SENSCR_SHIFT;
+                g->leaf_filler[leaf_base + i] = links[k].filler;
+                found = 1;
+                break;
+            }
+        if (!found) {
+            ssw_set_error("internal: a word-final HMM without its link");
+            goto done;
+        }
+    }
+    /* the slots.  Word exits into a state come first, by (context phone shown, ordinal) as in
+     * in_leaf -- fsg_history_end_frame files a frame's entries by (state, left context) --
+     * then the null hops into it, by the same key of their leaf: fsg_search_null_prop runs
+     * after the word exits were filed, so every null entry is newer than every word exit */
+    ns = (nslot_t *)malloc(sizeof(nslot_t) * (size_t)(nl ? nl : 1) * (size_t)(n_nulls + 1));
+    if (!ns)
+        goto oom;
+    {
+        int n_ns = 0, k2 = 0, st;
+        for (i = 0; i < nl; ++i) {
+            const int node = node_base + g->leaf_node[leaf_base + i];
+            const uint64_t ci = (uint64_t)((g->info[node] >> 8) & 0xff);
+            const int to = g->leaf_to[leaf_base + i];
+            int k;
+            ns[n_ns].key = ((uint64_t)to << 42) | (ci << 32) | (uint64_t)i;
+            ns[n_ns].leaf = i;
+            ns[n_ns].pen = INT32_MIN; /* a word exit */
+            ++n_ns;
+            for (k = 0; k < n_nulls; ++k)
+                if (nulls[2 * k] == to) {
+                    const ssw_fsg_link_t *nlk = NULL;
+                    int q;
+                    for (q = c->state_off[to]; q < c->state_off[to + 1]; ++q)
+                        if (c->links[q].wid < 0 && c->links[q].to == nulls[2 * k + 1])
+                            nlk = &c->links[q];
+                    ns[n_ns].key = ((uint64_t)nulls[2 * k + 1] << 42) | (1ull << 41) | (ci << 32) | (uint64_t)i;
+                    ns[n_ns].leaf = i;
+                    ns[n_ns].pen = nlk->logp >> SSW_SENSCR_SHIFT;
+                    ++n_ns;
+                }
+        }
+        qsort(ns, (size_t)n_ns, sizeof(nslot_t), cmp_nslot);
+        if (n_ns >= 65536) {
+            ssw_set_error("a grammar with %d entries in its states' entering lists: the grammar "
+                          "search handles at most 65535", n_ns);
+            goto done;
+        }
+        if (grow((void **)&g->slot_leaf, cap_slots, g->n_slots + n_ns + 1, sizeof(int32_t)) < 0)
+            goto oom;
+        {
+            const size_t cs = (size_t)*cap_slots;
+            int32_t *q1 = (int32_t *)realloc(g->slot_pen, sizeof(int32_t) * cs);
+            int32_t *q2 = q1 ? (int32_t *)realloc(g->slot_null, sizeof(int32_t) * cs) : NULL;
+            int32_t *q3 = q2 ? (int32_t *)realloc(g->slot_state, sizeof(int32_t) * cs) : NULL;
+            if (q1) g->slot_pen = q1;
+            if (q2) g->slot_null = q2;
+            if (q3) g->slot_state = q3;
+            if (!q3)
+                goto oom;
+        }
+        {
+            const int slot_base = g->n_slots;
+            for (st = 0; st < c->n_state; ++st) {
+                g->slot_off[state_base + st] = g->n_slots;
+                while (k2 < n_ns && (int)(ns[k2].key >> 42) == st) {
+                    g->slot_leaf[g->n_slots] = ns[k2].leaf;
+                    g->slot_null[g->n_slots] = ns[k2].pen != INT32_MIN;
+                    g->slot_pen[g->n_slots] = ns[k2].pen != INT32_MIN ? ns[k2].pen : 0;
+                    g->slot_state[g->n_slots] = st;
+                    ++g->n_slots;
+                    ++k2;
+                }
+            }
+            g->slot_off[state_base + c->n_state] = g->n_slots;
+            /* a leaf's slots, its word exit first */
+            if (grow((void **)&g->ls_slot, cap_ls, g->n_ls + n_ns + 1, sizeof(int32_t)) < 0)
+                goto oom;
+            {
+                int32_t *q = (int32_t *)realloc(g->ls_off, sizeof(int32_t) * ((size_t)g->n_leaves + 2));
+                if (q == NULL)
+                    goto oom;
+                g->ls_off = q;
+            }
+            for (i = 0; i < nl; ++i) {
+                int j, pass;
+                g->ls_off[leaf_base + i] = g->n_ls;
+                for (pass = 0; pass < 2; ++pass)
+                    for (j = slot_base; j < g->n_slots; ++j)
+                        if (g->slot_leaf[j] == i && g->slot_null[j] == pass)
+                            g->ls_slot[g->n_ls++] = j - slot_base;
+            }
+            g->ls_off[leaf_base + nl] = g->n_ls;
+        }
+    }
+    /* the null transitions out of the start state (fsg_search_start's null_prop) */
+    g->sn_off[gi] = g->n_sn;
+    for (i = c->state_off[c->start]; i < c->state_off[c->start + 1]; ++i)
+        if (c->links[i].wid < 0) {
+            if (grow((void **)&g->sn_to, cap_sn, g->n_sn + 1, sizeof(int32_t)) < 0)
+                goto oom;
+            {
+                int32_t *q = (int32_t *)realloc(g->sn_pen, sizeof(int32_t) * (size_t)*cap_sn);
+                if (q == NULL)
+                    goto oom;
+                g->sn_pen = q;
+            }
+            g->sn_to[g->n_sn] = c->links[i].to;
+            g->sn_pen[g->n_sn] = c->links[i].logp >> SSW_SENSCR_SHIFT;
+            ++g->n_sn;
+        }
+    g->sn_off[gi + 1] = g->n_sn;
+    rc = 0;
+    goto done;
+oom:
+    ssw_set_error("out of memory building the grammar's graph");
+done:
+    free(links);
+    free(link_off);
+    free(nulls);
+    free(ns);
+    ssw_fsg_compiled_free(c);
+    return rc;
+}
+
+ssw_fp_graphs_t *
+ssw_grammar_graphs_build(const ssw_model_t *m, const ssw_dict_t *d,
+                         const ssw_first_pass_config_t *cfg_in, int32_t n_fsgs,
+                         const ssw_fsg_t *const *fsgs)
+{
+    const ssw_host_model_t *h = ssw_model_host(m);
+    ssw_first_pass_config_t cfg;
+    builder_t b;
+    ssw_fp_graphs_t *g;
+    int u, wip, pip, cap_slots = 0, cap_ls = 0, cap_sn = 0, cap_ll = 0, total_states = 0;
+    const double base = h->cfg.logbase;
+
+    if (cfg_in)
+        cfg = *cfg_in;
+    else
+        ssw_first_pass_config_defaults(&cfg);
+    if (h->sil < 0 || h->sseq == NULL || h->cd_tree == NULL || h->n_emit_state != 3) {
+        ssw_set_error("the grammar search needs a 3-state model loaded with its mdef");
+        return NULL;
+    }
+    if (h->n_ciphone > 64) {
+        ssw_set_error("%d CI phones: the grammar search handles at most 64", h->n_ciphone);
+        return NULL;
+    }
+    for (u = 0; u < n_fsgs; ++u) {
+        if (fsgs[u] == NULL) {
+            ssw_set_error("grammar %d is NULL", u);
+            return NULL;
+        }
+        total_states += ssw_fsg_n_states(fsgs[u]);
+    }
+    memset(&b, 0, sizeof(b));
+    g = b.g = (ssw_fp_graphs_t *)calloc(1, sizeof(*g));
+    if (g == NULL)
+        return NULL;
+    g->n_utts = n_fsgs;
+    g->node_off = (int32_t *)calloc((size_t)n_fsgs + 1, sizeof(int32_t));
+    g->leaf_off = (int32_t *)calloc((size_t)n_fsgs + 1, sizeof(int32_t));
+    g->state_off = (int32_t *)calloc((size_t)n_fsgs + 1, sizeof(int32_t));
+    g->tw_off = (int32_t *)calloc((size_t)n_fsgs + 1, sizeof(int32_t));
+    g->tw_rk = (int32_t *)calloc((size_t)n_fsgs + 1, sizeof(int32_t));
+    g->g_start = (int32_t *)calloc((size_t)n_fsgs + 1, sizeof(int32_t));
+    g->g_final = (int32_t *)calloc((size_t)n_fsgs + 1, sizeof(int32_t));
+    g->sn_off = (int32_t *)calloc((size_t)n_fsgs + 1, sizeof(int32_t));
+    g->slot_off = (int32_t *)calloc((size_t)total_states + 1, sizeof(int32_t));
+    if (!g->node_off || !g->leaf_off || !g->state_off || !g->tw_off || !g->tw_rk || !g->g_start
+        || !g->g_final || !g->sn_off || !g->slot_off) {
+        ssw_fp_graphs_free(g);
+        ssw_set_error("out of memory building the grammar's graph");
+        return NULL;
+    }
+    g->beam = ilog0(base, cfg.beam) >> SSW_SENSCR_SHIFT;
+    g->pbeam = ilog0(base, cfg.pbeam) >> SSW_SENSCR_SHIFT;
+    g->wbeam = ilog0(base, cfg.wbeam) >> SSW_SENSCR_SHIFT;
+    pip = (int32_t)((float)ilog0(base, cfg.pip) * cfg.lw) >> SSW_SENSCR_SHIFT;
+    wip = (int32_t)((float)ilog0(base, cfg.wip) * cfg.lw) >> SSW_SENSCR_SHIFT;
+    for (u = 0; u < n_fsgs; ++u) {
+        g->node_off[u] = g->n_nodes;
+        g->leaf_off[u] = g->n_leaves;
+        g->state_off[u] = g->n_states;
+        g->tw_off[u] = g->n_tw;
+        if (build_grammar(&b, m, h, d, &cfg, fsgs[u], u, wip, pip, &cap_slots, &cap_ls, &cap_sn,
+                          &cap_ll) < 0) {
+            ssw_fp_graphs_free(g);
+            return NULL;
+        }
+        g->tw_rk[u] = b.rk_last;
+    }
+    g->tw_off[n_fsgs] = g->n_tw;
+    g->node_off[n_fsgs] = g->n_nodes;
+    g->leaf_off[n_fsgs] = g->n_leaves;
+    g->state_off[n_fsgs] = g->n_states;
+    {
+        static uint64_t next_uid = 1ull << 40; /* apart from the texts' uids */
+        g->uid = __atomic_add_fetch(&next_uid, 1, __ATOMIC_RELAXED);
+    }
+    return g;
+}
+
+int32_t
+ssw_grammar_graph(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
+                  const ssw_fsg_t *fsg, int32_t max_nodes, ssw_fp_node_t *nodes, int32_t *beams)
+{
+    ssw_fp_graphs_t *g;
+    int32_t n;
+    if (m == NULL || d == NULL || fsg == NULL) {
+        ssw_set_error("bad arguments to ssw_grammar_graph");
+        return -1;
+    }
+    if ((g = ssw_grammar_graphs_build(m, d, cfg, 1, &fsg)) == NULL)
+        return -1;
+    n = graph_nodes_out(g, max_nodes, nodes, beams);
     ssw_fp_graphs_free(g);
     return n;
 }

@@ -1,0 +1,521 @@
+/* ssw_host_grammar.inc -- host: ssw_grammar_prepare, ssw_grammar_search_batch,
+ * ssw_recognize_batch and the recognition set.
+ * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
+/* ---------------------------------------------------------------------------------- */
+/* recognition against word FSGs (decoder_set_fsg; ssw_k9_grammar.inc)                  */
+/* ---------------------------------------------------------------------------------- */
+struct ssw_grammar_plan_s {
+    ssw_fp_graphs_t *g;
+    int32_t n_fsgs;
+    size_t lds_ints; /* the largest grammar's exchange arrays */
+    int32_t max_nodes;
+};
+
+/* LDS ints of one grammar's exchange arrays: XS XH FLG [N] | EXJ IL[3] LS[2] per slot | TW |
+ * RK | SMAX [2 NS] (grammar_search_kernel) */
+static size_t
+grammar_lds_ints(const ssw_fp_graphs_t *g, int u)
+{
+    const size_t nn = (size_t)(g->node_off[u + 1] - g->node_off[u]);
+    const size_t ns = (size_t)(g->state_off[u + 1] - g->state_off[u]);
+    const size_t ne = (size_t)(g->slot_off[g->state_off[u + 1]] - g->slot_off[g->state_off[u]]);
+    return 3 * nn + 6 * ne + 2 * ns + (size_t)(g->tw_off[u + 1] - g->tw_off[u]) + (size_t)g->tw_rk[u];
+}
+
+#define SSW_GRAMMAR_LDS_BYTES (160 * 1024 - 512)
+
+extern "C" ssw_grammar_plan_t *
+ssw_grammar_prepare(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
+                    int32_t n_fsgs, const ssw_fsg_t *const *fsgs)
+{
+    if (m == NULL || d == NULL || n_fsgs < 1 || fsgs == NULL) {
+        ssw_set_error("bad arguments to ssw_grammar_prepare");
+        return NULL;
+    }
+    /* built on the calling thread, one grammar after the other (a plan's grammars are few next
+     * to a batch of texts); no device call: another host thread may prepare the next plan while
+     * the GPU searches this one */
+    ssw_fp_graphs_t *g = ssw_grammar_graphs_build(m, d, cfg, n_fsgs, fsgs);
+    if (g == NULL)
+        return NULL;
+    size_t lds = 0;
+    int32_t max_nodes = 0;
+    for (int u = 0; u < n_fsgs; ++u) {
+        const int nn = g->node_off[u + 1] - g->node_off[u];
+        const size_t li = grammar_lds_ints(g, u);
+        if (nn > SSW_GRAMMAR_MAX_HMMS) {
+            ssw_set_error("grammar %d (%s) has %d phone-tree HMMs: the grammar search holds at "
+                          "most %d in one workgroup", u, ssw_fsg_name(fsgs[u]), nn,
+                          SSW_GRAMMAR_MAX_HMMS);
+            ssw_fp_graphs_free(g);
+            return NULL;
+        }
+        if (li * sizeof(int) > SSW_GRAMMAR_LDS_BYTES) {
+            ssw_set_error("grammar %d (%s): %d phone-tree HMMs and %d entering-list entries need "
+                          "%zu bytes of exchange arrays: the workgroup's LDS holds at most %d",
+                          u, ssw_fsg_name(fsgs[u]), nn,
+                          g->slot_off[g->state_off[u + 1]] - g->slot_off[g->state_off[u]],
+                          li * sizeof(int), (int)SSW_GRAMMAR_LDS_BYTES);
+            ssw_fp_graphs_free(g);
+            return NULL;
+        }
+        lds = std::max(lds, li);
+        max_nodes = std::max(max_nodes, nn);
+    }
+    ssw_grammar_plan_t *p = new ssw_grammar_plan_t();
+    p->g = g;
+    p->n_fsgs = n_fsgs;
+    p->lds_ints = lds;
+    p->max_nodes = max_nodes;
+    return p;
+}
+
+extern "C" void
+ssw_grammar_plan_free(ssw_grammar_plan_t *p)
+{
+    if (p == NULL)
+        return;
+    ssw_fp_graphs_free(p->g);
+    delete p;
+}
+
+extern "C" int32_t
+ssw_grammar_plan_hmms(const ssw_grammar_plan_t *p, int32_t fsg)
+{
+    if (p == NULL || fsg < 0 || fsg >= p->n_fsgs)
+        return -1;
+    return p->g->node_off[fsg + 1] - p->g->node_off[fsg];
+}
+
+struct ssw_recognition_set_s {
+    const ssw_model_t *m;
+    const ssw_dict_t *d;
+    int32_t n_utts;
+    std::vector<int32_t> n_frames, status, score, seg_off, n_seg;
+    std::vector<std::string> message, hyp;
+    std::vector<char> has_hyp;
+    std::vector<ssw_fsg_seg_t> seg;
+};
+
+static size_t
+grammar_hist_budget()
+{
+    const char *e = getenv("SSW_GRAMMAR_HIST_MB");
+    if (e != NULL && atoll(e) > 0)
+        return (size_t)atoll(e) << 20;
+    return SSW_GRAMMAR_HIST_BYTES;
+}
+
+extern "C" ssw_recognition_set_t *
+ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_plan_t *plan,
+                         const int32_t *fsg_of_utt, const int16_t *d_senscr, int32_t n_frames,
+                         const int32_t *utt_off, int32_t n_utts, void *stream)
+{
+    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
+        || utt_off[0] != 0 || utt_off[n_utts] != n_frames || (n_frames > 0 && d_senscr == NULL)) {
+        ssw_set_error("bad arguments to ssw_grammar_search_batch");
+        return NULL;
+    }
+    if (m->device == SSW_DEVICE_NONE) {
+        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+        return NULL;
+    }
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return NULL;
+    const ssw_fp_graphs_t *g = plan->g;
+    hipStream_t st = (hipStream_t)stream;
+    /* the history table: (frames + 1) rows of one entry per slot, per utterance */
+    std::vector<long long> hist_off((size_t)n_utts + 1);
+    size_t hist_total = 0;
+    int max_seg = 1;
+    for (int u = 0; u < n_utts; ++u) {
+        const int gi = fsg_of_utt ? fsg_of_utt[u] : 0;
+        if (gi < 0 || gi >= plan->n_fsgs) {
+            ssw_set_error("utterance %d: grammar %d is not one of the plan's %d", u, gi, plan->n_fsgs);
+            return NULL;
+        }
+        const int T = utt_off[u + 1] - utt_off[u];
+        if (T < 0) {
+            ssw_set_error("bad arguments to ssw_grammar_search_batch");
+            return NULL;
+        }
+        const size_t ne = (size_t)(g->slot_off[g->state_off[gi + 1]] - g->slot_off[g->state_off[gi]]);
+        const size_t nsn = (size_t)(g->sn_off[gi + 1] - g->sn_off[gi]);
+        const size_t row = std::max<size_t>(std::max(ne, nsn), 1);
+        if (row * ((size_t)T + 1) >= (size_t)INT_MAX) { /* entry ids are int32 */
+            ssw_set_error("utterance %d: %zu entering-list entries x %d frames exceed the history "
+                          "table's 2^31 entries", u, row, T);
+            return NULL;
+        }
+        hist_off[(size_t)u] = (long long)hist_total;
+        hist_total += row * ((size_t)T + 1);
+        /* a path has at most one word exit per frame, each followed by at most one null entry,
+         * after at most one null entry of frame -1 */
+        max_seg = std::max(max_seg, 2 * T + 1);
+    }
+    if (hist_total * sizeof(int2) > grammar_hist_budget()) {
+        ssw_set_error("the history table of this call (%zu entries, %zu bytes: frames x "
+                      "entering-list entries, summed over %d utterances) exceeds the budget of "
+                      "%zu bytes; search fewer utterances per call", hist_total,
+                      hist_total * sizeof(int2), n_utts, grammar_hist_budget());
+        return NULL;
+    }
+    ssw_recognition_set_t *r = new ssw_recognition_set_t();
+    r->m = m;
+    r->d = d;
+    r->n_utts = n_utts;
+    r->n_frames.resize((size_t)n_utts);
+    r->status.assign((size_t)n_utts, 0);
+    r->score.assign((size_t)n_utts, 0);
+    r->message.assign((size_t)n_utts, std::string());
+    r->hyp.assign((size_t)n_utts, std::string());
+    r->has_hyp.assign((size_t)n_utts, 0);
+    r->seg_off.assign((size_t)n_utts + 1, 0);
+    r->n_seg.assign((size_t)n_utts, 0);
+    for (int u = 0; u < n_utts; ++u)
+        r->n_frames[(size_t)u] = utt_off[u + 1] - utt_off[u];
+    if (n_utts == 0)
+        return r;
+
+    /* one staging buffer -> one copy, every array at a 256-byte boundary; the graph's tables
+     * first (they stay while the plan is the last one searched), the call's after them */
+    struct piece { const void *src; size_t bytes, off; };
+    const size_t nG = (size_t)g->n_utts;
+    piece pc[] = {
+        { g->node_off, sizeof(int) * (nG + 1), 0 },                       /* 0 */
+        { g->leaf_off, sizeof(int) * (nG + 1), 0 },
+        { g->state_off, sizeof(int) * (nG + 1), 0 },
+        { g->senid, sizeof(uint16_t) * 4 * (size_t)g->n_nodes, 0 },
+        { g->pen, sizeof(int) * (size_t)g->n_nodes, 0 },
+        { g->parent, sizeof(int) * (size_t)g->n_nodes, 0 },               /* 5 */
+        { g->info, sizeof(uint32_t) * (size_t)g->n_nodes, 0 },
+        { g->ctxt, sizeof(uint64_t) * (size_t)g->n_nodes, 0 },
+        { g->leaf_ord, sizeof(int) * (size_t)g->n_nodes, 0 },
+        { g->leaf_wid, sizeof(int) * (size_t)g->n_leaves, 0 },
+        { g->leaf_node, sizeof(int) * (size_t)g->n_leaves, 0 },           /* 10 */
+        { g->leaf_lscr, sizeof(int) * (size_t)g->n_leaves, 0 },
+        { g->slot_off, sizeof(int) * ((size_t)g->n_states + 1), 0 },
+        { g->slot_leaf, sizeof(int) * (size_t)g->n_slots, 0 },
+        { g->slot_pen, sizeof(int) * (size_t)g->n_slots, 0 },
+        { g->slot_null, sizeof(int) * (size_t)g->n_slots, 0 },            /* 15 */
+        { g->slot_state, sizeof(int) * (size_t)g->n_slots, 0 },
+        { g->ls_off, sizeof(int) * ((size_t)g->n_leaves + 1), 0 },
+        { g->ls_slot, sizeof(int) * (size_t)g->n_ls, 0 },
+        { g->g_start, sizeof(int) * nG, 0 },
+        { g->g_final, sizeof(int) * nG, 0 },                              /* 20 */
+        { g->sn_off, sizeof(int) * (nG + 1), 0 },
+        { g->sn_to, sizeof(int) * (size_t)g->n_sn, 0 },
+        { g->sn_pen, sizeof(int) * (size_t)g->n_sn, 0 },
+        { g->tw, sizeof(int) * (size_t)g->n_tw, 0 },
+        { g->tw_off, sizeof(int) * (nG + 1), 0 },                         /* 25 */
+        { g->twin_ref, sizeof(int) * (size_t)g->n_nodes, 0 },
+        { g->tw_rk, sizeof(int) * nG, 0 },
+        { utt_off, sizeof(int) * ((size_t)n_utts + 1), 0 },               /* 28: the call's */
+        { fsg_of_utt, fsg_of_utt ? sizeof(int) * (size_t)n_utts : 0, 0 },
+        { hist_off.data(), sizeof(long long) * (size_t)n_utts, 0 },       /* 30 */
+    };
+    enum { PC_CALL = 28 };
+    const int n_pc = (int)(sizeof(pc) / sizeof(pc[0]));
+    size_t off = 0;
+    for (int i = 0; i < n_pc; ++i) {
+        pc[i].off = off;
+        off = (off + pc[i].bytes + 255) & ~(size_t)255;
+    }
+    const size_t in_bytes = off;
+    const size_t nseg_off = off;
+    off += (sizeof(int) * (size_t)n_utts + 255) & ~(size_t)255;
+    const size_t score_off = off;
+    off += (sizeof(int) * (size_t)n_utts + 255) & ~(size_t)255;
+    const size_t seg_off = off;
+    off += (sizeof(ssw_fsg_seg_t) * (size_t)n_utts * (size_t)max_seg + 255) & ~(size_t)255;
+    const size_t hist_at = off;
+    off += (sizeof(int2) * (hist_total ? hist_total : 1) + 255) & ~(size_t)255;
+
+    hipError_t e = hipSetDevice(m->device);
+    if (e == hipSuccess && off > m->gr_ws_cap) { /* grow-only workspace */
+        (void)hipFree(m->d_gr_ws);
+        m->d_gr_ws = NULL;
+        m->gr_ws_cap = 0;
+        m->gr_ws_uid = 0;
+        e = hipMalloc((void **)&m->d_gr_ws, off + off / 4);
+        if (e == hipSuccess)
+            m->gr_ws_cap = off + off / 4;
+    }
+    const bool cached = m->gr_ws_uid != 0 && m->gr_ws_uid == g->uid;
+    const size_t up_from = cached ? pc[PC_CALL].off : 0;
+    std::vector<unsigned char> stage(in_bytes - up_from + 1);
+    std::vector<int> n_seg((size_t)n_utts), score((size_t)n_utts);
+    std::vector<ssw_fsg_seg_t> seg((size_t)n_utts * (size_t)max_seg);
+    if (e == hipSuccess) {
+        for (int i = 0; i < n_pc; ++i)
+            if (pc[i].bytes && pc[i].off >= up_from)
+                memcpy(stage.data() + (pc[i].off - up_from), pc[i].src, pc[i].bytes);
+        e = hipMemcpyAsync(m->d_gr_ws + up_from, stage.data(), in_bytes - up_from,
+                           hipMemcpyHostToDevice, st);
+        m->gr_ws_uid = e == hipSuccess ? g->uid : 0;
+    }
+    if (e == hipSuccess) {
+        unsigned char *ws = m->d_gr_ws;
+        GrammarParams P;
+        P.senscr = d_senscr;
+        P.node_off = (const int *)(ws + pc[0].off);
+        P.leaf_off = (const int *)(ws + pc[1].off);
+        P.state_off = (const int *)(ws + pc[2].off);
+        P.senid = (const uint16_t *)(ws + pc[3].off);
+        P.pen = (const int *)(ws + pc[4].off);
+        P.parent = (const int *)(ws + pc[5].off);
+        P.info = (const uint32_t *)(ws + pc[6].off);
+        P.ctxt = (const unsigned long long *)(ws + pc[7].off);
+        P.leaf_ord = (const int *)(ws + pc[8].off);
+        P.leaf_wid = (const int *)(ws + pc[9].off);
+        P.leaf_node = (const int *)(ws + pc[10].off);
+        P.leaf_lscr = (const int *)(ws + pc[11].off);
+        P.slot_off = (const int *)(ws + pc[12].off);
+        P.slot_leaf = (const int *)(ws + pc[13].off);
+        P.slot_pen = (const int *)(ws + pc[14].off);
+        P.slot_null = (const int *)(ws + pc[15].off);
+        P.slot_state = (const int *)(ws + pc[16].off);
+        P.ls_off = (const int *)(ws + pc[17].off);
+        P.ls_slot = (const int *)(ws + pc[18].off);
+        P.g_start = (const int *)(ws + pc[19].off);
+        P.g_final = (const int *)(ws + pc[20].off);
+        P.sn_off = (const int *)(ws + pc[21].off);
+        P.sn_to = (const int *)(ws + pc[22].off);
+        P.sn_pen = (const int *)(ws + pc[23].off);
+        P.tw = (const int *)(ws + pc[24].off);
+        P.tw_off = (const int *)(ws + pc[25].off);
+        P.twin_ref = (const int *)(ws + pc[26].off);
+        P.tw_rk = (const int *)(ws + pc[27].off);
+        P.utt_off = (const int *)(ws + pc[28].off);
+        P.fsg_of_utt = fsg_of_utt ? (const int *)(ws + pc[29].off) : NULL;
+        P.hist_off = (const long long *)(ws + pc[30].off);
+        P.tp = (const uint32_t *)m->d_tp;
+        P.hist = (int2 *)(ws + hist_at);
+        P.n_seg = (int *)(ws + nseg_off);
+        P.score = (int *)(ws + score_off);
+        P.seg = (ssw_fsg_seg_t *)(ws + seg_off);
+        P.n_sen = m->h->n_sen;
+        P.max_seg = max_seg;
+        P.beam = g->beam;
+        P.pbeam = g->pbeam;
+        P.wbeam = g->wbeam;
+        P.sil = m->h->sil;
+        /* one HMM per thread while a workgroup can hold the largest grammar of the plan; beyond
+         * 1024, four or eight per thread of a 512-thread workgroup: two waves per SIMD leave a
+         * lane 256 registers, which hold eight HMMs' state (1024 threads leave 128: four HMMs
+         * per thread spilt there) */
+        void (*kern)(GrammarParams);
+        int tpb;
+        const int mn = plan->max_nodes;
+        if (mn <= 256) {
+            kern = grammar_search_kernel<1, 256>;
+            tpb = 256;
+        } else if (mn <= 512) {
+            kern = grammar_search_kernel<1, 512>;
+            tpb = 512;
+        } else if (mn <= 1024) {
+            kern = grammar_search_kernel<1, 1024>;
+            tpb = 1024;
+        } else if (mn <= 2048) {
+            kern = grammar_search_kernel<4, 512>;
+            tpb = 512;
+        } else {
+            kern = grammar_search_kernel<8, 512>;
+            tpb = 512;
+        }
+        const size_t lds_bytes = plan->lds_ints * sizeof(int);
+        if (lds_bytes > 48 * 1024)
+            e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds_bytes);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(kern, dim3(n_utts), dim3(tpb), lds_bytes, st, P);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(n_seg.data(), ws + nseg_off, sizeof(int) * (size_t)n_utts,
+                               hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(score.data(), ws + score_off, sizeof(int) * (size_t)n_utts,
+                               hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(seg.data(), ws + seg_off,
+                               sizeof(ssw_fsg_seg_t) * (size_t)n_utts * (size_t)max_seg,
+                               hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(st);
+    else
+        (void)hipStreamSynchronize(st); /* `stage` must outlive its copy */
+    if (e != hipSuccess) {
+        m->gr_ws_uid = 0;
+        ssw_set_error("ssw_grammar_search_batch: %s", hipGetErrorString(e));
+        delete r;
+        return NULL;
+    }
+    for (int u = 0; u < n_utts; ++u) {
+        const int gi = fsg_of_utt ? fsg_of_utt[u] : 0;
+        const int n = n_seg[(size_t)u];
+        r->seg_off[(size_t)u] = (int32_t)r->seg.size();
+        if (n == -1) {
+            /* fsg_search_find_exit's frame_idx is fsgs->frame at the end: the frames searched */
+            char msg[96];
+            snprintf(msg, sizeof(msg), "Final result does not match the grammar in frame %d",
+                     r->n_frames[(size_t)u]);
+            r->status[(size_t)u] = 1;
+            r->message[(size_t)u] = msg;
+            continue;
+        }
+        if (n < 0) { /* (-(3 + k) cannot happen: max_seg bounds every path) */
+            r->status[(size_t)u] = 2;
+            r->message[(size_t)u] = "No hypothesis: no word exit in any frame";
+            continue;
+        }
+        r->n_seg[(size_t)u] = n;
+        r->score[(size_t)u] = score[(size_t)u];
+        const ssw_fsg_seg_t *sg = seg.data() + (size_t)u * (size_t)max_seg;
+        r->seg.insert(r->seg.end(), sg, sg + n);
+        /* fsg_search_hyp, src/fsg_search.c:980-1029: base words, fillers and nulls left out */
+        std::string &hyp = r->hyp[(size_t)u];
+        for (int i = 0; i < n; ++i) {
+            if (sg[i].wid < 0)
+                continue;
+            /* the grammar's notion of a filler (fsg_model_is_filler): the leaf's flag; all
+             * leaves of one word in one grammar agree, so the first one found tells */
+            bool filler = false;
+            for (int l = g->leaf_off[gi]; l < g->leaf_off[gi + 1]; ++l)
+                if (g->leaf_wid[l] == sg[i].wid) {
+                    filler = g->leaf_filler[l] != 0;
+                    break;
+                }
+            if (filler)
+                continue;
+            const char *w = ssw_dict_word(d, ssw_dict_base_id(d, sg[i].wid));
+            if (!hyp.empty())
+                hyp += ' ';
+            hyp += w ? w : "";
+        }
+        r->has_hyp[(size_t)u] = hyp.empty() ? 0 : 1;
+    }
+    r->seg_off[(size_t)n_utts] = (int32_t)r->seg.size();
+    return r;
+}
+
+extern "C" ssw_recognition_set_t *
+ssw_recognize_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_plan_t *plan,
+                    const int32_t *fsg_of_utt, int scorer, const float *d_feats, int32_t n_frames,
+                    const int32_t *utt_off, int32_t n_utts, void *stream)
+{
+    if (m == NULL || n_frames < 0 || (n_frames > 0 && d_feats == NULL)) {
+        ssw_set_error("bad arguments to ssw_recognize_batch");
+        return NULL;
+    }
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return NULL;
+    if (m->device == SSW_DEVICE_NONE) {
+        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+        return NULL;
+    }
+    const size_t need = (size_t)n_frames * (size_t)m->h->n_sen;
+    if (hipSetDevice(m->device) != hipSuccess)
+        return NULL;
+    if (need > m->text_scr_cap) {
+        (void)hipFree(m->d_text_scr);
+        m->d_text_scr = NULL;
+        m->text_scr_cap = 0;
+        hipError_t e = hipMalloc((void **)&m->d_text_scr, sizeof(int16_t) * need);
+        if (e != hipSuccess) {
+            ssw_set_error("ssw_recognize_batch: %s", hipGetErrorString(e));
+            return NULL;
+        }
+        m->text_scr_cap = need;
+    }
+    if (n_frames > 0
+        && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, m->d_text_scr, stream) < 0)
+        return NULL;
+    return ssw_grammar_search_batch(m, d, plan, fsg_of_utt, m->d_text_scr, n_frames, utt_off,
+                                    n_utts, stream);
+}
+
+extern "C" int32_t
+ssw_recognition_set_status(const ssw_recognition_set_t *r, int32_t utt)
+{
+    return (r == NULL || utt < 0 || utt >= r->n_utts) ? -1 : r->status[(size_t)utt];
+}
+
+extern "C" const char *
+ssw_recognition_set_message(const ssw_recognition_set_t *r, int32_t utt)
+{
+    return (r == NULL || utt < 0 || utt >= r->n_utts) ? NULL : r->message[(size_t)utt].c_str();
+}
+
+extern "C" int32_t
+ssw_recognition_set_segments(const ssw_recognition_set_t *r, int32_t utt, const ssw_fsg_seg_t **seg)
+{
+    if (r == NULL || utt < 0 || utt >= r->n_utts)
+        return -1;
+    if (seg)
+        *seg = r->seg.data() + r->seg_off[(size_t)utt];
+    return r->n_seg[(size_t)utt];
+}
+
+extern "C" int32_t
+ssw_recognition_set_score(const ssw_recognition_set_t *r, int32_t utt, int32_t *score)
+{
+    if (r == NULL || utt < 0 || utt >= r->n_utts || r->status[(size_t)utt] != 0)
+        return -1;
+    if (score)
+        *score = r->score[(size_t)utt];
+    return 0;
+}
+
+extern "C" int32_t
+ssw_recognition_set_hyp(const ssw_recognition_set_t *r, int32_t utt, char *out, int32_t out_len)
+{
+    if (r == NULL || utt < 0 || utt >= r->n_utts || !r->has_hyp[(size_t)utt])
+        return -1;
+    const std::string &h = r->hyp[(size_t)utt];
+    if (out != NULL && out_len > 0)
+        snprintf(out, (size_t)out_len, "%s", h.c_str());
+    return (int32_t)h.size();
+}
+
+extern "C" int32_t
+ssw_recognition_set_json(const ssw_recognition_set_t *r, int32_t utt, double utt_start,
+                         int32_t frate, char *out, int32_t out_len)
+{
+    if (r == NULL || utt < 0 || utt >= r->n_utts || frate <= 0)
+        return -1;
+    const double base = r->m->h->cfg.logbase;
+    std::string s;
+    char tmp[128];
+    /* format_hyp: duration = decoder_n_frames / frate = (frames + 1) / frate, prob =
+     * logmath_exp(decoder_prob = 0) */
+    snprintf(tmp, sizeof(tmp), "{\"b\":%.3f,\"d\":%.3f,\"p\":%.3f,\"t\":\"", utt_start,
+             (double)(r->n_frames[(size_t)utt] + 1) / frate, pow(base, 0.0));
+    s += tmp;
+    s += r->hyp[(size_t)utt];
+    s += "\",\"w\":[";
+    const ssw_fsg_seg_t *sg = r->seg.data() + r->seg_off[(size_t)utt];
+    for (int i = 0; i < r->n_seg[(size_t)utt]; ++i) {
+        /* format_seg: st = start + sf / frate, dur = (ef + 1 - sf) / frate */
+        const char *w = sg[i].wid < 0 ? "(NULL)" : ssw_dict_word(r->d, sg[i].wid);
+        snprintf(tmp, sizeof(tmp), "%s{\"b\":%.3f,\"d\":%.3f,\"p\":%.3f,\"t\":\"", i ? "," : "",
+                 utt_start + (double)sg[i].sf / frate, (double)(sg[i].ef + 1 - sg[i].sf) / frate,
+                 pow(base, (double)(sg[i].ascr + sg[i].lscr)));
+        s += tmp;
+        s += w ? w : "";
+        s += "\"}";
+    }
+    s += "]}\n";
+    if (out != NULL && out_len > 0)
+        snprintf(out, (size_t)out_len, "%s", s.c_str());
+    return (int32_t)s.size();
+}
+
+extern "C" void
+ssw_recognition_set_free(ssw_recognition_set_t *r)
+{
+    delete r;
+}

@@ -245,6 +245,11 @@ struct ssw_model_s {
     int64_t fpa_stats[4]; /* utterances, verify rounds summed over them, rounds of the last call, utterances that needed more than one */
     int16_t *d_text_scr; /* ssw_align_text_batch's score rows (grow-only) */
     size_t text_scr_cap;
+    /* grammar search (ssw_host_grammar.inc): workspace (grow-only) and the plan whose graphs
+     * it holds (ssw_fp_graphs_t::uid, 0 = none) */
+    unsigned char *d_gr_ws;
+    size_t gr_ws_cap;
+    uint64_t gr_ws_uid;
     size_t align_ws_bytes;
     /* ssw_score_batch_compact's fall-back: full rows of a launch that has no COMPACT instance */
     int16_t *d_full_tmp;
@@ -653,6 +658,7 @@ ssw_model_free(ssw_model_t *m)
     (void)hipFree(m->d_align_ws);
     (void)hipFree(m->d_fp_ws);
     (void)hipFree(m->d_fpa_ws);
+    (void)hipFree(m->d_gr_ws);
     (void)hipFree(m->d_text_scr);
     (void)hipFree(m->d_feat_off);
     (void)hipFree(m->d_fe_tab);

@@ -189,7 +189,47 @@ typedef struct ssw_fp_graphs_s {
     int32_t *tw, *tw_off, *twin_ref, *tw_rk;
     int32_t beam, pbeam, wbeam;
     uint64_t uid; /* unique per built set of graphs (never 0): the device copy's cache key */
+    /* Grammar graphs only (ssw_grammar_graphs_build; NULL / 0 otherwise): one "utterance" per
+     * grammar.  A state's entering list holds SLOTS: one per word-final HMM that leads into the
+     * state, then one per (word-final HMM into a state s, closed null transition s -> state),
+     * which is how fsg_search_null_prop's entries are folded in.  Slot indices are local to
+     * their grammar (slot_off[state_off[g]] is its first). */
+    int32_t n_slots, n_ls, n_sn;
+    int32_t *g_start, *g_final; /* [n_utts] start and final state */
+    int32_t *slot_off;   /* [n_states + 1] into the slot arrays */
+    int32_t *slot_leaf;  /* [n_slots] leaf ordinal */
+    int32_t *slot_pen;   /* [n_slots] the null transition's log probability >> 10; 0 for a word exit */
+    int32_t *slot_null;  /* [n_slots] 1 for a null-hop slot */
+    int32_t *slot_state; /* [n_slots] the state the slot enters */
+    int32_t *ls_off;     /* [n_leaves + 1] a leaf's slots, into ls_slot: its word exit first */
+    int32_t *ls_slot;    /* [n_ls] */
+    int32_t *leaf_lscr;  /* [n_leaves] the link's log probability >> 10 (seg->lscr) */
+    int32_t *leaf_filler;/* [n_leaves] fsg_model_is_filler of the link's word */
+    int32_t *sn_off;     /* [n_utts + 1] null transitions out of the start state, into sn_* */
+    int32_t *sn_to, *sn_pen; /* [n_sn] */
 } ssw_fp_graphs_t;
+
+/* a grammar as fsg_search_init leaves it (ssw_fsg_model.inc): the links of every state in the
+ * order fsg_model_arcs walks them, words first, then the closed null transitions */
+typedef struct ssw_fsg_link_s {
+    int32_t from, to, logp, wid; /* logp: logs2prob (not shifted); wid: vocabulary index, -1 null */
+} ssw_fsg_link_t;
+typedef struct ssw_fsg_compiled_s {
+    int32_t n_state, start, final, n_word, n_links;
+    char **vocab;       /* [n_word] */
+    int32_t *dict_wid;  /* [n_word] dictionary id, -1 when the dictionary lacks the word */
+    uint8_t *is_sil;    /* [n_word] fsg_model_is_filler */
+    ssw_fsg_link_t *links;
+    int32_t *state_off; /* [n_state + 1] */
+    float lw;
+    double logbase;
+} ssw_fsg_compiled_t;
+ssw_fsg_compiled_t *ssw_fsg_compile(const ssw_fsg_t *f, const struct ssw_dict_s *d,
+                                    const ssw_first_pass_config_t *cfg, int searched);
+void ssw_fsg_compiled_free(ssw_fsg_compiled_t *c);
+ssw_fp_graphs_t *ssw_grammar_graphs_build(const ssw_model_t *m, const struct ssw_dict_s *d,
+                                          const ssw_first_pass_config_t *cfg, int32_t n_fsgs,
+                                          const ssw_fsg_t *const *fsgs);
 ssw_fp_graphs_t *ssw_fp_graphs_build(const ssw_model_t *m, const struct ssw_dict_s *d,
                                      const ssw_first_pass_config_t *cfg, int32_t n_utts,
                                      const int32_t *word_off, const char *const *words);

@@ -1,0 +1,462 @@
+/* ssw_k9_grammar.inc -- device: grammar_search_kernel.
+ * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
+/* ---------------------------------------------------------------------------------- */
+/* K9: recognition against a word FSG (decoder_set_fsg)                                 */
+/*   fsg_search_start             src/fsg_search.c:747-798                               */
+/*   fsg_search_step and its parts  :331-402, 404-435, 437-490, 498-541, 598-662, 665-739 */
+/*   fsg_search_null_prop         :543-591                                               */
+/*   fsg_search_find_exit (final), fsg_seg_bp2itor, fsg_search_seg_iter                   */
+/*                                :854-924, 1033-1055, 1085-1142                         */
+/* The design of K5 (ssw_k5_firstpass.inc): one workgroup per utterance, one thread per    */
+/* phone-tree HMM with its state in registers, a frame in three phases with two LDS-only   */
+/* barriers.  What a grammar adds to the linear text:                                      */
+/*   - any start and final state;                                                         */
+/*   - null transitions.  The grammar holds their transitive closure, so a word exit into  */
+/*     state s reaches, in the same frame, exactly the states one null hop from s, and the */
+/*     set of hops per state is static.  The host folds them into the states' entering     */
+/*     lists: a list entry (SLOT) is a word-final HMM that leads into the state, or a pair  */
+/*     (word-final HMM into s, null s -> state) with the null's log probability.  In phase  */
+/*     B a word-final HMM writes its exit score into every one of its slots (plus the       */
+/*     penalty, kept only if >= best + wbeam, as fsg_search_null_prop keeps it); phase C    */
+/*     is K5's: a word-initial HMM takes the best compatible slot of its state's list.      */
+/*     No extra barrier, no extra LDS round trip in phase C.                               */
+/*   - history: entry id = 1 + (frame + 1) * NE + slot (NE slots per grammar, row 0 is      */
+/*     frame -1: the null transitions out of the start state); a null slot's entry has the  */
+/*     word exit's entry of the same frame as its predecessor, as in the reference.         */
+/* Ties.  A word-initial HMM takes the first strictly better entry in history order        */
+/* (fsg_search_word_trans); fsg_search_find_exit takes the oldest of the best entries into  */
+/* the final state.  The reference files a frame's word exits by (state, left context) and  */
+/* adds the null entries after them; the lists here are in that order -- word exits by      */
+/* (left-context phone, ordinal), then null hops by the same key -- and both scans take the  */
+/* first of equals.  Alternates pronounced alike follow K5's twin records.                  */
+/* ---------------------------------------------------------------------------------- */
+struct GrammarParams {
+    const int16_t *senscr; /* [n_frames][n_sen] */
+    const int *utt_off;    /* [n_utts + 1] */
+    const int *fsg_of_utt; /* [n_utts] or NULL: grammar 0 */
+    const int *node_off, *leaf_off, *state_off; /* [n_fsgs + 1] */
+    const uint16_t *senid; /* [n_nodes][4] */
+    const int *pen, *parent;
+    const uint32_t *info;
+    const unsigned long long *ctxt;
+    const int *leaf_ord, *leaf_wid, *leaf_node, *leaf_lscr;
+    const int *slot_off; /* [n_states + 1] */
+    const int *slot_leaf, *slot_pen, *slot_null, *slot_state;
+    const int *ls_off, *ls_slot;
+    const int *g_start, *g_final, *sn_off, *sn_to, *sn_pen;
+    const int *tw, *tw_off, *twin_ref, *tw_rk;
+    const uint32_t *tp; /* [n_tmat][3] rows of 4 uint8 */
+    int2 *hist;               /* (predecessor entry, score) of every (frame + 1, slot) */
+    const long long *hist_off; /* [n_utts] */
+    int *n_seg, *score;       /* [n_utts]: segments (-1 no match, -2 no entry at all, -(3 + k): k
+                                 segments do not fit), hypothesis score */
+    ssw_fsg_seg_t *seg;       /* [n_utts][max_seg] */
+    int n_sen, max_seg, beam, pbeam, wbeam, sil;
+};
+
+/* what a phase needs of a node's constants: in registers with one HMM per thread, read again
+ * from HBM (L2-resident) every frame with more */
+struct GrNodeA {
+    uint32_t sen01, sen2t, tpa, tpb, tpc;
+};
+struct GrNodeB {
+    int leaf, ls0, ls1, twin;
+};
+struct GrNodeC {
+    int parent, pen, j0, j1;
+    uint32_t info;
+    unsigned long long ctxt;
+};
+
+/* with several HMMs per thread: keeps the compiler from fetching the constants of all of them
+ * ahead of the first one's work (their constants beside their state would not fit a lane's
+ * registers) */
+#define GR_ONE_AT_A_TIME() asm volatile("" ::: "memory")
+
+template <int NPT, int TPB> /* HMMs per thread, threads */
+__global__ void __launch_bounds__(TPB)
+grammar_search_kernel(GrammarParams P)
+{
+    extern __shared__ int gr_lds[];
+    const int u = (int)blockIdx.x, tid = threadIdx.x;
+    const int gi = P.fsg_of_utt != NULL ? P.fsg_of_utt[u] : 0;
+    const int nb = P.node_off[gi], N = P.node_off[gi + 1] - nb;
+    const int lb = P.leaf_off[gi];
+    const int sb = P.state_off[gi], NS = P.state_off[gi + 1] - sb;
+    const int f0 = P.utt_off[u], T = P.utt_off[u + 1] - f0;
+    const int W = SSW_WORST_SCORE;
+    const int *slot_off = P.slot_off + sb;
+    const int j_base = slot_off[0], NE = slot_off[NS] - j_base;
+    const int snb = P.sn_off[gi], NSN = P.sn_off[gi + 1] - snb;
+    const int ROW = NE > NSN ? (NE > 0 ? NE : 1) : NSN; /* history entries per frame */
+    const int start = P.g_start[gi], fin = P.g_final[gi];
+    /* LDS: XS / XH the exit a node offers its successors; FLG how it came through the frame
+     * (twins); EXJ the frame's entries by slot; IL three ints per slot (left-context phone shown |
+     * "any right context", right-context set); LS two ints per (leaf, slot): slot | state << 16,
+     * penalty; TW / RK the twin records; SMAX best entry into each state, by frame parity */
+    const int NTW = P.tw_off[gi + 1] - P.tw_off[gi], NRK = P.tw_rk[gi];
+    int *XS = gr_lds, *XH = XS + N, *FLG = XH + N, *EXJ = FLG + N, *IL = EXJ + NE;
+    int *LS = IL + 3 * NE, *TW = LS + 2 * NE, *RK = TW + NTW, *SMAX = RK + NRK;
+    __shared__ int s_red[TPB / 64], s_any[2], s_final_id, s_final_score, s_have;
+    const uint16_t *senid = P.senid + (size_t)nb * 4;
+    const int *pen = P.pen + nb, *parent = P.parent + nb, *leaf_ord = P.leaf_ord + nb;
+    const uint32_t *info = P.info + nb;
+    const unsigned long long *ctxt = P.ctxt + nb;
+    const int *leaf_node = P.leaf_node + lb;
+    const int *ls_off = P.ls_off + lb;
+    const int ls_base = ls_off[0];
+    int2 *hist = P.hist + P.hist_off[u];
+
+    for (int j = tid; j < NE; j += TPB) {
+        const int lo = P.slot_leaf[j_base + j], ln = leaf_node[lo];
+        const uint32_t li = info[ln];
+        IL[3 * j] = (int)((((li >> 8) & 0xff) << 16) | ((li & FP_ALLRC) ? 1u << 24 : 0u));
+        IL[3 * j + 1] = (int)(uint32_t)(ctxt[ln] & 0xffffffffull);
+        IL[3 * j + 2] = (int)(uint32_t)(ctxt[ln] >> 32);
+        EXJ[j] = FP_NO_EXIT;
+        /* (a leaf's slots are ls_slot[ls_off[leaf] ..): NE of them in all */
+        const int sj = P.ls_slot[ls_base + j];
+        LS[2 * j] = sj | (P.slot_state[j_base + sj] << 16);
+        LS[2 * j + 1] = P.slot_pen[j_base + sj];
+    }
+    for (int i = tid; i < NTW; i += TPB)
+        TW[i] = P.tw[P.tw_off[gi] + i];
+    for (int i = tid; i < NRK; i += TPB)
+        RK[i] = FP_RANK_NONE;
+    for (int i = tid; i < 2 * NS; i += TPB)
+        SMAX[i] = FP_NO_EXIT;
+    if (tid == 0) {
+        /* fsg_search_start: the null transitions out of the start state are history entries of
+         * frame -1 (kept under 0 + wbeam), row 0 of the table; the best of them into the final
+         * state is what find_exit returns when no word ever exits */
+        int be = INT_MIN, bid = -1, have = 0;
+        for (int k = 0; k < NSN; ++k) {
+            const int sc = P.sn_pen[snb + k];
+            hist[k] = make_int2(0, sc);
+            if (sc >= P.wbeam) {
+                have = 1;
+                if (P.sn_to[snb + k] == fin && sc > be) {
+                    be = sc;
+                    bid = 1 + k;
+                }
+            }
+        }
+        s_final_id = bid;
+        s_final_score = be;
+        s_have = have;
+        s_any[0] = s_any[1] = 0;
+    }
+    if (tid < TPB / 64)
+        s_red[tid] = W; /* waves that leave below never write their slot */
+
+    auto node_a = [&](int n) {
+        const uint16_t *sn = senid + (size_t)n * 4;
+        const uint32_t *tp = P.tp + (size_t)sn[3] * 3;
+        return GrNodeA{ (uint32_t)sn[0] | ((uint32_t)sn[1] << 16),
+                        (uint32_t)sn[2] | ((uint32_t)sn[3] << 16), tp[0], tp[1], tp[2] };
+    };
+    auto node_b = [&](int n) {
+        const int lf = leaf_ord[n];
+        const int l = lf >= 0 ? lf : 0;
+        return GrNodeB{ lf, ls_off[l] - ls_base, ls_off[l + 1] - ls_base, P.twin_ref[nb + n] };
+    };
+    auto node_c = [&](int n) {
+        const uint32_t inf = info[n];
+        const int d = (int)(inf >> 16);
+        const bool root = (inf & FP_ROOT) != 0;
+        return GrNodeC{ parent[n], pen[n], root ? slot_off[d] - j_base : 0,
+                        root ? slot_off[d + 1] - j_base : 0, inf, ctxt[n] };
+    };
+
+    int s0[NPT], s1[NPT], s2[NPT], h0[NPT], h1[NPT], h2[NPT], os[NPT], oh[NPT], bsc[NPT];
+    bool act[NPT];
+    /* one HMM per thread: its constants stay in registers, and so do the dwords that hold its
+     * next two frames' scores (K5: frame f's are requested at the top of frame f - 2) */
+    GrNodeA ra = {};
+    GrNodeB rb = {};
+    GrNodeC rc = {};
+    uint32_t nx0 = 0, nx1 = 0, nx2 = 0, ny0 = 0, ny1 = 0, ny2 = 0;
+    if (NPT == 1) {
+        const int nn = tid < N ? tid : 0;
+        ra = node_a(nn);
+        rb = node_b(nn);
+        rc = node_c(nn);
+        if (tid >= N) {
+            rb.leaf = -1;
+            rb.twin = -1;
+            rc.parent = -1;
+            rc.info = 0u;
+            rc.j0 = rc.j1 = 0;
+        }
+        if (T > 0) { /* (uniform) */
+            const ScoreRow r0 = score_row(P.senscr, (size_t)f0 * P.n_sen);
+            const ScoreRow r1 = score_row(P.senscr, (size_t)(f0 + (T > 1 ? 1 : 0)) * P.n_sen);
+            nx0 = score_dword(r0, ra.sen01 & 0xffff);
+            nx1 = score_dword(r0, ra.sen01 >> 16);
+            nx2 = score_dword(r0, ra.sen2t & 0xffff);
+            ny0 = score_dword(r1, ra.sen01 & 0xffff);
+            ny1 = score_dword(r1, ra.sen01 >> 16);
+            ny2 = score_dword(r1, ra.sen2t & 0xffff);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+        const int n = tid + k * TPB;
+        const bool v = n < N;
+        s0[k] = s1[k] = s2[k] = os[k] = bsc[k] = W;
+        h0[k] = h1[k] = h2[k] = oh[k] = -1;
+        act[k] = false;
+        if (v) {
+            const GrNodeC c = NPT == 1 ? rc : node_c(n);
+            /* fsg_search_start: the dummy entry 0 (score 0, left context SIL, every right
+             * context), then the entries null_prop made of it, enter the word-initial HMMs of
+             * their states under beam alone; the first strictly better one stays */
+            if ((c.info & FP_ROOT) && ((c.ctxt >> P.sil) & 1)) {
+                const int d = (int)(c.info >> 16);
+                if (d == start && c.pen > P.beam && c.pen > s0[k]) {
+                    s0[k] = c.pen;
+                    h0[k] = 0;
+                    act[k] = true;
+                }
+                for (int q = 0; q < NSN; ++q) {
+                    const int sc = P.sn_pen[snb + q];
+                    if (P.sn_to[snb + q] == d && sc >= P.wbeam && sc + c.pen > P.beam
+                        && sc + c.pen > s0[k]) {
+                        s0[k] = sc + c.pen;
+                        h0[k] = 1 + q;
+                        act[k] = true;
+                    }
+                }
+            }
+            FLG[n] = act[k] ? (FP_F_NEXT | FP_F_ENTW) : 0;
+        }
+    }
+    __syncthreads();
+    /* waves without a single HMM of THIS grammar leave now (K5) */
+    if ((tid & ~63) >= N && tid >= 64) /* (the first wave stays: it writes the result) */
+        return;
+    const int alive = N <= 64 ? 64 : ((N + 63) & ~63) < TPB ? ((N + 63) & ~63) : TPB; /* threads that stay */
+
+    auto frame = [&](const int f, uint32_t &q0, uint32_t &q1, uint32_t &q2) {
+        const ScoreRow rf = score_row(P.senscr, (size_t)(f0 + f) * P.n_sen);
+        /* A: hmm_vit_eval of the active nodes, best score of the frame */
+        int bs = W;
+        if (NPT == 1) {
+            /* the empty asm pins the wait for this frame's loads HERE (K5) */
+            uint32_t a = q0, b = q1, c = q2;
+            asm volatile("" : "+v"(a), "+v"(b), "+v"(c));
+            const int c0 = score_of(a, rf.lo, ra.sen01 & 0xffff);
+            const int c1 = score_of(b, rf.lo, ra.sen01 >> 16);
+            const int c2 = score_of(c, rf.lo, ra.sen2t & 0xffff);
+            const int fn = f + 2 < T ? f + 2 : T - 1;
+            const ScoreRow rn = score_row(P.senscr, (size_t)(f0 + fn) * P.n_sen);
+            q0 = score_dword(rn, ra.sen01 & 0xffff);
+            q1 = score_dword(rn, ra.sen01 >> 16);
+            q2 = score_dword(rn, ra.sen2t & 0xffff);
+            if (act[0]) {
+                bsc[0] = vit_eval_3st(s0[0], s1[0], s2[0], h0[0], h1[0], h2[0], os[0], oh[0], -c0,
+                                      -c1, -c2, ra.tpa, ra.tpb, ra.tpc);
+                bs = bsc[0];
+            }
+        } else {
+            /* several HMMs per thread: one after the other, the constants and the scores of the
+             * active ones fetched as they come (registers for four HMMs' state, not for their
+             * constants as well) */
+#pragma unroll
+            for (int k = 0; k < NPT; ++k) {
+                if (act[k]) {
+                    const GrNodeA na = node_a(tid + k * TPB);
+                    const int c0 = score_of(score_dword(rf, na.sen01 & 0xffff), rf.lo, na.sen01 & 0xffff);
+                    const int c1 = score_of(score_dword(rf, na.sen01 >> 16), rf.lo, na.sen01 >> 16);
+                    const int c2 = score_of(score_dword(rf, na.sen2t & 0xffff), rf.lo, na.sen2t & 0xffff);
+                    bsc[k] = vit_eval_3st(s0[k], s1[k], s2[k], h0[k], h1[k], h2[k], os[k], oh[k],
+                                          -c0, -c1, -c2, na.tpa, na.tpb, na.tpc);
+                    bs = bsc[k] > bs ? bsc[k] : bs;
+                }
+                GR_ONE_AT_A_TIME();
+            }
+        }
+        bs = wave_max_dpp(bs);
+        if ((tid & 63) == 0)
+            s_red[tid >> 6] = bs;
+        lds_barrier();
+        int best = s_red[0];
+#pragma unroll
+        for (int k = 1; k < TPB / 64; ++k)
+            best = s_red[k] > best ? s_red[k] : best;
+        const int thresh = best + P.beam, pth = best + P.pbeam, wth = best + P.wbeam;
+
+        /* B: every node offers its exit to its successors; a word-final HMM that passes the
+         * word beam files a word exit, and from it one entry per null transition out of the
+         * state it leads to (fsg_search_hmm_prune_prop, fsg_search_null_prop) */
+        bool keep[NPT];
+        int any = 0;
+        const int hrow = (f + 1) * ROW;
+        for (int i = tid; i < NS; i += alive) /* next frame's buffer */
+            SMAX[((f + 1) & 1) * NS + i] = FP_NO_EXIT;
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            const int n = tid + k * TPB;
+            keep[k] = act[k] && bsc[k] >= thresh;
+            if (n < N) {
+                const GrNodeB b = NPT == 1 ? rb : node_b(n);
+                XS[n] = (keep[k] && os[k] >= pth) ? os[k] : INT_MIN;
+                XH[n] = oh[k];
+                if (b.leaf >= 0) {
+                    bool ex = keep[k] && os[k] >= wth;
+                    if (b.twin >= 0)
+                        ex = twin_first_in_list(TW + b.twin, RK, FLG, f) && ex;
+                    int id0 = 0;
+                    for (int i = b.ls0; i < b.ls1; ++i) {
+                        const int w = LS[2 * i], j = w & 0xffff;
+                        const int sc = os[k] + LS[2 * i + 1];
+                        /* (the word exit's own slot comes first, with penalty 0) */
+                        const bool in = ex && sc >= wth;
+                        EXJ[j] = in ? sc : FP_NO_EXIT;
+                        if (in) {
+                            hist[(size_t)hrow + j] = make_int2(i == b.ls0 ? oh[k] : id0, sc);
+                            atomicMax(&SMAX[(f & 1) * NS + (int)((uint32_t)w >> 16)], sc);
+                        }
+                        if (i == b.ls0)
+                            id0 = 1 + hrow + j;
+                    }
+                    any |= ex ? 1 : 0;
+                }
+            }
+            if (NPT > 1)
+                GR_ONE_AT_A_TIME();
+        }
+        if (any)
+            s_any[f & 1] = 1;
+        lds_barrier();
+
+        /* C: phone transition into every node from its one predecessor, cross-word transition
+         * into every word-initial node from the entries into its state, then the node settles
+         * whether it stays active */
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            const int n = tid + k * TPB;
+            if (n >= N)
+                continue;
+            if (NPT > 1)
+                GR_ONE_AT_A_TIME();
+            const GrNodeC c = NPT == 1 ? rc : node_c(n);
+            bool entered = false, entered_p = false, entered_w = false;
+            const int p = c.parent >= 0 ? c.parent : 0;
+            const int xs = XS[p], xh = XH[p];
+            if (c.parent >= 0 && xs != INT_MIN) {
+                const int ns = xs + c.pen;
+                if (ns > thresh && ns > s0[k]) {
+                    s0[k] = ns; /* hmm_enter */
+                    h0[k] = xh;
+                    entered = entered_p = true;
+                }
+            }
+            if (c.info & FP_ROOT) {
+                const int mx = SMAX[(f & 1) * NS + (int)(c.info >> 16)];
+                if (mx != FP_NO_EXIT && mx + c.pen > thresh && mx + c.pen > s0[k]) {
+                    const int ci = (int)((c.info >> 8) & 0xff);
+                    int be = FP_NO_EXIT, bid = -1;
+                    for (int j = c.j0; j < c.j1; ++j) {
+                        const int ex = EXJ[j];
+                        if (ex == FP_NO_EXIT || ex <= be)
+                            continue;
+                        const uint32_t w = (uint32_t)IL[3 * j];
+                        if (!((c.ctxt >> ((w >> 16) & 0xff)) & 1))
+                            continue;
+                        const unsigned long long rcs = (unsigned long long)(uint32_t)IL[3 * j + 1]
+                            | ((unsigned long long)(uint32_t)IL[3 * j + 2] << 32);
+                        if (!((w >> 24) & 1) && !((rcs >> ci) & 1))
+                            continue;
+                        be = ex;
+                        bid = j;
+                    }
+                    if (bid >= 0) {
+                        const int ns = be + c.pen;
+                        if (ns > thresh && ns > s0[k]) {
+                            s0[k] = ns;
+                            h0[k] = 1 + hrow + bid;
+                            entered = entered_w = true;
+                        }
+                    }
+                }
+            }
+            const bool stay = keep[k] || entered;
+            FLG[n] = (stay ? FP_F_NEXT : 0) | (keep[k] ? FP_F_KEEP : 0)
+                | (entered_p ? FP_F_ENTP : 0) | (entered_w ? FP_F_ENTW : 0);
+            if (act[k] && !stay) { /* fsg_psubtree_pnode_deactivate -> hmm_clear */
+                s0[k] = s1[k] = s2[k] = os[k] = bsc[k] = W;
+                h0[k] = h1[k] = h2[k] = oh[k] = -1;
+            }
+            act[k] = stay;
+        }
+        /* fsg_search_find_exit, final: the LAST frame that has any entry, the best entry into
+         * the final state, null entries included; of equals the oldest (first in the list) */
+        if (tid == 0) {
+            if (s_any[f & 1]) {
+                int be = INT_MIN, bid = -1;
+                for (int j = slot_off[fin] - j_base; j < slot_off[fin + 1] - j_base; ++j)
+                    if (EXJ[j] != FP_NO_EXIT && EXJ[j] > be) {
+                        be = EXJ[j];
+                        bid = j;
+                    }
+                s_final_id = bid >= 0 ? 1 + hrow + bid : -1;
+                s_final_score = be;
+                s_have = 1;
+            }
+            s_any[(f + 1) & 1] = 0;
+        }
+        /* no barrier here: the next frame writes XS / EXJ only after its own first barrier,
+         * which every reader above has to reach first */
+    };
+    for (int f = 0; f < T; f += 2) { /* (T is the same in every wave of the group: barriers) */
+        frame(f, nx0, nx1, nx2);
+        if (f + 1 < T)
+            frame(f + 1, ny0, ny1, ny2);
+    }
+    __syncthreads(); /* the entries written to HBM during the loop are read back below */
+
+    /* fsg_search_seg_iter + fsg_seg_bp2itor: walk the predecessors back, then write the entries
+     * in order.  Entry id -> row (id - 1) / ROW = frame + 1, slot (id - 1) % ROW. */
+    if (tid == 0) {
+        int id = s_final_id, n = 0;
+        ssw_fsg_seg_t *seg = P.seg + (size_t)u * P.max_seg;
+        if (id < 0)
+            n = s_have ? -1 : -2;
+        else {
+            for (int k = id; k > 0; k = hist[k - 1].x)
+                ++n;
+            if (n > P.max_seg)
+                n = -(3 + n);
+            else {
+                int j = n - 1;
+                for (int k = id; k > 0; k = hist[k - 1].x, --j) {
+                    const int row = (k - 1) / ROW, sl = (k - 1) % ROW;
+                    const int2 e = hist[k - 1];
+                    const int pk = e.x;
+                    const int pscore = pk > 0 ? hist[pk - 1].y : 0;
+                    const int ef = row - 1;
+                    int sf = pk > 0 ? (pk - 1) / ROW : 0; /* predecessor's frame + 1 */
+                    sf = sf > ef ? ef : sf;
+                    int wid = -1, lscr;
+                    if (row == 0)
+                        lscr = P.sn_pen[snb + sl];
+                    else if (P.slot_null[j_base + sl])
+                        lscr = P.slot_pen[j_base + sl];
+                    else {
+                        const int lo = P.slot_leaf[j_base + sl];
+                        wid = P.leaf_wid[lb + lo];
+                        lscr = P.leaf_lscr[lb + lo];
+                    }
+                    seg[j].wid = wid;
+                    seg[j].sf = sf;
+                    seg[j].ef = ef;
+                    seg[j].lscr = lscr;
+                    seg[j].ascr = e.y - pscore - lscr;
+                }
+            }
+            P.score[u] = s_final_score;
+        }
+        P.n_seg[u] = n;
+    }
+}

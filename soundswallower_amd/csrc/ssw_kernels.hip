@@ -38,6 +38,9 @@
  *                        fe_noise_kernel (fe_remove_noise, one wave per utterance),
  *                        fe_cep_kernel (log, DCT-II or legacy transform, lifter),
  *                        src/fe_sigproc.c:219-738, src/fe_noise.c:111-327
+ *   ssw_k9_grammar.inc   grammar_search_kernel: K5's search over the phone trees of any word FSG,
+ *                        null transitions folded into the states' entering lists
+ *                        (fsg_search_start / _null_prop / _find_exit, src/fsg_search.c:543-924)
  *   ssw_host_*.inc       device model and loaders' upload, batched scoring, alignment, the
  *                        mgau_t / search-module shaped objects, features, the front end
  *                        (ssw_host_fe.inc; its tables are built in ssw_model.c), device-memory
@@ -90,6 +93,7 @@ namespace {
 #include "ssw_k6_compact.inc"
 #include "ssw_k7_fpactive.inc"
 #include "ssw_k8_fe.inc"
+#include "ssw_k9_grammar.inc"
 
 } // namespace
 
@@ -104,5 +108,6 @@ namespace {
 #include "ssw_host_fe.inc"
 #include "ssw_host_firstpass.inc"
 #include "ssw_host_fpactive.inc"
+#include "ssw_host_grammar.inc"
 #include "ssw_host_devmem.inc"
 #include "ssw_host_comm.inc"

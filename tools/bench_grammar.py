@@ -1,0 +1,126 @@
+"""Times the grammar search (ssw_grammar_search_batch) on the GPU and writes
+profiles/grammar_bench.json.
+
+256 copies of the committed recording (tests/golden/goforward.raw, 278 frames each), scored once
+(front end, features and all senones on the GPU; not timed), then, alternating and repeated:
+
+    goforward   the search against tests/golden/fsg/goforward.fsg
+    loop        the search against tests/golden/fsg/loop.fsg
+    chain_fsg   the chain "go forward ten meters" as an FSG through the grammar instance
+    chain_text  the same text through ssw_first_pass_batch with its graphs prepared
+                (ssw_first_pass_run), the path the grammar instance is compared with
+
+Each figure is the host clock around one call that ends in the call's own stream synchronise
+(graph upload where it is not cached, launch, results back), the median and the spread of
+--reps calls after --warmup calls; `ratio_chain` = chain_fsg / chain_text medians.  Needs a GPU:
+there is no CPU figure, and without a device the script fails.
+
+    python tools/bench_grammar.py [--utts 256] [--reps 30] [--warmup 5] [--out FILE]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--utts", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grammar_bench.json"))
+    a = ap.parse_args()
+
+    import torch
+
+    import soundswallower_amd as ssw
+    from soundswallower_amd import _lib
+    from soundswallower_amd.api import WORD_SEG_DTYPE, _ptr
+    from tests import fsg_common as G
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_grammar: no GPU; nothing is measured without one")
+    mdir = ssw.model_dir("en-us")
+    m = ssw.Model(mdir)
+    lex = ssw.Lexicon(m, os.path.join(mdir, "dict.txt"), os.path.join(mdir, "noisedict.txt"))
+    cep, _ = m.fe_batch(G.pcm("goforward.raw", 0))
+    scr = m.score_batch(m.feat_batch(cep))
+    T, n = len(scr), a.utts
+    d = torch.from_numpy(np.ascontiguousarray(np.tile(scr, (n, 1)))).cuda()
+    off = (np.arange(n + 1) * T).astype(np.int32)
+    words = "go forward ten meters".split()
+
+    plans = {
+        "goforward": lex.grammar_plan(ssw.Fsg.read(m, lex, G.fsg_path("goforward"))),
+        "loop": lex.grammar_plan(ssw.Fsg.read(m, lex, G.fsg_path("loop"))),
+        "chain_fsg": lex.grammar_plan(ssw.Fsg.create(
+            m, lex, "chain", 0, len(words), [(i, i + 1, 1.0, w) for i, w in enumerate(words)])),
+    }
+    text_plan = ssw.FirstPassPlan(m, lex, [words] * n)
+    L = _lib.lib()
+    max_seg = 4 * len(words) + 8
+    n_seg = np.zeros(n, np.int32)
+    seg = np.zeros((n, max_seg), WORD_SEG_DTYPE)
+
+    def run_text():
+        rc = L.ssw_first_pass_run(m._m, text_plan._p, _ptr(d), int(off[-1]), _ptr(off), max_seg,
+                                  _ptr(n_seg), _ptr(seg), None)
+        assert rc == 0, _lib.last_error()
+
+    def run_fsg(name):
+        r = ssw.grammar_search_batch(m, lex, d, off, plans[name])
+        r.free()
+
+    calls = {"goforward": lambda: run_fsg("goforward"), "loop": lambda: run_fsg("loop"),
+             "chain_fsg": lambda: run_fsg("chain_fsg"), "chain_text": run_text}
+    # the results the timed calls compute, once, for the record
+    r = ssw.grammar_search_batch(m, lex, d, off, plans["chain_fsg"])
+    run_text()
+    total, got = 0, []
+    for w, sf, ef, ascr, lscr in r.segments(n - 1):
+        total += ascr + lscr
+        got.append((w, sf, ef - sf + 1, total))
+    want = [(lex.word(int(s["wid"])), int(s["start"]), int(s["duration"]), int(s["score"]))
+            for s in seg[n - 1, :n_seg[n - 1]]]
+    same = got == want
+    hyp = {k: ssw.grammar_search_batch(m, lex, d, off, plans[k]).hyp(0) for k in plans}
+
+    times = {k: [] for k in calls}
+    for i in range(a.warmup + a.reps):
+        for k, fn in calls.items():          # alternating: the versions share whatever the box does
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            dt = (time.perf_counter() - t0) * 1e3
+            if i >= a.warmup:
+                times[k].append(dt)
+    out = {
+        "what": "ssw_grammar_search_batch / ssw_first_pass_run, host clock around one synchronous "
+                "call, ms; measured on the GPU named below",
+        "device": torch.cuda.get_device_name(0),
+        "utterances": n, "frames_per_utterance": T, "reps": a.reps, "warmup": a.warmup,
+        "hmms": {k: plans[k].hmms() for k in plans},
+        "hyp": hyp,
+        "chain_fsg_equals_chain_text": bool(same),
+        "ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4),
+                   "max": round(max(v), 4)} for k, v in times.items()},
+    }
+    out["us_per_frame"] = {k: round(1e3 * out["ms"][k]["median"] / T, 3) for k in times}
+    out["ratio_chain"] = round(out["ms"]["chain_fsg"]["median"] / out["ms"]["chain_text"]["median"], 3)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
