@@ -741,6 +741,37 @@ ssw_recognition_set_t *ssw_recognize_batch(ssw_model_t *m, const ssw_dict_t *d,
                                            const int32_t *fsg_of_utt, int scorer,
                                            const float *d_feats, int32_t n_frames,
                                            const int32_t *utt_off, int32_t n_utts, void *stream);
+/* ssw_recognize_batch in the reference's DEFAULT configuration (compallsen = no): what a caller
+ * of decoder_set_fsg, decoder_process_int16 and decoder_hyp gets from an unmodified library.
+ * Replaces, per frame, fsg_search_sen_active (src/fsg_search.c:310-325: the senones of the HMMs
+ * in pnode_active are the ones acmod scores), acmod's flags2list with its bridge entries
+ * (src/acmod.c:947-999) in front of the scorer, and fsg_search_step (src/fsg_search.c:664-739),
+ * for a batch, by the speculation and proof ssw_first_pass_batch_active describes above: the
+ * sets of active HMMs are assumed, the batch is scored with them, searched, and an utterance
+ * whose search took the assumed sets frame for frame is the reference's search.  Hypotheses,
+ * scores and segments are those of the default configuration (the texts are the compallsen = yes
+ * ones on the reference's recordings, every score differs).  Limits as
+ * ssw_first_pass_batch_active: 3-state HMMs, <= 64 codebooks, ds = 1 with the PTM scorer, the
+ * per-frame kernels' LDS against the plan's largest grammar; refused with a message otherwise.
+ *   d_senscr  NULL, or device int16 [n_frames][n_sen]: the rows as acmod's buffer would hold
+ *             them (ssw_grammar_search_batch over them gives the same set)
+ *   listed    NULL, or host uint32 [n_frames][(n_sen + 31) / 32]: the proven listed senones of
+ *             every frame, bridges included
+ *   rounds    NULL, or host int32 [n_utts]: searches over default-configuration scores the
+ *             utterance took (1: its first assumption was proven; 0 only for a call without
+ *             utterances)
+ * The set is read through the ssw_recognition_set_* calls below.  Synchronous on `stream`. */
+ssw_recognition_set_t *ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d,
+                                                  const ssw_grammar_plan_t *plan,
+                                                  const int32_t *fsg_of_utt, int scorer,
+                                                  const float *d_feats, int32_t n_frames,
+                                                  const int32_t *utt_off, int32_t n_utts,
+                                                  int16_t *d_senscr, uint32_t *listed,
+                                                  int32_t *rounds, void *stream);
+/* ssw_first_pass_active_stats for ssw_recognize_batch_active: [0] utterances searched that way
+ * since ssw_model_load, [1] their rounds summed, [2] rounds of the last call, [3] utterances
+ * that needed more than one */
+int ssw_grammar_active_stats(ssw_model_t *m, int64_t stats[4]);
 int32_t ssw_recognition_set_status(const ssw_recognition_set_t *r, int32_t utt);
 const char *ssw_recognition_set_message(const ssw_recognition_set_t *r, int32_t utt);
 /* decoder_seg_iter (src/fsg_search.c:1084-1142): the path's entries, null transitions

@@ -237,6 +237,10 @@ def lib() -> C.CDLL:
     L.ssw_grammar_search_batch.argtypes = [vp, vp, vp, vp, vp, i32, vp, i32, vp]
     L.ssw_recognize_batch.restype = vp
     L.ssw_recognize_batch.argtypes = [vp, vp, vp, vp, C.c_int, vp, i32, vp, i32, vp]
+    L.ssw_recognize_batch_active.restype = vp
+    L.ssw_recognize_batch_active.argtypes = [vp, vp, vp, vp, C.c_int, vp, i32, vp, i32, vp, vp, vp, vp]
+    L.ssw_grammar_active_stats.restype = C.c_int
+    L.ssw_grammar_active_stats.argtypes = [vp, vp]
     L.ssw_recognition_set_status.restype = i32
     L.ssw_recognition_set_status.argtypes = [vp, i32]
     L.ssw_recognition_set_message.restype = C.c_char_p

@@ -295,6 +295,12 @@ class Model:
         self._L.ssw_first_pass_active_stats(self._m, _ptr(st))
         return tuple(int(x) for x in st)
 
+    def grammar_active_stats(self):
+        """ssw_grammar_active_stats: first_pass_active_stats for recognize_batch_active"""
+        st = np.zeros(4, np.int64)
+        self._L.ssw_grammar_active_stats(self._m, _ptr(st))
+        return tuple(int(x) for x in st)
+
     def first_pass_active_carry(self, n_utts):
         """ssw_first_pass_active_carry: uint8 [n_utts][n_cb][n_feat][4] codewords, best first --
         what the last align_text_batch_active call with two_pass_history handed on."""
@@ -1317,13 +1323,37 @@ def recognize_batch(model: Model, lex: Lexicon, d_feats, utt_off, plan: GrammarP
     return RecognitionSet(L, h, lex, n_utts)
 
 
+def recognize_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, plan: GrammarPlan,
+                           fsg_of_utt=None, scorer=SCORER_PTM, d_senscr=None, want_listed=False,
+                           stream=None):
+    """ssw_recognize_batch_active: recognition in the reference's DEFAULT configuration
+    (compallsen = no) from feature rows in HBM.  Returns (RecognitionSet, rounds int32 [n_utts])
+    and, with want_listed, the uint32 [n_frames][(n_sen + 31) / 32] bitmap of the listed senones
+    of every frame (bridges included) as a third item.  d_senscr: optional device int16
+    [n_frames][n_sen] that receives the rows as acmod's buffer would hold them."""
+    off = np.ascontiguousarray(utt_off, np.int32)
+    n_utts = len(off) - 1
+    g = _fsg_of_utt(fsg_of_utt, n_utts)
+    rounds = np.zeros(n_utts, np.int32)
+    listed = np.zeros((int(off[-1]), (model.n_sen + 31) // 32), np.uint32) if want_listed else None
+    L = _lib.lib()
+    h = L.ssw_recognize_batch_active(model._m, lex._d, plan._p, _ptr(g), scorer, _ptr(d_feats),
+                                     int(off[-1]), _ptr(off), n_utts, _ptr(d_senscr),
+                                     _ptr(listed), _ptr(rounds), _ptr(stream))
+    if not h:
+        raise SswError("ssw_recognize_batch_active: " + _lib.last_error())
+    r = RecognitionSet(L, h, lex, n_utts)
+    return (r, rounds, listed) if want_listed else (r, rounds)
+
+
 def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: GrammarPlan,
                           fsg_of_utt=None, samprate=None, fe_cfg=None, scorer=SCORER_PTM,
-                          stream=None) -> RecognitionSet:
+                          stream=None, active=False) -> RecognitionSet:
     """Audio in, hypotheses out: decoder_process_int16(full_utt) + decoder_hyp / decoder_seg_iter
     under decoder_set_fsg with compallsen = yes, for a batch.  int16 PCM (host array or device
     tensor; utterance u = samples samp_off[u] .. samp_off[u + 1]) -> ssw_fe_batch (samprate None:
-    16 kHz) or ssw_fe_batch_ex -> ssw_feat_batch -> ssw_recognize_batch."""
+    16 kHz) or ssw_fe_batch_ex -> ssw_feat_batch -> ssw_recognize_batch, or
+    ssw_recognize_batch_active when active=True (the reference's default compallsen = no)."""
     off = np.ascontiguousarray(samp_off, np.int64)
     n_frames = int(fe_frame_counts(np.diff(off)).sum() if samprate is None else
                    model.fe_frame_counts_rates(np.diff(off), samprate, fe_cfg).sum())
@@ -1341,6 +1371,9 @@ def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: Gramm
         if n_frames:
             _check(model._L.ssw_feat_batch(model._m, d_cep, n_frames, _ptr(fo), len(fo) - 1,
                                            FE_NCEP, d_feat, _ptr(stream)), "ssw_feat_batch")
+        if active:
+            return recognize_batch_active(model, lex, d_feat if d_feat else 0, fo, plan,
+                                          fsg_of_utt, scorer=scorer, stream=stream)[0]
         return recognize_batch(model, lex, d_feat if d_feat else 0, fo, plan, fsg_of_utt,
                                scorer=scorer, stream=stream)
     finally:

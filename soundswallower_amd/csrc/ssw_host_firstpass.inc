@@ -401,7 +401,7 @@ first_pass_run_impl(ssw_model_t *m, ssw_fp_graphs_t *g, double fp_t0, const int1
         if (e == hipSuccess && exp && big) {
             /* the long-text kernels export only the words that hold an active HMM */
             hipLaunchKernelGGL(fpa_clear_kernel, dim3(n_run), dim3(256), 0, st, P.act_mask, P.act_off,
-                               P.utt_off, P.node_off, P.only);
+                               P.utt_off, m->fpa_node_cnt, P.only);
             e = hipGetLastError();
         }
         if (e == hipSuccess) {

@@ -3,40 +3,95 @@
  * ssw_align_text_batch_active.  Kernels and the argument why this is exact: ssw_k7_fpactive.inc.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 
-/* One run of the search over `rows` with the sets of active HMMs exported to `mask`
- * (first_pass_kernel<.., EXPORT>); `only` as first_pass_run_impl takes it. */
+/* What the loop of speculation and proof (fpa_run) needs of the search it drives.  Two kinds:
+ * the first pass of forced alignment, one phone-tree graph per utterance (first_pass_kernel
+ * <.., EXPORT> and the long-text kernels), and recognition against a grammar plan, where the
+ * HMMs are those of grammar fsg_of_utt[u] and many utterances share them (grammar_search_kernel
+ * <.., EXPORT>, ssw_host_grammar.inc).  Everything else -- plan, scoring, comparison, rounds --
+ * is the same. */
+struct fpa_graph_t {
+    const char *who;              /* the entry point, for messages */
+    int n_nodes;                  /* rows of senid */
+    const uint16_t *senid;        /* host [n_nodes][4] */
+    std::vector<int> node_base;   /* [n_utts]: the utterance's first row of senid */
+    std::vector<int> node_cnt;    /* [n_utts]: its phone-tree HMMs */
+    int max_nodes;                /* at least the largest node_cnt: what the per-frame kernels'
+                                     LDS is sized and checked for (a plan's largest grammar) */
+    /* one run of the search over `rows`, the sets of active HMMs exported to `mask` (cleared
+     * here where the kernel does not write every word); `only`: empty, or the utterances to
+     * search; d_node_cnt: node_cnt on the device */
+    int (*search)(void *arg, const int16_t *rows, const std::vector<int> &only,
+                  unsigned long long *mask, const long long *d_act_off, const int *d_node_cnt);
+    void *arg;
+};
+
+/* the first pass's: first_pass_run_impl with the export switched on; `only` as it takes it */
+struct fpa_fp_search_t {
+    ssw_model_t *m;
+    ssw_fp_graphs_t *g;
+    int32_t n_frames;
+    const int32_t *utt_off;
+    int32_t n_utts, max_seg;
+    int32_t *n_seg;
+    ssw_word_seg_t *seg;
+    void *stream;
+};
+
 static int
-fpa_search(ssw_model_t *m, ssw_fp_graphs_t *g, const int16_t *rows, int32_t n_frames,
-           const int32_t *utt_off, int32_t n_utts, int32_t max_seg, int32_t *n_seg,
-           ssw_word_seg_t *seg, void *stream, const std::vector<int> &only,
-           unsigned long long *mask, const long long *d_act_off)
+fpa_fp_search(void *arg, const int16_t *rows, const std::vector<int> &only,
+              unsigned long long *mask, const long long *d_act_off, const int *d_node_cnt)
 {
+    const fpa_fp_search_t &a = *static_cast<const fpa_fp_search_t *>(arg);
+    ssw_model_t *m = a.m;
     struct Export {
         ssw_model_s *m;
         ~Export()
         {
             m->fpa_mask = NULL;
             m->fpa_act_off = NULL;
+            m->fpa_node_cnt = NULL;
         }
     } export_{ m };
     m->fpa_mask = mask;
     m->fpa_act_off = d_act_off;
+    m->fpa_node_cnt = d_node_cnt;
     const double t0 = std::chrono::duration<double, std::milli>(
                           std::chrono::steady_clock::now().time_since_epoch()).count();
     /* (through the levels of the long-text kernels, as ssw_first_pass_batch goes) */
-    return first_pass_run(m, g, t0, rows, n_frames, utt_off, n_utts, max_seg, n_seg, seg, stream,
-                          &only);
+    return first_pass_run(m, a.g, t0, rows, a.n_frames, a.utt_off, a.n_utts, a.max_seg, a.n_seg,
+                          a.seg, a.stream, &only);
+}
+
+/* what the loop serves: refused with a message before anything is uploaded or launched */
+static int
+fpa_check_limits(ssw_model_t *m, const char *who, int scorer)
+{
+    const ssw_host_model_t *h = m->h;
+    if (check_scorer_shape(m, scorer) < 0)
+        return -1;
+    if (h->n_cb > 64 || h->n_emit_state != 3) {
+        ssw_set_error("%s: built for <= 64 codebooks and 3-state HMMs", who);
+        return -1;
+    }
+    if (scorer == SSW_SCORER_PTM && (h->cfg.ds != 1 || m->force_exact)) {
+        ssw_set_error("%s: frame down-sampling (ds != 1) is served by "
+                      "the per-frame calls only", who);
+        return -1;
+    }
+    return 0;
 }
 
 /* d_rows: int16 [n_frames][n_sen] device rows the call scores into (workspace and, with
  * full_rows, output).  seed_out: NULL or host [n_utts][(n_sen + 31) / 32].  rounds_out: NULL or
  * host [n_utts]: searches of the utterance over default-configuration scores until its sets
- * were proven (1 = the assumed trajectory was already the right one). */
+ * were proven (1 = the assumed trajectory was already the right one).
+ * listed_out: NULL or host [n_frames][(n_sen + 31) / 32]: the proven listed senones of every
+ * frame, bridges included.  stats: the caller's four counters. */
 static int
-first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const float *d_feats,
-                      int32_t n_frames, const int32_t *utt_off, int32_t n_utts, int32_t max_seg,
-                      int32_t *n_seg, ssw_word_seg_t *seg, int16_t *d_rows, bool full_rows,
-                      uint32_t *seed_out, int32_t *rounds_out, void *stream, uint32_t *d_carry_out)
+fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, int32_t n_frames,
+        const int32_t *utt_off, int32_t n_utts, int16_t *d_rows, bool full_rows, uint32_t *seed_out,
+        int32_t *rounds_out, uint32_t *listed_out, int64_t *stats, void *stream,
+        uint32_t *d_carry_out)
 {
     ModelBusy busy_(m);
     if (!busy_.ok)
@@ -45,17 +100,8 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
     hipStream_t st = (hipStream_t)stream;
     if (n_utts <= 0)
         return 0;
-    if (check_scorer_shape(m, scorer) < 0)
+    if (fpa_check_limits(m, G.who, scorer) < 0)
         return -1;
-    if (h->n_cb > 64 || h->n_emit_state != 3) {
-        ssw_set_error("ssw_first_pass_batch_active: built for <= 64 codebooks and 3-state HMMs");
-        return -1;
-    }
-    if (scorer == SSW_SCORER_PTM && (h->cfg.ds != 1 || m->force_exact)) {
-        ssw_set_error("ssw_first_pass_batch_active: frame down-sampling (ds != 1) is served by "
-                      "the per-frame calls only");
-        return -1;
-    }
     HIP_OK(hipSetDevice(m->device));
     refresh_knobs(m);
     const bool timing = m->kn.align_timing;
@@ -66,9 +112,9 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
     /* the exported sets: [n_frames_u][ceil(N_u / 64)] 64-bit words per utterance */
     std::vector<long long> act_off((size_t)n_utts);
     long long mask_words = 0;
-    int max_nodes = 0;
+    int max_nodes = G.max_nodes;
     for (int u = 0; u < n_utts; ++u) {
-        const int nn = g->node_off[u + 1] - g->node_off[u];
+        const int nn = G.node_cnt[(size_t)u];
         act_off[(size_t)u] = mask_words;
         mask_words += (long long)(utt_off[u + 1] - utt_off[u]) * ((nn + 63) / 64);
         max_nodes = std::max(max_nodes, nn);
@@ -82,8 +128,8 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
         const size_t sen_lds = 4 * (((scorer == SSW_SCORER_MS ? 0 : 8 * (size_t)m->n_cbf)
                                      + 4 * (size_t)((cap + 1) & ~1) + 16 + 15) & ~(size_t)15);
         if (std::max(plan_lds, sen_lds) > 156 * 1024) {
-            ssw_set_error("ssw_first_pass_batch_active: %d senones x texts of up to %d phone-tree "
-                          "HMMs need %zu KB of LDS per workgroup (160 KB a CU)", h->n_sen, max_nodes,
+            ssw_set_error("%s: %d senones x texts of up to %d phone-tree "
+                          "HMMs need %zu KB of LDS per workgroup (160 KB a CU)", G.who, h->n_sen, max_nodes,
                           std::max(plan_lds, sen_lds) / 1024);
             return -1;
         }
@@ -97,11 +143,12 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
     const size_t nf = (size_t)std::max(n_frames, 1);
     const size_t o_ma = carve(sizeof(unsigned long long) * (size_t)std::max(mask_words, 1ll));
     const size_t o_mb = carve(sizeof(unsigned long long) * (size_t)std::max(mask_words, 1ll));
-    const size_t o_up = off; /* uploaded in one copy: act_off | utt_off | node_off | senid */
+    const size_t o_up = off; /* uploaded in one copy: act_off | utt_off | node base, count | senid */
     const size_t o_ao = carve(sizeof(long long) * (size_t)n_utts);
     const size_t o_uo = carve(sizeof(int) * ((size_t)n_utts + 1));
-    const size_t o_no = carve(sizeof(int) * ((size_t)n_utts + 1));
-    const size_t o_sid = carve(sizeof(uint16_t) * 4 * (size_t)std::max(g->n_nodes, 1));
+    const size_t o_nb = carve(sizeof(int) * (size_t)n_utts);
+    const size_t o_nc = carve(sizeof(int) * (size_t)n_utts);
+    const size_t o_sid = carve(sizeof(uint16_t) * 4 * (size_t)std::max(G.n_nodes, 1));
     const size_t up_bytes = off - o_up;
     const size_t o_listed = carve(sizeof(uint32_t) * nf * (size_t)nw32);
     const size_t o_cbm = carve(sizeof(unsigned long long) * nf);
@@ -133,8 +180,9 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
             return -1;
         memcpy(hs + (o_ao - o_up), act_off.data(), sizeof(long long) * (size_t)n_utts);
         memcpy(hs + (o_uo - o_up), utt_off, sizeof(int) * ((size_t)n_utts + 1));
-        memcpy(hs + (o_no - o_up), g->node_off, sizeof(int) * ((size_t)n_utts + 1));
-        memcpy(hs + (o_sid - o_up), g->senid, sizeof(uint16_t) * 4 * (size_t)g->n_nodes);
+        memcpy(hs + (o_nb - o_up), G.node_base.data(), sizeof(int) * (size_t)n_utts);
+        memcpy(hs + (o_nc - o_up), G.node_cnt.data(), sizeof(int) * (size_t)n_utts);
+        memcpy(hs + (o_sid - o_up), G.senid, sizeof(uint16_t) * 4 * (size_t)G.n_nodes);
         HIP_OK(hipMemcpyAsync(ws + o_up, hs, up_bytes, hipMemcpyHostToDevice, st));
         HIP_OK(hipEventRecord(m->ev_stage[slot], st));
     }
@@ -142,7 +190,8 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
     unsigned long long *mask_y = reinterpret_cast<unsigned long long *>(ws + o_mb);
     const long long *d_act_off = reinterpret_cast<const long long *>(ws + o_ao);
     const int *d_utt_off = reinterpret_cast<const int *>(ws + o_uo);
-    const int *d_node_off = reinterpret_cast<const int *>(ws + o_no);
+    const int *d_node_base = reinterpret_cast<const int *>(ws + o_nb);
+    const int *d_node_cnt = reinterpret_cast<const int *>(ws + o_nc);
     uint32_t *d_listed = reinterpret_cast<uint32_t *>(ws + o_listed);
     unsigned long long *d_cbm = reinterpret_cast<unsigned long long *>(ws + o_cbm);
     int32_t *d_iota = reinterpret_cast<int32_t *>(ws + o_iota);
@@ -158,8 +207,7 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
         && score_batch_impl(m, scorer, d_feats, n_frames, utt_off, n_utts, d_rows, stream, 0u, NULL,
                             NULL) < 0)
         return -1;
-    if (fpa_search(m, g, d_rows, n_frames, utt_off, n_utts, max_seg, n_seg, seg, stream, only,
-                   mask_x, d_act_off) < 0)
+    if (G.search(G.arg, d_rows, only, mask_x, d_act_off, d_node_cnt) < 0)
         return -1;
     const double t_spec = now();
     std::vector<int32_t> rounds((size_t)n_utts, 0), diff((size_t)n_utts);
@@ -171,7 +219,8 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
         Q.act_mask = mask_x;
         Q.act_off = d_act_off;
         Q.utt_off = d_utt_off;
-        Q.node_off = d_node_off;
+        Q.node_base = d_node_base;
+        Q.node_cnt = d_node_cnt;
         Q.senid = reinterpret_cast<const uint16_t *>(ws + o_sid);
         Q.sen2cb = m->d_sen2cb;
         Q.listed = d_listed;
@@ -252,8 +301,7 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
             HIP_OK(hipStreamSynchronize(st));
         const double r1 = now();
         /* 4: the search over those scores, its sets into mask_y */
-        if (fpa_search(m, g, d_rows, n_frames, utt_off, n_utts, max_seg, n_seg, seg, stream, only,
-                       mask_y, d_act_off) < 0)
+        if (G.search(G.arg, d_rows, only, mask_y, d_act_off, d_node_cnt) < 0)
             return -1;
         const double r2 = now();
         /* 5: proven where the sets are the assumed ones */
@@ -272,7 +320,7 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
         const unsigned slices = (unsigned)std::min<long long>(
             64, std::max<long long>(1, mask_words / std::max(1, n_cmp) / (256 * 16)));
         hipLaunchKernelGGL(fpa_compare_kernel, dim3((unsigned)n_cmp, slices), dim3(256), 0, st, mask_x, mask_y,
-                           d_act_off, d_utt_off, d_node_off, only.empty() ? (const int *)NULL : d_only,
+                           d_act_off, d_utt_off, d_node_cnt, only.empty() ? (const int *)NULL : d_only,
                            d_diff);
         HIP_OK(hipGetLastError());
         HIP_OK(hipMemcpyAsync(diff.data(), d_diff, sizeof(int32_t) * (size_t)n_utts,
@@ -293,17 +341,17 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
             }
         }
         if (timing)
-            fprintf(stderr, "ssw_first_pass_batch_active: round %d, %d searched, %zu not yet proven "
+            fprintf(stderr, "%s: round %d, %d searched, %zu not yet proven "
                             "(plan + scoring %.2f ms, search %.2f, comparison %.2f)\n",
-                    n_round, n_cmp, again.size(), r1 - r0, r2 - r1, now() - r2);
+                    G.who, n_round, n_cmp, again.size(), r1 - r0, r2 - r1, now() - r2);
         if (again.empty())
             break;
         /* every round proves at least one more frame of each of them (the first differing
          * frame's set in mask_y is the reference's), so this ends; the cap is a guard against
          * a defect, not a budget */
         if (n_round > 4 * 16384) {
-            ssw_set_error("ssw_first_pass_batch_active: utterance %d not proven after %d rounds",
-                          again[0], n_round);
+            ssw_set_error("%s: utterance %d not proven after %d rounds", G.who, again[0],
+                          n_round);
             return -1;
         }
         std::swap(mask_x, mask_y); /* (the proven utterances' sets are the same in both) */
@@ -355,6 +403,9 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
                            st, F, m->d_rec28, d_feats, d_utt_off, d_carry_out);
         HIP_OK(hipGetLastError());
     }
+    if (listed_out != NULL && n_frames > 0)
+        HIP_OK(hipMemcpyAsync(listed_out, d_listed, sizeof(uint32_t) * (size_t)n_frames * (size_t)nw32,
+                              hipMemcpyDeviceToHost, st));
     if (seed_out != NULL)
         HIP_OK(hipMemcpyAsync(seed_out, d_seed, sizeof(uint32_t) * (size_t)n_utts * (size_t)nw32,
                               hipMemcpyDeviceToHost, st));
@@ -365,16 +416,39 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
         sum += rounds[(size_t)u];
         more += rounds[(size_t)u] > 1 ? 1 : 0;
     }
-    m->fpa_stats[0] += n_utts;
-    m->fpa_stats[1] += sum;
-    m->fpa_stats[2] = n_round;
-    m->fpa_stats[3] += more;
+    stats[0] += n_utts;
+    stats[1] += sum;
+    stats[2] = n_round;
+    stats[3] += more;
     if (rounds_out != NULL)
         memcpy(rounds_out, rounds.data(), sizeof(int32_t) * (size_t)n_utts);
     if (timing)
-        fprintf(stderr, "ssw_first_pass_batch_active: assumption (compallsen = yes scoring + search) "
-                        "%.2f ms, %d round(s) %.2f ms\n", t_spec - t_in, n_round, now() - t_spec);
+        fprintf(stderr, "%s: assumption (compallsen = yes scoring + search) "
+                        "%.2f ms, %d round(s) %.2f ms\n", G.who, t_spec - t_in, n_round, now() - t_spec);
     return 0;
+}
+
+/* the first pass's graphs: every utterance its own */
+static int
+first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const float *d_feats,
+                      int32_t n_frames, const int32_t *utt_off, int32_t n_utts, int32_t max_seg,
+                      int32_t *n_seg, ssw_word_seg_t *seg, int16_t *d_rows, bool full_rows,
+                      uint32_t *seed_out, int32_t *rounds_out, void *stream, uint32_t *d_carry_out)
+{
+    fpa_fp_search_t a = { m, g, n_frames, utt_off, n_utts, max_seg, n_seg, seg, stream };
+    fpa_graph_t G;
+    G.who = "ssw_first_pass_batch_active";
+    G.n_nodes = g->n_nodes;
+    G.senid = g->senid;
+    G.max_nodes = 0;
+    for (int u = 0; u < n_utts; ++u) {
+        G.node_base.push_back(g->node_off[u]);
+        G.node_cnt.push_back(g->node_off[u + 1] - g->node_off[u]);
+    }
+    G.search = fpa_fp_search;
+    G.arg = &a;
+    return fpa_run(m, G, scorer, d_feats, n_frames, utt_off, n_utts, d_rows, full_rows, seed_out,
+                   rounds_out, NULL, m->fpa_stats, stream, d_carry_out);
 }
 
 extern "C" int

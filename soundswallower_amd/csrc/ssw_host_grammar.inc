@@ -1,5 +1,5 @@
 /* ssw_host_grammar.inc -- host: ssw_grammar_prepare, ssw_grammar_search_batch,
- * ssw_recognize_batch and the recognition set.
+ * ssw_recognize_batch, ssw_recognize_batch_active and the recognition set.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 /* ---------------------------------------------------------------------------------- */
 /* recognition against word FSGs (decoder_set_fsg; ssw_k9_grammar.inc)                  */
@@ -106,39 +106,68 @@ grammar_hist_budget()
     return SSW_GRAMMAR_HIST_BYTES;
 }
 
-extern "C" ssw_recognition_set_t *
-ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_plan_t *plan,
-                         const int32_t *fsg_of_utt, const int16_t *d_senscr, int32_t n_frames,
-                         const int32_t *utt_off, int32_t n_utts, void *stream)
+/* One call's grammar search in three steps, so that the default configuration can launch it
+ * once per round (ssw_recognize_batch_active): begin() checks the call, makes the empty set and
+ * uploads the tables; launch() runs the kernel over some rows; finish() fetches the results and
+ * fills the set.  ssw_grammar_search_batch is begin, one launch, finish. */
+struct grammar_run_t {
+    ssw_model_t *m;
+    const ssw_dict_t *d;
+    const ssw_grammar_plan_t *plan;
+    const int32_t *fsg_of_utt;
+    int32_t n_utts;
+    hipStream_t st;
+    ssw_recognition_set_t *r;
+    GrammarParams P;
+    int max_seg;
+    size_t nseg_off, score_off, seg_off, only_off;
+    std::vector<unsigned char> stage; /* must outlive its copy */
+    std::vector<int> only_host;
+    bool uploaded;
+
+    grammar_run_t() : m(NULL), d(NULL), plan(NULL), fsg_of_utt(NULL), n_utts(0), st(NULL), r(NULL),
+                      max_seg(1), nseg_off(0), score_off(0), seg_off(0), only_off(0), uploaded(false) {}
+    ~grammar_run_t()
+    {
+        if (uploaded)
+            (void)hipStreamSynchronize(st);
+        delete r;
+    }
+    int begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_plan_t *plan_,
+              const int32_t *fsg_of_utt_, int32_t n_frames, const int32_t *utt_off, int32_t n_utts_,
+              void *stream);
+    hipError_t launch(const int16_t *d_senscr, const std::vector<int> *only, unsigned long long *mask,
+                      const long long *d_act_off, const int *d_node_cnt);
+    ssw_recognition_set_t *finish();
+};
+
+int
+grammar_run_t::begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_plan_t *plan_,
+                     const int32_t *fsg_of_utt_, int32_t n_frames, const int32_t *utt_off,
+                     int32_t n_utts_, void *stream)
 {
-    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
-        || utt_off[0] != 0 || utt_off[n_utts] != n_frames || (n_frames > 0 && d_senscr == NULL)) {
-        ssw_set_error("bad arguments to ssw_grammar_search_batch");
-        return NULL;
-    }
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
-        return NULL;
-    }
-    ModelBusy busy_(m);
-    if (!busy_.ok)
-        return NULL;
+    m = m_;
+    d = d_;
+    plan = plan_;
+    fsg_of_utt = fsg_of_utt_;
+    n_utts = n_utts_;
+    (void)n_frames;
     const ssw_fp_graphs_t *g = plan->g;
-    hipStream_t st = (hipStream_t)stream;
+    st = (hipStream_t)stream;
     /* the history table: (frames + 1) rows of one entry per slot, per utterance */
     std::vector<long long> hist_off((size_t)n_utts + 1);
     size_t hist_total = 0;
-    int max_seg = 1;
+    max_seg = 1;
     for (int u = 0; u < n_utts; ++u) {
         const int gi = fsg_of_utt ? fsg_of_utt[u] : 0;
         if (gi < 0 || gi >= plan->n_fsgs) {
             ssw_set_error("utterance %d: grammar %d is not one of the plan's %d", u, gi, plan->n_fsgs);
-            return NULL;
+            return -1;
         }
         const int T = utt_off[u + 1] - utt_off[u];
         if (T < 0) {
             ssw_set_error("bad arguments to ssw_grammar_search_batch");
-            return NULL;
+            return -1;
         }
         const size_t ne = (size_t)(g->slot_off[g->state_off[gi + 1]] - g->slot_off[g->state_off[gi]]);
         const size_t nsn = (size_t)(g->sn_off[gi + 1] - g->sn_off[gi]);
@@ -146,7 +175,7 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
         if (row * ((size_t)T + 1) >= (size_t)INT_MAX) { /* entry ids are int32 */
             ssw_set_error("utterance %d: %zu entering-list entries x %d frames exceed the history "
                           "table's 2^31 entries", u, row, T);
-            return NULL;
+            return -1;
         }
         hist_off[(size_t)u] = (long long)hist_total;
         hist_total += row * ((size_t)T + 1);
@@ -159,9 +188,9 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
                       "entering-list entries, summed over %d utterances) exceeds the budget of "
                       "%zu bytes; search fewer utterances per call", hist_total,
                       hist_total * sizeof(int2), n_utts, grammar_hist_budget());
-        return NULL;
+        return -1;
     }
-    ssw_recognition_set_t *r = new ssw_recognition_set_t();
+    r = new ssw_recognition_set_t();
     r->m = m;
     r->d = d;
     r->n_utts = n_utts;
@@ -176,7 +205,7 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
     for (int u = 0; u < n_utts; ++u)
         r->n_frames[(size_t)u] = utt_off[u + 1] - utt_off[u];
     if (n_utts == 0)
-        return r;
+        return 0;
 
     /* one staging buffer -> one copy, every array at a 256-byte boundary; the graph's tables
      * first (they stay while the plan is the last one searched), the call's after them */
@@ -223,11 +252,13 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
         off = (off + pc[i].bytes + 255) & ~(size_t)255;
     }
     const size_t in_bytes = off;
-    const size_t nseg_off = off;
+    nseg_off = off;
     off += (sizeof(int) * (size_t)n_utts + 255) & ~(size_t)255;
-    const size_t score_off = off;
+    score_off = off;
     off += (sizeof(int) * (size_t)n_utts + 255) & ~(size_t)255;
-    const size_t seg_off = off;
+    only_off = off; /* (the utterances a round of the default configuration searches) */
+    off += (sizeof(int) * (size_t)n_utts + 255) & ~(size_t)255;
+    seg_off = off;
     off += (sizeof(ssw_fsg_seg_t) * (size_t)n_utts * (size_t)max_seg + 255) & ~(size_t)255;
     const size_t hist_at = off;
     off += (sizeof(int2) * (hist_total ? hist_total : 1) + 255) & ~(size_t)255;
@@ -244,9 +275,7 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
     }
     const bool cached = m->gr_ws_uid != 0 && m->gr_ws_uid == g->uid;
     const size_t up_from = cached ? pc[PC_CALL].off : 0;
-    std::vector<unsigned char> stage(in_bytes - up_from + 1);
-    std::vector<int> n_seg((size_t)n_utts), score((size_t)n_utts);
-    std::vector<ssw_fsg_seg_t> seg((size_t)n_utts * (size_t)max_seg);
+    stage.resize(in_bytes - up_from + 1);
     if (e == hipSuccess) {
         for (int i = 0; i < n_pc; ++i)
             if (pc[i].bytes && pc[i].off >= up_from)
@@ -254,11 +283,14 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
         e = hipMemcpyAsync(m->d_gr_ws + up_from, stage.data(), in_bytes - up_from,
                            hipMemcpyHostToDevice, st);
         m->gr_ws_uid = e == hipSuccess ? g->uid : 0;
+        uploaded = true;
     }
     if (e == hipSuccess) {
         unsigned char *ws = m->d_gr_ws;
-        GrammarParams P;
-        P.senscr = d_senscr;
+        P.senscr = NULL;
+        P.only = NULL;
+        P.act_mask = NULL;
+        P.act_off = NULL;
         P.node_off = (const int *)(ws + pc[0].off);
         P.leaf_off = (const int *)(ws + pc[1].off);
         P.state_off = (const int *)(ws + pc[2].off);
@@ -301,6 +333,41 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
         P.pbeam = g->pbeam;
         P.wbeam = g->wbeam;
         P.sil = m->h->sil;
+    }
+    if (e != hipSuccess) {
+        m->gr_ws_uid = 0;
+        ssw_set_error("ssw_grammar_search_batch: %s", hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
+/* `mask` != NULL: the EXPORT instances, the sets of active HMMs into mask (cleared first);
+ * `only`: NULL or empty for every utterance, else the ones to search */
+hipError_t
+grammar_run_t::launch(const int16_t *d_senscr, const std::vector<int> *only, unsigned long long *mask,
+                      const long long *d_act_off, const int *d_node_cnt)
+{
+    hipError_t e = hipSuccess;
+    unsigned char *ws = m->d_gr_ws;
+    const bool exp = mask != NULL;
+    const int n_run = only != NULL && !only->empty() ? (int)only->size() : n_utts;
+    P.senscr = d_senscr;
+    P.only = NULL;
+    P.act_mask = mask;
+    P.act_off = d_act_off;
+    if (only != NULL && !only->empty()) {
+        only_host = *only; /* (kept here: every round ends in a synchronisation of the stream) */
+        e = hipMemcpyAsync(ws + only_off, only_host.data(), sizeof(int) * (size_t)n_run,
+                           hipMemcpyHostToDevice, st);
+        P.only = (const int *)(ws + only_off);
+    }
+    if (e == hipSuccess && exp) {
+        hipLaunchKernelGGL(fpa_clear_kernel, dim3((unsigned)n_run), dim3(256), 0, st, mask, d_act_off,
+                           P.utt_off, d_node_cnt, P.only);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
         /* one HMM per thread while a workgroup can hold the largest grammar of the plan; beyond
          * 1024, four or eight per thread of a 512-thread workgroup: two waves per SIMD leave a
          * lane 256 registers, which hold eight HMMs' state (1024 threads leave 128: four HMMs
@@ -309,19 +376,19 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
         int tpb;
         const int mn = plan->max_nodes;
         if (mn <= 256) {
-            kern = grammar_search_kernel<1, 256>;
+            kern = exp ? grammar_search_kernel<1, 256, true> : grammar_search_kernel<1, 256>;
             tpb = 256;
         } else if (mn <= 512) {
-            kern = grammar_search_kernel<1, 512>;
+            kern = exp ? grammar_search_kernel<1, 512, true> : grammar_search_kernel<1, 512>;
             tpb = 512;
         } else if (mn <= 1024) {
-            kern = grammar_search_kernel<1, 1024>;
+            kern = exp ? grammar_search_kernel<1, 1024, true> : grammar_search_kernel<1, 1024>;
             tpb = 1024;
         } else if (mn <= 2048) {
-            kern = grammar_search_kernel<4, 512>;
+            kern = exp ? grammar_search_kernel<4, 512, true> : grammar_search_kernel<4, 512>;
             tpb = 512;
         } else {
-            kern = grammar_search_kernel<8, 512>;
+            kern = exp ? grammar_search_kernel<8, 512, true> : grammar_search_kernel<8, 512>;
             tpb = 512;
         }
         const size_t lds_bytes = plan->lds_ints * sizeof(int);
@@ -329,9 +396,28 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
             e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)lds_bytes);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(kern, dim3(n_utts), dim3(tpb), lds_bytes, st, P);
+            hipLaunchKernelGGL(kern, dim3(n_run), dim3(tpb), lds_bytes, st, P);
             e = hipGetLastError();
         }
+    }
+    return e;
+}
+
+/* the set, filled; NULL after an error (the set is freed with the run) */
+ssw_recognition_set_t *
+grammar_run_t::finish()
+{
+    const ssw_fp_graphs_t *g = plan->g;
+    if (n_utts == 0) {
+        ssw_recognition_set_t *out = r;
+        r = NULL;
+        return out;
+    }
+    std::vector<int> n_seg((size_t)n_utts), score((size_t)n_utts);
+    std::vector<ssw_fsg_seg_t> seg((size_t)n_utts * (size_t)max_seg);
+    hipError_t e = hipSuccess;
+    {
+        unsigned char *ws = m->d_gr_ws;
         if (e == hipSuccess)
             e = hipMemcpyAsync(n_seg.data(), ws + nseg_off, sizeof(int) * (size_t)n_utts,
                                hipMemcpyDeviceToHost, st);
@@ -346,11 +432,10 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
     else
-        (void)hipStreamSynchronize(st); /* `stage` must outlive its copy */
+        (void)hipStreamSynchronize(st);
     if (e != hipSuccess) {
         m->gr_ws_uid = 0;
         ssw_set_error("ssw_grammar_search_batch: %s", hipGetErrorString(e));
-        delete r;
         return NULL;
     }
     for (int u = 0; u < n_utts; ++u) {
@@ -398,7 +483,40 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
         r->has_hyp[(size_t)u] = hyp.empty() ? 0 : 1;
     }
     r->seg_off[(size_t)n_utts] = (int32_t)r->seg.size();
-    return r;
+    ssw_recognition_set_t *out = r;
+    r = NULL;
+    return out;
+}
+
+extern "C" ssw_recognition_set_t *
+ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_plan_t *plan,
+                         const int32_t *fsg_of_utt, const int16_t *d_senscr, int32_t n_frames,
+                         const int32_t *utt_off, int32_t n_utts, void *stream)
+{
+    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
+        || utt_off[0] != 0 || utt_off[n_utts] != n_frames || (n_frames > 0 && d_senscr == NULL)) {
+        ssw_set_error("bad arguments to ssw_grammar_search_batch");
+        return NULL;
+    }
+    if (m->device == SSW_DEVICE_NONE) {
+        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+        return NULL;
+    }
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return NULL;
+    grammar_run_t R;
+    if (R.begin(m, d, plan, fsg_of_utt, n_frames, utt_off, n_utts, stream) < 0)
+        return NULL;
+    if (n_utts > 0) {
+        const hipError_t e = R.launch(d_senscr, NULL, NULL, NULL, NULL);
+        if (e != hipSuccess) {
+            m->gr_ws_uid = 0;
+            ssw_set_error("ssw_grammar_search_batch: %s", hipGetErrorString(e));
+            return NULL;
+        }
+    }
+    return R.finish();
 }
 
 extern "C" ssw_recognition_set_t *
@@ -436,6 +554,99 @@ ssw_recognize_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_plan_
         return NULL;
     return ssw_grammar_search_batch(m, d, plan, fsg_of_utt, m->d_text_scr, n_frames, utt_off,
                                     n_utts, stream);
+}
+
+/* the loop's search step (fpa_graph_t): the EXPORT instances of grammar_search_kernel */
+static int
+grammar_active_search(void *arg, const int16_t *rows, const std::vector<int> &only,
+                      unsigned long long *mask, const long long *d_act_off, const int *d_node_cnt)
+{
+    grammar_run_t &R = *static_cast<grammar_run_t *>(arg);
+    const hipError_t e = R.launch(rows, &only, mask, d_act_off, d_node_cnt);
+    if (e != hipSuccess) {
+        R.m->gr_ws_uid = 0;
+        ssw_set_error("ssw_recognize_batch_active: %s", hipGetErrorString(e));
+        return -1;
+    }
+    return 0;
+}
+
+/* decoder_set_fsg + decoder_process + decoder_hyp in the reference's DEFAULT configuration
+ * (compallsen = no) for a batch, from features: every frame scored for the senones of the HMMs
+ * fsg_search_sen_active lists (src/fsg_search.c:310-325), through acmod's flags2list with its
+ * bridges (src/acmod.c:947-999), then searched by fsg_search_step (src/fsg_search.c:664-739) --
+ * by speculation and proof (ssw_k7_fpactive.inc, ssw_k9_grammar.inc). */
+extern "C" ssw_recognition_set_t *
+ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_plan_t *plan,
+                           const int32_t *fsg_of_utt, int scorer, const float *d_feats,
+                           int32_t n_frames, const int32_t *utt_off, int32_t n_utts,
+                           int16_t *d_senscr, uint32_t *listed, int32_t *rounds, void *stream)
+{
+    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
+        || utt_off[0] != 0 || utt_off[n_utts] != n_frames || (n_frames > 0 && d_feats == NULL)) {
+        ssw_set_error("bad arguments to ssw_recognize_batch_active");
+        return NULL;
+    }
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return NULL;
+    if (m->device == SSW_DEVICE_NONE) {
+        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+        return NULL;
+    }
+    if (fpa_check_limits(m, "ssw_recognize_batch_active", scorer) < 0)
+        return NULL;
+    if (hipSetDevice(m->device) != hipSuccess)
+        return NULL;
+    int16_t *rows = d_senscr;
+    if (rows == NULL) { /* the model's own rows */
+        const size_t need = (size_t)n_frames * (size_t)m->h->n_sen;
+        if (need > m->text_scr_cap) {
+            (void)hipFree(m->d_text_scr);
+            m->d_text_scr = NULL;
+            m->text_scr_cap = 0;
+            hipError_t e = hipMalloc((void **)&m->d_text_scr, sizeof(int16_t) * std::max(need, (size_t)1));
+            if (e != hipSuccess) {
+                ssw_set_error("ssw_recognize_batch_active: %s", hipGetErrorString(e));
+                return NULL;
+            }
+            m->text_scr_cap = need;
+        }
+        rows = m->d_text_scr;
+    }
+    grammar_run_t R;
+    if (R.begin(m, d, plan, fsg_of_utt, n_frames, utt_off, n_utts, stream) < 0)
+        return NULL;
+    if (n_utts == 0)
+        return R.finish();
+    const ssw_fp_graphs_t *g = plan->g;
+    fpa_graph_t G;
+    G.who = "ssw_recognize_batch_active";
+    G.n_nodes = g->n_nodes;
+    G.senid = g->senid;
+    G.max_nodes = plan->max_nodes;
+    for (int u = 0; u < n_utts; ++u) {
+        const int gi = fsg_of_utt ? fsg_of_utt[u] : 0; /* (checked by begin) */
+        G.node_base.push_back(g->node_off[gi]);
+        G.node_cnt.push_back(g->node_off[gi + 1] - g->node_off[gi]);
+    }
+    G.search = grammar_active_search;
+    G.arg = &R;
+    if (fpa_run(m, G, scorer, d_feats, n_frames, utt_off, n_utts, rows, d_senscr != NULL, NULL,
+                rounds, listed, m->gra_stats, stream, NULL) < 0)
+        return NULL;
+    return R.finish();
+}
+
+/* [0] utterances searched by ssw_recognize_batch_active since the model was loaded, [1] their
+ * verify rounds summed, [2] rounds of the last call, [3] utterances whose first assumption (the
+ * compallsen = yes trajectory) was not the reference's */
+extern "C" int
+ssw_grammar_active_stats(ssw_model_t *m, int64_t stats[4])
+{
+    for (int i = 0; i < 4; ++i)
+        stats[i] = m->gra_stats[i];
+    return 0;
 }
 
 extern "C" int32_t

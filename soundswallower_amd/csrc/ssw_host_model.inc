@@ -242,6 +242,8 @@ struct ssw_model_s {
     size_t fpa_ws_cap;
     unsigned long long *fpa_mask;
     const long long *fpa_act_off;
+    const int *fpa_node_cnt; /* device [n_utts]: phone-tree HMMs of every utterance's graph */
+    int64_t gra_stats[4]; /* as fpa_stats, of ssw_recognize_batch_active */
     int64_t fpa_stats[4]; /* utterances, verify rounds summed over them, rounds of the last call, utterances that needed more than one */
     int16_t *d_text_scr; /* ssw_align_text_batch's score rows (grow-only) */
     size_t text_scr_cap;

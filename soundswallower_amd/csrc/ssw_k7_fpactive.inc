@@ -26,7 +26,10 @@
 struct FpaPlanParams {
     const unsigned long long *act_mask; /* first_pass_kernel<.., EXPORT> */
     const long long *act_off;           /* [n_utts] */
-    const int *utt_off, *node_off;      /* [n_utts + 1] */
+    const int *utt_off;                 /* [n_utts + 1] */
+    const int *node_base, *node_cnt;    /* [n_utts]: the utterance's phone-tree HMMs among senid's
+                                           rows -- a text's own graph, or the grammar it is searched
+                                           against (many utterances may share one) */
     const uint16_t *senid;              /* [n_nodes][4] */
     const uint8_t *sen2cb;
     uint32_t *listed;                   /* [n_frames][nw32] listed senones, bridges included */
@@ -64,7 +67,7 @@ fpa_plan_kernel(FpaPlanParams P, int cap)
             hi = mid - 1;
     }
     const int u = lo;
-    const int nb = P.node_off[u], N = P.node_off[u + 1] - nb, MW = (N + 63) >> 6;
+    const int nb = P.node_base[u], N = P.node_cnt[u], MW = (N + 63) >> 6;
     const int f = t - P.utt_off[u];
     const unsigned long long *mask = P.act_mask + P.act_off[u] + (long long)f * MW;
     for (int i = lane; i < P.nw32; i += 64)
@@ -169,14 +172,15 @@ fpa_plan_kernel(FpaPlanParams P, int cap)
 
 /* The rows of the utterances a launch of the sliding-window or the HBM-resident search kernel
  * is about to export into (those kernels write only the words that hold an active HMM; the
- * register kernel writes every word).  One workgroup per utterance. */
+ * register kernel writes every word), and of the ones grammar_search_kernel<.., EXPORT> is about
+ * to search.  One workgroup per utterance. */
 __global__ void __launch_bounds__(256)
 fpa_clear_kernel(unsigned long long *__restrict__ mask, const long long *__restrict__ act_off,
-                 const int *__restrict__ utt_off, const int *__restrict__ node_off,
+                 const int *__restrict__ utt_off, const int *__restrict__ node_cnt,
                  const int *__restrict__ only)
 {
     const int u = only != nullptr ? only[blockIdx.x] : (int)blockIdx.x;
-    const int MW = (node_off[u + 1] - node_off[u] + 63) >> 6;
+    const int MW = (node_cnt[u] + 63) >> 6;
     const long long n = (long long)(utt_off[u + 1] - utt_off[u]) * MW;
     unsigned long long *p = mask + act_off[u];
     for (long long i = threadIdx.x; i < n; i += 256)
@@ -220,11 +224,11 @@ fpa_carry_rows_kernel(FramesParams P, const float *__restrict__ rec28, const flo
 __global__ void __launch_bounds__(256)
 fpa_compare_kernel(const unsigned long long *__restrict__ a, const unsigned long long *__restrict__ b,
                    const long long *__restrict__ act_off, const int *__restrict__ utt_off,
-                   const int *__restrict__ node_off, const int *__restrict__ only,
+                   const int *__restrict__ node_cnt, const int *__restrict__ only,
                    int32_t *__restrict__ first_diff)
 {
     const int u = only != nullptr ? only[blockIdx.x] : (int)blockIdx.x;
-    const int MW = (node_off[u + 1] - node_off[u] + 63) >> 6;
+    const int MW = (node_cnt[u] + 63) >> 6;
     const long long n = (long long)(utt_off[u + 1] - utt_off[u]) * MW, base = act_off[u];
     int mine = FPA_NO_DIFF;
     for (long long i = (long long)blockIdx.y * 256 + threadIdx.x; i < n; i += 256ll * gridDim.y)

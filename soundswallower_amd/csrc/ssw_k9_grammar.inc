@@ -29,6 +29,23 @@
 /* adds the null entries after them; the lists here are in that order -- word exits by      */
 /* (left-context phone, ordinal), then null hops by the same key -- and both scans take the  */
 /* first of equals.  Alternates pronounced alike follow K5's twin records.                  */
+/* The default configuration (compallsen = no; ssw_recognize_batch_active, host half in           */
+/* ssw_host_grammar.inc).  grammar_search_kernel<.., EXPORT> writes, for every frame f, one bit per */
+/* phone-tree HMM: set iff the HMM is in the reference's pnode_active when fsg_search_step(f)       */
+/* starts (hmm_frame == f) -- the list fsg_search_sen_active walks before the frame is scored       */
+/* (src/fsg_search.c:310-325, :676-679).  Frame 0's set is what fsg_search_start leaves: the roots   */
+/* of the start state and of the states its null transitions reach (:775-787).  Here that is act[]  */
+/* as the frame begins.  HMM n = tid + k TPB is bit (tid & 63) of word (tid >> 6) + k (TPB / 64) of  */
+/* the frame's row, that is bit n of the row: one wave ballot per k writes a whole word, with any    */
+/* number of HMMs per thread.                                                                        */
+/* The proof in the header of ssw_k7_fpactive.inc never looks at the shape of the grammar.  It needs */
+/* (a) that a frame's search reads only the scores of the senones of the HMMs active as it starts,   */
+/* and (b) that the sets of frame f + 1 are a function of those scores and the state after frame f.  */
+/* Both hold for any word FSG, nulls and loops included: phase A evaluates the active HMMs alone,    */
+/* and everything phases B and C decide follows from phase A's results and the static tables.  So    */
+/* an utterance whose exported sets equal the assumed ones frame for frame has been searched on the  */
+/* reference's scores, and any other is right up to and including the set of its first differing     */
+/* frame.                                                                                            */
 /* ---------------------------------------------------------------------------------- */
 struct GrammarParams {
     const int16_t *senscr; /* [n_frames][n_sen] */
@@ -52,6 +69,12 @@ struct GrammarParams {
                                  segments do not fit), hypothesis score */
     ssw_fsg_seg_t *seg;       /* [n_utts][max_seg] */
     int n_sen, max_seg, beam, pbeam, wbeam, sil;
+    /* grammar_search_kernel<.., EXPORT> only: */
+    const int *only;              /* NULL, or the utterances this launch searches (one workgroup
+                                     each): the ones a round has not proven yet */
+    unsigned long long *act_mask; /* [n_frames_u][(N + 63) / 64] words at act_off[u], cleared
+                                     before the launch (fpa_clear_kernel) */
+    const long long *act_off;     /* [n_utts] */
 };
 
 /* what a phase needs of a node's constants: in registers with one HMM per thread, read again
@@ -73,12 +96,12 @@ struct GrNodeC {
  * registers) */
 #define GR_ONE_AT_A_TIME() asm volatile("" ::: "memory")
 
-template <int NPT, int TPB> /* HMMs per thread, threads */
+template <int NPT, int TPB, bool EXPORT = false> /* HMMs per thread, threads, the sets of active HMMs written out */
 __global__ void __launch_bounds__(TPB)
 grammar_search_kernel(GrammarParams P)
 {
     extern __shared__ int gr_lds[];
-    const int u = (int)blockIdx.x, tid = threadIdx.x;
+    const int u = (EXPORT && P.only != NULL) ? P.only[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;
     const int gi = P.fsg_of_utt != NULL ? P.fsg_of_utt[u] : 0;
     const int nb = P.node_off[gi], N = P.node_off[gi + 1] - nb;
     const int lb = P.leaf_off[gi];
@@ -239,6 +262,19 @@ grammar_search_kernel(GrammarParams P)
 
     auto frame = [&](const int f, uint32_t &q0, uint32_t &q1, uint32_t &q2) {
         const ScoreRow rf = score_row(P.senscr, (size_t)(f0 + f) * P.n_sen);
+        if (EXPORT) {
+            /* the HMMs active as the frame starts: what fsg_search_sen_active hands acmod.  Every
+             * wave is whole here (the lanes beyond N hold act = false) */
+            const int MW = (N + 63) >> 6;
+            unsigned long long *row = P.act_mask + P.act_off[u] + (long long)f * MW;
+#pragma unroll
+            for (int k = 0; k < NPT; ++k) {
+                const unsigned long long bm = __ballot(act[k]);
+                const int word = (tid >> 6) + k * (TPB / 64);
+                if ((tid & 63) == 0 && word < MW)
+                    row[word] = bm;
+            }
+        }
         /* A: hmm_vit_eval of the active nodes, best score of the frame */
         int bs = W;
         if (NPT == 1) {

@@ -16,6 +16,18 @@ Each figure is the host clock around one call that ends in the call's own stream
 there is no CPU figure, and without a device the script fails.
 
     python tools/bench_grammar.py [--utts 256] [--reps 30] [--warmup 5] [--out FILE]
+
+With --active it times, instead, recognition in the reference's DEFAULT configuration
+(compallsen = no) from feature rows and writes profiles/grammar_active_bench.json: the same 256
+copies, every utterance against grammar 0 (goforward) or 1 (loop) of one plan in turn,
+
+    active      ssw_recognize_batch_active: speculation and proof, scoring included
+    yes         ssw_recognize_batch on the same features and plan: all senones scored, one search
+
+alternating, with the rounds every utterance took and their histogram; `ratio` = active / yes
+medians.
+
+    python tools/bench_grammar.py --active [--utts 256] [--reps 10] [--warmup 2] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -31,13 +43,85 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def active(a):
+    import torch
+
+    import soundswallower_amd as ssw
+    from tests import fsg_common as G
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_grammar: no GPU; nothing is measured without one")
+    mdir = ssw.model_dir("en-us")
+    m = ssw.Model(mdir)
+    lex = ssw.Lexicon(m, os.path.join(mdir, "dict.txt"), os.path.join(mdir, "noisedict.txt"))
+    cep, _ = m.fe_batch(G.pcm("goforward.raw", 0))
+    feats = np.ascontiguousarray(m.feat_batch(cep), np.float32)
+    T, n = len(feats), a.utts
+    d = torch.from_numpy(np.ascontiguousarray(np.tile(feats, (n, 1)))).cuda()
+    off = (np.arange(n + 1) * T).astype(np.int32)
+    names = ["goforward", "loop"]
+    plan = lex.grammar_plan([ssw.Fsg.read(m, lex, G.fsg_path(g)) for g in names])
+    which = (np.arange(n) % 2).astype(np.int32)
+    last = {}
+
+    def run_active():
+        r, rounds = ssw.recognize_batch_active(m, lex, d, off, plan, which)
+        last["active"] = (r.hyp(0), r.score(0), r.hyp(1), r.score(1))
+        last["rounds"] = rounds
+        r.free()
+
+    def run_yes():
+        r = ssw.recognize_batch(m, lex, d, off, plan, which)
+        last["yes"] = (r.hyp(0), r.score(0), r.hyp(1), r.score(1))
+        r.free()
+
+    calls = {"active": run_active, "yes": run_yes}
+    times = {k: [] for k in calls}
+    for i in range(a.warmup + a.reps):
+        for k, fn in calls.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            dt = (time.perf_counter() - t0) * 1e3
+            if i >= a.warmup:
+                times[k].append(dt)
+    rounds = last["rounds"]
+    out = {
+        "what": "ssw_recognize_batch_active (compallsen = no) / ssw_recognize_batch (compallsen = "
+                "yes) from feature rows, host clock around one synchronous call, ms; measured on "
+                "the GPU named below",
+        "device": torch.cuda.get_device_name(0),
+        "utterances": n, "frames_per_utterance": T, "reps": a.reps, "warmup": a.warmup,
+        "grammars": names, "hmms": [plan.hmms(i) for i in range(len(names))],
+        "hyp_and_score": {"active": last["active"], "yes": last["yes"]},
+        "ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4),
+                   "max": round(max(v), 4)} for k, v in times.items()},
+        "rounds_per_utterance": [int(x) for x in rounds],
+        "rounds_histogram": np.bincount(rounds, minlength=2).tolist(),
+        "rounds_of_the_call": int(m.grammar_active_stats()[2]),
+    }
+    out["ratio"] = round(out["ms"]["active"]["median"] / out["ms"]["yes"]["median"], 3)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--active", action="store_true",
+                    help="time ssw_recognize_batch_active next to ssw_recognize_batch instead")
     ap.add_argument("--utts", type=int, default=256)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grammar_bench.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "grammar_active_bench.json" if a.active
+                             else "grammar_bench.json")
+    if a.active:
+        return active(a)
 
     import torch
 
