@@ -660,7 +660,9 @@ int32_t ssw_alignment_json(const ssw_model_t *m, const char *hyp, int32_t hyp_lo
 /*   fsg_search_start / _null_prop / _word_trans / _step      src/fsg_search.c:543-802          */
 /*   fsg_search_find_exit / _hyp / _seg_iter, fsg_seg_bp2itor src/fsg_search.c:854-1143         */
 /* Not covered: JSGF, the default compallsen = no normalisation, lattices / best path /       */
-/* N-best, tag transitions, grammars beyond what one workgroup holds (4096 phone-tree HMMs).  */
+/* N-best, tag transitions, grammars of more than 30000 phone-tree HMMs (up to there with     */
+/* ssw_grammar_prepare_large; the default configuration, ssw_recognize_batch_active, is        */
+/* limited to grammars one workgroup holds: 4096 phone-tree HMMs).                             */
 /* ------------------------------------------------------------------------------------ */
 typedef struct ssw_fsg_s ssw_fsg_t;
 /* fsg_model_init + fsg_model_trans_add / fsg_model_null_trans_add per transition, in the order
@@ -709,6 +711,31 @@ ssw_grammar_plan_t *ssw_grammar_prepare(const ssw_model_t *m, const ssw_dict_t *
 void ssw_grammar_plan_free(ssw_grammar_plan_t *plan);
 /* phone-tree HMMs of grammar `fsg` of the plan (fsg_lextree_n_pnode), -1 when out of range */
 int32_t ssw_grammar_plan_hmms(const ssw_grammar_plan_t *plan, int32_t fsg);
+/* ssw_grammar_prepare for grammars of up to max_hmms phone-tree HMMs, with exchange arrays of
+ * any size; max_hmms <= SSW_GRAMMAR_LARGE_MAX_HMMS, the reference's default maxhmmpf: beyond it
+ * the reference narrows its beams frame by frame (src/fsg_search.c:376-394), which is not
+ * rebuilt.  Refused, on the host: max_hmms beyond the ceiling, a grammar of more than max_hmms
+ * HMMs (the message names the count and the limit), and what ssw_grammar_prepare refuses
+ * otherwise (a grammar keeps at most 65535 states and entering-list entries).
+ * The plan is opt-in because it costs.  A plan whose grammars all fit ssw_grammar_prepare's
+ * limits is searched by the same kernels as a plan made there.  A plan that holds at least one
+ * grammar beyond them is searched ENTIRELY by a kernel that keeps the HMMs and the exchange
+ * arrays in a per-utterance HBM workspace (about 100 bytes per HMM and entering-list entry),
+ * small grammars included, which the one-workgroup kernels hold in registers and search faster.  Its history tables
+ * ((frames + 1) x entering-list entries x 8 bytes per utterance) are held to
+ * SSW_GRAMMAR_HIST_BYTES by searching the call's utterances in groups, one launch after the other;
+ * only an utterance that exceeds the budget alone is refused.  ssw_grammar_search_batch,
+ * ssw_recognize_batch and the ssw_recognition_set_* readers take such a plan as any other;
+ * ssw_recognize_batch_active refuses it, naming the grammar and its HMM count. */
+#define SSW_GRAMMAR_LARGE_MAX_HMMS 30000
+ssw_grammar_plan_t *ssw_grammar_prepare_large(const ssw_model_t *m, const ssw_dict_t *d,
+                                              const ssw_first_pass_config_t *cfg, int32_t n_fsgs,
+                                              const ssw_fsg_t *const *fsgs, int32_t max_hmms);
+/* launches ssw_grammar_search_batch would search these utterances in (host only): 1 unless the
+ * plan is on the HBM-workspace kernel and the history tables exceed the budget; 0 without
+ * utterances; -1 where the call would be refused */
+int32_t ssw_grammar_history_groups(const ssw_grammar_plan_t *plan, const int32_t *fsg_of_utt,
+                                   const int32_t *utt_off, int32_t n_utts);
 
 /* one history entry of the best path (fsg_seg_bp2itor, src/fsg_search.c:1032-1055) */
 typedef struct ssw_fsg_seg_s {

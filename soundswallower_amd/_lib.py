@@ -229,6 +229,10 @@ def lib() -> C.CDLL:
     L.ssw_grammar_graph.argtypes = [vp, vp, vp, vp, i32, vp, vp]
     L.ssw_grammar_prepare.restype = vp
     L.ssw_grammar_prepare.argtypes = [vp, vp, vp, i32, vp]
+    L.ssw_grammar_prepare_large.restype = vp
+    L.ssw_grammar_prepare_large.argtypes = [vp, vp, vp, i32, vp, i32]
+    L.ssw_grammar_history_groups.restype = i32
+    L.ssw_grammar_history_groups.argtypes = [vp, vp, vp, i32]
     L.ssw_grammar_plan_free.argtypes = [vp]
     L.ssw_grammar_plan_free.restype = None
     L.ssw_grammar_plan_hmms.restype = i32

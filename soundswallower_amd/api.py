@@ -835,10 +835,12 @@ class Lexicon:
         _check(n, "ssw_grammar_graph")
         return nodes[:n].copy(), beams
 
-    def grammar_plan(self, fsgs, cfg=None) -> "GrammarPlan":
+    def grammar_plan(self, fsgs, cfg=None, max_hmms=None) -> "GrammarPlan":
         """ssw_grammar_prepare: decoder_set_fsg for a list of Fsg (or one); the graphs are built
-        once on the host and cached on the device while the plan is searched."""
-        return GrammarPlan(self, fsgs, cfg)
+        once on the host and cached on the device while the plan is searched.  max_hmms (up to
+        30000): ssw_grammar_prepare_large, grammars beyond the 4096 phone-tree HMMs one workgroup
+        holds; a plan with such a grammar is searched from an HBM workspace, all of it."""
+        return GrammarPlan(self, fsgs, cfg, max_hmms)
 
     def first_pass(self, d_senscr, utt_off, texts, cfg=None, max_seg=None, stream=None):
         """ssw_first_pass_batch: device senone scores of a batch + one word list per utterance
@@ -1210,18 +1212,31 @@ class Fsg:
 class GrammarPlan:
     """ssw_grammar_plan_t: the phone-tree graphs of one or more grammars."""
 
-    def __init__(self, lex: Lexicon, fsgs, cfg=None):
+    def __init__(self, lex: Lexicon, fsgs, cfg=None, max_hmms=None):
         self._L = _lib.lib()
         fsgs = [fsgs] if isinstance(fsgs, Fsg) else list(fsgs)
         self.n_fsgs = len(fsgs)
         arr = (C.c_void_p * max(1, len(fsgs)))(*[f._f for f in fsgs])
-        self._p = self._L.ssw_grammar_prepare(lex.model._m, lex._d,
-                                              None if cfg is None else C.byref(cfg), len(fsgs), arr)
+        pcfg = None if cfg is None else C.byref(cfg)
+        if max_hmms is None:
+            self._p = self._L.ssw_grammar_prepare(lex.model._m, lex._d, pcfg, len(fsgs), arr)
+        else:
+            self._p = self._L.ssw_grammar_prepare_large(lex.model._m, lex._d, pcfg, len(fsgs), arr,
+                                                        int(max_hmms))
         if not self._p:
-            raise SswError("ssw_grammar_prepare: " + _lib.last_error())
+            raise SswError(("ssw_grammar_prepare: " if max_hmms is None
+                            else "ssw_grammar_prepare_large: ") + _lib.last_error())
 
     def hmms(self, fsg=0) -> int:
         return int(self._L.ssw_grammar_plan_hmms(self._p, fsg))
+
+    def history_groups(self, utt_off, fsg_of_utt=None) -> int:
+        """ssw_grammar_history_groups: the launches a search of these utterances takes"""
+        off = np.ascontiguousarray(utt_off, np.int32)
+        g = _fsg_of_utt(fsg_of_utt, len(off) - 1)
+        n = self._L.ssw_grammar_history_groups(self._p, _ptr(g), _ptr(off), len(off) - 1)
+        _check(n, "ssw_grammar_history_groups")
+        return int(n)
 
     def free(self):
         if getattr(self, "_p", None):

@@ -1,4 +1,4 @@
-/* ssw_host_grammar.inc -- host: ssw_grammar_prepare, ssw_grammar_search_batch,
+/* ssw_host_grammar.inc -- host: ssw_grammar_prepare(_large), ssw_grammar_search_batch,
  * ssw_recognize_batch, ssw_recognize_batch_active and the recognition set.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 /* ---------------------------------------------------------------------------------- */
@@ -9,6 +9,11 @@ struct ssw_grammar_plan_s {
     int32_t n_fsgs;
     size_t lds_ints; /* the largest grammar's exchange arrays */
     int32_t max_nodes;
+    /* ssw_grammar_prepare_large: a grammar beyond one workgroup's registers or LDS puts the whole
+     * plan on grammar_search_big_kernel; the first such grammar, for the refusals that name it */
+    bool big;
+    int32_t big_fsg, big_nodes;
+    std::string big_name;
 };
 
 /* LDS ints of one grammar's exchange arrays: XS XH FLG [N] | EXJ IL[3] LS[2] per slot | TW |
@@ -24,12 +29,31 @@ grammar_lds_ints(const ssw_fp_graphs_t *g, int u)
 
 #define SSW_GRAMMAR_LDS_BYTES (160 * 1024 - 512)
 
-extern "C" ssw_grammar_plan_t *
-ssw_grammar_prepare(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
-                    int32_t n_fsgs, const ssw_fsg_t *const *fsgs)
+/* ints of one utterance's workspace on grammar_search_big_kernel (layout: see there) */
+static size_t
+grammar_big_ws_ints(const ssw_fp_graphs_t *g, int u)
 {
-    if (m == NULL || d == NULL || n_fsgs < 1 || fsgs == NULL) {
-        ssw_set_error("bad arguments to ssw_grammar_prepare");
+    const size_t nn = (size_t)(g->node_off[u + 1] - g->node_off[u]);
+    const size_t ns = (size_t)(g->state_off[u + 1] - g->state_off[u]);
+    const size_t ne = (size_t)(g->slot_off[g->state_off[u + 1]] - g->slot_off[g->state_off[u]]);
+    const size_t ntw = (size_t)(g->tw_off[u + 1] - g->tw_off[u]);
+    return 13 * nn + 9 * ne + ntw + (size_t)g->tw_rk[u] + 2 * ns + ntw / 4 + 1;
+}
+
+/* max_hmms < 0: ssw_grammar_prepare, every grammar within one workgroup */
+static ssw_grammar_plan_t *
+grammar_prepare(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
+                int32_t n_fsgs, const ssw_fsg_t *const *fsgs, int32_t max_hmms)
+{
+    const bool large = max_hmms >= 0;
+    if (m == NULL || d == NULL || n_fsgs < 1 || fsgs == NULL || (large && max_hmms < 1)) {
+        ssw_set_error("bad arguments to %s", large ? "ssw_grammar_prepare_large" : "ssw_grammar_prepare");
+        return NULL;
+    }
+    if (large && max_hmms > SSW_GRAMMAR_LARGE_MAX_HMMS) {
+        ssw_set_error("max_hmms = %d: the grammar search handles at most %d phone-tree HMMs per "
+                      "grammar (the reference narrows its beams beyond its maxhmmpf)", max_hmms,
+                      SSW_GRAMMAR_LARGE_MAX_HMMS);
         return NULL;
     }
     /* built on the calling thread, one grammar after the other (a plan's grammars are few next
@@ -40,14 +64,39 @@ ssw_grammar_prepare(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_p
         return NULL;
     size_t lds = 0;
     int32_t max_nodes = 0;
+    ssw_grammar_plan_t *p = new ssw_grammar_plan_t();
+    p->big = false;
+    p->big_fsg = -1;
+    p->big_nodes = 0;
     for (int u = 0; u < n_fsgs; ++u) {
         const int nn = g->node_off[u + 1] - g->node_off[u];
         const size_t li = grammar_lds_ints(g, u);
+        if (large) {
+            if (nn > max_hmms) {
+                ssw_set_error("grammar %d (%s) has %d phone-tree HMMs: max_hmms allows at most %d",
+                              u, ssw_fsg_name(fsgs[u]), nn, max_hmms);
+                ssw_fp_graphs_free(g);
+                delete p;
+                return NULL;
+            }
+            if (!p->big && (nn > SSW_GRAMMAR_MAX_HMMS || li * sizeof(int) > SSW_GRAMMAR_LDS_BYTES)) {
+                p->big = true;
+                p->big_fsg = u;
+                p->big_nodes = nn;
+                p->big_name = ssw_fsg_name(fsgs[u]);
+            }
+            if (nn <= SSW_GRAMMAR_MAX_HMMS && li * sizeof(int) <= SSW_GRAMMAR_LDS_BYTES) {
+                lds = std::max(lds, li);
+                max_nodes = std::max(max_nodes, nn);
+            }
+            continue;
+        }
         if (nn > SSW_GRAMMAR_MAX_HMMS) {
             ssw_set_error("grammar %d (%s) has %d phone-tree HMMs: the grammar search holds at "
                           "most %d in one workgroup", u, ssw_fsg_name(fsgs[u]), nn,
                           SSW_GRAMMAR_MAX_HMMS);
             ssw_fp_graphs_free(g);
+            delete p;
             return NULL;
         }
         if (li * sizeof(int) > SSW_GRAMMAR_LDS_BYTES) {
@@ -57,17 +106,34 @@ ssw_grammar_prepare(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_p
                           g->slot_off[g->state_off[u + 1]] - g->slot_off[g->state_off[u]],
                           li * sizeof(int), (int)SSW_GRAMMAR_LDS_BYTES);
             ssw_fp_graphs_free(g);
+            delete p;
             return NULL;
         }
         lds = std::max(lds, li);
         max_nodes = std::max(max_nodes, nn);
     }
-    ssw_grammar_plan_t *p = new ssw_grammar_plan_t();
     p->g = g;
     p->n_fsgs = n_fsgs;
     p->lds_ints = lds;
     p->max_nodes = max_nodes;
     return p;
+}
+
+extern "C" ssw_grammar_plan_t *
+ssw_grammar_prepare(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
+                    int32_t n_fsgs, const ssw_fsg_t *const *fsgs)
+{
+    return grammar_prepare(m, d, cfg, n_fsgs, fsgs, -1);
+}
+
+extern "C" ssw_grammar_plan_t *
+ssw_grammar_prepare_large(const ssw_model_t *m, const ssw_dict_t *d,
+                          const ssw_first_pass_config_t *cfg, int32_t n_fsgs,
+                          const ssw_fsg_t *const *fsgs, int32_t max_hmms)
+{
+    if (max_hmms < 0)
+        max_hmms = 0; /* (refused as a bad argument) */
+    return grammar_prepare(m, d, cfg, n_fsgs, fsgs, max_hmms);
 }
 
 extern "C" void
@@ -106,6 +172,90 @@ grammar_hist_budget()
     return SSW_GRAMMAR_HIST_BYTES;
 }
 
+/* The history tables of a call: (frames + 1) rows of one entry per slot, per utterance.
+ * hist_off[u]: the utterance's first entry within its group's table; group: the first utterance
+ * of every group, then n_utts; *hist_cap: the entries of the largest group.  A plan on the
+ * one-workgroup kernels is one group, refused when it exceeds the budget; a plan on
+ * grammar_search_big_kernel starts another group where the budget is reached (the groups are
+ * searched one after the other in the same table), and refuses an utterance that exceeds it alone. */
+static int
+grammar_history_layout(const ssw_grammar_plan_t *plan, const int32_t *fsg_of_utt,
+                       const int32_t *utt_off, int32_t n_utts, std::vector<long long> &hist_off,
+                       std::vector<int> &group, size_t *hist_cap, int *max_seg)
+{
+    const ssw_fp_graphs_t *g = plan->g;
+    const size_t budget = grammar_hist_budget();
+    size_t hist_total = 0, sum = 0;
+    hist_off.assign((size_t)n_utts + 1, 0);
+    group.assign(1, 0);
+    *hist_cap = 0;
+    *max_seg = 1;
+    for (int u = 0; u < n_utts; ++u) {
+        const int gi = fsg_of_utt ? fsg_of_utt[u] : 0;
+        if (gi < 0 || gi >= plan->n_fsgs) {
+            ssw_set_error("utterance %d: grammar %d is not one of the plan's %d", u, gi, plan->n_fsgs);
+            return -1;
+        }
+        const int T = utt_off[u + 1] - utt_off[u];
+        if (T < 0) {
+            ssw_set_error("bad arguments to ssw_grammar_search_batch");
+            return -1;
+        }
+        const size_t ne = (size_t)(g->slot_off[g->state_off[gi + 1]] - g->slot_off[g->state_off[gi]]);
+        const size_t nsn = (size_t)(g->sn_off[gi + 1] - g->sn_off[gi]);
+        const size_t row = std::max<size_t>(std::max(ne, nsn), 1);
+        if (row * ((size_t)T + 1) >= (size_t)INT_MAX) { /* entry ids are int32 */
+            ssw_set_error("utterance %d: %zu entering-list entries x %d frames exceed the history "
+                          "table's 2^31 entries", u, row, T);
+            return -1;
+        }
+        const size_t mine = row * ((size_t)T + 1);
+        if (plan->big && (hist_total + mine) * sizeof(int2) > budget) {
+            if (mine * sizeof(int2) > budget) {
+                ssw_set_error("the history table of utterance %d (%zu entries, %zu bytes: frames x "
+                              "entering-list entries) exceeds the budget of %zu bytes", u, mine,
+                              mine * sizeof(int2), budget);
+                return -1;
+            }
+            group.push_back(u);
+            hist_total = 0;
+        }
+        hist_off[(size_t)u] = (long long)hist_total;
+        hist_total += mine;
+        sum += mine;
+        *hist_cap = std::max(*hist_cap, hist_total);
+        /* a path has at most one word exit per frame, each followed by at most one null entry,
+         * after at most one null entry of frame -1 */
+        *max_seg = std::max(*max_seg, 2 * T + 1);
+    }
+    group.push_back(n_utts);
+    if (!plan->big && sum * sizeof(int2) > budget) {
+        ssw_set_error("the history table of this call (%zu entries, %zu bytes: frames x "
+                      "entering-list entries, summed over %d utterances) exceeds the budget of "
+                      "%zu bytes; search fewer utterances per call", sum, sum * sizeof(int2), n_utts,
+                      budget);
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int32_t
+ssw_grammar_history_groups(const ssw_grammar_plan_t *plan, const int32_t *fsg_of_utt,
+                           const int32_t *utt_off, int32_t n_utts)
+{
+    std::vector<long long> hist_off;
+    std::vector<int> group;
+    size_t cap;
+    int max_seg;
+    if (plan == NULL || utt_off == NULL || n_utts < 0) {
+        ssw_set_error("bad arguments to ssw_grammar_history_groups");
+        return -1;
+    }
+    if (grammar_history_layout(plan, fsg_of_utt, utt_off, n_utts, hist_off, group, &cap, &max_seg) < 0)
+        return -1;
+    return n_utts > 0 ? (int32_t)group.size() - 1 : 0;
+}
+
 /* One call's grammar search in three steps, so that the default configuration can launch it
  * once per round (ssw_recognize_batch_active): begin() checks the call, makes the empty set and
  * uploads the tables; launch() runs the kernel over some rows; finish() fetches the results and
@@ -123,10 +273,14 @@ struct grammar_run_t {
     size_t nseg_off, score_off, seg_off, only_off;
     std::vector<unsigned char> stage; /* must outlive its copy */
     std::vector<int> only_host;
+    std::vector<int> group; /* first utterance of every history group, then n_utts */
+    int *big_ws;            /* grammar_search_big_kernel's workspaces and their offsets */
+    const long long *big_ws_off;
     bool uploaded;
 
     grammar_run_t() : m(NULL), d(NULL), plan(NULL), fsg_of_utt(NULL), n_utts(0), st(NULL), r(NULL),
-                      max_seg(1), nseg_off(0), score_off(0), seg_off(0), only_off(0), uploaded(false) {}
+                      max_seg(1), nseg_off(0), score_off(0), seg_off(0), only_off(0), big_ws(NULL),
+                      big_ws_off(NULL), uploaded(false) {}
     ~grammar_run_t()
     {
         if (uploaded)
@@ -154,42 +308,20 @@ grammar_run_t::begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_pl
     (void)n_frames;
     const ssw_fp_graphs_t *g = plan->g;
     st = (hipStream_t)stream;
-    /* the history table: (frames + 1) rows of one entry per slot, per utterance */
-    std::vector<long long> hist_off((size_t)n_utts + 1);
-    size_t hist_total = 0;
-    max_seg = 1;
-    for (int u = 0; u < n_utts; ++u) {
-        const int gi = fsg_of_utt ? fsg_of_utt[u] : 0;
-        if (gi < 0 || gi >= plan->n_fsgs) {
-            ssw_set_error("utterance %d: grammar %d is not one of the plan's %d", u, gi, plan->n_fsgs);
-            return -1;
-        }
-        const int T = utt_off[u + 1] - utt_off[u];
-        if (T < 0) {
-            ssw_set_error("bad arguments to ssw_grammar_search_batch");
-            return -1;
-        }
-        const size_t ne = (size_t)(g->slot_off[g->state_off[gi + 1]] - g->slot_off[g->state_off[gi]]);
-        const size_t nsn = (size_t)(g->sn_off[gi + 1] - g->sn_off[gi]);
-        const size_t row = std::max<size_t>(std::max(ne, nsn), 1);
-        if (row * ((size_t)T + 1) >= (size_t)INT_MAX) { /* entry ids are int32 */
-            ssw_set_error("utterance %d: %zu entering-list entries x %d frames exceed the history "
-                          "table's 2^31 entries", u, row, T);
-            return -1;
-        }
-        hist_off[(size_t)u] = (long long)hist_total;
-        hist_total += row * ((size_t)T + 1);
-        /* a path has at most one word exit per frame, each followed by at most one null entry,
-         * after at most one null entry of frame -1 */
-        max_seg = std::max(max_seg, 2 * T + 1);
-    }
-    if (hist_total * sizeof(int2) > grammar_hist_budget()) {
-        ssw_set_error("the history table of this call (%zu entries, %zu bytes: frames x "
-                      "entering-list entries, summed over %d utterances) exceeds the budget of "
-                      "%zu bytes; search fewer utterances per call", hist_total,
-                      hist_total * sizeof(int2), n_utts, grammar_hist_budget());
+    std::vector<long long> hist_off, ws_off((size_t)n_utts + 1, 0);
+    size_t hist_total = 0, ws_ints = 0;
+    if (grammar_history_layout(plan, fsg_of_utt, utt_off, n_utts, hist_off, group, &hist_total,
+                               &max_seg) < 0)
         return -1;
-    }
+    if (plan->big) /* the workspaces of a group's utterances, the largest group's in all */
+        for (size_t k = 0; k + 1 < group.size(); ++k) {
+            size_t at = 0;
+            for (int u = group[k]; u < group[k + 1]; ++u) {
+                ws_off[(size_t)u] = (long long)at;
+                at += grammar_big_ws_ints(g, fsg_of_utt ? fsg_of_utt[u] : 0);
+            }
+            ws_ints = std::max(ws_ints, at);
+        }
     r = new ssw_recognition_set_t();
     r->m = m;
     r->d = d;
@@ -243,6 +375,7 @@ grammar_run_t::begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_pl
         { utt_off, sizeof(int) * ((size_t)n_utts + 1), 0 },               /* 28: the call's */
         { fsg_of_utt, fsg_of_utt ? sizeof(int) * (size_t)n_utts : 0, 0 },
         { hist_off.data(), sizeof(long long) * (size_t)n_utts, 0 },       /* 30 */
+        { ws_off.data(), sizeof(long long) * (size_t)n_utts, 0 },
     };
     enum { PC_CALL = 28 };
     const int n_pc = (int)(sizeof(pc) / sizeof(pc[0]));
@@ -262,6 +395,8 @@ grammar_run_t::begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_pl
     off += (sizeof(ssw_fsg_seg_t) * (size_t)n_utts * (size_t)max_seg + 255) & ~(size_t)255;
     const size_t hist_at = off;
     off += (sizeof(int2) * (hist_total ? hist_total : 1) + 255) & ~(size_t)255;
+    const size_t big_at = off;
+    off += (sizeof(int) * ws_ints + 255) & ~(size_t)255;
 
     hipError_t e = hipSetDevice(m->device);
     if (e == hipSuccess && off > m->gr_ws_cap) { /* grow-only workspace */
@@ -322,6 +457,8 @@ grammar_run_t::begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_pl
         P.utt_off = (const int *)(ws + pc[28].off);
         P.fsg_of_utt = fsg_of_utt ? (const int *)(ws + pc[29].off) : NULL;
         P.hist_off = (const long long *)(ws + pc[30].off);
+        big_ws = (int *)(ws + big_at);
+        big_ws_off = (const long long *)(ws + pc[31].off);
         P.tp = (const uint32_t *)m->d_tp;
         P.hist = (int2 *)(ws + hist_at);
         P.n_seg = (int *)(ws + nseg_off);
@@ -356,6 +493,20 @@ grammar_run_t::launch(const int16_t *d_senscr, const std::vector<int> *only, uns
     P.only = NULL;
     P.act_mask = mask;
     P.act_off = d_act_off;
+    if (plan->big) {
+        /* (ssw_recognize_batch_active refuses such a plan: no rounds, no exported sets) */
+        GrammarBigParams B;
+        B.g = P;
+        B.ws = big_ws;
+        B.ws_off = big_ws_off;
+        for (size_t k = 0; k + 1 < group.size() && e == hipSuccess; ++k) {
+            B.u0 = group[k];
+            hipLaunchKernelGGL(grammar_search_big_kernel<1024>, dim3((unsigned)(group[k + 1] - group[k])),
+                               dim3(1024), 0, st, B);
+            e = hipGetLastError();
+        }
+        return e;
+    }
     if (only != NULL && !only->empty()) {
         only_host = *only; /* (kept here: every round ends in a synchronisation of the stream) */
         e = hipMemcpyAsync(ws + only_off, only_host.data(), sizeof(int) * (size_t)n_run,
@@ -592,6 +743,13 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
         return NULL;
     if (m->device == SSW_DEVICE_NONE) {
         ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+        return NULL;
+    }
+    if (plan->big) {
+        ssw_set_error("grammar %d (%s) has %d phone-tree HMMs and is searched from an HBM workspace: "
+                      "the default configuration (compallsen = no) holds a plan's largest grammar "
+                      "in one workgroup; use ssw_recognize_batch", plan->big_fsg,
+                      plan->big_name.c_str(), plan->big_nodes);
         return NULL;
     }
     if (fpa_check_limits(m, "ssw_recognize_batch_active", scorer) < 0)

@@ -1,4 +1,4 @@
-/* ssw_k9_grammar.inc -- device: grammar_search_kernel.
+/* ssw_k9_grammar.inc -- device: grammar_search_kernel, grammar_search_big_kernel.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 /* ---------------------------------------------------------------------------------- */
 /* K9: recognition against a word FSG (decoder_set_fsg)                                 */
@@ -454,6 +454,373 @@ grammar_search_kernel(GrammarParams P)
 
     /* fsg_search_seg_iter + fsg_seg_bp2itor: walk the predecessors back, then write the entries
      * in order.  Entry id -> row (id - 1) / ROW = frame + 1, slot (id - 1) % ROW. */
+    if (tid == 0) {
+        int id = s_final_id, n = 0;
+        ssw_fsg_seg_t *seg = P.seg + (size_t)u * P.max_seg;
+        if (id < 0)
+            n = s_have ? -1 : -2;
+        else {
+            for (int k = id; k > 0; k = hist[k - 1].x)
+                ++n;
+            if (n > P.max_seg)
+                n = -(3 + n);
+            else {
+                int j = n - 1;
+                for (int k = id; k > 0; k = hist[k - 1].x, --j) {
+                    const int row = (k - 1) / ROW, sl = (k - 1) % ROW;
+                    const int2 e = hist[k - 1];
+                    const int pk = e.x;
+                    const int pscore = pk > 0 ? hist[pk - 1].y : 0;
+                    const int ef = row - 1;
+                    int sf = pk > 0 ? (pk - 1) / ROW : 0; /* predecessor's frame + 1 */
+                    sf = sf > ef ? ef : sf;
+                    int wid = -1, lscr;
+                    if (row == 0)
+                        lscr = P.sn_pen[snb + sl];
+                    else if (P.slot_null[j_base + sl])
+                        lscr = P.slot_pen[j_base + sl];
+                    else {
+                        const int lo = P.slot_leaf[j_base + sl];
+                        wid = P.leaf_wid[lb + lo];
+                        lscr = P.leaf_lscr[lb + lo];
+                    }
+                    seg[j].wid = wid;
+                    seg[j].sf = sf;
+                    seg[j].ef = ef;
+                    seg[j].lscr = lscr;
+                    seg[j].ascr = e.y - pscore - lscr;
+                }
+            }
+            P.score[u] = s_final_score;
+        }
+        P.n_seg[u] = n;
+    }
+}
+
+/* K9 for grammars beyond what one workgroup holds in registers and LDS (more than 4096 phone-tree
+ * HMMs, or exchange arrays beyond 160 KB; ssw_grammar_prepare_large): the same three phases per
+ * frame, the same decisions in the same order, but every thread walks its nodes (n = tid, tid +
+ * TPB, ...) and the node state and the exchange arrays live in a per-utterance HBM workspace
+ * (L2-resident), as in first_pass_big_kernel.  The barriers are full __syncthreads(): they order
+ * the workgroup's global traffic as well, and every thread reaches every one of them.
+ * Layout of the workspace (ints): 13 arrays of N (s0 s1 s2 h0 h1 h2 os oh bsc act xs xh flg) |
+ * IL[3 NE] | LS[3 NE] (slot, state, penalty: no 16-bit packing) | TW | RK | SMAX[2 NS] |
+ * TWL[NTW / 4 + 1] | FL[3 NE].
+ * A frame of such a grammar has hundreds of active HMMs among thousands and about ten history
+ * entries among thousands of slots, and the work follows that:
+ *   - the walks over all N nodes read act[] alone; constants, scores and state are fetched for
+ *     active nodes only (phase C reads a node's parent and info as well: whether it is entered
+ *     depends on them).  act bit 0: active; bit 1: kept by the beam (phase B -> C); bit 2: the
+ *     node was deactivated with an exit on offer, which the next phase B withdraws -- an inactive
+ *     node has XS = INT_MIN by that, and is not touched otherwise;
+ *   - there is no EXJ: phase B appends every entry it files to the frame's list FL (slot, score,
+ *     state; count in LDS, by frame parity), a word-initial HMM scans that list instead of its
+ *     state's slots, and so does fsg_search_find_exit.  The list is in no order, so of equal
+ *     scores the lowest slot wins explicitly: the first in the reference's history order, the one
+ *     the dense scan meets first;
+ *   - the rank buffers of a twin group need every member's call in every frame: the inactive
+ *     members are called from TWL, the list of twin leaves made once, not found by a walk. */
+struct GrammarBigParams {
+    GrammarParams g;
+    int *ws;                 /* the workspaces of the launch's utterances */
+    const long long *ws_off; /* [n_utts] offset (ints) of the utterance's part of ws */
+    int u0;                  /* workgroup b searches utterance u0 + b: a call whose history exceeds
+                                the budget is searched group by group */
+};
+
+template <int TPB>
+__global__ void __launch_bounds__(TPB)
+grammar_search_big_kernel(GrammarBigParams B)
+{
+    const GrammarParams &P = B.g;
+    const int u = B.u0 + (int)blockIdx.x, tid = threadIdx.x;
+    const int gi = P.fsg_of_utt != NULL ? P.fsg_of_utt[u] : 0;
+    const int nb = P.node_off[gi], N = P.node_off[gi + 1] - nb;
+    const int lb = P.leaf_off[gi];
+    const int sb = P.state_off[gi], NS = P.state_off[gi + 1] - sb;
+    const int f0 = P.utt_off[u], T = P.utt_off[u + 1] - f0;
+    const int W = SSW_WORST_SCORE;
+    const int *slot_off = P.slot_off + sb;
+    const int j_base = slot_off[0], NE = slot_off[NS] - j_base;
+    const int snb = P.sn_off[gi], NSN = P.sn_off[gi + 1] - snb;
+    const int ROW = NE > NSN ? (NE > 0 ? NE : 1) : NSN; /* history entries per frame */
+    const int start = P.g_start[gi], fin = P.g_final[gi];
+    const int NTW = P.tw_off[gi + 1] - P.tw_off[gi], NRK = P.tw_rk[gi];
+    const int NTWL = NTW / 4 + 1; /* (a twin record is 4 + L ints, L >= 2) */
+    int *ws = B.ws + B.ws_off[u];
+    int *S0 = ws, *S1 = S0 + N, *S2 = S1 + N, *H0 = S2 + N, *H1 = H0 + N, *H2 = H1 + N;
+    int *OS = H2 + N, *OH = OS + N, *BSC = OH + N, *ACT = BSC + N;
+    int *XS = ACT + N, *XH = XS + N, *FLG = XH + N;
+    int *IL = FLG + N, *LS = IL + 3 * NE, *TW = LS + 3 * NE, *RK = TW + NTW, *SMAX = RK + NRK;
+    int *TWL = SMAX + 2 * NS, *FL = TWL + NTWL;
+    __shared__ int s_red[TPB / 64], s_cnt[2], s_ntwl, s_final_id, s_final_score, s_have;
+    const uint16_t *senid = P.senid + (size_t)nb * 4;
+    const int *pen = P.pen + nb, *parent = P.parent + nb, *leaf_ord = P.leaf_ord + nb;
+    const uint32_t *info = P.info + nb;
+    const unsigned long long *ctxt = P.ctxt + nb;
+    const int *leaf_node = P.leaf_node + lb;
+    const int *ls_off = P.ls_off + lb;
+    const int *twin_ref = P.twin_ref + nb;
+    const int ls_base = ls_off[0];
+    int2 *hist = P.hist + P.hist_off[u];
+
+    for (int j = tid; j < NE; j += TPB) {
+        const int lo = P.slot_leaf[j_base + j], ln = leaf_node[lo];
+        const uint32_t li = info[ln];
+        IL[3 * j] = (int)((((li >> 8) & 0xff) << 16) | ((li & FP_ALLRC) ? 1u << 24 : 0u));
+        IL[3 * j + 1] = (int)(uint32_t)(ctxt[ln] & 0xffffffffull);
+        IL[3 * j + 2] = (int)(uint32_t)(ctxt[ln] >> 32);
+        /* (a leaf's slots are ls_slot[ls_off[leaf] ..): NE of them in all */
+        const int sj = P.ls_slot[ls_base + j];
+        LS[3 * j] = sj;
+        LS[3 * j + 1] = P.slot_state[j_base + sj];
+        LS[3 * j + 2] = P.slot_pen[j_base + sj];
+    }
+    for (int i = tid; i < NTW; i += TPB)
+        TW[i] = P.tw[P.tw_off[gi] + i];
+    for (int i = tid; i < NRK; i += TPB)
+        RK[i] = FP_RANK_NONE;
+    for (int i = tid; i < 2 * NS; i += TPB)
+        SMAX[i] = FP_NO_EXIT;
+    if (tid == 0) {
+        /* fsg_search_start, as in grammar_search_kernel */
+        int be = INT_MIN, bid = -1, have = 0;
+        for (int k = 0; k < NSN; ++k) {
+            const int sc = P.sn_pen[snb + k];
+            hist[k] = make_int2(0, sc);
+            if (sc >= P.wbeam) {
+                have = 1;
+                if (P.sn_to[snb + k] == fin && sc > be) {
+                    be = sc;
+                    bid = 1 + k;
+                }
+            }
+        }
+        s_final_id = bid;
+        s_final_score = be;
+        s_have = have;
+        s_cnt[0] = s_cnt[1] = 0;
+        s_ntwl = 0;
+    }
+    __syncthreads();
+    for (int n = tid; n < N; n += TPB) {
+        int s0 = W, h0 = -1, a = 0;
+        const uint32_t inf = info[n];
+        const int pn = pen[n];
+        if ((inf & FP_ROOT) && ((ctxt[n] >> P.sil) & 1)) {
+            const int d = (int)(inf >> 16);
+            if (d == start && pn > P.beam && pn > s0) {
+                s0 = pn;
+                h0 = 0;
+                a = 1;
+            }
+            for (int q = 0; q < NSN; ++q) {
+                const int sc = P.sn_pen[snb + q];
+                if (P.sn_to[snb + q] == d && sc >= P.wbeam && sc + pn > P.beam && sc + pn > s0) {
+                    s0 = sc + pn;
+                    h0 = 1 + q;
+                    a = 1;
+                }
+            }
+        }
+        S0[n] = s0;
+        S1[n] = S2[n] = OS[n] = BSC[n] = W;
+        H0[n] = h0;
+        H1[n] = H2[n] = OH[n] = -1;
+        ACT[n] = a;
+        XS[n] = INT_MIN;
+        XH[n] = -1;
+        FLG[n] = a ? (FP_F_NEXT | FP_F_ENTW) : 0;
+        if (leaf_ord[n] >= 0 && twin_ref[n] >= 0) {
+            const int i = atomicAdd(&s_ntwl, 1);
+            if (i < NTWL)
+                TWL[i] = n;
+        }
+    }
+    __syncthreads();
+    const int ntwl = s_ntwl < NTWL ? s_ntwl : NTWL;
+
+    for (int f = 0; f < T; ++f) { /* (T is the same in every thread of the group: barriers) */
+        /* A: hmm_vit_eval of the active nodes, best score of the frame */
+        const uint16_t *urow =
+            reinterpret_cast<const uint16_t *>(P.senscr + (size_t)(f0 + f) * P.n_sen);
+        int bs = W;
+        for (int n = tid; n < N; n += TPB) {
+            if (!(ACT[n] & 1))
+                continue;
+            const uint16_t *sn = senid + (size_t)n * 4;
+            const uint32_t *tp = P.tp + (size_t)sn[3] * 3;
+            int s0 = S0[n], s1 = S1[n], s2 = S2[n], h0 = H0[n], h1 = H1[n], h2 = H2[n];
+            int os = OS[n], oh = OH[n];
+            const int c0 = (int)(short)urow[sn[0]], c1 = (int)(short)urow[sn[1]],
+                      c2 = (int)(short)urow[sn[2]];
+            const int b = vit_eval_3st(s0, s1, s2, h0, h1, h2, os, oh, -c0, -c1, -c2, tp[0], tp[1],
+                                       tp[2]);
+            S0[n] = s0, S1[n] = s1, S2[n] = s2, H0[n] = h0, H1[n] = h1, H2[n] = h2;
+            OS[n] = os, OH[n] = oh, BSC[n] = b;
+            bs = b > bs ? b : bs;
+        }
+        bs = wave_max_dpp(bs);
+        if ((tid & 63) == 0)
+            s_red[tid >> 6] = bs;
+        __syncthreads();
+        int best = s_red[0];
+#pragma unroll
+        for (int k = 1; k < TPB / 64; ++k)
+            best = s_red[k] > best ? s_red[k] : best;
+        const int thresh = best + P.beam, pth = best + P.pbeam, wth = best + P.wbeam;
+
+        /* B: the active nodes offer their exits; a word-final HMM that passes the word beam files
+         * a word exit and one entry per null transition out of the state it leads to, each into
+         * the history table, the state's maximum and the frame's list */
+        const int hrow = (f + 1) * ROW;
+        for (int i = tid; i < NS; i += TPB) /* next frame's buffer */
+            SMAX[((f + 1) & 1) * NS + i] = FP_NO_EXIT;
+        for (int n = tid; n < N; n += TPB) {
+            const int a = ACT[n];
+            if (!(a & 1)) {
+                if (a & 4) { /* deactivated last frame: its offer is withdrawn */
+                    XS[n] = INT_MIN;
+                    ACT[n] = 0;
+                }
+                continue;
+            }
+            const int os = OS[n], oh = OH[n];
+            const bool keep = BSC[n] >= thresh;
+            ACT[n] = 1 | (keep ? 2 : 0);
+            XS[n] = (keep && os >= pth) ? os : INT_MIN;
+            XH[n] = oh;
+            const int lf = leaf_ord[n];
+            if (lf < 0)
+                continue;
+            bool ex = keep && os >= wth;
+            const int tw = twin_ref[n];
+            if (tw >= 0)
+                ex = twin_first_in_list(TW + tw, RK, FLG, f) && ex;
+            if (!ex)
+                continue;
+            const int ls0 = ls_off[lf] - ls_base, ls1 = ls_off[lf + 1] - ls_base;
+            int id0 = 0;
+            for (int i = ls0; i < ls1; ++i) {
+                const int j = LS[3 * i], st = LS[3 * i + 1], sc = os + LS[3 * i + 2];
+                /* (the word exit's own slot comes first, with penalty 0) */
+                if (sc >= wth) {
+                    hist[(size_t)hrow + j] = make_int2(i == ls0 ? oh : id0, sc);
+                    atomicMax(&SMAX[(f & 1) * NS + st], sc);
+                    const int q = atomicAdd(&s_cnt[f & 1], 1);
+                    if (q < NE) { /* (a slot is filed at most once per frame) */
+                        FL[3 * q] = j;
+                        FL[3 * q + 1] = sc;
+                        FL[3 * q + 2] = st;
+                    }
+                }
+                if (i == ls0)
+                    id0 = 1 + hrow + j;
+            }
+        }
+        for (int i = tid; i < ntwl; i += TPB) { /* every member keeps its group's order up to date */
+            const int n = TWL[i];
+            if (!(ACT[n] & 1)) /* (bit 0 does not change in this phase) */
+                (void)twin_first_in_list(TW + twin_ref[n], RK, FLG, f);
+        }
+        __syncthreads();
+
+        /* C: phone transitions, cross-word transitions out of the frame's list, activity */
+        const int cnt = s_cnt[f & 1] < NE ? s_cnt[f & 1] : NE;
+        for (int n = tid; n < N; n += TPB) {
+            const int actf = ACT[n];
+            const bool act = actf & 1, keep = (actf & 2) != 0;
+            const int par = parent[n];
+            const uint32_t inf = info[n];
+            int xs = INT_MIN, xh = -1;
+            if (par >= 0) {
+                xs = XS[par];
+                xh = XH[par];
+            }
+            int mx = FP_NO_EXIT;
+            if ((inf & FP_ROOT) && cnt > 0)
+                mx = SMAX[(f & 1) * NS + (int)(inf >> 16)];
+            if (!act && xs == INT_MIN && mx == FP_NO_EXIT)
+                continue; /* (FLG is 0 and XS is INT_MIN already: it was not active) */
+            const int pn = pen[n];
+            int s0 = S0[n], h0 = H0[n];
+            bool entered = false, entered_p = false, entered_w = false;
+            if (par >= 0 && xs != INT_MIN) {
+                const int ns = xs + pn;
+                if (ns > thresh && ns > s0) {
+                    s0 = ns; /* hmm_enter */
+                    h0 = xh;
+                    entered = entered_p = true;
+                }
+            }
+            if ((inf & FP_ROOT) && mx != FP_NO_EXIT && mx + pn > thresh && mx + pn > s0) {
+                const int ci = (int)((inf >> 8) & 0xff), d = (int)(inf >> 16);
+                const unsigned long long cx = ctxt[n];
+                int be = FP_NO_EXIT, bid = -1;
+                for (int q = 0; q < cnt; ++q) {
+                    if (FL[3 * q + 2] != d)
+                        continue;
+                    const int j = FL[3 * q], ex = FL[3 * q + 1];
+                    if (ex < be || (ex == be && j > bid))
+                        continue;
+                    const uint32_t w = (uint32_t)IL[3 * j];
+                    if (!((cx >> ((w >> 16) & 0xff)) & 1))
+                        continue;
+                    const unsigned long long rcs = (unsigned long long)(uint32_t)IL[3 * j + 1]
+                        | ((unsigned long long)(uint32_t)IL[3 * j + 2] << 32);
+                    if (!((w >> 24) & 1) && !((rcs >> ci) & 1))
+                        continue;
+                    be = ex;
+                    bid = j;
+                }
+                if (bid >= 0) {
+                    const int ns = be + pn;
+                    if (ns > thresh && ns > s0) {
+                        s0 = ns;
+                        h0 = 1 + hrow + bid;
+                        entered = entered_w = true;
+                    }
+                }
+            }
+            const bool stay = keep || entered;
+            FLG[n] = (stay ? FP_F_NEXT : 0) | (keep ? FP_F_KEEP : 0) | (entered_p ? FP_F_ENTP : 0)
+                | (entered_w ? FP_F_ENTW : 0);
+            if (entered) {
+                S0[n] = s0;
+                H0[n] = h0;
+            }
+            if (act && !stay) { /* fsg_psubtree_pnode_deactivate -> hmm_clear */
+                S0[n] = S1[n] = S2[n] = OS[n] = BSC[n] = W;
+                H0[n] = H1[n] = H2[n] = OH[n] = -1;
+            }
+            ACT[n] = stay ? 1 : (act ? 4 : 0);
+        }
+        /* fsg_search_find_exit, final: the LAST frame that has any entry, the best entry into the
+         * final state, null entries included; of equals the oldest (the lowest slot) */
+        if (tid == 0) {
+            if (cnt > 0) {
+                int be = INT_MIN, bid = -1;
+                for (int q = 0; q < cnt; ++q) {
+                    if (FL[3 * q + 2] != fin)
+                        continue;
+                    const int j = FL[3 * q], ex = FL[3 * q + 1];
+                    if (ex > be || (ex == be && j < bid)) {
+                        be = ex;
+                        bid = j;
+                    }
+                }
+                s_final_id = bid >= 0 ? 1 + hrow + bid : -1;
+                s_final_score = be;
+                s_have = 1;
+            }
+            s_cnt[(f + 1) & 1] = 0;
+        }
+        /* no barrier here: the next frame's phase A touches a thread's own nodes only; XS, FL and
+         * the counts are written after its barrier, which every reader above has to reach first */
+    }
+    __syncthreads(); /* the entries written during the loop are read back below */
+
+    /* fsg_search_seg_iter + fsg_seg_bp2itor, as in grammar_search_kernel */
     if (tid == 0) {
         int id = s_final_id, n = 0;
         ssw_fsg_seg_t *seg = P.seg + (size_t)u * P.max_seg;

@@ -41,6 +41,8 @@
  *   ssw_k9_grammar.inc   grammar_search_kernel: K5's search over the phone trees of any word FSG,
  *                        null transitions folded into the states' entering lists
  *                        (fsg_search_start / _null_prop / _find_exit, src/fsg_search.c:543-924)
+ *                        grammar_search_big_kernel: the same search from an HBM workspace, for
+ *                        grammars beyond one workgroup (ssw_grammar_prepare_large)
  *   ssw_host_*.inc       device model and loaders' upload, batched scoring, alignment, the
  *                        mgau_t / search-module shaped objects, features, the front end
  *                        (ssw_host_fe.inc; its tables are built in ssw_model.c), device-memory

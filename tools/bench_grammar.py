@@ -28,6 +28,14 @@ alternating, with the rounds every utterance took and their histogram; `ratio` =
 medians.
 
     python tools/bench_grammar.py --active [--utts 256] [--reps 10] [--warmup 2] [--out FILE]
+
+With --large it times grammars beyond one workgroup (ssw_grammar_prepare_large: node state and
+exchange arrays in an HBM workspace) and writes profiles/grammar_large_bench.json: loop200 and
+loop400 (tests/golden/fsg/, 5613 and 11818 phone-tree HMMs) and, as the yardstick, loop110 (3083,
+the one-workgroup kernel with eight HMMs per thread), each at 1, 16 and 256 copies of the
+recording; per figure the number of history groups the call is searched in, and `ratio_400_200`.
+
+    python tools/bench_grammar.py --large [--reps 10] [--warmup 2] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -108,20 +116,90 @@ def active(a):
     print(json.dumps(out))
 
 
+def large(a):
+    import torch
+
+    import soundswallower_amd as ssw
+    from tests import fsg_common as G
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_grammar: no GPU; nothing is measured without one")
+    mdir = ssw.model_dir("en-us")
+    m = ssw.Model(mdir)
+    lex = ssw.Lexicon(m, os.path.join(mdir, "dict.txt"), os.path.join(mdir, "noisedict.txt"))
+    cep, _ = m.fe_batch(G.pcm("goforward.raw", 0))
+    scr = m.score_batch(m.feat_batch(cep))
+    T, sizes = len(scr), (1, 16, 256)
+    d = torch.from_numpy(np.ascontiguousarray(np.tile(scr, (max(sizes), 1)))).cuda()
+    names = ["loop110", "loop200", "loop400"]
+    plans = {g: lex.grammar_plan(ssw.Fsg.read(m, lex, G.fsg_path(g)),
+                                 max_hmms=None if g == "loop110" else 30000) for g in names}
+    offs = {n: (np.arange(n + 1) * T).astype(np.int32) for n in sizes}
+    last = {}
+
+    def run(g, n):
+        r = ssw.grammar_search_batch(m, lex, d, offs[n], plans[g])
+        last[g] = (r.hyp(n - 1), r.score(n - 1))
+        r.free()
+
+    times = {(g, n): [] for n in sizes for g in names}
+    for n in sizes:
+        for i in range(a.warmup + a.reps):
+            for g in names:                  # alternating: the grammars share whatever the box does
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run(g, n)
+                dt = (time.perf_counter() - t0) * 1e3
+                if i >= a.warmup:
+                    times[(g, n)].append(dt)
+    out = {
+        "what": "ssw_grammar_search_batch, host clock around one synchronous call, ms; loop200 and "
+                "loop400 on grammar_search_big_kernel (ssw_grammar_prepare_large), loop110 on "
+                "grammar_search_kernel<8, 512>; measured on the GPU named below",
+        "device": torch.cuda.get_device_name(0),
+        "frames_per_utterance": T, "reps": a.reps, "warmup": a.warmup,
+        "hmms": {g: plans[g].hmms() for g in names},
+        "hyp_and_score": last,
+        "history_groups": {g: {str(n): plans[g].history_groups(offs[n]) for n in sizes}
+                           for g in names},
+        "ms": {g: {str(n): {"median": round(statistics.median(times[(g, n)]), 4),
+                            "min": round(min(times[(g, n)]), 4),
+                            "max": round(max(times[(g, n)]), 4)} for n in sizes} for g in names},
+        "reference": "about 200 ms of one CPU core per utterance for these grammars, model load "
+                     "included (an upper bound)",
+    }
+    out["ms_per_utterance"] = {g: {str(n): round(out["ms"][g][str(n)]["median"] / n, 4)
+                                   for n in sizes} for g in names}
+    out["ratio_400_200"] = {str(n): round(out["ms"]["loop400"][str(n)]["median"]
+                                          / out["ms"]["loop200"][str(n)]["median"], 3)
+                            for n in sizes}
+    out["hmm_ratio_400_200"] = round(out["hmms"]["loop400"] / out["hmms"]["loop200"], 3)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--active", action="store_true",
                     help="time ssw_recognize_batch_active next to ssw_recognize_batch instead")
+    ap.add_argument("--large", action="store_true",
+                    help="time grammars beyond one workgroup (ssw_grammar_prepare_large) instead")
     ap.add_argument("--utts", type=int, default=256)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "grammar_active_bench.json" if a.active
+        a.out = os.path.join(ROOT, "profiles", "grammar_large_bench.json" if a.large
+                             else "grammar_active_bench.json" if a.active
                              else "grammar_bench.json")
     if a.active:
         return active(a)
+    if a.large:
+        return large(a)
 
     import torch
 
