@@ -661,8 +661,8 @@ int32_t ssw_alignment_json(const ssw_model_t *m, const char *hyp, int32_t hyp_lo
 /*   fsg_search_find_exit / _hyp / _seg_iter, fsg_seg_bp2itor src/fsg_search.c:854-1143         */
 /* Not covered: JSGF, the default compallsen = no normalisation, lattices / best path /       */
 /* N-best, tag transitions, grammars of more than 30000 phone-tree HMMs (up to there with     */
-/* ssw_grammar_prepare_large; the default configuration, ssw_recognize_batch_active, is        */
-/* limited to grammars one workgroup holds: 4096 phone-tree HMMs).                             */
+/* ssw_grammar_prepare_large, and in the default configuration, ssw_recognize_batch_active,    */
+/* with ssw_grammar_prepare_large_active).                                                     */
 /* ------------------------------------------------------------------------------------ */
 typedef struct ssw_fsg_s ssw_fsg_t;
 /* fsg_model_init + fsg_model_trans_add / fsg_model_null_trans_add per transition, in the order
@@ -726,11 +726,30 @@ int32_t ssw_grammar_plan_hmms(const ssw_grammar_plan_t *plan, int32_t fsg);
  * SSW_GRAMMAR_HIST_BYTES by searching the call's utterances in groups, one launch after the other;
  * only an utterance that exceeds the budget alone is refused.  ssw_grammar_search_batch,
  * ssw_recognize_batch and the ssw_recognition_set_* readers take such a plan as any other;
- * ssw_recognize_batch_active refuses it, naming the grammar and its HMM count. */
+ * ssw_recognize_batch_active refuses it, naming the grammar and its HMM count, unless it was made
+ * by ssw_grammar_prepare_large_active below. */
 #define SSW_GRAMMAR_LARGE_MAX_HMMS 30000
 ssw_grammar_plan_t *ssw_grammar_prepare_large(const ssw_model_t *m, const ssw_dict_t *d,
                                               const ssw_first_pass_config_t *cfg, int32_t n_fsgs,
                                               const ssw_fsg_t *const *fsgs, int32_t max_hmms);
+/* ssw_grammar_prepare_large -- the same checks, limits and messages -- for a plan that
+ * ssw_recognize_batch_active takes as well where it holds a grammar beyond one workgroup: the
+ * reference's DEFAULT configuration (compallsen = no) for grammars of up to max_hmms phone-tree
+ * HMMs.  Per frame the senones of the HMMs in pnode_active are the ones scored
+ * (fsg_search_sen_active, src/fsg_search.c:310-325, through acmod's flags2list with its bridges,
+ * src/acmod.c:947-999) before fsg_search_step searches it (src/fsg_search.c:664-739); here the
+ * HBM-workspace kernel writes those sets out, one bit per HMM and frame, and the rounds of
+ * speculation and proof run over them as over a small plan's -- each round searches the
+ * utterances not yet proven, history group by history group.  The sets take frames x
+ * ceil(HMMs / 64) x 8 bytes per utterance, twice, for the whole call.  The flag changes nothing
+ * in ssw_grammar_search_batch and ssw_recognize_batch, and a flagged plan whose grammars all fit
+ * one workgroup is searched by the one-workgroup kernels in either configuration. */
+ssw_grammar_plan_t *ssw_grammar_prepare_large_active(const ssw_model_t *m, const ssw_dict_t *d,
+                                                     const ssw_first_pass_config_t *cfg,
+                                                     int32_t n_fsgs, const ssw_fsg_t *const *fsgs,
+                                                     int32_t max_hmms);
+/* 1 for a plan made by ssw_grammar_prepare_large_active, 0 for any other, -1 for NULL */
+int32_t ssw_grammar_plan_active(const ssw_grammar_plan_t *plan);
 /* launches ssw_grammar_search_batch would search these utterances in (host only): 1 unless the
  * plan is on the HBM-workspace kernel and the history tables exceed the budget; 0 without
  * utterances; -1 where the call would be refused */
@@ -779,7 +798,9 @@ ssw_recognition_set_t *ssw_recognize_batch(ssw_model_t *m, const ssw_dict_t *d,
  * scores and segments are those of the default configuration (the texts are the compallsen = yes
  * ones on the reference's recordings, every score differs).  Limits as
  * ssw_first_pass_batch_active: 3-state HMMs, <= 64 codebooks, ds = 1 with the PTM scorer, the
- * per-frame kernels' LDS against the plan's largest grammar; refused with a message otherwise.
+ * per-frame kernels' LDS against the plan's largest grammar; refused with a message otherwise,
+ * as is a plan with a grammar beyond one workgroup that ssw_grammar_prepare_large_active did not
+ * make.
  *   d_senscr  NULL, or device int16 [n_frames][n_sen]: the rows as acmod's buffer would hold
  *             them (ssw_grammar_search_batch over them gives the same set)
  *   listed    NULL, or host uint32 [n_frames][(n_sen + 31) / 32]: the proven listed senones of

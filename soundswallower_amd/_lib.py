@@ -231,6 +231,10 @@ def lib() -> C.CDLL:
     L.ssw_grammar_prepare.argtypes = [vp, vp, vp, i32, vp]
     L.ssw_grammar_prepare_large.restype = vp
     L.ssw_grammar_prepare_large.argtypes = [vp, vp, vp, i32, vp, i32]
+    L.ssw_grammar_prepare_large_active.restype = vp
+    L.ssw_grammar_prepare_large_active.argtypes = [vp, vp, vp, i32, vp, i32]
+    L.ssw_grammar_plan_active.restype = i32
+    L.ssw_grammar_plan_active.argtypes = [vp]
     L.ssw_grammar_history_groups.restype = i32
     L.ssw_grammar_history_groups.argtypes = [vp, vp, vp, i32]
     L.ssw_grammar_plan_free.argtypes = [vp]

@@ -835,12 +835,18 @@ class Lexicon:
         _check(n, "ssw_grammar_graph")
         return nodes[:n].copy(), beams
 
-    def grammar_plan(self, fsgs, cfg=None, max_hmms=None) -> "GrammarPlan":
+    def grammar_plan(self, fsgs, cfg=None, max_hmms=None, active=False) -> "GrammarPlan":
         """ssw_grammar_prepare: decoder_set_fsg for a list of Fsg (or one); the graphs are built
         once on the host and cached on the device while the plan is searched.  max_hmms (up to
         30000): ssw_grammar_prepare_large, grammars beyond the 4096 phone-tree HMMs one workgroup
-        holds; a plan with such a grammar is searched from an HBM workspace, all of it."""
-        return GrammarPlan(self, fsgs, cfg, max_hmms)
+        holds; a plan with such a grammar is searched from an HBM workspace, all of it.
+        active=True (needs max_hmms): ssw_grammar_prepare_large_active, the same plan, which
+        recognize_batch_active takes as well (the reference's default compallsen = no)."""
+        if active and max_hmms is None:
+            raise ValueError("grammar_plan(active=True) needs max_hmms: the flag is for plans of "
+                             "grammars beyond one workgroup (a plan made without max_hmms is "
+                             "taken by recognize_batch_active as it is)")
+        return GrammarPlan(self, fsgs, cfg, max_hmms, active)
 
     def first_pass(self, d_senscr, utt_off, texts, cfg=None, max_seg=None, stream=None):
         """ssw_first_pass_batch: device senone scores of a batch + one word list per utterance
@@ -1212,20 +1218,24 @@ class Fsg:
 class GrammarPlan:
     """ssw_grammar_plan_t: the phone-tree graphs of one or more grammars."""
 
-    def __init__(self, lex: Lexicon, fsgs, cfg=None, max_hmms=None):
+    def __init__(self, lex: Lexicon, fsgs, cfg=None, max_hmms=None, active=False):
         self._L = _lib.lib()
         fsgs = [fsgs] if isinstance(fsgs, Fsg) else list(fsgs)
         self.n_fsgs = len(fsgs)
         arr = (C.c_void_p * max(1, len(fsgs)))(*[f._f for f in fsgs])
         pcfg = None if cfg is None else C.byref(cfg)
         if max_hmms is None:
+            who = "ssw_grammar_prepare"
             self._p = self._L.ssw_grammar_prepare(lex.model._m, lex._d, pcfg, len(fsgs), arr)
         else:
-            self._p = self._L.ssw_grammar_prepare_large(lex.model._m, lex._d, pcfg, len(fsgs), arr,
-                                                        int(max_hmms))
+            who = "ssw_grammar_prepare_large_active" if active else "ssw_grammar_prepare_large"
+            self._p = getattr(self._L, who)(lex.model._m, lex._d, pcfg, len(fsgs), arr,
+                                            int(max_hmms))
         if not self._p:
-            raise SswError(("ssw_grammar_prepare: " if max_hmms is None
-                            else "ssw_grammar_prepare_large: ") + _lib.last_error())
+            raise SswError(who + ": " + _lib.last_error())
+        # ssw_grammar_plan_active: recognize_batch_active takes the plan even where a grammar is
+        # beyond one workgroup
+        self.active = self._L.ssw_grammar_plan_active(self._p) == 1
 
     def hmms(self, fsg=0) -> int:
         return int(self._L.ssw_grammar_plan_hmms(self._p, fsg))

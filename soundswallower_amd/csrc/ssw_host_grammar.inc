@@ -1,4 +1,4 @@
-/* ssw_host_grammar.inc -- host: ssw_grammar_prepare(_large), ssw_grammar_search_batch,
+/* ssw_host_grammar.inc -- host: ssw_grammar_prepare(_large, _large_active), ssw_grammar_search_batch,
  * ssw_recognize_batch, ssw_recognize_batch_active and the recognition set.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 /* ---------------------------------------------------------------------------------- */
@@ -14,6 +14,9 @@ struct ssw_grammar_plan_s {
     bool big;
     int32_t big_fsg, big_nodes;
     std::string big_name;
+    /* ssw_grammar_prepare_large_active: ssw_recognize_batch_active takes the plan when it is big
+     * (the exporting instance of grammar_search_big_kernel); nothing else looks at it */
+    bool active;
 };
 
 /* LDS ints of one grammar's exchange arrays: XS XH FLG [N] | EXJ IL[3] LS[2] per slot | TW |
@@ -40,14 +43,16 @@ grammar_big_ws_ints(const ssw_fp_graphs_t *g, int u)
     return 13 * nn + 9 * ne + ntw + (size_t)g->tw_rk[u] + 2 * ns + ntw / 4 + 1;
 }
 
-/* max_hmms < 0: ssw_grammar_prepare, every grammar within one workgroup */
+/* max_hmms < 0: ssw_grammar_prepare, every grammar within one workgroup; `active`:
+ * ssw_grammar_prepare_large_active */
 static ssw_grammar_plan_t *
 grammar_prepare(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
-                int32_t n_fsgs, const ssw_fsg_t *const *fsgs, int32_t max_hmms)
+                int32_t n_fsgs, const ssw_fsg_t *const *fsgs, int32_t max_hmms, bool active)
 {
     const bool large = max_hmms >= 0;
     if (m == NULL || d == NULL || n_fsgs < 1 || fsgs == NULL || (large && max_hmms < 1)) {
-        ssw_set_error("bad arguments to %s", large ? "ssw_grammar_prepare_large" : "ssw_grammar_prepare");
+        ssw_set_error("bad arguments to %s", active ? "ssw_grammar_prepare_large_active"
+                      : large ? "ssw_grammar_prepare_large" : "ssw_grammar_prepare");
         return NULL;
     }
     if (large && max_hmms > SSW_GRAMMAR_LARGE_MAX_HMMS) {
@@ -68,6 +73,7 @@ grammar_prepare(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_
     p->big = false;
     p->big_fsg = -1;
     p->big_nodes = 0;
+    p->active = active;
     for (int u = 0; u < n_fsgs; ++u) {
         const int nn = g->node_off[u + 1] - g->node_off[u];
         const size_t li = grammar_lds_ints(g, u);
@@ -123,7 +129,7 @@ extern "C" ssw_grammar_plan_t *
 ssw_grammar_prepare(const ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
                     int32_t n_fsgs, const ssw_fsg_t *const *fsgs)
 {
-    return grammar_prepare(m, d, cfg, n_fsgs, fsgs, -1);
+    return grammar_prepare(m, d, cfg, n_fsgs, fsgs, -1, false);
 }
 
 extern "C" ssw_grammar_plan_t *
@@ -133,7 +139,23 @@ ssw_grammar_prepare_large(const ssw_model_t *m, const ssw_dict_t *d,
 {
     if (max_hmms < 0)
         max_hmms = 0; /* (refused as a bad argument) */
-    return grammar_prepare(m, d, cfg, n_fsgs, fsgs, max_hmms);
+    return grammar_prepare(m, d, cfg, n_fsgs, fsgs, max_hmms, false);
+}
+
+extern "C" ssw_grammar_plan_t *
+ssw_grammar_prepare_large_active(const ssw_model_t *m, const ssw_dict_t *d,
+                                 const ssw_first_pass_config_t *cfg, int32_t n_fsgs,
+                                 const ssw_fsg_t *const *fsgs, int32_t max_hmms)
+{
+    if (max_hmms < 0)
+        max_hmms = 0; /* (refused as a bad argument) */
+    return grammar_prepare(m, d, cfg, n_fsgs, fsgs, max_hmms, true);
+}
+
+extern "C" int32_t
+ssw_grammar_plan_active(const ssw_grammar_plan_t *p)
+{
+    return p == NULL ? -1 : p->active ? 1 : 0;
 }
 
 extern "C" void
@@ -479,8 +501,9 @@ grammar_run_t::begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_pl
     return 0;
 }
 
-/* `mask` != NULL: the EXPORT instances, the sets of active HMMs into mask (cleared first);
- * `only`: NULL or empty for every utterance, else the ones to search */
+/* `mask` != NULL: the EXPORT instances, the sets of active HMMs into mask (cleared first where
+ * the kernel does not write every word of a searched utterance's rows: the one-workgroup
+ * kernels); `only`: NULL or empty for every utterance, else the ones to search */
 hipError_t
 grammar_run_t::launch(const int16_t *d_senscr, const std::vector<int> *only, unsigned long long *mask,
                       const long long *d_act_off, const int *d_node_cnt)
@@ -494,15 +517,39 @@ grammar_run_t::launch(const int16_t *d_senscr, const std::vector<int> *only, uns
     P.act_mask = mask;
     P.act_off = d_act_off;
     if (plan->big) {
-        /* (ssw_recognize_batch_active refuses such a plan: no rounds, no exported sets) */
+        /* the history groups one after the other in the same table and workspace; of a round's
+         * utterances, the members of each group (hist_off and ws_off are offsets within an
+         * utterance's own group: they hold for any subset of it), a group without one skipped.
+         * The exporting instance writes every word of a searched utterance's rows: nothing to
+         * clear, d_node_cnt not needed */
+        (void)d_node_cnt;
+        const bool sub = exp && only != NULL && !only->empty();
+        if (sub) {
+            only_host = *only; /* (kept here: every round ends in a synchronisation of the stream) */
+            if (!std::is_sorted(only_host.begin(), only_host.end())) /* (fpa_run's are ascending) */
+                std::sort(only_host.begin(), only_host.end());
+            e = hipMemcpyAsync(ws + only_off, only_host.data(), sizeof(int) * (size_t)n_run,
+                               hipMemcpyHostToDevice, st); /* once per round, every group's part */
+            P.only = (const int *)(ws + only_off);
+        }
         GrammarBigParams B;
         B.g = P;
         B.ws = big_ws;
         B.ws_off = big_ws_off;
+        void (*kern)(GrammarBigParams) =
+            exp ? grammar_search_big_kernel<1024, true> : grammar_search_big_kernel<1024>;
         for (size_t k = 0; k + 1 < group.size() && e == hipSuccess; ++k) {
-            B.u0 = group[k];
-            hipLaunchKernelGGL(grammar_search_big_kernel<1024>, dim3((unsigned)(group[k + 1] - group[k])),
-                               dim3(1024), 0, st, B);
+            int first = group[k], n = group[k + 1] - group[k];
+            if (sub) { /* only_host[first .. first + n): the ones within [group[k], group[k + 1]) */
+                const auto lo = std::lower_bound(only_host.begin(), only_host.end(), group[k]);
+                const auto hi = std::lower_bound(lo, only_host.end(), group[k + 1]);
+                first = (int)(lo - only_host.begin());
+                n = (int)(hi - lo);
+            }
+            if (n <= 0)
+                continue;
+            B.u0 = first;
+            hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(1024), 0, st, B);
             e = hipGetLastError();
         }
         return e;
@@ -707,7 +754,8 @@ ssw_recognize_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_plan_
                                     n_utts, stream);
 }
 
-/* the loop's search step (fpa_graph_t): the EXPORT instances of grammar_search_kernel */
+/* the loop's search step (fpa_graph_t): the EXPORT instances of grammar_search_kernel, or of
+ * grammar_search_big_kernel for a plan with a grammar beyond one workgroup */
 static int
 grammar_active_search(void *arg, const int16_t *rows, const std::vector<int> &only,
                       unsigned long long *mask, const long long *d_act_off, const int *d_node_cnt)
@@ -745,7 +793,7 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
         ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
         return NULL;
     }
-    if (plan->big) {
+    if (plan->big && !plan->active) {
         ssw_set_error("grammar %d (%s) has %d phone-tree HMMs and is searched from an HBM workspace: "
                       "the default configuration (compallsen = no) holds a plan's largest grammar "
                       "in one workgroup; use ssw_recognize_batch", plan->big_fsg,

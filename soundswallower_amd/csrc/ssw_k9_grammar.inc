@@ -69,11 +69,12 @@ struct GrammarParams {
                                  segments do not fit), hypothesis score */
     ssw_fsg_seg_t *seg;       /* [n_utts][max_seg] */
     int n_sen, max_seg, beam, pbeam, wbeam, sil;
-    /* grammar_search_kernel<.., EXPORT> only: */
+    /* the EXPORT instances (grammar_search_kernel, grammar_search_big_kernel) only: */
     const int *only;              /* NULL, or the utterances this launch searches (one workgroup
                                      each): the ones a round has not proven yet */
-    unsigned long long *act_mask; /* [n_frames_u][(N + 63) / 64] words at act_off[u], cleared
-                                     before the launch (fpa_clear_kernel) */
+    unsigned long long *act_mask; /* [n_frames_u][(N + 63) / 64] words at act_off[u]; cleared
+                                     before a launch of grammar_search_kernel (fpa_clear_kernel),
+                                     written whole by grammar_search_big_kernel */
     const long long *act_off;     /* [n_utts] */
 };
 
@@ -519,21 +520,33 @@ grammar_search_kernel(GrammarParams P)
  *     scores the lowest slot wins explicitly: the first in the reference's history order, the one
  *     the dense scan meets first;
  *   - the rank buffers of a twin group need every member's call in every frame: the inactive
- *     members are called from TWL, the list of twin leaves made once, not found by a walk. */
+ *     members are called from TWL, the list of twin leaves made once, not found by a walk.
+ * The default configuration (EXPORT; see the header of this file): phase A's walk is where the
+ * frame begins, and ACT[n] & 1 as it finds it is the reference's pnode_active -- a node with bit 2
+ * alone was deactivated in the frame before and is not in it; frame 0 finds what the start-up code
+ * left.  With n = tid + k TPB a wave's 64 lanes hold the 64 consecutive nodes of one word of the
+ * frame's row, so one ballot per trip is that word: no atomics.  The exporting walk makes the same
+ * number of trips in every lane (the plain one leaves inactive lanes through `continue`, and a
+ * ballot inside that divergence would see part of the wave); lanes at n >= N vote 0, so the tail
+ * word is written whole.  The trips cover every word of the row and the frames every row: a
+ * searched utterance's rows need no clearing first (grammar_search_kernel's do: its waves without
+ * a node leave before the first frame). */
 struct GrammarBigParams {
     GrammarParams g;
     int *ws;                 /* the workspaces of the launch's utterances */
     const long long *ws_off; /* [n_utts] offset (ints) of the utterance's part of ws */
     int u0;                  /* workgroup b searches utterance u0 + b: a call whose history exceeds
-                                the budget is searched group by group */
+                                the budget is searched group by group.  EXPORT with g.only: utterance
+                                g.only[u0 + b], the members of one group that a round searches */
 };
 
-template <int TPB>
+template <int TPB, bool EXPORT = false> /* threads, the sets of active HMMs written out */
 __global__ void __launch_bounds__(TPB)
 grammar_search_big_kernel(GrammarBigParams B)
 {
     const GrammarParams &P = B.g;
-    const int u = B.u0 + (int)blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
+    const int u = (EXPORT && P.only != NULL) ? P.only[B.u0 + (int)blockIdx.x] : B.u0 + (int)blockIdx.x;
     const int gi = P.fsg_of_utt != NULL ? P.fsg_of_utt[u] : 0;
     const int nb = P.node_off[gi], N = P.node_off[gi + 1] - nb;
     const int lb = P.leaf_off[gi];
@@ -645,9 +658,7 @@ grammar_search_big_kernel(GrammarBigParams B)
         const uint16_t *urow =
             reinterpret_cast<const uint16_t *>(P.senscr + (size_t)(f0 + f) * P.n_sen);
         int bs = W;
-        for (int n = tid; n < N; n += TPB) {
-            if (!(ACT[n] & 1))
-                continue;
+        auto eval = [&](const int n) {
             const uint16_t *sn = senid + (size_t)n * 4;
             const uint32_t *tp = P.tp + (size_t)sn[3] * 3;
             int s0 = S0[n], s1 = S1[n], s2 = S2[n], h0 = H0[n], h1 = H1[n], h2 = H2[n];
@@ -659,6 +670,26 @@ grammar_search_big_kernel(GrammarBigParams B)
             S0[n] = s0, S1[n] = s1, S2[n] = s2, H0[n] = h0, H1[n] = h1, H2[n] = h2;
             OS[n] = os, OH[n] = oh, BSC[n] = b;
             bs = b > bs ? b : bs;
+        };
+        if (EXPORT) {
+            /* the HMMs active as the frame starts: what fsg_search_sen_active hands acmod */
+            const int MW = (N + 63) >> 6;
+            unsigned long long *row = P.act_mask + P.act_off[u] + (long long)f * MW;
+            for (int n0 = 0; n0 < N; n0 += TPB) { /* (the same trips in every lane) */
+                const int n = n0 + tid;
+                const bool on = n < N && (ACT[n] & 1);
+                const unsigned long long bm = __ballot(on);
+                if ((tid & 63) == 0 && (n >> 6) < MW)
+                    row[n >> 6] = bm;
+                if (on)
+                    eval(n);
+            }
+        } else {
+            for (int n = tid; n < N; n += TPB) {
+                if (!(ACT[n] & 1))
+                    continue;
+                eval(n);
+            }
         }
         bs = wave_max_dpp(bs);
         if ((tid & 63) == 0)
