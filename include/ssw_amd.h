@@ -204,6 +204,14 @@ int ssw_debug_mfma_f16_tiles(ssw_model_t *m, const uint16_t *A, const uint16_t *
  * keys: host float [n_frames][128]; inert rows (SCAN_EXACT_MFMA densities) read about -3e38. */
 int ssw_debug_scan_keys(ssw_model_t *m, const float *d_feats, int32_t n_frames, int32_t cbf,
                         float *keys);
+/* Debug view of the scan's selection alone: the five best of caller-supplied keys per frame, found
+ * as the matrix-core scan finds them (the keys laid out as its tiles deliver them, then its
+ * selection network, swap of the wave's halves and merge).  Host pointers: keys float
+ * [n_frames][128] by density (their low 7 bits are overwritten with labels, as in the scan); idx
+ * int32 [n_frames][5] densities, best first; top float [n_frames][5] their keys, label bits
+ * cleared.  Needs a model loaded on a device, nothing of the model itself. */
+int ssw_debug_scan_top5(ssw_model_t *m, const float *keys, int32_t n_frames, int32_t *idx,
+                        float *top);
 /* Counters of the last PTM batch: [0] = (chain,frame) pairs the history-free pass could not
  * prove order-independent and handed to the exact sequential pass, [1] = pairs total. */
 int ssw_score_batch_stats(ssw_model_t *m, int64_t stats[2]);

@@ -124,6 +124,9 @@ def lib() -> C.CDLL:
     L.ssw_score_batch_compact.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_uint32]
     L.ssw_align_batch_compact.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
     L.ssw_debug_scan_keys.argtypes = [vp, vp, i32, i32, vp]
+    if hasattr(L, "ssw_debug_scan_top5"):   # (an older build loaded through SSW_AMD_LIB has none:
+        # api.Model.debug_scan_top5 raises)
+        L.ssw_debug_scan_top5.argtypes = [vp, vp, i32, vp, vp]
     L.ssw_debug_mfma_f16_tiles.argtypes = [vp, vp, vp, vp, vp, i32]
     L.ssw_set_kernel_timing.argtypes = [vp, C.c_int]
     L.ssw_get_kernel_timing.argtypes = [vp, vp, C.c_int]

@@ -256,6 +256,20 @@ class Model:
             self.device_free(d)
         return out
 
+    def debug_scan_top5(self, keys):
+        """The scan's selection on caller-supplied keys float32 [n_frames][128]: (densities
+        int32 [n_frames][5], best first; their keys with the 7 label bits cleared)."""
+        if not hasattr(self._L, "ssw_debug_scan_top5"):
+            raise RuntimeError("the loaded libssw_amd.so has no ssw_debug_scan_top5 "
+                               "(an older build loaded through SSW_AMD_LIB?)")
+        keys = np.ascontiguousarray(keys, np.float32)
+        assert keys.ndim == 2 and keys.shape[1] == 128
+        idx = np.zeros((len(keys), 5), np.int32)
+        top = np.zeros((len(keys), 5), np.float32)
+        _check(self._L.ssw_debug_scan_top5(self._m, _ptr(keys), len(keys), _ptr(idx), _ptr(top)),
+               "ssw_debug_scan_top5")
+        return idx, top
+
     def set_kernel_timing(self, enable=True):
         _check(self._L.ssw_set_kernel_timing(self._m, int(bool(enable))), "ssw_set_kernel_timing")
 

@@ -1160,6 +1160,40 @@ ssw_debug_scan_keys(ssw_model_t *m, const float *d_feats, int32_t n_frames, int3
     return 0;
 }
 
+/* The scan's selection on caller-supplied keys (host pointers): keys [n_frames][128] by density;
+ * idx and top [n_frames][5] = the densities of the five best keys of every frame, best first, and
+ * those keys with the 7 label bits cleared (ptm_scan_top5_debug_kernel).  Needs a device, no
+ * particular model: tests/test_gpu_scan_top5.py. */
+extern "C" int
+ssw_debug_scan_top5(ssw_model_t *m, const float *keys, int32_t n_frames, int32_t *idx, float *top)
+{
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return -1;
+    if (m->device == SSW_DEVICE_NONE || n_frames <= 0 || !keys || !idx || !top) {
+        ssw_set_error("ssw_debug_scan_top5: no device or bad arguments");
+        return -1;
+    }
+    HIP_OK(hipSetDevice(m->device));
+    const size_t nk = sizeof(float) * 128 * (size_t)n_frames, no = 4 * 5 * (size_t)n_frames;
+    unsigned char *d = NULL;
+    HIP_OK(hipMalloc((void **)&d, nk + 2 * no));
+    hipError_t e = hipMemcpy(d, keys, nk, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(ptm_scan_top5_debug_kernel, dim3((unsigned)((n_frames + 63) / 64)),
+                           dim3(64), 0, 0, reinterpret_cast<const float *>(d), n_frames,
+                           reinterpret_cast<int32_t *>(d + nk), reinterpret_cast<float *>(d + nk + no));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        e = hipMemcpy(idx, d + nk, no, hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+        e = hipMemcpy(top, d + nk + no, no, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    HIP_OK(e);
+    return 0;
+}
+
 /* D = A B + C on the matrix cores, one v_mfma_f32_32x32x16_f16 per tile (host pointers; A and B
  * are binary16 bit patterns): tests/test_gpu_mfma_bound.py measures the instruction's
  * accumulation error with it against the eps the scan's bound assumes (ssw_model.c). */

@@ -27,7 +27,8 @@
  * Work split: a wave owns one (codebook, stream) and 128 frames = 4 column blocks of 32.  In the
  * 32 x 32 output tile of one MFMA lane l holds column (frame) l % 32 and 16 of the 32 rows
  * (densities): lanes l and l + 32 share a frame.  Each lane keeps the top 5 of its 16 rows per
- * row block, for two column blocks at a time; then the halves swap one list each, so that the
+ * row block (found from sorted triples of keys: ssw_top5_select.inc), for two column blocks at
+ * a time; then the halves swap one list each, so that the
  * lower half finishes the first block's frames and the upper half the second's (merge, exact
  * re-evaluation of the four candidates, sort, proof: once per frame).
  */
@@ -191,15 +192,49 @@ ptm_mfma_keys_kernel(const uint4 *__restrict__ wfrag, const float *__restrict__ 
     }
 }
 
-/* (v_max_f32 as asm: fmaxf would add a canonicalising v_max per insert) */
-#define SSW_TOP5_INSERT(L, key)                                                              \
-    {                                                                                        \
-        L[4] = med3f(L[3], L[4], key);                                                       \
-        L[3] = med3f(L[2], L[3], key);                                                       \
-        L[2] = med3f(L[1], L[2], key);                                                       \
-        L[1] = med3f(L[0], L[1], key);                                                       \
-        asm("v_max_f32 %0, %1, %2" : "=v"(L[0]) : "v"(L[0]), "v"(key));                      \
+/* (the list operations: ssw_top5_select.inc) */
+#define SSW_TOP5_INSERT(L, key) ssw_top5_insert(L, key);
+
+/* The 16 keys of a lane's share of one tile, labelled: label = register + 16 x row block (0..63):
+ * wave-uniform, an SGPR operand; bit 6 = the lane's half, added when the halves swap lists.  (No
+ * inline asm on the accumulator: the compiler pads the MFMA -> VALU read hazard only for
+ * instructions it can see.) */
+__device__ __forceinline__ void
+mfma_label_keys(const v16f &acc, int rb, uint32_t keymask, float (&key)[16])
+{
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        uint32_t lab;
+        asm("s_add_i32 %0, %1, %2" : "=s"(lab) : "s"(16 * rb), "i"(r) : "scc");
+        key[r] = __uint_as_float((__float_as_uint(acc[r]) & keymask) | lab);
     }
+}
+
+/* The halves swap: each sends the list of the column block it does not finish (the lower half
+ * finishes A, the upper half B) and merges what it receives -- the other half's rows of ITS
+ * block -- into its own.  LA is reused for the received list. */
+__device__ __forceinline__ void
+mfma_swap_merge(float (&LA)[5], const float (&LB)[5], bool hi, float (&L)[5])
+{
+    const uint32_t half_bit = hi ? 64u : 0u;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const float mine = hi ? LB[k] : LA[k], send = hi ? LA[k] : LB[k];
+        const float got = __shfl_xor(__uint_as_float(__float_as_uint(send) | half_bit), 32, WAVE);
+        L[k] = __uint_as_float(__float_as_uint(mine) | half_bit);
+        LA[k] = got;
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+        SSW_TOP5_INSERT(L, LA[k])
+}
+
+/* density index of a label: 32 rb + 8 (r / 4) + 4 half + r % 4 */
+__device__ __forceinline__ uint32_t
+mfma_label_density(uint32_t lab)
+{
+    return ((lab >> 4) & 3u) * 32u + ((lab >> 2) & 3u) * 8u + (lab >> 6) * 4u + (lab & 3u);
+}
 
 /* NSTEP = 64-frame steps per wave: 2 (a wave owns 128 frames) or 1 (64 frames, twice the
  * workgroups: the chip's 1,024 workgroup slots are then refilled as groups finish instead of
@@ -347,7 +382,6 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
     unsigned long long audited[2] = { 0ull, 0ull }; /* AUDIT: proven pairs redone all the same */
     const bool audit_wave = AUDIT && P.audit_k > 0
         && (pair * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) % P.audit_k == 0;
-    const uint32_t half_bit = hi ? 64u : 0u;
 
 #pragma unroll 1
     for (int step = 0; step < NSTEP; ++step) {
@@ -356,10 +390,11 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
             mfma_build_x<VECLEN>(x_row(t0 + col), hi, xconst, bxa);
             mfma_build_x<VECLEN>(x_row(t0 + 32 + col), hi, xconst, bxb);
         }
-        float LA[5], LB[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-            LA[k] = LB[k] = NEG_INF;
+        /* selection state per column block: the list of 5, the two best middles and the best
+         * smallest of the key triples (ssw_top5_select.inc) */
+        float LA[5], LB[5], MA[2], MB[2], ZA, ZB;
+        ssw_top5_reset(LA, MA, ZA, NEG_INF);
+        ssw_top5_reset(LB, MB, ZB, NEG_INF);
         /* (a rolled loop: unrolled, the compiler runs the MFMAs of all row blocks ahead into
          * dozens of accumulator registers, which costs the 4th wave per SIMD; the overlap of
          * the matrix pipe with the inserts comes from the other waves) */
@@ -373,45 +408,22 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
                     a[kb][p] = __builtin_bit_cast(f16x8, s_w[((rb * 2 + kb) * 2 + p) * 64 + lane]);
             {
                 const v16f acc = mfma_key_tile_frag(a, bxa);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    /* label = register + 16 x row block (0..63): wave-uniform, an SGPR operand;
-                     * bit 6 = the lane's half, added when the halves swap lists.  (No inline
-                     * asm on the accumulator: the compiler pads the MFMA -> VALU read hazard
-                     * only for instructions it can see.) */
-                    uint32_t lab;
-                    asm("s_add_i32 %0, %1, %2" : "=s"(lab) : "s"(16 * rb), "i"(r) : "scc");
-                    const float key = __uint_as_float((__float_as_uint(acc[r]) & keymask) | lab);
-                    SSW_TOP5_INSERT(LA, key)
-                }
+                float key[16];
+                mfma_label_keys(acc, rb, keymask, key);
+                ssw_top5_tile(LA, MA, ZA, key);
             }
             {
                 const v16f acc = mfma_key_tile_frag(a, bxb);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    uint32_t lab;
-                    asm("s_add_i32 %0, %1, %2" : "=s"(lab) : "s"(16 * rb), "i"(r) : "scc");
-                    const float key = __uint_as_float((__float_as_uint(acc[r]) & keymask) | lab);
-                    SSW_TOP5_INSERT(LB, key)
-                }
+                float key[16];
+                mfma_label_keys(acc, rb, keymask, key);
+                ssw_top5_tile(LB, MB, ZB, key);
             }
         }
-        /* the halves swap: each sends the list of the block it does not finish and merges what
-         * it receives (the other half's rows of ITS block) into its own */
+        /* back to plain lists of 5, then the halves swap */
+        ssw_top5_fold(LA, MA, ZA);
+        ssw_top5_fold(LB, MB, ZB);
         float L[5];
-        {
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const float mine = hi ? LB[k] : LA[k], send = hi ? LA[k] : LB[k];
-                const float got = __shfl_xor(__uint_as_float(__float_as_uint(send) | half_bit), 32,
-                                             WAVE);
-                L[k] = __uint_as_float(__float_as_uint(mine) | half_bit);
-                LA[k] = got; /* reused as the received list */
-            }
-#pragma unroll
-            for (int k = 0; k < 5; ++k)
-                SSW_TOP5_INSERT(L, LA[k])
-        }
+        mfma_swap_merge(LA, LB, hi, L);
         /* from here on lane l works on frame t0 + l alone */
         const int t = t0 + lane;
         const int tl = t < P.n_frames ? t : P.n_frames - 1;
@@ -489,8 +501,7 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const uint32_t lab = __float_as_uint(L[k]) & 127u;
-            c[k] = (int)(((lab >> 4) & 3u) * 32u + ((lab >> 2) & 3u) * 8u + (lab >> 6) * 4u
-                         + (lab & 3u));
+            c[k] = (int)mfma_label_density(lab);
             dv[k] = exact_row((uint32_t)c[k]);
             sk[k] = MS ? ms_fden(dv[k]) : dens2int(dv[k]);
         }
@@ -691,6 +702,58 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
     SSW_TL(3)
 }
 #undef SSW_TOP5_INSERT
+
+/* Selection view (ssw_debug_scan_top5): the scan's selection alone, on keys the caller supplies
+ * -- keys [n_frames][128] by density.  One wave per 64 frames; each lane takes the keys the MFMA
+ * tiles would hand it (lane l, register r of row block rb: density 32 rb + 8 (r >> 2) + 4 half +
+ * (r & 3) of frame l % 32 of the column block, as ptm_mfma_keys_kernel writes them), labels
+ * them and runs what the scan runs: the tiles' selection network, the fold, the swap of the
+ * halves and the merge.  Out, per frame: the densities of the five best keys and those keys
+ * with the label bits cleared. */
+__global__ void __launch_bounds__(64)
+ptm_scan_top5_debug_kernel(const float *__restrict__ keys, int n_frames, int32_t *__restrict__ out_idx,
+                           float *__restrict__ out_key)
+{
+    const int lane = threadIdx.x & 63, col = lane & 31;
+    const bool hi = lane >= 32;
+    const int t0 = (int)blockIdx.x * 64;
+    uint32_t keymask;
+    asm volatile("v_mov_b32 %0, 0xffffff80" : "=v"(keymask));
+    const float NEG_INF = -__builtin_huge_valf();
+    float LA[5], LB[5], MA[2], MB[2], ZA, ZB;
+    ssw_top5_reset(LA, MA, ZA, NEG_INF);
+    ssw_top5_reset(LB, MB, ZB, NEG_INF);
+    auto tile_of = [&](int blk, int rb) {
+        const int t = t0 + 32 * blk + col;
+        const float *kp = keys + (size_t)(t < n_frames ? t : n_frames - 1) * 128 + 32 * rb
+            + (hi ? 4 : 0);
+        v16f acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            acc[r] = kp[8 * (r >> 2) + (r & 3)];
+        return acc;
+    };
+#pragma unroll 1
+    for (int rb = 0; rb < 4; ++rb) {
+        float key[16];
+        mfma_label_keys(tile_of(0, rb), rb, keymask, key);
+        ssw_top5_tile(LA, MA, ZA, key);
+        mfma_label_keys(tile_of(1, rb), rb, keymask, key);
+        ssw_top5_tile(LB, MB, ZB, key);
+    }
+    ssw_top5_fold(LA, MA, ZA);
+    ssw_top5_fold(LB, MB, ZB);
+    float L[5];
+    mfma_swap_merge(LA, LB, hi, L);
+    const int t = t0 + lane;
+    if (t < n_frames)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const uint32_t bits = __float_as_uint(L[k]);
+            out_idx[(size_t)t * 5 + k] = (int32_t)mfma_label_density(bits & 127u);
+            out_key[(size_t)t * 5 + k] = __uint_as_float(bits & ~127u);
+        }
+}
 
 /* Parity aid (ssw_debug_mfma_eps): one v_mfma_f32_32x32x16_f16 per 32 x 32 tile, D = A B + C with
  * A [32][16], B [16][32] binary16 and C [32][32] fp32 as the host laid them out -- so that the

@@ -86,6 +86,7 @@ namespace {
 #include "ssw_dev_common.inc"
 #include "ssw_k1a_chain.inc"
 #include "ssw_k1a_frames.inc"
+#include "ssw_top5_select.inc"
 #include "ssw_k1a_mfma.inc"
 #include "ssw_k1b_senone.inc"
 #include "ssw_k4_feat.inc"

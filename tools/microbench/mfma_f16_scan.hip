@@ -2,7 +2,9 @@
 // significand bits, three part products (1,1) (1,2) (2,1) = 6 MFMAs per 32 x 32 tile) instead of
 // three bf16 parts and six part products (12 MFMAs).
 //  (a) throughput of one tile: N MFMAs + 16 top-5 inserts per lane, N = 6 (f16) and 12 (bf16),
-//      4 and 5 waves per SIMD;
+//      4 and 5 waves per SIMD; and (MODE 3) the same tile with the selection network of
+//      csrc/ssw_top5_select.inc in place of the 16 inserts: five sorted triples, their ranks into
+//      lists of 5, 2 and 1, the 16th key into the list of 5 (58 list instructions for 80);
 //  (b) accuracy of the f16 MFMA's fp32 accumulation against an exact (double) sum on random,
 //      cancelling and wide-range data (the eps of csrc/ssw_model.c);
 //  (c) fp16 SUBNORMAL inputs: are they honoured or flushed by the matrix pipe, and by
@@ -31,6 +33,13 @@ __global__ void __launch_bounds__(256) k(float *out, float s)
         bh[i] = (_Float16)(1.0f + s * i);
     }
     float L0 = threadIdx.x, L1 = 2, L2 = 3, L3 = 4, L4 = 5, key = s;
+    float M0 = 6, M1 = 7, Z = 8;
+#define INSERT5(k)                                                                             \
+    asm volatile("v_med3_f32 %0, %1, %0, %2" : "+v"(L4) : "v"(L3), "v"(k));                    \
+    asm volatile("v_med3_f32 %0, %1, %0, %2" : "+v"(L3) : "v"(L2), "v"(k));                    \
+    asm volatile("v_med3_f32 %0, %1, %0, %2" : "+v"(L2) : "v"(L1), "v"(k));                    \
+    asm volatile("v_med3_f32 %0, %1, %0, %2" : "+v"(L1) : "v"(L0), "v"(k));                    \
+    asm volatile("v_max_f32 %0, %0, %1" : "+v"(L0) : "v"(k));
     for (int r = 0; r < REP; ++r) {
         if (MODE != 1) {
 #pragma unroll
@@ -38,7 +47,27 @@ __global__ void __launch_bounds__(256) k(float *out, float s)
                 acc0 = F16 ? __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0, 0, 0, 0)
                            : __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc0, 0, 0, 0);
         }
-        if (MODE != 0) {
+        if (MODE == 3) {
+            float lk[16], r3[5];
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                asm volatile("v_and_or_b32 %0, %1, %2, %3" : "=v"(lk[i]) : "v"(acc0[i]), "v"(L1), "v"(L2));
+#pragma unroll
+            for (int g = 0; g < 5; ++g) {
+                float r1, r2;
+                asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(r1) : "v"(lk[3 * g]), "v"(lk[3 * g + 1]), "v"(lk[3 * g + 2]));
+                asm volatile("v_med3_f32 %0, %1, %2, %3" : "=v"(r2) : "v"(lk[3 * g]), "v"(lk[3 * g + 1]), "v"(lk[3 * g + 2]));
+                asm volatile("v_min3_f32 %0, %1, %2, %3" : "=v"(r3[g]) : "v"(lk[3 * g]), "v"(lk[3 * g + 1]), "v"(lk[3 * g + 2]));
+                INSERT5(r1)
+                asm volatile("v_med3_f32 %0, %1, %0, %2" : "+v"(M1) : "v"(M0), "v"(r2));
+                asm volatile("v_max_f32 %0, %0, %1" : "+v"(M0) : "v"(r2));
+                if (g & 1)
+                    asm volatile("v_max3_f32 %0, %0, %1, %2" : "+v"(Z) : "v"(r3[g - 1]), "v"(r3[g]));
+            }
+            asm volatile("v_max_f32 %0, %0, %1" : "+v"(Z) : "v"(r3[4]));
+            INSERT5(lk[15])
+            acc0 = (v16f){};
+        } else if (MODE != 0) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 float kk = MODE == 2 ? acc0[i] : key;
@@ -53,7 +82,7 @@ __global__ void __launch_bounds__(256) k(float *out, float s)
                 acc0 = (v16f){};
         }
     }
-    float t = L0 + L1 + L2 + L3 + L4;
+    float t = L0 + L1 + L2 + L3 + L4 + M0 + M1 + Z;
     for (int i = 0; i < 16; ++i) t += acc0[i];
     out[blockIdx.x * 256 + threadIdx.x] = t;
 }
@@ -113,6 +142,7 @@ int main()
         run<6, true, 1>("valu only", out, w);
         run<12, false, 2>("12 bf16 mfma + inserts (dependent)", out, w);
         run<6, true, 2>("6 f16 mfma + inserts (dependent)", out, w);
+        run<6, true, 3>("6 f16 mfma + selection network", out, w);
     }
     const int trials = 2000;
     std::vector<_Float16> hA(32 * 16), hB(16 * 32);
