@@ -667,7 +667,8 @@ int32_t ssw_alignment_json(const ssw_model_t *m, const char *hyp, int32_t hyp_lo
 /*   fsg_lextree_init with null transitions                  src/fsg_lextree.c:85-276, 356-660 */
 /*   fsg_search_start / _null_prop / _word_trans / _step      src/fsg_search.c:543-802          */
 /*   fsg_search_find_exit / _hyp / _seg_iter, fsg_seg_bp2itor src/fsg_search.c:854-1143         */
-/* Not covered: JSGF, the default compallsen = no normalisation, lattices / best path /       */
+/* Not covered: JSGF imports and the three half-built grammars the reference searches after   */
+/* logging an error (see ssw_jsgf_build_fsg), lattices / best path /                           */
 /* N-best, tag transitions, grammars of more than 30000 phone-tree HMMs (up to there with     */
 /* ssw_grammar_prepare_large, and in the default configuration, ssw_recognize_batch_active,    */
 /* with ssw_grammar_prepare_large_active).                                                     */
@@ -700,6 +701,51 @@ int32_t ssw_fsg_n_states(const ssw_fsg_t *f);
  * order (:248-302).  cfg NULL = defaults.  snprintf-style return; -1 on error. */
 int32_t ssw_fsg_write(const ssw_fsg_t *f, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
                       int32_t searched, char *out, int32_t out_len);
+/* ------------------------------------------------------------------------------------ */
+/* JSGF grammars: decoder_set_jsgf_string / decoder_set_jsgf_file (src/decoder.c:609-683).    */
+/* Replaces, on the host (none of these calls touches the device):                            */
+/*   the scanner and parser                       src/jsgf_scanner.l, src/jsgf_parser.y        */
+/*   jsgf_define_rule, _kleene_new, _optional_new, the rule table  src/jsgf.c:173-205, 611-642 */
+/*   jsgf_rule_iter, jsgf_get_rule, jsgf_get_public_rule           src/jsgf.c:423-481          */
+/*   expand_rule / expand_rhs / jsgf_build_fsg                     src/jsgf.c:298-421, 483-539 */
+/* Not covered: import (refused as unsupported); and, a deliberate difference, the grammars    */
+/* whose expansion fails -- an undefined rule in a right-hand side, recursion that is not      */
+/* right-recursion, <VOID>.  The reference logs the error, ignores it and searches what was    */
+/* built up to there; here the build is refused with the reference's error text.              */
+/* ------------------------------------------------------------------------------------ */
+typedef struct ssw_jsgf_s ssw_jsgf_t;
+/* jsgf_parse_string / jsgf_parse_file (src/jsgf.c:820-887).  NULL with the error set: a syntax
+ * error ("... at line %d current token '%s'"), an import, a file that cannot be read ("Failed to
+ * open %s for parsing").  Tags are parsed and dropped; a quoted token keeps its quotes. */
+ssw_jsgf_t *ssw_jsgf_parse_string(const char *text);
+ssw_jsgf_t *ssw_jsgf_parse_file(const char *path);
+void ssw_jsgf_free(ssw_jsgf_t *j);
+/* jsgf_grammar_name */
+const char *ssw_jsgf_name(const ssw_jsgf_t *j);
+/* jsgf_rule_iter / jsgf_rule_name / jsgf_rule_public: the rules, internal ones (<grammar.gNNNNN>)
+ * included, index i in the order the reference's hash table walks them (src/hash_table.c) */
+int32_t ssw_jsgf_n_rules(const ssw_jsgf_t *j);
+const char *ssw_jsgf_rule_name(const ssw_jsgf_t *j, int32_t i);
+int32_t ssw_jsgf_rule_public(const ssw_jsgf_t *j, int32_t i);
+/* jsgf_get_public_rule (src/jsgf.c:444-469): the first public rule in that order, or -1 */
+int32_t ssw_jsgf_public_rule(const ssw_jsgf_t *j);
+/* jsgf_get_rule (:429-442): name is "grammar.rule", looked up as <grammar.rule>; index or -1 */
+int32_t ssw_jsgf_find_rule(const ssw_jsgf_t *j, const char *name);
+/* jsgf_build_fsg (:483-539): rule `rule` expanded, state number for state number; the grammar is
+ * named after the rule, angle brackets included.  As in the reference the expansion divides the
+ * leading weights of a rule's alternatives by their sum IN PLACE, so j changes: a second build
+ * starts from the weights the first left.  d may be NULL, as for ssw_fsg_create.  Refused: the
+ * three cases above ("Undefined rule in RHS: %s", "Only right-recursion is permitted (in %s.%s)"),
+ * a weight that is not in (0, 1] after normalisation, a word the dictionary lacks. */
+ssw_fsg_t *ssw_jsgf_build_fsg(const ssw_model_t *m, const ssw_dict_t *d, ssw_jsgf_t *j, int32_t rule);
+/* decoder_set_jsgf_string / decoder_set_jsgf_file up to decoder_set_fsg (src/decoder.c:609-683):
+ * toprule ("grammar.rule", the reference's -toprule) or, when NULL, the first public rule.
+ * "Start rule %s not found", "No public rules found in input string" / "... in PATH". */
+ssw_fsg_t *ssw_fsg_from_jsgf_string(const ssw_model_t *m, const ssw_dict_t *d, const char *text,
+                                    const char *toprule);
+ssw_fsg_t *ssw_fsg_from_jsgf_file(const ssw_model_t *m, const ssw_dict_t *d, const char *path,
+                                  const char *toprule);
+
 /* ssw_first_pass_graph for a grammar: the phone-tree HMMs fsg_lextree_init makes of it
  * (src/fsg_lextree.c:85-276, 356-660), host only. */
 int32_t ssw_grammar_graph(const ssw_model_t *m, const ssw_dict_t *d,

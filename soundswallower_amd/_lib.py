@@ -226,6 +226,32 @@ def lib() -> C.CDLL:
     L.ssw_fsg_name.argtypes = [vp]
     L.ssw_fsg_n_states.restype = i32
     L.ssw_fsg_n_states.argtypes = [vp]
+    if hasattr(L, "ssw_jsgf_parse_string"):   # (the Makefile's timeline / variant builds, loaded
+        # through SSW_AMD_LIB, carry no ssw_jsgf.o: a JSGF call on them raises AttributeError)
+        L.ssw_jsgf_parse_string.restype = vp
+        L.ssw_jsgf_parse_string.argtypes = [C.c_char_p]
+        L.ssw_jsgf_parse_file.restype = vp
+        L.ssw_jsgf_parse_file.argtypes = [C.c_char_p]
+        L.ssw_jsgf_free.argtypes = [vp]
+        L.ssw_jsgf_free.restype = None
+        L.ssw_jsgf_name.restype = C.c_char_p
+        L.ssw_jsgf_name.argtypes = [vp]
+        L.ssw_jsgf_n_rules.restype = i32
+        L.ssw_jsgf_n_rules.argtypes = [vp]
+        L.ssw_jsgf_rule_name.restype = C.c_char_p
+        L.ssw_jsgf_rule_name.argtypes = [vp, i32]
+        L.ssw_jsgf_rule_public.restype = i32
+        L.ssw_jsgf_rule_public.argtypes = [vp, i32]
+        L.ssw_jsgf_public_rule.restype = i32
+        L.ssw_jsgf_public_rule.argtypes = [vp]
+        L.ssw_jsgf_find_rule.restype = i32
+        L.ssw_jsgf_find_rule.argtypes = [vp, C.c_char_p]
+        L.ssw_jsgf_build_fsg.restype = vp
+        L.ssw_jsgf_build_fsg.argtypes = [vp, vp, vp, i32]
+        L.ssw_fsg_from_jsgf_string.restype = vp
+        L.ssw_fsg_from_jsgf_string.argtypes = [vp, vp, C.c_char_p, C.c_char_p]
+        L.ssw_fsg_from_jsgf_file.restype = vp
+        L.ssw_fsg_from_jsgf_file.argtypes = [vp, vp, C.c_char_p, C.c_char_p]
     L.ssw_fsg_write.restype = i32
     L.ssw_fsg_write.argtypes = [vp, vp, vp, i32, C.c_char_p, i32]
     L.ssw_grammar_graph.restype = i32

@@ -1202,6 +1202,25 @@ class Fsg:
             raise SswError("ssw_fsg_read: " + _lib.last_error())
         return cls(h)
 
+    @classmethod
+    def from_jsgf(cls, model: Model, lex, text=None, path=None, toprule=None):
+        """decoder_set_jsgf_string (text) / decoder_set_jsgf_file (path) up to decoder_set_fsg:
+        toprule "grammar.rule", or the first public rule in the reference's order."""
+        if (text is None) == (path is None):
+            raise ValueError("Fsg.from_jsgf takes either text or path")
+        L = _lib.lib()
+        top = None if toprule is None else toprule.encode()
+        d = None if lex is None else lex._d
+        if text is not None:
+            who = "ssw_fsg_from_jsgf_string"
+            h = L.ssw_fsg_from_jsgf_string(model._m, d, text.encode() if isinstance(text, str) else text, top)
+        else:
+            who = "ssw_fsg_from_jsgf_file"
+            h = L.ssw_fsg_from_jsgf_file(model._m, d, os.fsencode(path), top)
+        if not h:
+            raise SswError(who + ": " + _lib.last_error())
+        return cls(h)
+
     @property
     def name(self):
         return self._L.ssw_fsg_name(self._f).decode()
@@ -1225,6 +1244,74 @@ class Fsg:
         if getattr(self, "_f", None):
             self._L.ssw_fsg_free(self._f)
             self._f = None
+
+    __del__ = free
+
+
+class Jsgf:
+    """ssw_jsgf_t: a parsed JSGF grammar (jsgf_t).  Rule indices are positions in rules(), the
+    order the reference's rule table is walked in."""
+
+    def __init__(self, handle):
+        self._L = _lib.lib()
+        self._j = handle
+
+    @classmethod
+    def parse_string(cls, text):
+        h = _lib.lib().ssw_jsgf_parse_string(text.encode() if isinstance(text, str) else text)
+        if not h:
+            raise SswError("ssw_jsgf_parse_string: " + _lib.last_error())
+        return cls(h)
+
+    @classmethod
+    def parse_file(cls, path):
+        h = _lib.lib().ssw_jsgf_parse_file(os.fsencode(path))
+        if not h:
+            raise SswError("ssw_jsgf_parse_file: " + _lib.last_error())
+        return cls(h)
+
+    @property
+    def name(self):
+        return self._L.ssw_jsgf_name(self._j).decode()
+
+    def rules(self):
+        """[(name, is_public)] in jsgf_rule_iter order"""
+        return [(self._L.ssw_jsgf_rule_name(self._j, i).decode(),
+                 bool(self._L.ssw_jsgf_rule_public(self._j, i)))
+                for i in range(self._L.ssw_jsgf_n_rules(self._j))]
+
+    def public_rule(self):
+        """jsgf_get_public_rule: index of the first public rule, or None"""
+        i = self._L.ssw_jsgf_public_rule(self._j)
+        return None if i < 0 else int(i)
+
+    def find_rule(self, name):
+        """jsgf_get_rule("grammar.rule"): index, or None"""
+        i = self._L.ssw_jsgf_find_rule(self._j, name.encode())
+        return None if i < 0 else int(i)
+
+    def fsg(self, model: Model, lex, rule=None) -> Fsg:
+        """jsgf_build_fsg of rule (an index, a "grammar.rule" name, or None: the first public
+        rule).  As in the reference, every build renormalises the grammar's weights in place."""
+        if rule is None:
+            i = self.public_rule()
+            if i is None:
+                raise SswError("ssw_jsgf_public_rule: No public rules found in input string")
+        elif isinstance(rule, str):
+            i = self.find_rule(rule)
+            if i is None:
+                raise SswError("ssw_jsgf_find_rule: Start rule %s not found" % rule)
+        else:
+            i = int(rule)
+        h = self._L.ssw_jsgf_build_fsg(model._m, None if lex is None else lex._d, self._j, i)
+        if not h:
+            raise SswError("ssw_jsgf_build_fsg: " + _lib.last_error())
+        return Fsg(h)
+
+    def free(self):
+        if getattr(self, "_j", None):
+            self._L.ssw_jsgf_free(self._j)
+            self._j = None
 
     __del__ = free
 

@@ -36,6 +36,7 @@ struct ssw_fsg_s {
     int32_t *from, *to, *wid; /* wid: vocabulary index, -1 for a null transition */
     float *prob;
     double logbase;
+    int32_t jsgf; /* built by jsgf_build_fsg (ssw_jsgf.c): see ssw_fsg_create_jsgf */
 };
 
 /* ---- the reference's tables, restated ------------------------------------------------ */
@@ -290,9 +291,12 @@ ssw_fsg_compile(const ssw_fsg_t *f, const ssw_dict_t *d, const ssw_first_pass_co
     for (i = 0; i < f->n_word; ++i)
         if (vocab_add(c, &cap_vocab, f->vocab[i]) < 0)
             goto oom;
-    /* the transitions in the order given; the nulls met are listed newest first */
+    /* the transitions in the order given; the nulls met are listed newest first.
+     * jsgf_build_fsg_internal (src/jsgf.c:508-525) hands logmath_log(weight) over as it is,
+     * without the language weight the .fsg reader multiplies in (src/fsg_model.c:630) */
     for (i = 0; i < f->n_trans; ++i) {
-        const int logp = (int32_t)((float)ilog0(f->logbase, (double)f->prob[i]) * cfg.lw);
+        const int logp = f->jsgf ? ilog0(f->logbase, (double)f->prob[i])
+                                 : (int32_t)((float)ilog0(f->logbase, (double)f->prob[i]) * cfg.lw);
         if (f->wid[i] >= 0) {
             if (trans_add(&md, f->from[i], f->to[i], logp, f->wid[i]) < 0)
                 goto oom;
@@ -300,7 +304,7 @@ ssw_fsg_compile(const ssw_fsg_t *f, const ssw_dict_t *d, const ssw_first_pass_co
             const int r = null_add(&md, f->from[i], f->to[i], logp);
             if (r == -2)
                 goto oom;
-            if (r == 1) {
+            if (r == 1 && !f->jsgf) {
                 if (nl_n == nl_cap) {
                     const int nc = nl_cap ? 2 * nl_cap : 32;
                     int *a = (int *)realloc(nl_link, sizeof(int) * (size_t)nc);
@@ -317,6 +321,25 @@ ssw_fsg_compile(const ssw_fsg_t *f, const ssw_dict_t *d, const ssw_first_pass_co
             }
         }
     }
+    /* jsgf_build_fsg calls the closure without a list, which then makes its own: every state's
+     * null transitions in the order of its table, each put in FRONT (src/fsg_model.c:164-176) */
+    if (f->jsgf)
+        for (s = 0; s < f->n_state; ++s)
+            for (k = 0; k < md.nulls[s].n; ++k) {
+                if (nl_n == nl_cap) {
+                    const int nc = nl_cap ? 2 * nl_cap : 32;
+                    int *a = (int *)realloc(nl_link, sizeof(int) * (size_t)nc);
+                    int *b = a ? (int *)realloc(nl_next, sizeof(int) * (size_t)nc) : NULL;
+                    if (a) nl_link = a;
+                    if (b) nl_next = b;
+                    if (!b)
+                        goto oom;
+                    nl_cap = nc;
+                }
+                nl_link[nl_n] = md.nulls[s].d[k].lnk[0];
+                nl_next[nl_n] = nl_head;
+                nl_head = nl_n++;
+            }
     /* fsg_model_null_trans_closure, src/fsg_model.c:178-215 */
     for (;;) {
         int updated = 0, gn;
@@ -597,6 +620,19 @@ bad:
     return NULL;
 }
 
+/* ssw_fsg_create for the transitions jsgf_build_fsg_internal adds (src/jsgf.c:483-532): their
+ * log probabilities take no language weight, and the closure lists the null transitions itself */
+ssw_fsg_t *
+ssw_fsg_create_jsgf(const ssw_model_t *m, const ssw_dict_t *d, const char *name, int32_t n_states,
+                    int32_t start, int32_t final, int32_t n_trans, const int32_t *from,
+                    const int32_t *to, const float *prob, const char *const *word)
+{
+    ssw_fsg_t *f = ssw_fsg_create(m, d, name, n_states, start, final, n_trans, from, to, prob, word);
+    if (f != NULL)
+        f->jsgf = 1;
+    return f;
+}
+
 /* s3file_nextword: the next run of non-blank characters of the line; NULL at its end */
 static const char *
 next_word(const char **ptr, int *len)
@@ -830,6 +866,8 @@ ssw_fsg_write(const ssw_fsg_t *f, const ssw_dict_t *d, const ssw_first_pass_conf
         return -1;
 #define PUT()                                                                      \
     do {                                                                           \
+        if (n >= (int)sizeof(line)) /* (a JSGF token may be longer than the line) */ \
+            n = (int)sizeof(line) - 1;                                             \
         if (out != NULL && len < cap) {                                            \
             const size_t room = cap - len - 1;                                     \
             memcpy(out + len, line, (size_t)n < room ? (size_t)n : room);          \

@@ -227,6 +227,11 @@ typedef struct ssw_fsg_compiled_s {
 ssw_fsg_compiled_t *ssw_fsg_compile(const ssw_fsg_t *f, const struct ssw_dict_s *d,
                                     const ssw_first_pass_config_t *cfg, int searched);
 void ssw_fsg_compiled_free(ssw_fsg_compiled_t *c);
+/* ssw_fsg_create as jsgf_build_fsg adds transitions (ssw_fsg_model.inc; used by ssw_jsgf.c) */
+ssw_fsg_t *ssw_fsg_create_jsgf(const ssw_model_t *m, const struct ssw_dict_s *d, const char *name,
+                               int32_t n_states, int32_t start, int32_t final, int32_t n_trans,
+                               const int32_t *from, const int32_t *to, const float *prob,
+                               const char *const *word);
 ssw_fp_graphs_t *ssw_grammar_graphs_build(const ssw_model_t *m, const struct ssw_dict_s *d,
                                           const ssw_first_pass_config_t *cfg, int32_t n_fsgs,
                                           const ssw_fsg_t *const *fsgs);
