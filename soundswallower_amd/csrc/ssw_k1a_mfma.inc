@@ -210,23 +210,25 @@ mfma_label_keys(const v16f &acc, int rb, uint32_t keymask, float (&key)[16])
     }
 }
 
-/* The halves swap: each sends the list of the column block it does not finish (the lower half
- * finishes A, the upper half B) and merges what it receives -- the other half's rows of ITS
- * block -- into its own.  LA is reused for the received list. */
+/* The halves swap: each hands over the list of the column block it does not finish (the lower
+ * half finishes A, the upper half B) and merges what it receives -- the other half's rows of ITS
+ * block -- into its own.  In registers: v_permlane32_swap_b32 exchanges the upper half of its
+ * first operand with the lower half of its second, which leaves {A.lo | B.lo} in the first and
+ * {A.hi | B.hi} in the second: for every lane the two lists of its own frame, the first from
+ * the lower half's rows and the second from the upper half's, so the half bit (64) goes into
+ * the second alone and no lane has to choose.  The second is sorted: it is merged by position
+ * (ssw_top5_merge).  LA and LB are used up. */
 __device__ __forceinline__ void
-mfma_swap_merge(float (&LA)[5], const float (&LB)[5], bool hi, float (&L)[5])
+mfma_swap_merge(float (&LA)[5], float (&LB)[5], float (&L)[5])
 {
-    const uint32_t half_bit = hi ? 64u : 0u;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        const float mine = hi ? LB[k] : LA[k], send = hi ? LA[k] : LB[k];
-        const float got = __shfl_xor(__uint_as_float(__float_as_uint(send) | half_bit), 32, WAVE);
-        L[k] = __uint_as_float(__float_as_uint(mine) | half_bit);
-        LA[k] = got;
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(LA[k]),
+                                                         __float_as_uint(LB[k]), false, false);
+        L[k] = __uint_as_float(sw[0]);
+        LB[k] = __uint_as_float(sw[1] | 64u);
     }
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-        SSW_TOP5_INSERT(L, LA[k])
+    ssw_top5_merge(L, LB);
 }
 
 /* density index of a label: 32 rb + 8 (r / 4) + 4 half + r % 4 */
@@ -390,11 +392,12 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
             mfma_build_x<VECLEN>(x_row(t0 + col), hi, xconst, bxa);
             mfma_build_x<VECLEN>(x_row(t0 + 32 + col), hi, xconst, bxb);
         }
-        /* selection state per column block: the list of 5, the two best middles and the best
-         * smallest of the key triples (ssw_top5_select.inc) */
-        float LA[5], LB[5], MA[2], MB[2], ZA, ZB;
-        ssw_top5_reset(LA, MA, ZA, NEG_INF);
-        ssw_top5_reset(LB, MB, ZB, NEG_INF);
+        /* selection state per column block: the list of 5; the two best middles and the best
+         * smallest of the key triples (M, Z) and of the triples of their largest (N, Y)
+         * (ssw_top5_select.inc) */
+        float LA[5], LB[5], NA[2], NB[2], YA, YB, MA[2], MB[2], ZA, ZB;
+        ssw_top5_reset2(LA, NA, YA, MA, ZA, NEG_INF);
+        ssw_top5_reset2(LB, NB, YB, MB, ZB, NEG_INF);
         /* (a rolled loop: unrolled, the compiler runs the MFMAs of all row blocks ahead into
          * dozens of accumulator registers, which costs the 4th wave per SIMD; the overlap of
          * the matrix pipe with the inserts comes from the other waves) */
@@ -410,20 +413,20 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
                 const v16f acc = mfma_key_tile_frag(a, bxa);
                 float key[16];
                 mfma_label_keys(acc, rb, keymask, key);
-                ssw_top5_tile(LA, MA, ZA, key);
+                ssw_top5_tile2(LA, NA, YA, MA, ZA, key);
             }
             {
                 const v16f acc = mfma_key_tile_frag(a, bxb);
                 float key[16];
                 mfma_label_keys(acc, rb, keymask, key);
-                ssw_top5_tile(LB, MB, ZB, key);
+                ssw_top5_tile2(LB, NB, YB, MB, ZB, key);
             }
         }
         /* back to plain lists of 5, then the halves swap */
-        ssw_top5_fold(LA, MA, ZA);
-        ssw_top5_fold(LB, MB, ZB);
+        ssw_top5_fold2(LA, NA, YA, MA, ZA);
+        ssw_top5_fold2(LB, NB, YB, MB, ZB);
         float L[5];
-        mfma_swap_merge(LA, LB, hi, L);
+        mfma_swap_merge(LA, LB, L);
         /* from here on lane l works on frame t0 + l alone */
         const int t = t0 + lane;
         const int tl = t < P.n_frames ? t : P.n_frames - 1;
@@ -720,9 +723,9 @@ ptm_scan_top5_debug_kernel(const float *__restrict__ keys, int n_frames, int32_t
     uint32_t keymask;
     asm volatile("v_mov_b32 %0, 0xffffff80" : "=v"(keymask));
     const float NEG_INF = -__builtin_huge_valf();
-    float LA[5], LB[5], MA[2], MB[2], ZA, ZB;
-    ssw_top5_reset(LA, MA, ZA, NEG_INF);
-    ssw_top5_reset(LB, MB, ZB, NEG_INF);
+    float LA[5], LB[5], NA[2], NB[2], YA, YB, MA[2], MB[2], ZA, ZB;
+    ssw_top5_reset2(LA, NA, YA, MA, ZA, NEG_INF);
+    ssw_top5_reset2(LB, NB, YB, MB, ZB, NEG_INF);
     auto tile_of = [&](int blk, int rb) {
         const int t = t0 + 32 * blk + col;
         const float *kp = keys + (size_t)(t < n_frames ? t : n_frames - 1) * 128 + 32 * rb
@@ -737,14 +740,14 @@ ptm_scan_top5_debug_kernel(const float *__restrict__ keys, int n_frames, int32_t
     for (int rb = 0; rb < 4; ++rb) {
         float key[16];
         mfma_label_keys(tile_of(0, rb), rb, keymask, key);
-        ssw_top5_tile(LA, MA, ZA, key);
+        ssw_top5_tile2(LA, NA, YA, MA, ZA, key);
         mfma_label_keys(tile_of(1, rb), rb, keymask, key);
-        ssw_top5_tile(LB, MB, ZB, key);
+        ssw_top5_tile2(LB, NB, YB, MB, ZB, key);
     }
-    ssw_top5_fold(LA, MA, ZA);
-    ssw_top5_fold(LB, MB, ZB);
+    ssw_top5_fold2(LA, NA, YA, MA, ZA);
+    ssw_top5_fold2(LB, NB, YB, MB, ZB);
     float L[5];
-    mfma_swap_merge(LA, LB, hi, L);
+    mfma_swap_merge(LA, LB, L);
     const int t = t0 + lane;
     if (t < n_frames)
 #pragma unroll
