@@ -357,7 +357,7 @@ first_pass_run_impl(ssw_model_t *m, ssw_fp_graphs_t *g, double fp_t0, const int1
         P.pbeam = g->pbeam;
         P.wbeam = g->wbeam;
         P.sil = m->h->sil;
-        /* one thread per HMM while a workgroup can hold them (1024 threads), then two */
+        /* one thread per HMM while a workgroup can hold them (1024 threads), then the long-text kernels */
         void (*kern)(FirstPassParams);
         int tpb;
         size_t lds_launch = lds_bytes;
@@ -386,13 +386,13 @@ first_pass_run_impl(ssw_model_t *m, ssw_fp_graphs_t *g, double fp_t0, const int1
             }
             lds_launch = 0;
         } else if (max_nodes <= 256) {
-            kern = exp ? first_pass_kernel<1, 256, true> : first_pass_kernel<1, 256>;
+            kern = exp ? first_pass_kernel<256, true> : first_pass_kernel<256>;
             tpb = 256;
         } else if (max_nodes <= 512) {
-            kern = exp ? first_pass_kernel<1, 512, true> : first_pass_kernel<1, 512>;
+            kern = exp ? first_pass_kernel<512, true> : first_pass_kernel<512>;
             tpb = 512;
         } else { /* (more than 1024 nodes: `big` above) */
-            kern = exp ? first_pass_kernel<1, 1024, true> : first_pass_kernel<1, 1024>;
+            kern = exp ? first_pass_kernel<1024, true> : first_pass_kernel<1024>;
             tpb = 1024;
         }
         if (lds_launch > 48 * 1024)

@@ -1,4 +1,4 @@
-/* ssw_k5_firstpass.inc -- device: first_pass_kernel.
+/* ssw_k5_firstpass.inc -- device: first_pass_kernel, first_pass_big_kernel, first_pass_win_kernel.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 /* ---------------------------------------------------------------------------------- */
 /* K5: first pass of forced alignment (SURVEY 8(f) row 4)                               */
@@ -6,9 +6,9 @@
 /*   fsg_search_hmm_eval, _hmm_prune_prop, _pnode_trans, _pnode_exit, _word_trans        */
 /*                                 src/fsg_search.c:331-402, 498-541, 404-435, 437-490, 598-662 */
 /*   fsg_search_find_exit, fsg_search_seg_iter   src/fsg_search.c:854-925, 1085-1143     */
-/* One workgroup per utterance, one thread per phone-tree HMM (ssw_fsg.c; two per thread     */
-/* above 1024), its state in registers; a frame is three phases with two LDS-only          */
-/* workgroup barriers between them:                                                       */
+/* One workgroup per utterance, one thread per phone-tree HMM (ssw_fsg.c; texts of more    */
+/* than 1024 HMMs take the long-text kernels below), its state in registers; a frame is    */
+/* three phases with two LDS-only workgroup barriers between them:                         */
 /*   A  hmm_vit_eval of the active nodes, best score of the frame                        */
 /*   B  every node offers its exit score to its successors, leaves that pass the word     */
 /*      beam publish a word exit                                                         */
@@ -19,9 +19,10 @@
 /* Node-centric instead of list-driven: a node has one predecessor in the tree, and a      */
 /* word-initial node takes the best compatible exit, which is what the reference's        */
 /* "first strictly better score wins" loops compute.  Exact score ties that do occur --    */
-/* alternates pronounced alike -- follow the reference's list order (twin_first_in_list   */
-/* below); any other tie goes to the entering leaf with the lowest (context phone,         */
-/* ordinal).  The reference's history table drops exits whose right contexts are covered   */
+/* alternates pronounced alike -- follow the reference's list order (twin_first_in_list,  */
+/* ssw_search_common.inc, which holds the decisions the three kernels of this file share); */
+/* any other tie goes to the entering leaf with the lowest (context phone, ordinal).       */
+/* The reference's history table drops exits whose right contexts are covered              */
 /* by better ones (src/fsg_history.c:129-205); that only removes candidates that could not */
 /* win, so here every exit keeps a slot: entry id = 1 + frame * n_leaves + leaf.           */
 /* ---------------------------------------------------------------------------------- */
@@ -53,79 +54,11 @@ struct FirstPassParams {
     const long long *act_off; /* [n_utts] */
 };
 
-#define FP_ROOT 1u
-#define FP_LEAF 2u
-#define FP_ALLRC 4u
-#define FP_TWIN 8u
-#define FP_TWIN_FIRST 16u
-#define FP_TWIN_LAST 32u
-#define FP_NO_EXIT INT_MIN
-#define FP_RANK_NONE (1 << 20)
-enum { FP_F_NEXT = 1, FP_F_KEEP = 2, FP_F_ENTP = 4, FP_F_ENTW = 8 };
-
-/* Alternates pronounced alike ("twins") exit together with equal scores, and the reference's
- * history table keeps the exit that is entered first (src/fsg_history.c:164-170): the twin that
- * stands first in the active list.  That list is rebuilt every frame by prepending
- * (src/fsg_search.c:498-541): a surviving node at its own turn, a node its predecessor
- * transitions into at the predecessor's turn (children in chain order), word-initial nodes
- * entered by cross-word transitions after all of those.  The relative order of a twin group and
- * its ancestors depends on nothing but their own turns and flags, so every member follows it:
- * rec = [L, n_anc, own index, rank-buffer offset, L nodes (root .. predecessor, members in chain
- * order)], two rank buffers of L (list positions among these L nodes in this frame's list /
- * the previous one's).  Called once per frame by every member; returns whether the member is
- * the first of its group in this frame's list. */
-__device__ __forceinline__ bool
-twin_first_in_list(const int *rec, int *RK, const int *FLG, int f, int flg_mask = -1)
-{
-    const int L = rec[0], n_anc = rec[1], me = rec[2];
-    const int *prev = RK + rec[3] + ((f + 1) & 1) * L;
-    int *cur = RK + rec[3] + (f & 1) * L, *key = RK + rec[3] + 2 * L;
-    /* when was element i put on this frame's list, in the previous frame's processing order?
-     * own turn: 128 * its position; by its predecessor: 128 * the predecessor's position + 1 +
-     * chain index; by a cross-word transition: after everything */
-    for (int i = 0; i < L; ++i) {
-        const int flg = FLG[rec[4 + i] & flg_mask];
-        const int par = i < n_anc ? i - 1 : n_anc - 1;
-        const int cidx = i < n_anc ? 0 : i - n_anc;
-        int k = INT_MAX;
-        if (flg & FP_F_NEXT) {
-            if (flg & FP_F_KEEP)
-                k = prev[i] * 128;
-            if ((flg & FP_F_ENTP) && par >= 0) {
-                const int k2 = prev[par] * 128 + 1 + cidx;
-                k = k2 < k ? k2 : k;
-            }
-            if (flg & FP_F_ENTW) {
-                const int k3 = (1 << 28) + cidx;
-                k = k3 < k ? k3 : k;
-            }
-        }
-        key[i] = k;
-    }
-    /* the list is the reverse of that order: position = number of elements put on it later */
-    int best = FP_RANK_NONE;
-    for (int i = 0; i < L; ++i) {
-        const int ki = key[i];
-        int r = FP_RANK_NONE;
-        if (ki != INT_MAX) {
-            r = 0;
-            for (int j = 0; j < L; ++j) {
-                const int kj = key[j];
-                r += (kj != INT_MAX && kj > ki) ? 1 : 0;
-            }
-        }
-        cur[i] = r;
-        if (i >= n_anc)
-            best = r < best ? r : best;
-    }
-    return cur[me] != FP_RANK_NONE && cur[me] == best;
-}
-
-template <int NPT, int TPB, bool EXPORT = false> /* nodes per thread, threads: at most NPT * TPB phone-tree HMMs */
+/* threads: at most TPB phone-tree HMMs; EXPORT: the sets of active HMMs written out */
+template <int TPB, bool EXPORT = false>
 __global__ void __launch_bounds__(TPB)
 first_pass_kernel(FirstPassParams P)
 {
-    static_assert(!EXPORT || NPT == 1, "the exported bit of an HMM is its lane");
     extern __shared__ int fp_lds[];
     const int u = P.only != NULL ? P.only[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;
     const int nb = P.node_off[u], N = P.node_off[u + 1] - nb;
@@ -136,8 +69,7 @@ first_pass_kernel(FirstPassParams P)
     /* A node's HMM lives in its thread's registers.  LDS only carries what another node
      * reads: XS / XH, the exit score and history a node offers its successors this frame
      * (INT_MIN when it does not pass the beams); EXJ, the word exits of the frame in the order
-     * of the per-state entering lists; IL, three ints per list entry (leaf ordinal, the phone it
-     * shows, "any right context", its right-context set). */
+     * of the per-state entering lists; IL, three ints per list entry (il_pack). */
     int *XS = fp_lds, *XH = XS + N, *EXJ = XH + N, *IL = EXJ + NL;
     /* FLG: how each node came through the frame (for the twins' order bookkeeping); TW: the
      * utterance's twin records; RK: their rank buffers */
@@ -158,18 +90,10 @@ first_pass_kernel(FirstPassParams P)
     /* list slot of every leaf (EXJ is used as scratch for the inverse map) */
     for (int j = tid; j < NL; j += TPB) {
         const int lo = P.in_leaf[j_base + j], ln = leaf_node[lo];
-        const uint32_t li = info[ln];
-        IL[3 * j] = (int)((uint32_t)lo | (((li >> 8) & 0xff) << 16) | ((li & FP_ALLRC) ? 1u << 24 : 0u));
-        IL[3 * j + 1] = (int)(uint32_t)(ctxt[ln] & 0xffffffffull);
-        IL[3 * j + 2] = (int)(uint32_t)(ctxt[ln] >> 32);
+        il_pack(IL, j, (uint32_t)lo, info[ln], ctxt[ln]);
         EXJ[lo] = j;
     }
-    for (int i = tid; i < NTW; i += TPB)
-        TW[i] = P.tw[P.tw_off[u] + i];
-    for (int i = tid; i < NRK; i += TPB)
-        RK[i] = FP_RANK_NONE;
-    for (int i = tid; i < 2 * NS; i += TPB)
-        SMAX[i] = FP_NO_EXIT;
+    search_tables_init<TPB>(TW, P.tw + P.tw_off[u], NTW, RK, NRK, SMAX, 2 * NS, tid);
     if (tid == 0) {
         s_final_id = -1;
         s_any[0] = s_any[1] = 0;
@@ -178,65 +102,32 @@ first_pass_kernel(FirstPassParams P)
         s_red[tid] = W; /* waves that leave below never write their slot */
     __syncthreads();
 
-    int s0[NPT], s1[NPT], s2[NPT], h0[NPT], h1[NPT], h2[NPT], os[NPT], oh[NPT], bsc[NPT];
-    bool act[NPT];
-    int r_twin[NPT]; /* offset of the node's twin record in TW, -1 */
-    int r_parent[NPT], r_pen[NPT], r_leaf[NPT], r_slot[NPT], r_j0[NPT], r_j1[NPT], r_to[NPT];
-    uint32_t r_info[NPT];
-    unsigned long long r_ctxt[NPT];
-    uint32_t sen01[NPT], sen2t[NPT], tpa[NPT], tpb[NPT], tpc[NPT];
-    /* the dwords that hold the 16-bit scores (score_dword, ssw_dev_common.inc), extracted at use:
-     * two rotating sets, frame f's scores are requested at the top of frame f - 2 (round 3: one
-     * frame ahead, a frame of ~1.3 us was shorter than a loaded DRAM round trip) */
-    uint32_t nx0[NPT], nx1[NPT], nx2[NPT], ny0[NPT], ny1[NPT], ny2[NPT];
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        const int n = tid + k * TPB;
-        const bool v = n < N;
-        const int nn = v ? n : 0;
-        r_parent[k] = v ? parent[nn] : -1;
-        r_pen[k] = pen[nn];
-        r_leaf[k] = v ? leaf_ord[nn] : -1;
-        r_slot[k] = r_leaf[k] >= 0 ? EXJ[r_leaf[k]] : 0;
-        r_to[k] = r_leaf[k] >= 0 ? P.leaf_to[lb + r_leaf[k]] : 0;
-        r_info[k] = v ? info[nn] : 0u;
-        r_ctxt[k] = ctxt[nn];
-        const int d = (int)(r_info[k] >> 16);
-        r_j0[k] = (r_info[k] & FP_ROOT) ? in_off[d] - j_base : 0;
-        r_j1[k] = (r_info[k] & FP_ROOT) ? in_off[d + 1] - j_base : 0;
-        const uint16_t *sn = senid + (size_t)nn * 4;
-        sen01[k] = (uint32_t)sn[0] | ((uint32_t)sn[1] << 16);
-        sen2t[k] = (uint32_t)sn[2] | ((uint32_t)sn[3] << 16);
-        const uint32_t *tp = P.tp + (size_t)sn[3] * 3;
-        tpa[k] = tp[0];
-        tpb[k] = tp[1];
-        tpc[k] = tp[2];
-        nx0[k] = nx1[k] = nx2[k] = ny0[k] = ny1[k] = ny2[k] = 0;
-        if (T > 0) { /* (uniform) */
-            const ScoreRow r0 = score_row(P.senscr, (size_t)f0 * P.n_sen);
-            const ScoreRow r1 = score_row(P.senscr, (size_t)(f0 + (T > 1 ? 1 : 0)) * P.n_sen);
-            nx0[k] = score_dword(r0, sen01[k] & 0xffff);
-            nx1[k] = score_dword(r0, sen01[k] >> 16);
-            nx2[k] = score_dword(r0, sen2t[k] & 0xffff);
-            ny0[k] = score_dword(r1, sen01[k] & 0xffff);
-            ny1[k] = score_dword(r1, sen01[k] >> 16);
-            ny2[k] = score_dword(r1, sen2t[k] & 0xffff);
-        }
-        s0[k] = s1[k] = s2[k] = os[k] = bsc[k] = W;
-        h0[k] = h1[k] = h2[k] = oh[k] = -1;
-        act[k] = false;
-        r_twin[k] = v ? P.twin_ref[nb + nn] : -1;
-        /* fsg_search_start: the dummy entry 0 (score 0, left context SIL, every right
-         * context) enters the word-initial nodes of state 0 under beam alone */
-        if (v && (r_info[k] & FP_ROOT) && (r_info[k] >> 16) == 0 && ((r_ctxt[k] >> P.sil) & 1)
-            && r_pen[k] > P.beam && r_pen[k] > W) {
-            s0[k] = r_pen[k];
-            h0[k] = 0;
-            act[k] = true;
-        }
-        if (v)
-            FLG[n] = act[k] ? (FP_F_NEXT | FP_F_ENTW) : 0;
+    /* the thread's node: constants, HMM, and the two sets of score dwords in flight */
+    const int n = tid;
+    const bool v = n < N;
+    const int nn = v ? n : 0;
+    const int r_parent = v ? parent[nn] : -1, r_pen = pen[nn], r_leaf = v ? leaf_ord[nn] : -1;
+    const int r_slot = r_leaf >= 0 ? EXJ[r_leaf] : 0, r_to = r_leaf >= 0 ? P.leaf_to[lb + r_leaf] : 0;
+    const uint32_t r_info = v ? info[nn] : 0u;
+    const unsigned long long r_ctxt = ctxt[nn];
+    const int r_st = (int)(r_info >> 16);
+    const int r_j0 = (r_info & FP_ROOT) ? in_off[r_st] - j_base : 0;
+    const int r_j1 = (r_info & FP_ROOT) ? in_off[r_st + 1] - j_base : 0;
+    const uint16_t *sn = senid + (size_t)nn * 4;
+    const uint32_t sen01 = (uint32_t)sn[0] | ((uint32_t)sn[1] << 16);
+    const uint32_t sen2t = (uint32_t)sn[2] | ((uint32_t)sn[3] << 16);
+    const uint32_t *tp = P.tp + (size_t)sn[3] * 3;
+    const uint32_t tpa = tp[0], tpb = tp[1], tpc = tp[2];
+    uint32_t nx0 = 0, nx1 = 0, nx2 = 0, ny0 = 0, ny1 = 0, ny2 = 0;
+    if (T > 0) { /* (uniform) */
+        scores_request(P.senscr, f0, 0, T, P.n_sen, sen01, sen2t, nx0, nx1, nx2);
+        scores_request(P.senscr, f0, 1, T, P.n_sen, sen01, sen2t, ny0, ny1, ny2);
     }
+    int s0 = W, s1 = W, s2 = W, os = W, bsc = W, h0 = -1, h1 = -1, h2 = -1, oh = -1;
+    const int r_twin = v ? P.twin_ref[nb + nn] : -1; /* offset of the node's twin record in TW, -1 */
+    bool act = v && search_start_text(r_info, r_ctxt, r_pen, P.sil, P.beam, s0, h0);
+    if (v)
+        FLG[n] = act ? (FP_F_NEXT | FP_F_ENTW) : 0;
     __syncthreads(); /* EXJ scratch has been read */
     /* The workgroup is sized for the batch's largest utterance; waves without a single HMM of
      * THIS utterance leave now, so the frame loop's barriers wait for fewer waves (a finished
@@ -244,78 +135,43 @@ first_pass_kernel(FirstPassParams P)
     if ((tid & ~63) >= N)
         return;
 
-    auto frame = [&](const int f, uint32_t (&q0)[NPT], uint32_t (&q1)[NPT], uint32_t (&q2)[NPT]) {
-        int c0[NPT], c1[NPT], c2[NPT];
+    auto frame = [&](const int f, uint32_t &q0, uint32_t &q1, uint32_t &q2) {
         if (EXPORT) { /* (every wave that is still here owns a word of the frame's mask) */
-            const unsigned long long bm = __ballot(act[0]);
+            const unsigned long long bm = __ballot(act);
             if ((tid & 63) == 0)
                 P.act_mask[P.act_off[u] + (long long)f * ((N + 63) >> 6) + (tid >> 6)] = bm;
         }
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            /* the empty asm pins the wait for this frame's loads HERE and keeps the compiler
-             * from pulling the sign extension (and with it the wait) up to the load */
-            uint32_t a = q0[k], b = q1[k], c = q2[k];
-            asm volatile("" : "+v"(a), "+v"(b), "+v"(c));
-            const uint32_t lo = score_row(P.senscr, (size_t)(f0 + f) * P.n_sen).lo;
-            c0[k] = score_of(a, lo, sen01[k] & 0xffff);
-            c1[k] = score_of(b, lo, sen01[k] >> 16);
-            c2[k] = score_of(c, lo, sen2t[k] & 0xffff);
-        }
-        { /* this set is free again: frame f + 2's scores (the last row again beyond the end:
-           * unconditional, so that the number of loads in flight is the same on every path) */
-            const int fn = f + 2 < T ? f + 2 : T - 1;
-            const ScoreRow rn = score_row(P.senscr, (size_t)(f0 + fn) * P.n_sen);
-#pragma unroll
-            for (int k = 0; k < NPT; ++k) {
-                q0[k] = score_dword(rn, sen01[k] & 0xffff);
-                q1[k] = score_dword(rn, sen01[k] >> 16);
-                q2[k] = score_dword(rn, sen2t[k] & 0xffff);
-            }
-        }
+        int c0, c1, c2;
+        scores_take(P.senscr, f0, f, T, P.n_sen, sen01, sen2t, q0, q1, q2, c0, c1, c2);
         /* A: hmm_vit_eval of the active nodes, best score of the frame */
         int bs = W;
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            if (act[k]) {
-                bsc[k] = vit_eval_3st(s0[k], s1[k], s2[k], h0[k], h1[k], h2[k], os[k], oh[k],
-                                      -c0[k], -c1[k], -c2[k], tpa[k], tpb[k], tpc[k]);
-                bs = bsc[k] > bs ? bsc[k] : bs;
-            }
+        if (act) {
+            bsc = vit_eval_3st(s0, s1, s2, h0, h1, h2, os, oh, -c0, -c1, -c2, tpa, tpb, tpc);
+            bs = bsc;
         }
-        bs = wave_max_dpp(bs); /* (DPP: six dependent LDS-crossbar shuffles were ~400 clocks of a frame) */
-        if ((tid & 63) == 0)
-            s_red[tid >> 6] = bs;
+        beams_publish(s_red, bs, tid);
         lds_barrier();
-        int best = s_red[0];
-#pragma unroll
-        for (int k = 1; k < TPB / 64; ++k)
-            best = s_red[k] > best ? s_red[k] : best;
-        const int thresh = best + P.beam, pth = best + P.pbeam, wth = best + P.wbeam;
+        const FrameBeams bm = beams_read<TPB>(s_red, P.beam, P.pbeam, P.wbeam);
+        const int thresh = bm.thresh, pth = bm.pth, wth = bm.wth;
 
         /* B: every node offers its exit to its successors; leaves that pass the word beam
          * publish a word exit (fsg_search_hmm_prune_prop) */
-        bool keep[NPT];
+        const bool keep = act && bsc >= thresh;
         int any = 0;
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            const int n = tid + k * TPB;
-            keep[k] = act[k] && bsc[k] >= thresh;
-            if (n < NS)
-                SMAX[((f + 1) & 1) * NS + n] = FP_NO_EXIT; /* next frame's buffer */
-            if (n < N) {
-                XS[n] = (keep[k] && os[k] >= pth) ? os[k] : INT_MIN;
-                XH[n] = oh[k];
-                if (r_leaf[k] >= 0) {
-                    bool ex = keep[k] && os[k] >= wth;
-                    if (r_twin[k] >= 0)
-                        ex = twin_first_in_list(TW + r_twin[k], RK, FLG, f) && ex;
-                    EXJ[r_slot[k]] = ex ? os[k] : FP_NO_EXIT;
-                    if (ex) {
-                        hist[(size_t)f * NL + r_leaf[k]] = make_int2(oh[k], os[k]);
-                        atomicMax(&SMAX[(f & 1) * NS + r_to[k]], os[k]);
-                        any = 1;
-                    }
+        if (n < NS)
+            SMAX[((f + 1) & 1) * NS + n] = FP_NO_EXIT; /* next frame's buffer */
+        if (v) {
+            XS[n] = (keep && os >= pth) ? os : INT_MIN;
+            XH[n] = oh;
+            if (r_leaf >= 0) {
+                bool ex = keep && os >= wth;
+                if (r_twin >= 0)
+                    ex = twin_first_in_list(TW + r_twin, RK, FLG, f) && ex;
+                EXJ[r_slot] = ex ? os : FP_NO_EXIT;
+                if (ex) {
+                    hist[(size_t)f * NL + r_leaf] = make_int2(oh, os);
+                    atomicMax(&SMAX[(f & 1) * NS + r_to], os);
+                    any = 1;
                 }
             }
         }
@@ -326,70 +182,22 @@ first_pass_kernel(FirstPassParams P)
         /* C: phone transition into every node from its one predecessor, cross-word
          * transition into every word-initial node from the exits that entered its state, then
          * the node settles whether it stays active */
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            const int n = tid + k * TPB;
-            if (n >= N)
-                continue;
-            bool entered = false, entered_p = false, entered_w = false;
-            const int p = r_parent[k] >= 0 ? r_parent[k] : 0;
-            const int xs = XS[p], xh = XH[p];
-            if (r_parent[k] >= 0 && xs != INT_MIN) {
-                const int ns = xs + r_pen[k];
-                if (ns > thresh && ns > s0[k]) {
-                    s0[k] = ns; /* hmm_enter */
-                    h0[k] = xh;
-                    entered = entered_p = true;
-                }
-            }
-            if (r_info[k] & FP_ROOT) {
-                const int mx = SMAX[(f & 1) * NS + (int)(r_info[k] >> 16)];
-                if (mx != FP_NO_EXIT && mx + r_pen[k] > thresh && mx + r_pen[k] > s0[k]) {
-                    const int ci = (int)((r_info[k] >> 8) & 0xff);
-                    int be = FP_NO_EXIT, bid = -1;
-                    for (int j = r_j0[k]; j < r_j1[k]; ++j) {
-                        const int ex = EXJ[j];
-                        if (ex == FP_NO_EXIT || ex <= be)
-                            continue;
-                        const uint32_t w = (uint32_t)IL[3 * j];
-                        if (!((r_ctxt[k] >> ((w >> 16) & 0xff)) & 1))
-                            continue;
-                        const unsigned long long rcs = (unsigned long long)(uint32_t)IL[3 * j + 1]
-                            | ((unsigned long long)(uint32_t)IL[3 * j + 2] << 32);
-                        if (!((w >> 24) & 1) && !((rcs >> ci) & 1))
-                            continue;
-                        be = ex;
-                        bid = (int)(w & 0xffff);
-                    }
-                    if (bid >= 0) {
-                        const int ns = be + r_pen[k];
-                        if (ns > thresh && ns > s0[k]) {
-                            s0[k] = ns;
-                            h0[k] = 1 + f * NL + bid;
-                            entered = entered_w = true;
-                        }
-                    }
-                }
-            }
-            const bool stay = keep[k] || entered;
-            FLG[n] = (stay ? FP_F_NEXT : 0) | (keep[k] ? FP_F_KEEP : 0)
-                | (entered_p ? FP_F_ENTP : 0) | (entered_w ? FP_F_ENTW : 0);
-            if (act[k] && !stay) { /* fsg_psubtree_pnode_deactivate -> hmm_clear */
-                s0[k] = s1[k] = s2[k] = os[k] = bsc[k] = W;
-                h0[k] = h1[k] = h2[k] = oh[k] = -1;
-            }
-            act[k] = stay;
+        if (v) {
+            const int p = r_parent >= 0 ? r_parent : 0;
+            const int mx = (r_info & FP_ROOT) ? SMAX[(f & 1) * NS + r_st] : FP_NO_EXIT;
+            const int ent = node_enter(r_parent >= 0, XS[p], XH[p], mx, r_pen, thresh, 1 + f * NL, s0, h0,
+                                       [&](int &be, int &bid) {
+                                           best_entry<false>(EXJ, IL, r_j0, r_j1, r_ctxt,
+                                                             (int)((r_info >> 8) & 0xff), be, bid);
+                                       });
+            settle_regs(act, keep, ent, FLG[n], s0, s1, s2, h0, h1, h2, os, oh, bsc);
         }
         /* fsg_search_find_exit looks at the LAST frame that has any exit, and only at exits
          * into the final state */
         if (tid == 0) {
             if (s_any[f & 1]) {
-                int be = INT_MIN, bid = -1;
-                for (int j = in_off[NS - 1] - j_base; j < in_off[NS] - j_base; ++j)
-                    if (EXJ[j] != FP_NO_EXIT && EXJ[j] > be) {
-                        be = EXJ[j];
-                        bid = IL[3 * j] & 0xffff;
-                    }
+                int be;
+                const int bid = final_exit<false>(EXJ, IL, in_off[NS - 1] - j_base, in_off[NS] - j_base, be);
                 s_final_id = bid >= 0 ? 1 + f * NL + bid : -1;
             }
             s_any[(f + 1) & 1] = 0;
@@ -404,34 +212,9 @@ first_pass_kernel(FirstPassParams P)
     }
     __syncthreads(); /* the exits written to HBM during the loop are read back below */
 
-    /* fsg_search_seg_iter: walk the predecessors back, then write the words in order */
-    if (tid == 0) {
-        int id = s_final_id, n = 0;
-        ssw_word_seg_t *seg = P.seg + (size_t)u * P.max_seg;
-        if (id < 0)
-            n = -1;
-        else {
-            for (int k = id; k > 0; k = hist[k - 1].x)
-                ++n;
-            if (n > P.max_seg)
-                n = -(2 + n); /* room for n segments is needed: not a search failure */
-            else {
-                int j = n - 1;
-                for (int k = id; k > 0; k = hist[k - 1].x, --j) {
-                    const int fr = (k - 1) / NL, lo = (k - 1) % NL;
-                    const int pk = hist[k - 1].x;
-                    int sf = pk > 0 ? (pk - 1) / NL + 1 : 0;
-                    sf = sf > fr ? fr : sf;
-                    seg[j].wid = P.leaf_wid[lb + lo];
-                    seg[j].start = sf;
-                    seg[j].duration = fr - sf + 1;
-                    seg[j].score = hist[k - 1].y;
-                }
-
-            }
-        }
-        P.n_seg[u] = n;
-    }
+    if (tid == 0) /* (the identity map: every (frame, leaf) has its slot) */
+        P.n_seg[u] = fp_write_segments(hist, [](int k) { return (size_t)(k - 1); }, s_final_id, NL,
+                                       P.leaf_wid + lb, P.seg + (size_t)u * P.max_seg, P.max_seg);
 }
 
 /* K5 for texts beyond what one workgroup holds in registers and LDS (more than 4096 phone-tree
@@ -484,19 +267,11 @@ first_pass_big_kernel(FirstPassParams P)
 
     for (int j = tid; j < NL; j += TPB) {
         const int lo = P.in_leaf[j_base + j], ln = leaf_node[lo];
-        const uint32_t li = info[ln];
-        IL[3 * j] = (int)((uint32_t)lo | (((li >> 8) & 0xff) << 16) | ((li & FP_ALLRC) ? 1u << 24 : 0u));
-        IL[3 * j + 1] = (int)(uint32_t)(ctxt[ln] & 0xffffffffull);
-        IL[3 * j + 2] = (int)(uint32_t)(ctxt[ln] >> 32);
+        il_pack(IL, j, (uint32_t)lo, info[ln], ctxt[ln]);
         SLOT[lo] = j;
         EXJ[j] = FP_NO_EXIT;
     }
-    for (int i = tid; i < NTW; i += TPB)
-        TW[i] = P.tw[P.tw_off[u] + i];
-    for (int i = tid; i < NRK; i += TPB)
-        RK[i] = FP_RANK_NONE;
-    for (int i = tid; i < 2 * NS; i += TPB)
-        SMAX[i] = FP_NO_EXIT;
+    search_tables_init<TPB>(TW, P.tw + P.tw_off[u], NTW, RK, NRK, SMAX, 2 * NS, tid);
     if (tid == 0) {
         s_final_id = -1;
         s_any[0] = s_any[1] = 0;
@@ -524,16 +299,8 @@ first_pass_big_kernel(FirstPassParams P)
             }
     }
     for (int n = tid; n < N; n += TPB) {
-        int s0 = W, h0 = -1, a = 0;
-        const uint32_t inf = info[n];
-        const int pn = pen[n];
-        /* fsg_search_start, as in first_pass_kernel */
-        if ((inf & FP_ROOT) && (inf >> 16) == 0 && ((ctxt[n] >> P.sil) & 1) && pn > P.beam
-            && pn > W) {
-            s0 = pn;
-            h0 = 0;
-            a = 1;
-        }
+        int s0 = W, h0 = -1;
+        const int a = search_start_text(info[n], ctxt[n], pen[n], P.sil, P.beam, s0, h0);
         S0[n] = s0;
         S1[n] = S2[n] = OS[n] = BSC[n] = W;
         H0[n] = h0;
@@ -589,9 +356,7 @@ first_pass_big_kernel(FirstPassParams P)
             OS[n] = os, OH[n] = oh, BSC[n] = b;
             bs = b > bs ? b : bs;
         }
-        bs = wave_max_dpp(bs); /* (DPP: six dependent LDS-crossbar shuffles were ~400 clocks of a frame) */
-        if ((tid & 63) == 0)
-            s_red[tid >> 6] = bs;
+        beams_publish(s_red, bs, tid);
         if (BAND) {
             alo = -wave_max_dpp(-alo);
             ahi = wave_max_dpp(ahi);
@@ -609,11 +374,8 @@ first_pass_big_kernel(FirstPassParams P)
             s_blo[(f + 1) & 1] = INT_MAX;
             s_bhi[(f + 1) & 1] = -1;
         }
-        int best = s_red[0];
-#pragma unroll
-        for (int k = 1; k < TPB / 64; ++k)
-            best = s_red[k] > best ? s_red[k] : best;
-        const int thresh = best + P.beam, pth = best + P.pbeam, wth = best + P.wbeam;
+        const FrameBeams bm = beams_read<TPB>(s_red, P.beam, P.pbeam, P.wbeam);
+        const int thresh = bm.thresh, pth = bm.pth, wth = bm.wth;
 
         /* B: exits offered to successors, word exits published */
         int any = 0;
@@ -680,47 +442,14 @@ first_pass_big_kernel(FirstPassParams P)
             }
             const int pn = pen[n];
             int s0 = S0[n], h0 = H0[n];
-            bool entered = false, entered_p = false, entered_w = false;
-            if (par >= 0 && xs != INT_MIN) {
-                const int ns = xs + pn;
-                if (ns > thresh && ns > s0) {
-                    s0 = ns;
-                    h0 = xh;
-                    entered = entered_p = true;
-                }
-            }
-            if ((inf & FP_ROOT) && mx != FP_NO_EXIT && mx + pn > thresh && mx + pn > s0) {
-                const int ci = (int)((inf >> 8) & 0xff);
-                const int d = (int)(inf >> 16);
-                const unsigned long long cx = ctxt[n];
-                int be = FP_NO_EXIT, bid = -1;
-                for (int j = in_off[d] - j_base; j < in_off[d + 1] - j_base; ++j) {
-                    const int ex = EXJ[j];
-                    if (ex == FP_NO_EXIT || ex <= be)
-                        continue;
-                    const uint32_t w = (uint32_t)IL[3 * j];
-                    if (!((cx >> ((w >> 16) & 0xff)) & 1))
-                        continue;
-                    const unsigned long long rcs = (unsigned long long)(uint32_t)IL[3 * j + 1]
-                        | ((unsigned long long)(uint32_t)IL[3 * j + 2] << 32);
-                    if (!((w >> 24) & 1) && !((rcs >> ci) & 1))
-                        continue;
-                    be = ex;
-                    bid = (int)(w & 0xffff);
-                }
-                if (bid >= 0) {
-                    const int ns = be + pn;
-                    if (ns > thresh && ns > s0) {
-                        s0 = ns;
-                        h0 = 1 + f * NL + bid;
-                        entered = entered_w = true;
-                    }
-                }
-            }
-            const bool stay = keep || entered;
-            FLG[n] = (stay ? FP_F_NEXT : 0) | (keep ? FP_F_KEEP : 0) | (entered_p ? FP_F_ENTP : 0)
-                | (entered_w ? FP_F_ENTW : 0);
-            if (entered) {
+            const int ent = node_enter(par >= 0, xs, xh, mx, pn, thresh, 1 + f * NL, s0, h0,
+                                       [&](int &be, int &bid) {
+                                           const int d = (int)(inf >> 16);
+                                           best_entry<false>(EXJ, IL, in_off[d] - j_base, in_off[d + 1] - j_base,
+                                                             ctxt[n], (int)((inf >> 8) & 0xff), be, bid);
+                                       });
+            const bool stay = settle(keep, ent, FLG[n]);
+            if (ent) {
                 S0[n] = s0;
                 H0[n] = h0;
             }
@@ -732,12 +461,8 @@ first_pass_big_kernel(FirstPassParams P)
         }
         if (tid == 0) {
             if (s_any[f & 1]) {
-                int be = INT_MIN, bid = -1;
-                for (int j = in_off[NS - 1] - j_base; j < in_off[NS] - j_base; ++j)
-                    if (EXJ[j] != FP_NO_EXIT && EXJ[j] > be) {
-                        be = EXJ[j];
-                        bid = IL[3 * j] & 0xffff;
-                    }
+                int be;
+                const int bid = final_exit<false>(EXJ, IL, in_off[NS - 1] - j_base, in_off[NS] - j_base, be);
                 s_final_id = bid >= 0 ? 1 + f * NL + bid : -1;
             }
             s_any[(f + 1) & 1] = 0;
@@ -757,39 +482,16 @@ first_pass_big_kernel(FirstPassParams P)
     }
     __syncthreads();
 
-    if (tid == 0) { /* fsg_search_seg_iter, as in first_pass_kernel */
-        int id = s_final_id, n = 0;
-        ssw_word_seg_t *seg = P.seg + (size_t)u * P.max_seg;
+    if (tid == 0) {
         auto at = [&](int k) -> size_t { /* entry id -> its slot */
             if (!BAND)
                 return (size_t)(k - 1);
             const int fr = (k - 1) / NL, lo = (k - 1) % NL;
             return (size_t)(FBASE[fr] + lo - FLLO[fr]);
         };
-        if (BAND && s_ovf)
-            n = -(1 << 30);
-        else if (id < 0)
-            n = -1;
-        else {
-            for (int k = id; k > 0; k = hist[at(k)].x)
-                ++n;
-            if (n > P.max_seg)
-                n = -(2 + n);
-            else {
-                int j = n - 1;
-                for (int k = id; k > 0; k = hist[at(k)].x, --j) {
-                    const int fr = (k - 1) / NL, lo = (k - 1) % NL;
-                    const int pk = hist[at(k)].x;
-                    int sf = pk > 0 ? (pk - 1) / NL + 1 : 0;
-                    sf = sf > fr ? fr : sf;
-                    seg[j].wid = P.leaf_wid[lb + lo];
-                    seg[j].start = sf;
-                    seg[j].duration = fr - sf + 1;
-                    seg[j].score = hist[at(k)].y;
-                }
-            }
-        }
-        P.n_seg[u] = n;
+        P.n_seg[u] = (BAND && s_ovf) ? -(1 << 30)
+                                     : fp_write_segments(hist, at, s_final_id, NL, P.leaf_wid + lb,
+                                                         P.seg + (size_t)u * P.max_seg, P.max_seg);
     }
 }
 
@@ -843,23 +545,16 @@ first_pass_win_kernel(FirstPassParams P)
     /* workspace tables, as in first_pass_big_kernel */
     for (int j = tid; j < NL; j += TPB) {
         const int lo = P.in_leaf[j_base + j], ln = leaf_node[lo];
-        const uint32_t li = info[ln];
-        IL[3 * j] = (int)((uint32_t)lo | (((li >> 8) & 0xff) << 16) | ((li & FP_ALLRC) ? 1u << 24 : 0u));
-        IL[3 * j + 1] = (int)(uint32_t)(ctxt[ln] & 0xffffffffull);
-        IL[3 * j + 2] = (int)(uint32_t)(ctxt[ln] >> 32);
+        il_pack(IL, j, (uint32_t)lo, info[ln], ctxt[ln]);
         SLOT[lo] = j;
     }
-    for (int i = tid; i < NTW; i += TPB)
-        TW[i] = P.tw[P.tw_off[u] + i];
-    for (int i = tid; i < NRK; i += TPB)
-        RK[i] = FP_RANK_NONE;
+    search_tables_init<TPB>(TW, P.tw + P.tw_off[u], NTW, RK, NRK, SMAX, 2 * TPB, tid);
     for (int i = tid; i < NS + 2; i += TPB) {
         SFIRST[i] = N;
         LFIRST[i] = NL;
     }
     for (int i = tid; i < EW; i += TPB)
         EXJ[i] = FP_NO_EXIT;
-    SMAX[tid] = SMAX[TPB + tid] = FP_NO_EXIT;
     FLG[tid] = 0;
     XS[tid] = INT_MIN;
     XH[tid] = -1;
@@ -896,9 +591,6 @@ first_pass_win_kernel(FirstPassParams P)
     uint32_t r_info = 0, sen01 = 0, sen2t = 0, tpa = 0, tpb = 0, tpc = 0;
     unsigned long long r_ctxt = 0;
     uint32_t nx0 = 0, nx1 = 0, nx2 = 0, ny0 = 0, ny1 = 0, ny2 = 0;
-    auto row_of = [&](int f) { /* (the last row again beyond the end) */
-        return score_row(P.senscr, (size_t)(f0 + (f < T ? f : T - 1)) * P.n_sen);
-    };
     auto load_node = [&](int nn_) { /* constants in, hmm_clear; FLG / SMAX slots of a fresh node */
         n = nn_;
         v = n < N;
@@ -937,23 +629,14 @@ first_pass_win_kernel(FirstPassParams P)
         had_exit = false;
     };
     auto load_scores = [&](int f, uint32_t &q0, uint32_t &q1, uint32_t &q2) {
-        const ScoreRow r = row_of(f);
-        q0 = score_dword(r, sen01 & 0xffff);
-        q1 = score_dword(r, sen01 >> 16);
-        q2 = score_dword(r, sen2t & 0xffff);
+        scores_request(P.senscr, f0, f, T, P.n_sen, sen01, sen2t, q0, q1, q2);
     };
     load_node(n);
     if (T > 0) {
         load_scores(0, nx0, nx1, nx2);
         load_scores(1, ny0, ny1, ny2);
     }
-    /* fsg_search_start, as in first_pass_kernel */
-    if (v && (r_info & FP_ROOT) && r_st == 0 && ((r_ctxt >> P.sil) & 1) && r_pen > P.beam
-        && r_pen > W) {
-        s0 = r_pen;
-        h0 = 0;
-        act = true;
-    }
+    act = v && search_start_text(r_info, r_ctxt, r_pen, P.sil, P.beam, s0, h0);
     FLG[tid] = act ? (FP_F_NEXT | FP_F_ENTW) : 0;
     /* the band the first frame's exits can come from: states 0 and 1 */
     int llo = 0, lw = LFIRST[NS > 2 ? 2 : NS] - 0;
@@ -971,13 +654,8 @@ first_pass_win_kernel(FirstPassParams P)
     auto frame = [&](const int f, uint32_t &q0, uint32_t &q1, uint32_t &q2, uint32_t &o0,
                      uint32_t &o1, uint32_t &o2) {
         const int par = f & 1;
-        uint32_t a = q0, b = q1, c = q2;
-        asm volatile("" : "+v"(a), "+v"(b), "+v"(c));
-        const uint32_t rlo = row_of(f).lo;
-        const int c0 = score_of(a, rlo, sen01 & 0xffff), c1 = score_of(b, rlo, sen01 >> 16),
-                  c2 = score_of(c, rlo, sen2t & 0xffff);
-        load_scores(f + 2, q0, q1, q2); /* (clamped to the last row; unconditional, see
-                                         * first_pass_kernel) */
+        int c0, c1, c2;
+        scores_take(P.senscr, f0, f, T, P.n_sen, sen01, sen2t, q0, q1, q2, c0, c1, c2);
         if (tid == 0) {
             FBASE[f] = (int)hbase;
             FLLO[f] = llo;
@@ -992,29 +670,23 @@ first_pass_win_kernel(FirstPassParams P)
             bsc = vit_eval_3st(s0, s1, s2, h0, h1, h2, os, oh, -c0, -c1, -c2, tpa, tpb, tpc);
             bs = bsc;
         }
-        bs = wave_max_dpp(bs); /* (DPP: six dependent LDS-crossbar shuffles were ~400 clocks of a frame) */
+        beams_publish(s_red, bs, tid);
         /* a wave's nodes are consecutive (whole waves move on together): n = n0 + lane */
         const unsigned long long am = __ballot(act);
         const int n0 = n - (tid & 63);
         const int amin = am ? n0 + __builtin_ctzll(am) : INT_MAX;
         const int amax = am ? n0 + 63 - __builtin_clzll(am) : -1;
-        if ((tid & 63) == 0) {
-            s_red[tid >> 6] = bs;
-            if (amax >= 0) {
-                atomicMin(&s_nlo[par], amin);
-                atomicMax(&s_nhi[par], amax);
-                /* the frame's set of active HMMs (ssw_host_fpactive.inc; the rows were cleared
-                 * before the launch: a word no wave writes stays 0) */
-                if (P.act_mask != nullptr)
-                    P.act_mask[P.act_off[u] + (long long)f * ((N + 63) >> 6) + (n0 >> 6)] = am;
-            }
+        if ((tid & 63) == 0 && amax >= 0) {
+            atomicMin(&s_nlo[par], amin);
+            atomicMax(&s_nhi[par], amax);
+            /* the frame's set of active HMMs (ssw_host_fpactive.inc; the rows were cleared
+             * before the launch: a word no wave writes stays 0) */
+            if (P.act_mask != nullptr)
+                P.act_mask[P.act_off[u] + (long long)f * ((N + 63) >> 6) + (n0 >> 6)] = am;
         }
         lds_barrier();
-        int best = s_red[0];
-#pragma unroll
-        for (int k = 1; k < TPB / 64; ++k)
-            best = s_red[k] > best ? s_red[k] : best;
-        const int thresh = best + P.beam, pth = best + P.pbeam, wth = best + P.wbeam;
+        const FrameBeams bm = beams_read<TPB>(s_red, P.beam, P.pbeam, P.wbeam);
+        const int thresh = bm.thresh, pth = bm.pth, wth = bm.wth;
         const int nlo = s_nlo[par], nhi = s_nhi[par];
         const bool stop = s_ovf != 0;
         if (v && n == nlo) {
@@ -1060,65 +732,21 @@ first_pass_win_kernel(FirstPassParams P)
         lds_barrier();
 
         /* C */
-        bool entered = false, entered_p = false, entered_w = false;
         if (v) {
             const int pp = r_parent >= 0 ? (r_parent & NM) : 0;
-            const int xs = XS[pp], xh = XH[pp];
-            if (r_parent >= 0 && xs != INT_MIN) {
-                const int ns = xs + r_pen;
-                if (ns > thresh && ns > s0) {
-                    s0 = ns;
-                    h0 = xh;
-                    entered = entered_p = true;
-                }
-            }
-            if (r_info & FP_ROOT) {
-                const int mx = SMAX[par * TPB + (r_st & NM)];
-                if (mx != FP_NO_EXIT && mx + r_pen > thresh && mx + r_pen > s0) {
-                    const int ci = (int)((r_info >> 8) & 0xff);
-                    int be = FP_NO_EXIT, bid = -1;
-                    for (int j = r_j0; j < r_j1; ++j) {
-                        const int ex = EXJ[j & EM];
-                        if (ex == FP_NO_EXIT || ex <= be)
-                            continue;
-                        const uint32_t w = (uint32_t)IL[3 * j];
-                        if (!((r_ctxt >> ((w >> 16) & 0xff)) & 1))
-                            continue;
-                        const unsigned long long rcs = (unsigned long long)(uint32_t)IL[3 * j + 1]
-                            | ((unsigned long long)(uint32_t)IL[3 * j + 2] << 32);
-                        if (!((w >> 24) & 1) && !((rcs >> ci) & 1))
-                            continue;
-                        be = ex;
-                        bid = (int)(w & 0xffff);
-                    }
-                    if (bid >= 0) {
-                        const int ns = be + r_pen;
-                        if (ns > thresh && ns > s0) {
-                            s0 = ns;
-                            h0 = 1 + f * NL + bid;
-                            entered = entered_w = true;
-                        }
-                    }
-                }
-            }
-            const bool stay = keep || entered;
-            FLG[tid] = (stay ? FP_F_NEXT : 0) | (keep ? FP_F_KEEP : 0) | (entered_p ? FP_F_ENTP : 0)
-                | (entered_w ? FP_F_ENTW : 0);
-            if (act && !stay) {
-                s0 = s1 = s2 = os = bsc = W;
-                h0 = h1 = h2 = oh = -1;
-            }
-            act = stay;
+            const int mx = (r_info & FP_ROOT) ? SMAX[par * TPB + (r_st & NM)] : FP_NO_EXIT;
+            const int ent = node_enter(r_parent >= 0, XS[pp], XH[pp], mx, r_pen, thresh, 1 + f * NL, s0, h0,
+                                       [&](int &be, int &bid) {
+                                           best_entry<false>(EXJ, IL, r_j0, r_j1, r_ctxt,
+                                                             (int)((r_info >> 8) & 0xff), be, bid, EM);
+                                       });
+            settle_regs(act, keep, ent, FLG[tid], s0, s1, s2, h0, h1, h2, os, oh, bsc);
         }
         if (tid == 0) {
             if (s_any[par]) {
-                int be = INT_MIN, bid = -1;
+                int be, bid = -1;
                 if (s_anyf[par]) /* (then the final state's entering list is inside the ring) */
-                    for (int j = in_off[NS - 1] - j_base; j < in_off[NS] - j_base; ++j)
-                        if (EXJ[j & EM] != FP_NO_EXIT && EXJ[j & EM] > be) {
-                            be = EXJ[j & EM];
-                            bid = IL[3 * j] & 0xffff;
-                        }
+                    bid = final_exit<false>(EXJ, IL, in_off[NS - 1] - j_base, in_off[NS] - j_base, be, EM);
                 s_final_id = bid >= 0 ? 1 + f * NL + bid : -1;
             }
             s_any[par ^ 1] = 0;
@@ -1159,36 +787,13 @@ first_pass_win_kernel(FirstPassParams P)
     }
     __syncthreads();
 
-    if (tid == 0) { /* fsg_search_seg_iter, as in first_pass_big_kernel<.., true> */
-        int id = s_final_id, nseg = 0;
-        ssw_word_seg_t *seg = P.seg + (size_t)u * P.max_seg;
-        auto at = [&](int k) -> size_t {
+    if (tid == 0) {
+        auto at = [&](int k) -> size_t { /* banded as in first_pass_big_kernel<.., true> */
             const int fr = (k - 1) / NL, lo = (k - 1) % NL;
             return (size_t)(FBASE[fr] + lo - FLLO[fr]);
         };
-        if (s_ovf)
-            nseg = -(1 << 30);
-        else if (id < 0)
-            nseg = -1;
-        else {
-            for (int k = id; k > 0; k = hist[at(k)].x)
-                ++nseg;
-            if (nseg > P.max_seg)
-                nseg = -(2 + nseg);
-            else {
-                int j = nseg - 1;
-                for (int k = id; k > 0; k = hist[at(k)].x, --j) {
-                    const int fr = (k - 1) / NL, lo = (k - 1) % NL;
-                    const int pk = hist[at(k)].x;
-                    int sf = pk > 0 ? (pk - 1) / NL + 1 : 0;
-                    sf = sf > fr ? fr : sf;
-                    seg[j].wid = P.leaf_wid[lb + lo];
-                    seg[j].start = sf;
-                    seg[j].duration = fr - sf + 1;
-                    seg[j].score = hist[at(k)].y;
-                }
-            }
-        }
-        P.n_seg[u] = nseg;
+        P.n_seg[u] = s_ovf ? -(1 << 30)
+                           : fp_write_segments(hist, at, s_final_id, NL, P.leaf_wid + lb,
+                                               P.seg + (size_t)u * P.max_seg, P.max_seg);
     }
 }

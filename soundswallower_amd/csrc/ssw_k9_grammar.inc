@@ -133,10 +133,7 @@ grammar_search_kernel(GrammarParams P)
 
     for (int j = tid; j < NE; j += TPB) {
         const int lo = P.slot_leaf[j_base + j], ln = leaf_node[lo];
-        const uint32_t li = info[ln];
-        IL[3 * j] = (int)((((li >> 8) & 0xff) << 16) | ((li & FP_ALLRC) ? 1u << 24 : 0u));
-        IL[3 * j + 1] = (int)(uint32_t)(ctxt[ln] & 0xffffffffull);
-        IL[3 * j + 2] = (int)(uint32_t)(ctxt[ln] >> 32);
+        il_pack(IL, j, 0u, info[ln], ctxt[ln]);
         EXJ[j] = FP_NO_EXIT;
         /* (a leaf's slots are ls_slot[ls_off[leaf] ..): NE of them in all */
         const int sj = P.ls_slot[ls_base + j];
@@ -213,14 +210,8 @@ grammar_search_kernel(GrammarParams P)
             rc.j0 = rc.j1 = 0;
         }
         if (T > 0) { /* (uniform) */
-            const ScoreRow r0 = score_row(P.senscr, (size_t)f0 * P.n_sen);
-            const ScoreRow r1 = score_row(P.senscr, (size_t)(f0 + (T > 1 ? 1 : 0)) * P.n_sen);
-            nx0 = score_dword(r0, ra.sen01 & 0xffff);
-            nx1 = score_dword(r0, ra.sen01 >> 16);
-            nx2 = score_dword(r0, ra.sen2t & 0xffff);
-            ny0 = score_dword(r1, ra.sen01 & 0xffff);
-            ny1 = score_dword(r1, ra.sen01 >> 16);
-            ny2 = score_dword(r1, ra.sen2t & 0xffff);
+            scores_request(P.senscr, f0, 0, T, P.n_sen, ra.sen01, ra.sen2t, nx0, nx1, nx2);
+            scores_request(P.senscr, f0, 1, T, P.n_sen, ra.sen01, ra.sen2t, ny0, ny1, ny2);
         }
     }
 #pragma unroll
@@ -393,21 +384,8 @@ grammar_search_kernel(GrammarParams P)
                 const int mx = SMAX[(f & 1) * NS + (int)(c.info >> 16)];
                 if (mx != FP_NO_EXIT && mx + c.pen > thresh && mx + c.pen > s0[k]) {
                     const int ci = (int)((c.info >> 8) & 0xff);
-                    int be = FP_NO_EXIT, bid = -1;
-                    for (int j = c.j0; j < c.j1; ++j) {
-                        const int ex = EXJ[j];
-                        if (ex == FP_NO_EXIT || ex <= be)
-                            continue;
-                        const uint32_t w = (uint32_t)IL[3 * j];
-                        if (!((c.ctxt >> ((w >> 16) & 0xff)) & 1))
-                            continue;
-                        const unsigned long long rcs = (unsigned long long)(uint32_t)IL[3 * j + 1]
-                            | ((unsigned long long)(uint32_t)IL[3 * j + 2] << 32);
-                        if (!((w >> 24) & 1) && !((rcs >> ci) & 1))
-                            continue;
-                        be = ex;
-                        bid = j;
-                    }
+                    int be, bid;
+                    best_entry<true>(EXJ, IL, c.j0, c.j1, c.ctxt, ci, be, bid);
                     if (bid >= 0) {
                         const int ns = be + c.pen;
                         if (ns > thresh && ns > s0[k]) {

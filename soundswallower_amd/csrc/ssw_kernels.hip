@@ -26,8 +26,13 @@
  *                        src/state_align_search.c:177-268, src/hmm.c:482-567)
  *   ssw_k2_anytopo.inc   viterbi_align_any_kernel: the same search over HMMs of 1, 2, 4 or 5 states
  *                        (hmm_vit_eval_5st_lr, hmm_vit_eval_anytopo, src/hmm.c:166-304, :671-739)
+ *   ssw_search_common.inc the decisions of the reference's fsg_search that the three K5 kernels
+ *                        share, once (start rule, beams, phone and cross-word transitions, twins'
+ *                        order, final exit, segment writer, score look-ahead); K9 uses its flags,
+ *                        twins' order, entering-list record and entry scan, src/fsg_search.c:310-925
  *   ssw_k5_firstpass.inc first_pass_kernel (fsg_search start/step/finish over the linear
- *                        grammar's phone trees, src/fsg_search.c:665-925)
+ *                        grammar's phone trees, HMMs in registers), first_pass_big_kernel (state in
+ *                        an HBM workspace), first_pass_win_kernel (a sliding window over LDS rings)
  *   ssw_k6_compact.inc   compact score rows: the plan of a batch of alignments (which of an
  *                        utterance's states share a senone, where each score goes), gather
  *   ssw_k7_fpactive.inc  the first pass in the default configuration (compallsen = no) as a
@@ -92,6 +97,7 @@ namespace {
 #include "ssw_k4_feat.inc"
 #include "ssw_k2_align.inc"
 #include "ssw_k2_anytopo.inc"
+#include "ssw_search_common.inc"
 #include "ssw_k5_firstpass.inc"
 #include "ssw_k6_compact.inc"
 #include "ssw_k7_fpactive.inc"

@@ -167,6 +167,65 @@ def test_chain_grammar_matches_first_pass(gpu_en, text):
     assert r.score(0) == want[-1][3]
 
 
+@pytest.mark.parametrize("mname,text", [("en-us", "go forward data ten meters"),
+                                        ("fr-fr", "avance abus de ait dix mètres")])
+def test_one_text_through_all_five_kernels(oracle_mod, gpu_en, gpu_fr, orc_en, orc_fr, monkeypatch,
+                                           mname, text):
+    """The five search kernels share every decision (ssw_search_common.inc) and differ in where the
+    state lives: one text on ~150 frames of synthetic scores, searched as a linear text through
+    first_pass_kernel, first_pass_win_kernel and first_pass_big_kernel and as its chain grammar
+    through grammar_search_kernel and grammar_search_big_kernel (a plan that also holds a grammar
+    beyond one workgroup is searched from the HBM workspace), gives the same words, frames and path
+    scores five times.
+    The en-us text has a word with an alternate ("data"); en-us lists no alternates pronounced
+    alike, so the fr-fr text brings the twin records ("abus", "ait").  No reference here: each
+    kernel is pinned to it by its own suite."""
+    from oracle import fsg_oracle as F
+    from tests.test_gpu_first_pass import synth_scores
+    model, orc = (gpu_en, orc_en) if mname == "en-us" else (gpu_fr, orc_fr)
+    lex = _lex(model, mname)
+    d_ = os.path.join(MODEL_ROOT, mname)
+    olex = F.Lexicon(orc, os.path.join(d_, "dict.txt"), os.path.join(d_, "noisedict.txt"))
+    words = text.split()
+    scr = synth_scores(F, orc, olex, words, 11, orc.n_sen)
+    assert 100 <= len(scr) <= 250
+    d = torch.from_numpy(scr).cuda()
+    got = {}
+    for kernel, env in (("first_pass_kernel", {}),
+                        ("first_pass_win_kernel", {"SSW_FP_KERNEL": "big", "SSW_FP_WIN_TPB": "256"}),
+                        ("first_pass_big_kernel", {"SSW_FP_KERNEL": "big", "SSW_FP_WIN": "0"})):
+        with monkeypatch.context() as mp:
+            for k, v in env.items():
+                mp.setenv(k, v)
+            got[kernel] = lex.first_pass(d, [0, len(scr)], [words])[0]
+    chain = ssw.Fsg.create(model, lex, "chain", 0, len(words),
+                           [(i, i + 1, 1.0, w) for i, w in enumerate(words)])
+    plans = {"grammar_search_kernel": (lex.grammar_plan(chain), None)}
+    if mname == "en-us":
+        big = _fsg(model, lex, mname, "loop200")
+    else:                       # (loop200 is an en-us grammar: a loop over 1000 fr-fr words)
+        pad = [lex.word(i) for i in range(200, 1400)]
+        pad = [w for w in pad if w and "(" not in w and not w.startswith("<")][:1000]
+        big = ssw.Fsg.create(model, lex, "pad", 0, 0, [(0, 0, 1.0 / len(pad), w) for w in pad])
+    plans["grammar_search_big_kernel"] = (lex.grammar_plan([chain, big], max_hmms=30000), [0])
+    assert plans["grammar_search_big_kernel"][0].hmms(1) > 4096
+    for kernel, (plan, which) in plans.items():
+        r = _search(model, lex, [scr], plan, which)
+        assert r.status(0) == 0, kernel
+        segs, total = [], 0
+        for w, sf, ef, ascr, lscr in r.segments(0):
+            total += ascr + lscr
+            segs.append((w, sf, ef - sf + 1, total))
+        assert r.score(0) == total, kernel
+        got[kernel] = segs
+    for kernel, segs in got.items():
+        print(kernel, segs)
+    want = got["first_pass_kernel"]
+    assert want is not None and len(want) >= len(words)
+    for kernel, segs in got.items():
+        assert segs == want, kernel
+
+
 @pytest.mark.parametrize("mname,recording,case", [("en-us", "goforward.raw", "goforward"),
                                                   ("fr-fr", "goforward_fr.raw", "fr")])
 def test_recognize_audio_batch(gpu_en, gpu_fr, mname, recording, case):
