@@ -43,77 +43,6 @@ struct AlignParams {
     int *band_ws;
 };
 
-/* hmm_vit_eval_3st_lr, src/hmm.c:482-567.  n0..n2 are the NEGATED senone scores.  Written
- * with selects instead of the reference's nested ifs (a lone wave pays for every branch with
- * scalar exec-mask bookkeeping); the decision tree is the same, including the t2 that the state-2
- * block inherits from the exit block when it has no 0->2 arc of its own (:496,501-502,519-520):
- *   exit   only if s1 + n1 > WORST:  t1 = a2 + tp23, t2 = a1 + tp13 if that arc exists else
- *          INT_MIN;  take t1 iff t1 > t2 (history of state 2), else t2 (history of state 1)
- *   state2 t0 = a2 + tp22, t1 = a1 + tp12, t2 = a0 + tp02 if that arc exists, else the exit
- *          block's t2;  if t0 > t1: (t2 > t0 ? t2/h0 : t0/h2) else (t2 > t1 ? t2/h0 : t1/h1)
- *   state1 t0 = a1 + tp11, t1 = a0 + tp01;  t0 > t1 ? t0/h1 : t1/h0
- *   state0 a0 + tp00;  every new score clamped to WORST, best = max over them and the exit. */
-/* a1_live / quirk (optional, for the byte-token kernel): whether the exit block ran, and whether
- * state 2 took the exit block's t2 -- a score that is state 1's with the history of state 0 */
-__device__ __forceinline__ int
-vit_eval_3st(int &s0, int &s1, int &s2, int &h0, int &h1, int &h2, int &os, int &oh, int n0,
-             int n1, int n2, uint32_t tpa, uint32_t tpb, uint32_t tpc, bool *a1_live_out = nullptr,
-             bool *quirk_out = nullptr)
-{
-#define TPQ(word, j) (-(int)(((word) >> (8 * (j))) & 0xffu))
-    const int tp00 = TPQ(tpa, 0), tp01 = TPQ(tpa, 1), tp02 = TPQ(tpa, 2);
-    const int tp11 = TPQ(tpb, 1), tp12 = TPQ(tpb, 2), tp13 = TPQ(tpb, 3);
-    const int tp22 = TPQ(tpc, 2), tp23 = TPQ(tpc, 3);
-#undef TPQ
-    const int a2 = s2 + n2, a1 = s1 + n1, a0 = s0 + n0;
-    const int W = SSW_WORST_SCORE;
-
-    /* exit */
-    const bool a1_live = a1 > W;
-    const int e1 = a2 + tp23;
-    const int e2 = (a1_live && tp13 > -255) ? a1 + tp13 : INT_MIN;
-    const bool from2 = e1 > e2;
-    int s3 = from2 ? e1 : e2;
-    s3 = s3 < W ? W : s3;
-    const int oh_new = from2 ? h2 : h1;
-    os = a1_live ? s3 : os;
-    oh = a1_live ? oh_new : oh;
-    int best = a1_live ? s3 : W;
-
-    /* state 2 (uses h1, h2 as they were) */
-    const int t0 = a2 + tp22, t1 = a1 + tp12;
-    const int t2 = (tp02 > -255) ? a0 + tp02 : e2;
-    const bool self2 = t0 > t1;
-    const int base2 = self2 ? t0 : t1;
-    const int hb2 = self2 ? h2 : h1;
-    const bool skip2 = t2 > base2;
-    int ns2 = skip2 ? t2 : base2;
-    h2 = skip2 ? h0 : hb2;
-    if (a1_live_out != nullptr)
-        *a1_live_out = a1_live;
-    if (quirk_out != nullptr)
-        *quirk_out = skip2 && !(tp02 > -255);
-    ns2 = ns2 < W ? W : ns2;
-    best = ns2 > best ? ns2 : best;
-
-    /* state 1 */
-    const int u0 = a1 + tp11, u1 = a0 + tp01;
-    const bool self1 = u0 > u1;
-    int ns1 = self1 ? u0 : u1;
-    h1 = self1 ? h1 : h0;
-    ns1 = ns1 < W ? W : ns1;
-    best = ns1 > best ? ns1 : best;
-
-    /* state 0 */
-    int ns0 = a0 + tp00;
-    ns0 = ns0 < W ? W : ns0;
-    best = ns0 > best ? ns0 : best;
-    s0 = ns0;
-    s1 = ns1;
-    s2 = ns2;
-    return best;
-}
-
 /* state_align_search_finish (state_align_search.c:215-268): one lane walks the token stack
  * back from frame n_frames - 2. */
 __device__ __forceinline__ void
@@ -275,7 +204,7 @@ viterbi_align_kernel(AlignParams P)
                 nxt2[w] = real ? (int)rown[sid2[w]] : 0;
             }
         }
-        const bool renorm = (best_score - 0x300000) < SSW_WORST_SCORE;
+        const bool renorm = align_renorm_due(best_score);
         int bs = SSW_WORST_SCORE;
 
         /* renormalize_hmms + evaluate_hmms + prune_hmms (state_align_search.c:57-106) */
@@ -428,22 +357,9 @@ viterbi_align_kernel(AlignParams P)
 }
 
 /* The same search with every phone's HMM in registers (lane = phone, WMAX words of 64 phones):
- * nothing of the frame step goes through LDS.  Neighbour values move by one lane with DPP wave
- * shifts, whose `old` operand supplies the value that crosses a 64-phone word boundary.  All of
- * phone_transition's reads see the state left by evaluate/prune (as in the reference's loop,
- * where hmm i+1 is examined before it is entered); the enters are applied afterwards. */
-__device__ __forceinline__ int
-lane_from_next(int v, int edge) /* lane i <- lane i+1, lane 63 <- edge */
-{
-    return __builtin_amdgcn_update_dpp(edge, v, 0x130, 0xf, 0xf, false);
-}
-
-__device__ __forceinline__ int
-lane_from_prev(int v, int edge) /* lane i <- lane i-1, lane 0 <- edge */
-{
-    return __builtin_amdgcn_update_dpp(edge, v, 0x138, 0xf, 0xf, false);
-}
-
+ * nothing of the frame step goes through LDS; the steps are ssw_align_common.inc's, word by word.
+ * All of phone_transition's reads see the state left by evaluate/prune (as in the reference's
+ * loop, where hmm i+1 is examined before it is entered); the enters are applied afterwards. */
 template <int WMAX>
 __global__ void __launch_bounds__(64)
 viterbi_align_reg_kernel(AlignParams P)
@@ -454,37 +370,21 @@ viterbi_align_reg_kernel(AlignParams P)
     const int NP = U.n_phones;
     const int n_states = NP * 3;
 
-    int s0[WMAX], s1[WMAX], s2[WMAX], h0[WMAX], h1[WMAX], h2[WMAX], os[WMAX], oh[WMAX], fr[WMAX];
-    uint32_t tpa[WMAX], tpb[WMAX], tpc[WMAX];
-    int sid01[WMAX], sid2[WMAX], sf_next[WMAX], ef[WMAX], cur01[WMAX], cur2[WMAX];
+    AlignHmm hm[WMAX];
+    AlignPhone phn[WMAX];
+    int cur01[WMAX], cur2[WMAX];
     const int16_t *row0 = P.senscr + U.scr_off;
 #pragma unroll
     for (int w = 0; w < WMAX; ++w) {
-        const int p = w * 64 + lane;
-        const bool real = p < NP;
-        const int gp = U.phone_off + (real ? p : 0);
-        s0[w] = s1[w] = s2[w] = os[w] = SSW_WORST_SCORE; /* hmm_clear, src/hmm.c:124-140 */
-        h0[w] = h1[w] = h2[w] = oh[w] = -1;
-        fr[w] = -1;
-        const uint32_t *tp = reinterpret_cast<const uint32_t *>(P.tp) + (size_t)P.tmatid[gp] * 3;
-        tpa[w] = real ? tp[0] : 0u;
-        tpb[w] = real ? tp[1] : 0u;
-        tpc[w] = real ? tp[2] : 0u;
-        sid01[w] = real ? ((int)P.senid[gp * 3] | ((int)P.senid[gp * 3 + 1] << 16)) : 0;
-        sid2[w] = real ? (int)P.senid[gp * 3 + 2] : 0;
-        ef[w] = real ? P.ef[gp] : INT_MAX;
-        sf_next[w] = (p + 1 < NP) ? P.sf[gp + 1] : INT_MAX; /* nothing enters past the end */
-        const bool have = real && U.n_frames > 0;
-        cur01[w] = have ? ((int)(uint16_t)row0[sid01[w] & 0xffff]
-                           | ((int)(uint16_t)row0[(sid01[w] >> 16) & 0xffff] << 16))
+        phn[w] = align_phone_load(w * 64 + lane, NP, U.phone_off, P.tp, P.tmatid, P.senid, P.sf, P.ef);
+        hmm_clear(hm[w]);
+        const bool have = phn[w].real && U.n_frames > 0;
+        cur01[w] = have ? ((int)(uint16_t)row0[phn[w].sid01 & 0xffff]
+                           | ((int)(uint16_t)row0[(phn[w].sid01 >> 16) & 0xffff] << 16))
                         : 0;
-        cur2[w] = have ? (int)row0[sid2[w]] : 0;
+        cur2[w] = have ? (int)row0[phn[w].sid2] : 0;
     }
-    if (lane == 0) { /* state_align_search_start: hmm_enter(hmms, 0, 0, 0) */
-        s0[0] = 0;
-        h0[0] = 0;
-        fr[0] = 0;
-    }
+    align_search_start(hm[0], phn[0].p);
 
     int2 *tok = P.tokens + U.tok_off;
     int best_score = 0;
@@ -495,90 +395,52 @@ viterbi_align_reg_kernel(AlignParams P)
         int nxt01[WMAX], nxt2[WMAX];
 #pragma unroll
         for (int w = 0; w < WMAX; ++w) {
-            const bool real = w * 64 + lane < NP;
-            nxt01[w] = real ? ((int)(uint16_t)rown[sid01[w] & 0xffff]
-                               | ((int)(uint16_t)rown[(sid01[w] >> 16) & 0xffff] << 16))
-                            : 0;
-            nxt2[w] = real ? (int)rown[sid2[w]] : 0;
+            nxt01[w] = phn[w].real ? ((int)(uint16_t)rown[phn[w].sid01 & 0xffff]
+                                     | ((int)(uint16_t)rown[(phn[w].sid01 >> 16) & 0xffff] << 16))
+                                  : 0;
+            nxt2[w] = phn[w].real ? (int)rown[phn[w].sid2] : 0;
         }
-        const bool renorm = (best_score - 0x300000) < SSW_WORST_SCORE;
         int bs = SSW_WORST_SCORE;
-
-        /* renormalize_hmms + evaluate_hmms + prune_hmms (state_align_search.c:57-106) */
+        /* (evaluated under a branch, a word at a time: as one block of selects the words'
+         * evaluations are interleaved and <4> needs 159 registers instead of 126) */
 #pragma unroll
         for (int w = 0; w < WMAX; ++w) {
-            if (w * 64 + lane < NP) {
-                if (renorm) { /* hmm_normalize, src/hmm.c:150-161 */
-                    if (s0[w] > SSW_WORST_SCORE)
-                        s0[w] -= best_score;
-                    if (s1[w] > SSW_WORST_SCORE)
-                        s1[w] -= best_score;
-                    if (s2[w] > SSW_WORST_SCORE)
-                        s2[w] -= best_score;
-                    if (os[w] > SSW_WORST_SCORE)
-                        os[w] -= best_score;
-                }
-                if (fr[w] >= t) {
-                    const int n0 = -(int)(int16_t)(cur01[w] & 0xffff);
-                    const int n1 = -(cur01[w] >> 16);
-                    const int n2 = -cur2[w];
-                    int b = vit_eval_3st(s0[w], s1[w], s2[w], h0[w], h1[w], h2[w], os[w], oh[w],
-                                         n0, n1, n2, tpa[w], tpb[w], tpc[w]);
-                    bs = b > bs ? b : bs;
-                    if (nf <= ef[w])
-                        fr[w] = nf;
-                }
+            AlignHmm &h = hm[w];
+            renormalize_hmm(h, best_score);
+            if (h.fr >= t) {
+                const int b = vit_eval_3st(h.s0, h.s1, h.s2, h.h0, h.h1, h.h2, h.os, h.oh,
+                                           -(int)(int16_t)(cur01[w] & 0xffff), -(cur01[w] >> 16),
+                                           -cur2[w], phn[w].tpa, phn[w].tpb, phn[w].tpc);
+                bs = b > bs ? b : bs;
+                if (nf <= phn[w].ef)
+                    h.fr = nf;
             }
         }
         best_score = wave_max_i32(bs);
 
-        /* phone_transition (state_align_search.c:108-133) as a carry chain, then
-         * record_transitions (:149-175).  entered(i+1) = C_i & (A_i | entered(i)) is the carry
-         * recurrence of the binary sum X + Y with X = C, Y = A & C. */
-        unsigned long long Am[WMAX], Cm[WMAX];
+        AlignCarry k[WMAX];
 #pragma unroll
         for (int w = 0; w < WMAX; ++w) {
-            const int p = w * 64 + lane;
             /* frame and entry score of phone p + 1 */
-            const int efr = (w + 1 < WMAX) ? __builtin_amdgcn_readlane(fr[w + 1 < WMAX ? w + 1 : w], 0) : -1;
-            const int es0 = (w + 1 < WMAX) ? __builtin_amdgcn_readlane(s0[w + 1 < WMAX ? w + 1 : w], 0) : 0;
-            const int nfr = lane_from_next(fr[w], efr);
-            const int ns0 = lane_from_next(s0[w], es0);
-            const bool a_bit = p < NP && fr[w] == nf;
-            const bool c_bit = p + 1 < NP && nf >= sf_next[w] && (nfr < t || os[w] > ns0);
-            Am[w] = __ballot(a_bit);
-            Cm[w] = __ballot(c_bit);
+            const int efr = (w + 1 < WMAX) ? __builtin_amdgcn_readlane(hm[w + 1 < WMAX ? w + 1 : w].fr, 0) : -1;
+            const int es0 = (w + 1 < WMAX) ? __builtin_amdgcn_readlane(hm[w + 1 < WMAX ? w + 1 : w].s0, 0) : 0;
+            k[w] = phone_transition(hm[w], phn[w], NP, efr, es0, t);
         }
-        unsigned long long cin = 0;
+        int cin = 0;
         int2 *tkrow = tok + (size_t)t * n_states;
         int prev_os = 0, prev_oh = 0; /* exit score/history of the last phone of the previous word */
 #pragma unroll
         for (int w = 0; w < WMAX; ++w) {
-            const int p = w * 64 + lane;
-            const unsigned long long X = Cm[w], Y = Am[w] & Cm[w];
-            const unsigned long long S = X + Y + cin;
-            const unsigned long long E = S ^ X ^ Y; /* bit i: phone (w*64+i) is entered */
-            cin = ((X & Y) | ((X | Y) & ~S)) >> 63;
-            const bool entered = (E >> lane) & 1ull;
-            const int src_os = lane_from_prev(os[w], prev_os);
-            const int src_oh = lane_from_prev(oh[w], prev_oh);
-            prev_os = __builtin_amdgcn_readlane(os[w], 63);
-            prev_oh = __builtin_amdgcn_readlane(oh[w], 63);
-            if (p < NP) {
-                if (entered) { /* hmm_enter, src/hmm.c:142-148 */
-                    s0[w] = src_os;
-                    h0[w] = src_oh;
-                    fr[w] = nf;
-                }
-                int2 k0 = make_int2(-1, -1), k1 = k0, k2 = k0;
-                if (fr[w] >= t) {
-                    k0 = make_int2(h0[w], s0[w]);
-                    k1 = make_int2(h1[w], s1[w]);
-                    k2 = make_int2(h2[w], s2[w]);
-                    h0[w] = p * 3;
-                    h1[w] = p * 3 + 1;
-                    h2[w] = p * 3 + 2;
-                }
+            const int p = phn[w].p;
+            int c_out;
+            const bool e_bit = phone_entered(k[w], cin, lane, &c_out);
+            cin = c_out;
+            hmm_enter(hm[w], phn[w].real && e_bit, nf, prev_os, prev_oh);
+            prev_os = __builtin_amdgcn_readlane(hm[w].os, 63); /* (an enter leaves the exit alone) */
+            prev_oh = __builtin_amdgcn_readlane(hm[w].oh, 63);
+            int2 k0, k1, k2;
+            record_transitions(hm[w], p, t, k0, k1, k2);
+            if (phn[w].real) {
                 tkrow[p * 3] = k0;
                 tkrow[p * 3 + 1] = k1;
                 tkrow[p * 3 + 2] = k2;
@@ -597,8 +459,8 @@ viterbi_align_reg_kernel(AlignParams P)
 #pragma unroll
     for (int w = 0; w < WMAX; ++w)
         if (w == lw) {
-            fin_oh = __shfl(oh[w], ll, WAVE);
-            fin_os = __shfl(os[w], ll, WAVE);
+            fin_oh = __shfl(hm[w].oh, ll, WAVE);
+            fin_os = __shfl(hm[w].os, ll, WAVE);
         }
     /* the token stack is read back by this workgroup only: workgroup-scope ordering (an
      * agent-scope fence would write back and invalidate the XCD's L2 under the other
@@ -608,32 +470,14 @@ viterbi_align_reg_kernel(AlignParams P)
         align_backtrace(P, U, u, tok, n_states, fin_oh, fin_os);
 }
 
-/* v_max3_i32 */
-__device__ __forceinline__ int
-max3_i32(int a, int b, int c)
-{
-    const int m = a > b ? a : b;
-    return m > c ? m : c;
-}
-
 /* One wave per 64-phone word of the utterance (workgroup = n_words waves, up to 16): the frame
- * step of every word runs in parallel, HMMs in registers as above.  Per frame the waves meet
- * twice at an LDS-only barrier (no drain of the outstanding token stores): once to publish their
- * boundary values (frame / entry score of their first phone, exit score / history of their last)
- * and their best score, once to publish the A and C masks of phone_transition, after which every
- * wave folds the carry chain up to its own word.  The exchange slots are double-buffered by
- * frame parity: a wave can be at most one barrier ahead of the slowest one. */
-#define SSW_ALIGN_MAX_WAVES 16
-
+ * step of every word runs in parallel, HMMs in registers as above, the waves meeting twice per
+ * frame at the exchange slots (ssw_align_common.inc).  This kernel adds the reference's tokens:
+ * three {history, score} per phone and frame, [n_frames][n_states]. */
 __global__ void __launch_bounds__(64 * SSW_ALIGN_MAX_WAVES)
 viterbi_align_mw_kernel(AlignParams P)
 {
-    /* x_bs / x_gp: all 16 slots are read by every wave (one round trip for everything a barrier
-     * publishes, no exec-masked reads); the slots of waves that do not exist hold WORST / 0 */
-    __shared__ __attribute__((aligned(16))) int x_bs[2][SSW_ALIGN_MAX_WAVES];
-    __shared__ int x_fr0[2][SSW_ALIGN_MAX_WAVES], x_s00[2][SSW_ALIGN_MAX_WAVES],
-        x_os63[2][SSW_ALIGN_MAX_WAVES], x_oh63[2][SSW_ALIGN_MAX_WAVES];
-    __shared__ int x_gp[2][SSW_ALIGN_MAX_WAVES]; /* bit 0: carry generated, bit 1: carry passed on */
+    __shared__ AlignExchange x;
     __shared__ int x_fin[2];
     const int u = blockIdx.x;
     const int lane = threadIdx.x & 63;
@@ -642,168 +486,49 @@ viterbi_align_mw_kernel(AlignParams P)
     const AlignUtt U = P.utts[u];
     const int NP = U.n_phones;
     const int n_states = NP * 3;
-    const int p = w * 64 + lane;
-    const bool real = p < NP;
-    const int gp = U.phone_off + (real ? p : 0);
-
-    int s0 = SSW_WORST_SCORE, s1 = SSW_WORST_SCORE, s2 = SSW_WORST_SCORE, os = SSW_WORST_SCORE;
-    int h0 = -1, h1 = -1, h2 = -1, oh = -1, fr = -1; /* hmm_clear, src/hmm.c:124-140 */
-    const uint32_t *tp = reinterpret_cast<const uint32_t *>(P.tp) + (size_t)P.tmatid[gp] * 3;
-    const uint32_t tpa = real ? tp[0] : 0u, tpb = real ? tp[1] : 0u, tpc = real ? tp[2] : 0u;
-    const int sid01 = real ? ((int)P.senid[gp * 3] | ((int)P.senid[gp * 3 + 1] << 16)) : 0;
-    const int sid2 = real ? (int)P.senid[gp * 3 + 2] : 0;
-    const int ef = real ? P.ef[gp] : INT_MAX;
-    const int sf_next = (p + 1 < NP) ? P.sf[gp + 1] : INT_MAX;
-    /* senone scores of this lane's phone: three rotating register sets, so that the scattered
-     * 2-byte gathers of frame t + 2 are requested at the top of frame t (a frame step is shorter
-     * than a DRAM round trip) */
-    const int last = U.n_frames - 1;
-    /* (round 3: the three scores stay in three registers until their frame -- packing two of
-     * them at the load made every frame wait for the loads it had just issued) */
-    /* Round 3.  Every lane loads (lanes without a phone read senone 0: their HMM is inert
-     * whatever the score), and what is loaded is the ALIGNED DWORD that holds the 16-bit score:
-     * a 32-bit value the compiler cannot narrow, so that the extraction below -- and with it
-     * the wait for the load -- stays behind the asm pin at the top of the frame two frames
-     * later.  (As 16-bit loads the extension was hoisted to the end of the previous frame,
-     * right behind that frame's token stores, and `s_waitcnt vmcnt(0)` waits for stores as
-     * well; before that, two scores packed into one register at the load made every frame
-     * wait for the loads it had just issued.)  An aligned dword that holds a valid half never
-     * leaves that half's page; the other half is discarded. */
-    const char *scr0 = reinterpret_cast<const char *>(P.senscr);
-    const uint32_t scr_lo = (uint32_t)(reinterpret_cast<uintptr_t>(scr0) & 3);
-    /* byte offset of the row of frame t from scr0, and what it leaves modulo 4 */
-    auto row_off = [&](int t) {
-        return (size_t)(U.scr_off + (long long)(t < last ? t : last) * U.scr_stride) * 2;
-    };
-    auto fetch = [&](int t, uint32_t &v0, uint32_t &v1, uint32_t &v2) {
-        const size_t ro = row_off(t);
-        const uint32_t lo = (scr_lo + (uint32_t)ro) & 3u;
-        const char *base = scr0 + ro - lo; /* 4-byte aligned */
-        v0 = *reinterpret_cast<const uint32_t *>(base + ((2u * (sid01 & 0xffff) + lo) & ~3u));
-        v1 = *reinterpret_cast<const uint32_t *>(base + ((2u * ((sid01 >> 16) & 0xffff) + lo) & ~3u));
-        v2 = *reinterpret_cast<const uint32_t *>(base + ((2u * (uint32_t)sid2 + lo) & ~3u));
-    };
-    /* the half of its dword a score sits in: bit offset 0 or 16 */
-    auto half_of = [&](int t, int sid) {
-        const uint32_t lo = (scr_lo + (uint32_t)row_off(t)) & 3u;
-        return ((2u * (uint32_t)sid + lo) & 2u) * 8u;
-    };
+    const AlignPhone phn =
+        align_phone_load(w * 64 + lane, NP, U.phone_off, P.tp, P.tmatid, P.senid, P.sf, P.ef);
+    const ScoreAhead sa = {P.senscr, U.scr_off, U.scr_stride, U.n_frames - 1};
+    AlignHmm hm;
+    hmm_clear(hm);
     uint32_t a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0, c0 = 0, c1 = 0, c2 = 0;
     if (U.n_frames > 0) { /* (uniform) an empty utterance has no row to read */
-        fetch(0, a0, a1, a2);
-        fetch(1, b0, b1, b2);
+        score_fetch(sa, phn, 0, a0, a1, a2);
+        score_fetch(sa, phn, 1, b0, b1, b2);
     }
-    if (p == 0) { /* state_align_search_start: hmm_enter(hmms, 0, 0, 0) */
-        s0 = 0;
-        h0 = 0;
-        fr = 0;
-    }
-
-    if (threadIdx.x < 2 * SSW_ALIGN_MAX_WAVES) {
-        x_bs[0][threadIdx.x] = SSW_WORST_SCORE; /* [0][16 ..] is [1][..] */
-        x_gp[0][threadIdx.x] = 0;
-    }
+    align_search_start(hm, phn.p);
+    exchange_init(x);
     __syncthreads();
     int2 *tok = P.tokens + U.tok_off;
     int best_score = 0;
-    /* The frame step is written with selects rather than branches: a lone wave pays for every
-     * divergent `if` with scalar exec-mask bookkeeping, and lanes without a phone hold an inert
-     * HMM (scores WORST, frame -1) that the arithmetic leaves inert.  Only stores are masked. */
-    int2 *tkrow = tok + (real ? p * 3 : 0);
+    int2 *tkrow = tok + (phn.real ? phn.p * 3 : 0);
     auto frame = [&](const int t, uint32_t raw0, uint32_t raw1, uint32_t raw2, uint32_t &fut0,
                      uint32_t &fut1, uint32_t &fut2) {
         const int nf = t + 1, par = t & 1;
-        const int W = SSW_WORST_SCORE;
-        fetch(t + 2, fut0, fut1, fut2);
-        /* the empty asm pins the wait for the loads of two frames ago HERE */
-        asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2));
-        const int cur0 = (int)(short)(raw0 >> half_of(t, sid01 & 0xffff));
-        const int cur1 = (int)(short)(raw1 >> half_of(t, (sid01 >> 16) & 0xffff));
-        const int cur2 = (int)(short)(raw2 >> half_of(t, sid2));
-        /* renormalize_hmms (hmm_normalize, src/hmm.c:150-161) */
-        const bool renorm = (best_score - 0x300000) < W;
-        s0 = (renorm && s0 > W) ? s0 - best_score : s0;
-        s1 = (renorm && s1 > W) ? s1 - best_score : s1;
-        s2 = (renorm && s2 > W) ? s2 - best_score : s2;
-        os = (renorm && os > W) ? os - best_score : os;
-        /* evaluate_hmms + prune_hmms (state_align_search.c:57-106): evaluated for every lane,
-         * kept for the phones that are active in this frame */
-        const bool active = fr >= t;
-        int e0 = s0, e1 = s1, e2 = s2, g0 = h0, g1 = h1, g2 = h2, eos = os, eoh = oh;
-        const int b = vit_eval_3st(e0, e1, e2, g0, g1, g2, eos, eoh,
-                                   -cur0, -cur1, -cur2, tpa, tpb, tpc);
-        s0 = active ? e0 : s0;
-        s1 = active ? e1 : s1;
-        s2 = active ? e2 : s2;
-        h1 = active ? g1 : h1;
-        h2 = active ? g2 : h2;
-        os = active ? eos : os;
-        oh = active ? eoh : oh;
-        fr = (active && nf <= ef) ? nf : fr;
-        int bs = wave_max_dpp(active ? b : W);
-        if (lane == 0) {
-            x_bs[par][w] = bs;
-            x_fr0[par][w] = fr;
-            x_s00[par][w] = s0;
-        }
-        if (lane == 63) {
-            x_os63[par][w] = os;
-            x_oh63[par][w] = oh;
-        }
+        int n0, n1, n2;
+        score_step(sa, phn, t, raw0, raw1, raw2, fut0, fut1, fut2, n0, n1, n2);
+        renormalize_hmm(hm, best_score);
+        const int b = evaluate_hmm(hm, phn, t, n0, n1, n2);
+        exchange_publish(x, par, w, lane, b, hm);
         lds_barrier();
-        /* everything the barrier published, requested at once: the 16 best-score slots (four
-         * 16-byte reads of one address: no cross-lane reduction) and the next word's boundary */
-        const int wnx = w + 1 < nw ? w + 1 : w;
-        const int4 *bq = reinterpret_cast<const int4 *>(x_bs[par]);
-        const int4 q0 = bq[0], q1 = bq[1], q2 = bq[2], q3 = bq[3];
-        const int efr_ = x_fr0[par][wnx], es0_ = x_s00[par][wnx];
-        best_score = max3_i32(max3_i32(max3_i32(q0.x, q0.y, q0.z), max3_i32(q0.w, q1.x, q1.y),
-                                       max3_i32(q1.z, q1.w, q2.x)),
-                              max3_i32(max3_i32(q2.y, q2.z, q2.w), max3_i32(q3.x, q3.y, q3.z), q3.w),
-                              W);
-
-        /* phone_transition (state_align_search.c:108-133): A/C masks of this word */
-        const int efr = w + 1 < nw ? efr_ : -1;
-        const int es0 = w + 1 < nw ? es0_ : 0;
-        const int nfr = lane_from_next(fr, efr);
-        const int ns0 = lane_from_next(s0, es0);
-        const bool a_bit = fr == nf; /* lanes without a phone keep frame -1 */
-        const bool c_bit = p + 1 < NP && nf >= sf_next && (nfr < t || os > ns0);
-        const unsigned long long Am = __ballot(a_bit), Cm = __ballot(c_bit);
-        /* The cascade entered(i+1) = C_i & (A_i | entered(i)) is the carry chain of X + Y with
-         * X = C, Y = A & C.  Across words it is a carry-lookahead: every word publishes whether
-         * it generates a carry out (g) and whether it would pass one through (p); the carry
-         * into word w is then bit w of the carries of (G | P) + G, one more add. */
-        const unsigned long long X = Cm, Y = Am & Cm;
-        const unsigned long long S0 = X + Y, S1 = S0 + 1ull;
-        const int g_out = (int)(((X & Y) | ((X | Y) & ~S0)) >> 63);
-        const int c1_out = (int)(((X & Y) | ((X | Y) & ~S1)) >> 63);
+        /* everything the barrier published, requested at once: the 16 best-score slots and the
+         * next word's boundary */
+        const bool has_next = w + 1 < nw;
+        const int wnx = has_next ? w + 1 : w;
+        const int efr = x.fr0[par][wnx], es0 = x.s00[par][wnx];
+        best_score = exchange_best_score(x, par);
+        const AlignCarry k = phone_transition(hm, phn, NP, has_next ? efr : -1, es0, t);
         if (lane == 0)
-            x_gp[par][w] = g_out | ((c1_out & ~g_out) << 1);
+            x.gp[par][w] = k.code;
         lds_barrier();
         const int wpv = w > 0 ? w - 1 : 0;
-        const int gp = x_gp[par][lane & (SSW_ALIGN_MAX_WAVES - 1)];
-        const int pos_ = x_os63[par][wpv], poh_ = x_oh63[par][wpv];
-        const unsigned long long Gm = __ballot(gp & 1) & 0xffffull, Pm = __ballot(gp & 2) & 0xffffull;
-        const unsigned long long XX = Gm | Pm;
-        const unsigned long long carries = (XX + Gm) ^ XX ^ Gm;
-        const unsigned long long cin = (carries >> w) & 1ull;
-        const unsigned long long E = (X + Y + cin) ^ X ^ Y; /* bit i: phone (w*64+i) is entered */
-        const bool entered = real && ((E >> lane) & 1ull);
-        const int src_os = lane_from_prev(os, w > 0 ? pos_ : 0);
-        const int src_oh = lane_from_prev(oh, w > 0 ? poh_ : 0);
-        /* hmm_enter (src/hmm.c:142-148), then record_transitions (:149-175) */
-        s0 = entered ? src_os : s0;
-        h0 = entered ? src_oh : h0;
-        fr = entered ? nf : fr;
-        const bool rec = fr >= t;
-        const int2 k0 = make_int2(rec ? h0 : -1, rec ? s0 : -1);
-        const int2 k1 = make_int2(rec ? h1 : -1, rec ? s1 : -1);
-        const int2 k2 = make_int2(rec ? h2 : -1, rec ? s2 : -1);
-        h0 = rec ? p * 3 : h0;
-        h1 = rec ? p * 3 + 1 : h1;
-        h2 = rec ? p * 3 + 2 : h2;
-        if (real) {
+        const int code = x.gp[par][lane & (SSW_ALIGN_MAX_WAVES - 1)];
+        const int pos = x.os63[par][wpv], poh = x.oh63[par][wpv];
+        const int cin = carry_into_word(code, w, SSW_ALIGN_MAX_WAVES);
+        hmm_enter(hm, phn.real && phone_entered(k, cin, lane), nf, pos, poh);
+        int2 k0, k1, k2;
+        record_transitions(hm, phn.p, t, k0, k1, k2);
+        if (phn.real) {
             tkrow[0] = k0;
             tkrow[1] = k1;
             tkrow[2] = k2;
@@ -819,9 +544,9 @@ viterbi_align_mw_kernel(AlignParams P)
     }
 
     /* state_align_search_finish (state_align_search.c:215-268) */
-    if (p == NP - 1) {
-        x_fin[0] = oh;
-        x_fin[1] = os;
+    if (phn.p == NP - 1) {
+        x_fin[0] = hm.oh;
+        x_fin[1] = hm.os;
     }
     /* the token stack is read back by this workgroup only: workgroup-scope ordering (an
      * agent-scope fence would write back and invalidate the XCD's L2 under the other
@@ -867,11 +592,9 @@ viterbi_align_mw_kernel(AlignParams P)
 __global__ void __launch_bounds__(64 * SSW_ALIGN_MAX_WAVES)
 viterbi_align_mwb_kernel(AlignParams P)
 {
-    __shared__ __attribute__((aligned(16))) int x_bs[2][SSW_ALIGN_MAX_WAVES];
-    __shared__ int x_fr0[2][SSW_ALIGN_MAX_WAVES], x_s00[2][SSW_ALIGN_MAX_WAVES],
-        x_os63[2][SSW_ALIGN_MAX_WAVES], x_oh63[2][SSW_ALIGN_MAX_WAVES],
-        x_fresh63[2][SSW_ALIGN_MAX_WAVES];
-    __shared__ int x_gp[2][SSW_ALIGN_MAX_WAVES];
+    __shared__ AlignExchange x;
+    /* beside os63 / oh63: was that exit score computed in this frame? */
+    __shared__ int x_fresh63[2][SSW_ALIGN_MAX_WAVES];
     __shared__ int x_fin[2], x_irr;
     __shared__ __attribute__((aligned(16))) uint8_t s_tile[64 * 128]; /* backtrace: 64 frames x 128 phones */
     const int u = blockIdx.x;
@@ -880,9 +603,6 @@ viterbi_align_mwb_kernel(AlignParams P)
     const int nw = blockDim.x >> 6;
     const AlignUtt U = P.utts[u];
     const int NP = U.n_phones;
-    const int p = w * 64 + lane;
-    const bool real = p < NP;
-    const int gp = U.phone_off + (real ? p : 0);
     const int W = SSW_WORST_SCORE;
     const int n_frames = U.n_frames;
     /* the utterance's byte tokens, renormalisation amounts and path (AlignParams::btok) */
@@ -891,147 +611,64 @@ viterbi_align_mwb_kernel(AlignParams P)
     int *norm_a = reinterpret_cast<int *>(tb + (((size_t)n_frames * tstride + 255) & ~(size_t)255));
     uint16_t *qpath = reinterpret_cast<uint16_t *>(norm_a + n_frames);
 
-    int s0 = W, s1 = W, s2 = W, os = W;
-    int h0 = -1, h1 = -1, h2 = -1, oh = -1, fr = -1; /* hmm_clear, src/hmm.c:124-140 */
-    const uint32_t *tp = reinterpret_cast<const uint32_t *>(P.tp) + (size_t)P.tmatid[gp] * 3;
-    const uint32_t tpa = real ? tp[0] : 0u, tpb = real ? tp[1] : 0u, tpc = real ? tp[2] : 0u;
-    const int sid01 = real ? ((int)P.senid[gp * 3] | ((int)P.senid[gp * 3 + 1] << 16)) : 0;
-    const int sid2 = real ? (int)P.senid[gp * 3 + 2] : 0;
-    const int ef = real ? P.ef[gp] : INT_MAX;
-    const int sf_next = (p + 1 < NP) ? P.sf[gp + 1] : INT_MAX;
-    const int last = n_frames - 1;
-    /* score fetches as in viterbi_align_mw_kernel: the aligned dword that holds the 16-bit score,
-     * requested two frames ahead, extracted behind an asm pin */
-    const char *scr0 = reinterpret_cast<const char *>(P.senscr);
-    const uint32_t scr_lo = (uint32_t)(reinterpret_cast<uintptr_t>(scr0) & 3);
-    auto row_off = [&](int t) {
-        return (size_t)(U.scr_off + (long long)(t < last ? t : last) * U.scr_stride) * 2;
-    };
-    auto fetch = [&](int t, uint32_t &v0, uint32_t &v1, uint32_t &v2) {
-        const size_t ro = row_off(t);
-        const uint32_t lo = (scr_lo + (uint32_t)ro) & 3u;
-        const char *base = scr0 + ro - lo; /* 4-byte aligned */
-        v0 = *reinterpret_cast<const uint32_t *>(base + ((2u * (sid01 & 0xffff) + lo) & ~3u));
-        v1 = *reinterpret_cast<const uint32_t *>(base + ((2u * ((sid01 >> 16) & 0xffff) + lo) & ~3u));
-        v2 = *reinterpret_cast<const uint32_t *>(base + ((2u * (uint32_t)sid2 + lo) & ~3u));
-    };
-    auto half_of = [&](int t, int sid) {
-        const uint32_t lo = (scr_lo + (uint32_t)row_off(t)) & 3u;
-        return ((2u * (uint32_t)sid + lo) & 2u) * 8u;
-    };
+    const AlignPhone phn =
+        align_phone_load(w * 64 + lane, NP, U.phone_off, P.tp, P.tmatid, P.senid, P.sf, P.ef);
+    const ScoreAhead sa = {P.senscr, U.scr_off, U.scr_stride, n_frames - 1};
+    AlignHmm hm;
+    hmm_clear(hm);
     uint32_t a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0, c0 = 0, c1 = 0, c2 = 0;
     if (n_frames > 0) {
-        fetch(0, a0, a1, a2);
-        fetch(1, b0, b1, b2);
+        score_fetch(sa, phn, 0, a0, a1, a2);
+        score_fetch(sa, phn, 1, b0, b1, b2);
     }
-    if (p == 0) { /* state_align_search_start: hmm_enter(hmms, 0, 0, 0) */
-        s0 = 0;
-        h0 = 0;
-        fr = 0;
-    }
-    if (threadIdx.x < 2 * SSW_ALIGN_MAX_WAVES) {
-        x_bs[0][threadIdx.x] = W; /* [0][16 ..] is [1][..] */
-        x_gp[0][threadIdx.x] = 0;
-    }
+    align_search_start(hm, phn.p);
+    exchange_init(x);
     if (threadIdx.x == 0)
         x_irr = 0;
     __syncthreads();
     int best_score = 0;
     bool irr = false; /* this lane saw something the replay cannot follow */
-    uint8_t *tkrow = tb + p; /* p < tstride always: lanes without a phone write "no token" */
+    uint8_t *tkrow = tb + phn.p; /* p < tstride always: lanes without a phone write "no token" */
     auto frame = [&](const int t, uint32_t raw0, uint32_t raw1, uint32_t raw2, uint32_t &fut0,
                      uint32_t &fut1, uint32_t &fut2) {
         const int nf = t + 1, par = t & 1;
-        fetch(t + 2, fut0, fut1, fut2);
-        asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2));
-        const int cur0 = (int)(short)(raw0 >> half_of(t, sid01 & 0xffff));
-        const int cur1 = (int)(short)(raw1 >> half_of(t, (sid01 >> 16) & 0xffff));
-        const int cur2 = (int)(short)(raw2 >> half_of(t, sid2));
-        /* renormalize_hmms (hmm_normalize, src/hmm.c:150-161); the amount goes on record */
-        const bool renorm = (best_score - 0x300000) < W;
+        int n0, n1, n2;
+        score_step(sa, phn, t, raw0, raw1, raw2, fut0, fut1, fut2, n0, n1, n2);
+        /* the amount goes on record */
+        const int amount = renormalize_hmm(hm, best_score);
         if (threadIdx.x == 0)
-            norm_a[t] = renorm ? best_score : 0;
-        s0 = (renorm && s0 > W) ? s0 - best_score : s0;
-        s1 = (renorm && s1 > W) ? s1 - best_score : s1;
-        s2 = (renorm && s2 > W) ? s2 - best_score : s2;
-        os = (renorm && os > W) ? os - best_score : os;
-        const bool active = fr >= t;
-        int e0 = s0, e1 = s1, e2 = s2, g0 = h0, g1 = h1, g2 = h2, eos = os, eoh = oh;
+            norm_a[t] = amount;
+        const bool active = hm.fr >= t;
         bool a1_live, quirk;
-        const int b = vit_eval_3st(e0, e1, e2, g0, g1, g2, eos, eoh, -cur0, -cur1, -cur2, tpa, tpb,
-                                   tpc, &a1_live, &quirk);
+        const int b = evaluate_hmm(hm, phn, t, n0, n1, n2, &a1_live, &quirk);
         irr = irr || (active && quirk);                         /* (3) */
         const bool fresh = active && a1_live; /* this frame's exit score is this frame's */
-        s0 = active ? e0 : s0;
-        s1 = active ? e1 : s1;
-        s2 = active ? e2 : s2;
-        h1 = active ? g1 : h1;
-        h2 = active ? g2 : h2;
-        os = active ? eos : os;
-        oh = active ? eoh : oh;
-        fr = (active && nf <= ef) ? nf : fr;
-        int bs = wave_max_dpp(active ? b : W);
-        if (lane == 0) {
-            x_bs[par][w] = bs;
-            x_fr0[par][w] = fr;
-            x_s00[par][w] = s0;
-        }
-        if (lane == 63) {
-            x_os63[par][w] = os;
-            x_oh63[par][w] = oh;
+        exchange_publish(x, par, w, lane, b, hm);
+        if (lane == 63)
             x_fresh63[par][w] = fresh ? 1 : 0;
-        }
         lds_barrier();
-        const int wnx = w + 1 < nw ? w + 1 : w;
-        const int4 *bq = reinterpret_cast<const int4 *>(x_bs[par]);
-        const int4 q0 = bq[0], q1 = bq[1], q2 = bq[2], q3 = bq[3];
-        const int efr_ = x_fr0[par][wnx], es0_ = x_s00[par][wnx];
-        best_score = max3_i32(max3_i32(max3_i32(q0.x, q0.y, q0.z), max3_i32(q0.w, q1.x, q1.y),
-                                       max3_i32(q1.z, q1.w, q2.x)),
-                              max3_i32(max3_i32(q2.y, q2.z, q2.w), max3_i32(q3.x, q3.y, q3.z), q3.w),
-                              W);
-        const int efr = w + 1 < nw ? efr_ : -1;
-        const int es0 = w + 1 < nw ? es0_ : 0;
-        const int nfr = lane_from_next(fr, efr);
-        const int ns0 = lane_from_next(s0, es0);
-        const bool a_bit = fr == nf;
-        const bool c_bit = p + 1 < NP && nf >= sf_next && (nfr < t || os > ns0);
-        const unsigned long long Am = __ballot(a_bit), Cm = __ballot(c_bit);
-        const unsigned long long X = Cm, Y = Am & Cm;
-        const unsigned long long S0 = X + Y, S1 = S0 + 1ull;
-        const int g_out = (int)(((X & Y) | ((X | Y) & ~S0)) >> 63);
-        const int c1_out = (int)(((X & Y) | ((X | Y) & ~S1)) >> 63);
+        const bool has_next = w + 1 < nw;
+        const int wnx = has_next ? w + 1 : w;
+        const int efr = x.fr0[par][wnx], es0 = x.s00[par][wnx];
+        best_score = exchange_best_score(x, par);
+        const AlignCarry k = phone_transition(hm, phn, NP, has_next ? efr : -1, es0, t);
         if (lane == 0)
-            x_gp[par][w] = g_out | ((c1_out & ~g_out) << 1);
+            x.gp[par][w] = k.code;
         lds_barrier();
         const int wpv = w > 0 ? w - 1 : 0;
-        const int gpv = x_gp[par][lane & (SSW_ALIGN_MAX_WAVES - 1)];
-        const int pos_ = x_os63[par][wpv], poh_ = x_oh63[par][wpv], pfr_ = x_fresh63[par][wpv];
-        const unsigned long long Gm = __ballot(gpv & 1) & 0xffffull, Pm = __ballot(gpv & 2) & 0xffffull;
-        const unsigned long long XX = Gm | Pm;
-        const unsigned long long carries = (XX + Gm) ^ XX ^ Gm;
-        const unsigned long long cin = (carries >> w) & 1ull;
-        const unsigned long long E = (X + Y + cin) ^ X ^ Y;
-        const bool entered = real && ((E >> lane) & 1ull);
-        const int src_os = lane_from_prev(os, w > 0 ? pos_ : 0);
-        const int src_oh = lane_from_prev(oh, w > 0 ? poh_ : 0);
-        const int src_fresh = lane_from_prev(fresh ? 1 : 0, w > 0 ? pfr_ : 0);
-        irr = irr || (entered && src_fresh == 0 && src_oh != -1);   /* (1) */
-        irr = irr || (entered && !active && (s1 > W || s2 > W));     /* (2) */
-        s0 = entered ? src_os : s0;
-        h0 = entered ? src_oh : h0;
-        fr = entered ? nf : fr;
-        const bool rec = fr >= t;
-        /* record_transitions as three 2-bit back-pointers: own id - history (0, 1, 2), 3 = none */
-        const int id0 = p * 3;
-        const uint32_t d0 = (rec && h0 >= 0) ? (uint32_t)(id0 - h0) : 3u;
-        const uint32_t d1 = (rec && h1 >= 0) ? (uint32_t)(id0 + 1 - h1) : 3u;
-        const uint32_t d2 = (rec && h2 >= 0) ? (uint32_t)(id0 + 2 - h2) : 3u;
-        irr = irr || (rec && ((h0 >= 0 && d0 > 2u) || (h1 >= 0 && d1 > 2u) || (h2 >= 0 && d2 > 2u)));
-        h0 = rec ? id0 : h0;
-        h1 = rec ? id0 + 1 : h1;
-        h2 = rec ? id0 + 2 : h2;
-        tkrow[0] = (uint8_t)((d0 & 3u) | (d1 & 3u) << 2 | (d2 & 3u) << 4);
+        const int code = x.gp[par][lane & (SSW_ALIGN_MAX_WAVES - 1)];
+        const int pos = x.os63[par][wpv], poh = x.oh63[par][wpv], pfr = x_fresh63[par][wpv];
+        const int cin = carry_into_word(code, w, SSW_ALIGN_MAX_WAVES);
+        const bool entered = phn.real && phone_entered(k, cin, lane);
+        const int src_fresh = lane_from_prev(fresh ? 1 : 0, pfr);
+        irr = irr || (entered && !active && (hm.s1 > W || hm.s2 > W)); /* (2) */
+        hmm_enter(hm, entered, nf, pos, poh);
+        /* (1); h0 is the history it entered with */
+        irr = irr || (entered && src_fresh == 0 && hm.h0 != -1);
+        uint8_t token;
+        const bool two_bits = record_transitions_2bit(hm, phn.p, t, token);
+        irr = irr || !two_bits;
+        tkrow[0] = token;
         tkrow += tstride;
     };
     for (int t = 0; t < n_frames; t += 3) { /* the same trip count in every wave: barriers */
@@ -1043,9 +680,9 @@ viterbi_align_mwb_kernel(AlignParams P)
     }
 
     /* state_align_search_finish (state_align_search.c:215-268) */
-    if (p == NP - 1) {
-        x_fin[0] = oh;
-        x_fin[1] = os;
+    if (phn.p == NP - 1) {
+        x_fin[0] = hm.oh;
+        x_fin[1] = hm.os;
     }
     if (__ballot(irr) != 0ull && lane == 0)
         atomicOr(&x_irr, 1);
@@ -1202,10 +839,9 @@ viterbi_align_mwb_kernel(AlignParams P)
 __global__ void __launch_bounds__(64 * SSW_ALIGN_MAX_WAVES)
 viterbi_align_win_kernel(AlignParams P)
 {
-    __shared__ __attribute__((aligned(16))) int x_bs[2][SSW_ALIGN_MAX_WAVES];
-    __shared__ int x_fr0[2][SSW_ALIGN_MAX_WAVES], x_s00[2][SSW_ALIGN_MAX_WAVES],
-        x_os63[2][SSW_ALIGN_MAX_WAVES], x_oh63[2][SSW_ALIGN_MAX_WAVES],
-        x_gp[2][SSW_ALIGN_MAX_WAVES], x_act[2][SSW_ALIGN_MAX_WAVES];
+    __shared__ AlignExchange x;
+    /* beside bs: has the wave's block an active phone? */
+    __shared__ int x_act[2][SSW_ALIGN_MAX_WAVES];
     __shared__ int x_fin[2], x_ovf[2];
     const int u = blockIdx.x;
     const int lane = threadIdx.x & 63;
@@ -1217,61 +853,26 @@ viterbi_align_win_kernel(AlignParams P)
     const int NB = (NP + 63) >> 6;
     const int W = SSW_WORST_SCORE;
     int g = w, glo = 0; /* this wave's block; the window's first block */
-    int p = 0, sid01 = 0, sid2 = 0, ef = INT_MAX, sf_next = INT_MAX;
-    bool real = false;
-    uint32_t tpa = 0, tpb = 0, tpc = 0;
-    int s0 = W, s1 = W, s2 = W, os = W, h0 = -1, h1 = -1, h2 = -1, oh = -1, fr = -1;
+    AlignPhone phn;
+    AlignHmm hm;
     auto load_block = [&](int gb) { /* the block's phones: constants in, hmm_clear */
-        p = gb * 64 + lane;
-        real = p < NP;
-        const int gp = U.phone_off + (real ? p : 0);
-        const uint32_t *tp = reinterpret_cast<const uint32_t *>(P.tp) + (size_t)P.tmatid[gp] * 3;
-        tpa = real ? tp[0] : 0u;
-        tpb = real ? tp[1] : 0u;
-        tpc = real ? tp[2] : 0u;
-        sid01 = real ? ((int)P.senid[gp * 3] | ((int)P.senid[gp * 3 + 1] << 16)) : 0;
-        sid2 = real ? (int)P.senid[gp * 3 + 2] : 0;
-        ef = real ? P.ef[gp] : INT_MAX;
-        sf_next = (p + 1 < NP) ? P.sf[gp + 1] : INT_MAX;
-        s0 = s1 = s2 = os = W;
-        h0 = h1 = h2 = oh = fr = -1;
+        phn = align_phone_load(gb * 64 + lane, NP, U.phone_off, P.tp, P.tmatid, P.senid, P.sf, P.ef);
+        hmm_clear(hm);
     };
     load_block(g);
-    const int last = U.n_frames - 1;
-    const char *scr0 = reinterpret_cast<const char *>(P.senscr);
-    const uint32_t scr_lo = (uint32_t)(reinterpret_cast<uintptr_t>(scr0) & 3);
-    auto row_off = [&](int t) {
-        return (size_t)(U.scr_off + (long long)(t < last ? t : last) * U.scr_stride) * 2;
-    };
-    auto fetch = [&](int t, uint32_t &v0, uint32_t &v1, uint32_t &v2) { /* as in the kernel above */
-        const size_t ro = row_off(t);
-        const uint32_t lo = (scr_lo + (uint32_t)ro) & 3u;
-        const char *base = scr0 + ro - lo;
-        v0 = *reinterpret_cast<const uint32_t *>(base + ((2u * (sid01 & 0xffff) + lo) & ~3u));
-        v1 = *reinterpret_cast<const uint32_t *>(base + ((2u * ((sid01 >> 16) & 0xffff) + lo) & ~3u));
-        v2 = *reinterpret_cast<const uint32_t *>(base + ((2u * (uint32_t)sid2 + lo) & ~3u));
-    };
-    auto half_of = [&](int t, int sid) {
-        const uint32_t lo = (scr_lo + (uint32_t)row_off(t)) & 3u;
-        return ((2u * (uint32_t)sid + lo) & 2u) * 8u;
-    };
+    const ScoreAhead sa = {P.senscr, U.scr_off, U.scr_stride, U.n_frames - 1};
     uint32_t a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0, c0 = 0, c1 = 0, c2 = 0;
     if (U.n_frames > 0) {
-        fetch(0, a0, a1, a2);
-        fetch(1, b0, b1, b2);
+        score_fetch(sa, phn, 0, a0, a1, a2);
+        score_fetch(sa, phn, 1, b0, b1, b2);
     }
-    if (p == 0) { /* state_align_search_start: hmm_enter(hmms, 0, 0, 0) */
-        s0 = 0;
-        h0 = 0;
-        fr = 0;
-    }
+    align_search_start(hm, phn.p);
     if (threadIdx.x == 0) {
         x_fin[0] = -1;
         x_fin[1] = W;
         x_ovf[0] = x_ovf[1] = 0;
     }
-    if (threadIdx.x < 2 * SSW_ALIGN_MAX_WAVES)
-        x_bs[0][threadIdx.x] = W; /* all 16 slots are read; [0][16 ..] is [1][..] */
+    exchange_init(x);
     int2 *tok = P.tokens + U.tok_off;
     int *TB = P.band_ws + 2 * (size_t)U.frame_off + 2 * (size_t)u;
     int *TL = TB + U.n_frames + 1;
@@ -1285,54 +886,23 @@ viterbi_align_win_kernel(AlignParams P)
     auto frame = [&](const int t, uint32_t raw0, uint32_t raw1, uint32_t raw2, uint32_t &nx0,
                      uint32_t &nx1, uint32_t &nx2, uint32_t &fut0, uint32_t &fut1, uint32_t &fut2) {
         const int nf = t + 1, par = t & 1;
-        fetch(t + 2, fut0, fut1, fut2);
-        asm volatile("" : "+v"(raw0), "+v"(raw1), "+v"(raw2));
-        const int cur0 = (int)(short)(raw0 >> half_of(t, sid01 & 0xffff));
-        const int cur1 = (int)(short)(raw1 >> half_of(t, (sid01 >> 16) & 0xffff));
-        const int cur2 = (int)(short)(raw2 >> half_of(t, sid2));
-        const bool renorm = (best_score - 0x300000) < W;
-        s0 = (renorm && s0 > W) ? s0 - best_score : s0;
-        s1 = (renorm && s1 > W) ? s1 - best_score : s1;
-        s2 = (renorm && s2 > W) ? s2 - best_score : s2;
-        os = (renorm && os > W) ? os - best_score : os;
-        const bool active = fr >= t;
-        int e0 = s0, e1 = s1, e2 = s2, g0 = h0, g1 = h1, g2 = h2, eos = os, eoh = oh;
-        const int b = vit_eval_3st(e0, e1, e2, g0, g1, g2, eos, eoh, -cur0, -cur1, -cur2, tpa, tpb,
-                                   tpc);
-        s0 = active ? e0 : s0;
-        s1 = active ? e1 : s1;
-        s2 = active ? e2 : s2;
-        h1 = active ? g1 : h1;
-        h2 = active ? g2 : h2;
-        os = active ? eos : os;
-        oh = active ? eoh : oh;
-        fr = (active && nf <= ef) ? nf : fr;
-        int bs = wave_max_dpp(active ? b : W);
-        const bool any_active = __ballot(active) != 0ull;
-        if (lane == 0) {
-            x_bs[par][w] = bs;
-            x_fr0[par][w] = fr;
-            x_s00[par][w] = s0;
+        int n0, n1, n2;
+        score_step(sa, phn, t, raw0, raw1, raw2, fut0, fut1, fut2, n0, n1, n2);
+        renormalize_hmm(hm, best_score);
+        const bool any_active = __ballot(hm.fr >= t) != 0ull;
+        const int b = evaluate_hmm(hm, phn, t, n0, n1, n2);
+        exchange_publish(x, par, w, lane, b, hm);
+        if (lane == 0)
             x_act[par][w] = any_active ? 1 : 0;
-        }
-        if (lane == 63) {
-            x_os63[par][w] = os;
-            x_oh63[par][w] = oh;
-        }
         lds_barrier();
         /* window order: position k is block glo + k, held by wave (k + r) % nw.  Everything the
          * barrier published is requested at once */
         const int r = glo & nwm;
         const int wk = (lane + r) & nwm;
         const int wn = (w + 1) & nwm, wp = (w - 1) & nwm;
-        const int4 *bq = reinterpret_cast<const int4 *>(x_bs[par]);
-        const int4 q0 = bq[0], q1 = bq[1], q2 = bq[2], q3 = bq[3];
         const int act_ = x_act[par][wk];
-        const int efr_ = x_fr0[par][wn], es0_ = x_s00[par][wn];
-        best_score = max3_i32(max3_i32(max3_i32(q0.x, q0.y, q0.z), max3_i32(q0.w, q1.x, q1.y),
-                                       max3_i32(q1.z, q1.w, q2.x)),
-                              max3_i32(max3_i32(q2.y, q2.z, q2.w), max3_i32(q3.x, q3.y, q3.z), q3.w),
-                              W);
+        const int efr = x.fr0[par][wn], es0 = x.s00[par][wn];
+        best_score = exchange_best_score(x, par);
         const unsigned long long M = __ballot(act_ != 0) & ((1ull << nw) - 1ull);
         const int kpos = (w - r) & nwm;
         const int kmin = M ? __builtin_ctzll(M) : 0;
@@ -1349,50 +919,25 @@ viterbi_align_win_kernel(AlignParams P)
         if (tbase + (long long)nblk * 192 > tcap)
             ovf = true;
 
-        /* phone_transition: A / C masks of this block */
         const bool has_next = kpos + 1 < nw; /* else: a block beyond the window, never entered */
-        const int efr = has_next ? efr_ : -1;
-        const int es0 = has_next ? es0_ : W;
-        const int nfr = lane_from_next(fr, efr);
-        const int ns0 = lane_from_next(s0, es0);
-        const bool a_bit = fr == nf;
-        const bool c_bit = p + 1 < NP && nf >= sf_next && (nfr < t || os > ns0);
-        const unsigned long long Am = __ballot(a_bit), Cm = __ballot(c_bit);
-        const unsigned long long X = Cm, Y = Am & Cm;
-        const unsigned long long S0 = X + Y, S1 = S0 + 1ull;
-        const int g_out = (int)(((X & Y) | ((X | Y) & ~S0)) >> 63);
-        const int c1_out = (int)(((X & Y) | ((X | Y) & ~S1)) >> 63);
+        const AlignCarry k = phone_transition(hm, phn, NP, has_next ? efr : -1, es0, t);
         if (lane == 0)
-            x_gp[par][w] = g_out | ((c1_out & ~g_out) << 1);
+            x.gp[par][w] = k.code;
         lds_barrier();
-        const int gpv = x_gp[par][wk];
-        const int pos_ = x_os63[par][wp], poh_ = x_oh63[par][wp];
-        const unsigned long long lowm = (1ull << nw) - 1ull;
-        const unsigned long long Gm = __ballot(gpv & 1) & lowm, Pm = __ballot(gpv & 2) & lowm;
-        const unsigned long long XX = Gm | Pm;
-        const unsigned long long carries = (XX + Gm) ^ XX ^ Gm;
-        const unsigned long long cin = kpos > 0 ? (carries >> kpos) & 1ull : 0ull;
-        const unsigned long long Ssum = X + Y + cin;
-        const unsigned long long E = Ssum ^ X ^ Y;
-        const bool entered = real && ((E >> lane) & 1ull);
+        const int code = x.gp[par][wk];
+        const int pos = x.os63[par][wp], poh = x.oh63[par][wp];
+        const int cin = carry_into_word(code, kpos, nw);
+        int c_out;
+        const bool e_bit = phone_entered(k, cin, lane, &c_out);
+        const bool entered = phn.real && e_bit;
         /* a transition out of the window's last block, or into a block beyond the token band */
-        const int c_out = (int)(((X & Y) | ((X | Y) & ~Ssum)) >> 63);
         if ((kpos == nw - 1 && c_out && g + 1 < NB) || (kpos > kend && __ballot(entered) != 0ull))
             ovf = true;
-        const int src_os = lane_from_prev(os, kpos > 0 ? pos_ : 0);
-        const int src_oh = lane_from_prev(oh, kpos > 0 ? poh_ : 0);
-        s0 = entered ? src_os : s0;
-        h0 = entered ? src_oh : h0;
-        fr = entered ? nf : fr;
-        const bool rec = fr >= t;
-        const int2 k0 = make_int2(rec ? h0 : -1, rec ? s0 : -1);
-        const int2 k1 = make_int2(rec ? h1 : -1, rec ? s1 : -1);
-        const int2 k2 = make_int2(rec ? h2 : -1, rec ? s2 : -1);
-        h0 = rec ? p * 3 : h0;
-        h1 = rec ? p * 3 + 1 : h1;
-        h2 = rec ? p * 3 + 2 : h2;
+        hmm_enter(hm, entered, nf, pos, poh);
+        int2 k0, k1, k2;
+        record_transitions(hm, phn.p, t, k0, k1, k2);
         const bool in_band = M != 0ull && kpos >= kmin && kpos <= kend;
-        if (real && in_band && !ovf) {
+        if (phn.real && in_band && !ovf) {
             int2 *tkrow = tok + tbase + (long long)(kpos - kmin) * 192 + lane * 3;
             tkrow[0] = k0;
             tkrow[1] = k1;
@@ -1411,8 +956,8 @@ viterbi_align_win_kernel(AlignParams P)
             if (kpos < kmin) {
                 g += nw;
                 load_block(g);
-                fetch(t + 1, nx0, nx1, nx2);
-                fetch(t + 2, fut0, fut1, fut2);
+                score_fetch(sa, phn, t + 1, nx0, nx1, nx2);
+                score_fetch(sa, phn, t + 2, fut0, fut1, fut2);
             }
         }
     };
@@ -1430,8 +975,8 @@ viterbi_align_win_kernel(AlignParams P)
             break;
     }
     if (g == NB - 1 && lane == ((NP - 1) & 63)) {
-        x_fin[0] = oh;
-        x_fin[1] = os;
+        x_fin[0] = hm.oh;
+        x_fin[1] = hm.os;
     }
     if (threadIdx.x == 0)
         TB[U.n_frames] = (int)tbase; /* end of the last frame's row (a global store, read back by

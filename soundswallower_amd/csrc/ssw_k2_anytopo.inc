@@ -226,7 +226,7 @@ viterbi_align_any_kernel(AlignParams P, int ne)
     for (int t = 0; t < U.n_frames; ++t) {
         const int16_t *row = P.senscr + U.scr_off + (long long)t * U.scr_stride;
         const int nf = t + 1;
-        const bool renorm = (best_score - 0x300000) < SSW_WORST_SCORE;
+        const bool renorm = align_renorm_due(best_score);
         int bs = SSW_WORST_SCORE;
         /* renormalize_hmms + evaluate_hmms + prune_hmms (state_align_search.c:57-106) */
         for (int w = 0; w < W; ++w) {

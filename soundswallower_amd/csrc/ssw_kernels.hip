@@ -21,9 +21,14 @@
  *   ssw_k1b_senone.inc   ptm_senone_kernel (codebook_norm + senone_eval, src/ptm_mgau.c:264-403),
  *                        ptm_senone_frame_kernel (one frame, active sets), ms_senone_kernel
  *   ssw_k4_feat.inc      feat_1s_c_d_dd_kernel (batch CMN + 1s_c_d_dd, src/feat.c:271-326)
- *   ssw_k2_align.inc     viterbi_align_mw_kernel / _reg_kernel / viterbi_align_kernel
- *                        (state_align_search step/finish + hmm_vit_eval_3st_lr,
- *                        src/state_align_search.c:177-268, src/hmm.c:482-567)
+ *   ssw_align_common.inc the frame step that the 3-state alignment kernels with their HMMs in
+ *                        registers share, once (hmm_vit_eval_3st_lr, a lane's constants and HMM,
+ *                        score look-ahead, renormalisation, evaluate-and-keep, the waves' exchange
+ *                        slots, phone_transition as a carry chain, hmm_enter, record_transitions),
+ *                        src/state_align_search.c:57-175, src/hmm.c:124-161, :482-567
+ *   ssw_k2_align.inc     viterbi_align_mw_kernel / _mwb_kernel / _win_kernel / _reg_kernel /
+ *                        viterbi_align_kernel (state_align_search step/finish,
+ *                        src/state_align_search.c:177-268): tokens, replay, window, LDS / HBM state
  *   ssw_k2_anytopo.inc   viterbi_align_any_kernel: the same search over HMMs of 1, 2, 4 or 5 states
  *                        (hmm_vit_eval_5st_lr, hmm_vit_eval_anytopo, src/hmm.c:166-304, :671-739)
  *   ssw_search_common.inc the decisions of the reference's fsg_search that the three K5 kernels
@@ -95,6 +100,7 @@ namespace {
 #include "ssw_k1a_mfma.inc"
 #include "ssw_k1b_senone.inc"
 #include "ssw_k4_feat.inc"
+#include "ssw_align_common.inc"
 #include "ssw_k2_align.inc"
 #include "ssw_k2_anytopo.inc"
 #include "ssw_search_common.inc"

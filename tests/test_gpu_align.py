@@ -391,3 +391,48 @@ def test_byte_token_kernel_hands_on_what_it_cannot_replay(gpu_en, orc_en):
     print("handed on to the full-token kernel: %d of %d (aligned: %d)"
           % (after[1] - mid[1], n_utts, seen_ok))
     assert after[1] > mid[1], "the windows were meant to make some utterances irregular"
+
+
+def test_renormalisation_across_waves_in_every_3state_kernel(gpu_en, orc_en, monkeypatch):
+    """hmm_normalize (src/hmm.c:150-161) on an utterance of several 64-phone words: 200 phones
+    over 17,500 frames of scores near 31,500, so that the path score falls below WORST + 0x300000
+    once, late in the utterance (the oracle renormalises near frame 16,974 with phone windows and
+    16,994 without; 94 and 114 distinct state durations: the paths are not degenerate).  The
+    amount passes through the exchange slots of four waves and the byte-token kernel's recorded
+    amount is replayed on a real path.  The sliding-window kernel (two waves over four blocks)
+    renormalises, with windows, in blocks it took over when it slid, the last of them near frame
+    11,000: none is reloaded after the renormalisation.  Without windows every block stays active,
+    its window overflows and the call falls back to the LDS kernel: that case checks the fall-back,
+    not the window kernel.  Every mode, with and without windows, must give the oracle's status
+    and entries."""
+    n_phones, n_frames = 200, 17500
+    senid, tmat, _ = synth_alignment_task(orc_en.sseq, orc_en.phone_ssid, orc_en.phone_tmat,
+                                          orc_en.n_ciphone, n_phones, 77)
+    scr = (31000 + np.random.default_rng(2026).integers(0, 1000, size=(n_frames, orc_en.n_sen))
+           ).astype(np.int16)
+    mid = (np.arange(n_phones) * n_frames) // n_phones
+    sf = np.maximum(mid - 6, 0).astype(np.int32)
+    ef = np.minimum(mid + n_frames // n_phones + 8, n_frames).astype(np.int32)
+    cases = {"windows": dict(sf=sf, ef=ef), "no windows": {}}
+    ref = {}
+    for name, kw in cases.items():
+        rv, rst, _, trace = orc_en.state_align(scr, senid, tmat, want_trace=True, **kw)
+        assert rv == 0, name
+        assert trace.min() - 0x300000 < -536870912, "test must actually reach the renormalisation"
+        ref[name] = rst
+    monkeypatch.setenv("SSW_ALIGN_WIN_WAVES", "2")
+    d = gpu_en.to_device(scr)
+    try:
+        for mode in ("mw", "mwb", "reg", "lds", "win"):
+            monkeypatch.setenv("SSW_ALIGN_KERNEL", mode)
+            before = gpu_en.align_stats()
+            for name, kw in cases.items():
+                st, status = gpu_en.align_batch(d, [0, n_frames], [0, n_phones], senid, tmat, **kw)
+                assert status[0] == 0, (mode, name)
+                assert np.array_equal(st, ref[name]), (mode, name)
+            if mode == "mwb":
+                after = gpu_en.align_stats()
+                print("handed on to the full-token kernel: %d of %d"
+                      % (after[1] - before[1], after[0] - before[0]))
+    finally:
+        gpu_en.device_free(d)
