@@ -169,7 +169,13 @@ int ssw_score_batch(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_
  *              acmod_rewind (with SSW_SCORE_CARRY_UTTS the batch's utterances are walked back to
  *              the last one with two frames; without it only the last utterance counts; if no
  *              frame wrote the slot, carry_in / the reset order comes back).
- * The ms scorer keeps no history: the three are ignored for it. */
+ *              Frame down-sampling (ssw_config_t.ds > 1): the call has no argument for the frame
+ *              number its first frame has within the utterance -- every utterance of a call is
+ *              numbered from 0, and with it the frames a codebook is re-scanned on (frame % ds ==
+ *              0, src/ptm_mgau.c:241).  A call that CONTINUES an utterance is therefore only the
+ *              reference's scoring when the calls before it end after a multiple of lcm(2, ds)
+ *              frames of that utterance (2: the parity above; ds: the phase).
+ * The ms scorer keeps no history and reads no ds: the three are ignored for it. */
 #define SSW_SCORE_CARRY_UTTS 1u
 /* the caller runs kernels of ANOTHER stream beside this call (the alignment of the previous
  * chunk beside the scoring of the next, section "Multi-GPU" / soundswallower_amd/jobs.py): the
@@ -185,7 +191,9 @@ int ssw_score_batch_ex(ssw_model_t *m, int scorer, const float *d_feats, int32_t
  * utterance.  An utterance of more than 16,384 frames (SSW_HOST_PIPE_CAP) is scored in pieces
  * of that many that hand the history on, so the staging the model keeps for this call stops at
  * 2 x 16,384 feature rows + score rows pinned on the host and as many on the device (en-us:
- * 2 x 171 MB each), however long the utterances are. */
+ * 2 x 171 MB each), however long the utterances are.  A piece keeps the frame numbers of its
+ * utterance: with ds > 1 it re-scans on the frames the uncut utterance re-scans on, whether or not
+ * ds divides the piece length (the cap is rounded down to even, nothing else). */
 int ssw_score_batch_host(ssw_model_t *m, int scorer, const float *feats, int32_t n_frames,
                          const int32_t *utt_off, int32_t n_utts, int16_t *out);
 /* Debug/parity view of the PTM top-N state after normalisation for every frame of the last

@@ -272,6 +272,11 @@ align_batch_active_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_
         ssw_set_error("ssw_align_batch_active: built for <= 64 codebooks and 3-state HMMs");
         return -1;
     }
+    /* (score_batch_impl's refusal, said here before the plan, the uploads and any launch) */
+    if (h->cfg.ds != 1 || m->force_exact) {
+        ssw_set_error("active-set batches: ds = 1 only");
+        return -1;
+    }
     if (!d_feats || !frame_off || !phone_off || !senid || !tmatid || !sf || !ef || !state_io
         || !status || frame_off[0] != 0 || phone_off[0] != 0) {
         ssw_set_error("ssw_align_batch_active: bad arguments");

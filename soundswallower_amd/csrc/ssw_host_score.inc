@@ -314,7 +314,7 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
                  const int32_t *utt_off, int32_t n_utts, int16_t *d_out, void *stream,
                  uint32_t flags, const uint32_t *carry_in, uint32_t *carry_out,
                  const ActiveSets *act = NULL, const uint32_t *d_carry_rows = NULL,
-                 const ssw_compact_plan_s *cp = NULL);
+                 const ssw_compact_plan_s *cp = NULL, int frame_base = 0);
 
 extern "C" int
 ssw_score_batch(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
@@ -337,7 +337,8 @@ static int
 score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
                  const int32_t *utt_off, int32_t n_utts, int16_t *d_out, void *stream,
                  uint32_t flags, const uint32_t *carry_in, uint32_t *carry_out,
-                 const ActiveSets *act, const uint32_t *d_carry_rows, const ssw_compact_plan_s *cp)
+                 const ActiveSets *act, const uint32_t *d_carry_rows, const ssw_compact_plan_s *cp,
+                 int frame_base)
 {
     ModelBusy busy_(m);
     if (!busy_.ok)
@@ -364,6 +365,10 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
     if (check_scorer_shape(m, scorer) < 0)
         return -1;
     const bool ms = scorer == SSW_SCORER_MS;
+    if (act != NULL && (m->h->cfg.ds != 1 || m->force_exact)) { /* (before anything is launched) */
+        ssw_set_error("active-set batches: ds = 1 only");
+        return -1;
+    }
     HIP_OK(hipSetDevice(m->device));
     /* history carried from utterance to utterance (the reference never resets it after
      * start-up, src/acmod.c:367): the batch is one chain, only its first frame is a start.  The
@@ -457,6 +462,9 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
     P.n_utts = n_utts;
     P.n_frames = n_frames;
     P.chain_utts = chain ? 1 : 0;
+    /* a call that continues an utterance (a piece of ssw_score_batch_host's cut): the in-utterance
+     * number of its frame 0, which decides the frames a ds > 1 model re-scans on */
+    P.frame_base = frame_base;
     P.carry_pk = (carry_in != NULL && !ms) ? m->d_carry0 : NULL;
     if (d_carry_rows != NULL && !ms) /* a row per utterance, already on the device */
         P.carry_pk = d_carry_rows;
@@ -718,10 +726,6 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
     else if (act != NULL) {
         if (cp != NULL) {
             ssw_set_error("internal error: compact rows with an active set");
-            return -1;
-        }
-        if (h->cfg.ds != 1 || m->force_exact) {
-            ssw_set_error("active-set batches: ds = 1 only");
             return -1;
         }
         HIP_OK(launch_active(0, n_frames));
@@ -1013,7 +1017,11 @@ ssw_score_batch_host(ssw_model_t *m, int scorer, const float *feats, int32_t n_f
              * overlap their scoring with the copies -- they are 16 K frames each) */
             const int rc = score_batch_impl(m, scorer, m->d_pipe_feat[slot], nf, off.data(), u1 - u0,
                                             m->d_pipe_out[slot], m->s_pipe, 0u,
-                                            S.cont ? carry.data() : NULL, S.more ? carry.data() : NULL);
+                                            S.cont ? carry.data() : NULL, S.more ? carry.data() : NULL,
+                                            NULL, NULL, NULL,
+                                            /* a continuing piece keeps its utterance's frame
+                                             * numbers (the ds phase); grouped utterances start at 0 */
+                                            S.cont ? f0 - utt_off[u0] : 0);
             m->d_topn_cw = topn_cw0;
             m->d_topn_sc = topn_sc0;
             if (rc < 0)
