@@ -353,30 +353,20 @@ align_batch_active_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_
         ~PlanGuard() { ssw_compact_plan_free(p); }
     } guard_{ plan };
     /* device workspace: segment tables and the compact rows */
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) {
-        size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t o_sof = carve(sizeof(int32_t) * (size_t)std::max(n_frames, 1));
-    const size_t o_su = carve(sizeof(int32_t) * std::max(n_seg, (size_t)1));
-    const size_t o_sn = carve(sizeof(int32_t) * std::max(n_seg, (size_t)1));
-    const size_t o_sb = carve(sizeof(int32_t) * (n_seg + 1));
-    const size_t o_cm = carve(sizeof(unsigned long long) * std::max(n_seg, (size_t)1));
-    const size_t o_uo = carve(sizeof(int32_t) * ((size_t)n_utts + 1));
-    const size_t o_re = carve(sizeof(uint32_t) * std::max(real_ent.size(), (size_t)1));
-    const size_t o_rr = carve(sizeof(uint16_t) * std::max(real_rank.size(), (size_t)1) + 16);
-    const size_t o_be = carve(sizeof(uint32_t) * std::max(bridge_ent.size(), (size_t)1));
-    const size_t o_scr = carve(sizeof(int16_t) * std::max(plan->elems, (size_t)1));
-    if (off > m->act_ws_cap) {
-        (void)hipFree(m->d_act_ws);
-        m->d_act_ws = NULL;
-        m->act_ws_cap = 0;
-        HIP_OK(hipMalloc((void **)&m->d_act_ws, off));
-        m->act_ws_cap = off;
-    }
-    unsigned char *ws = m->d_act_ws;
+    WsLayout L;
+    const size_t o_sof = L.out(sizeof(int32_t) * (size_t)std::max(n_frames, 1));
+    const size_t o_su = L.out(sizeof(int32_t) * std::max(n_seg, (size_t)1));
+    const size_t o_sn = L.out(sizeof(int32_t) * std::max(n_seg, (size_t)1));
+    const size_t o_sb = L.out(sizeof(int32_t) * (n_seg + 1));
+    const size_t o_cm = L.out(sizeof(unsigned long long) * std::max(n_seg, (size_t)1));
+    const size_t o_uo = L.out(sizeof(int32_t) * ((size_t)n_utts + 1));
+    const size_t o_re = L.out(sizeof(uint32_t) * std::max(real_ent.size(), (size_t)1));
+    const size_t o_rr = L.out(sizeof(uint16_t) * std::max(real_rank.size(), (size_t)1) + 16);
+    const size_t o_be = L.out(sizeof(uint32_t) * std::max(bridge_ent.size(), (size_t)1));
+    const size_t o_scr = L.out(sizeof(int16_t) * std::max(plan->elems, (size_t)1));
+    if (devbuf_reserve(m->act_ws, L.size(), "ssw_align_batch_active") < 0)
+        return -1;
+    unsigned char *ws = m->act_ws.p;
     auto up = [&](size_t at, const void *src, size_t bytes) {
         return bytes == 0 ? hipSuccess : hipMemcpyAsync(ws + at, src, bytes, hipMemcpyHostToDevice, st);
     };

@@ -94,45 +94,25 @@ align_batch_any(ssw_model_t *m, const int16_t *d_senscr, int32_t n_utts, const i
         }
     for (int u = 0; u < n_utts; ++u)
         utts[(size_t)u].ws_off = (long long)u * G_COUNT * (max_phones + 1);
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) {
-        size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    WsLayout L;
     const size_t b_state = sizeof(ssw_align_entry_t) * (size_t)ne * total_phones;
-    const size_t o_utts = carve(sizeof(AlignUtt) * n_utts);
-    const size_t o_senid = carve(sizeof(uint16_t) * (size_t)ne * total_phones + 16);
-    const size_t o_tmatid = carve(sizeof(int16_t) * (size_t)total_phones + 16);
-    const size_t o_sf = carve(sizeof(int32_t) * (size_t)total_phones);
-    const size_t o_ef = carve(sizeof(int32_t) * (size_t)total_phones);
-    const size_t o_state = carve(b_state);
-    const size_t o_status = carve(sizeof(int32_t) * n_utts);
-    const size_t o_tok = carve(sizeof(int2) * (size_t)(tok_total > 0 ? tok_total : 1));
-    const size_t o_big = carve(sizeof(int) * (size_t)n_utts * G_COUNT * (max_phones + 1));
-    if (off > m->align_ws_bytes) {
-        (void)hipFree(m->d_align_ws);
-        m->d_align_ws = NULL;
-        m->align_ws_bytes = 0;
-        HIP_OK(hipMalloc((void **)&m->d_align_ws, off));
-        m->align_ws_bytes = off;
-    }
-    unsigned char *ws = m->d_align_ws;
-    {
-        const size_t up_bytes = o_status - o_utts; /* utts | senid | tmatid | sf | ef | state */
-        int slot = 0;
-        unsigned char *hs = stage_acquire(m, up_bytes, &slot);
-        if (hs == NULL)
-            return -1;
-        memcpy(hs, utts.data(), sizeof(AlignUtt) * n_utts);
-        memcpy(hs + (o_senid - o_utts), senid, sizeof(uint16_t) * (size_t)ne * total_phones);
-        memcpy(hs + (o_tmatid - o_utts), tmatid, sizeof(int16_t) * (size_t)total_phones);
-        memcpy(hs + (o_sf - o_utts), sf, sizeof(int32_t) * (size_t)total_phones);
-        memcpy(hs + (o_ef - o_utts), ef, sizeof(int32_t) * (size_t)total_phones);
-        memcpy(hs + (o_state - o_utts), state_io, b_state);
-        HIP_OK(hipMemcpyAsync(ws + o_utts, hs, up_bytes, hipMemcpyHostToDevice, st));
-        HIP_OK(hipEventRecord(m->ev_stage[slot], st));
-    }
+    const size_t o_utts = L.in(utts.data(), sizeof(AlignUtt) * n_utts);
+    const size_t o_senid = L.in(senid, sizeof(uint16_t) * (size_t)ne * total_phones,
+                                sizeof(uint16_t) * (size_t)ne * total_phones + 16);
+    const size_t o_tmatid = L.in(tmatid, sizeof(int16_t) * (size_t)total_phones,
+                                 sizeof(int16_t) * (size_t)total_phones + 16);
+    const size_t o_sf = L.in(sf, sizeof(int32_t) * (size_t)total_phones);
+    const size_t o_ef = L.in(ef, sizeof(int32_t) * (size_t)total_phones);
+    const size_t o_state = L.in(state_io, b_state);
+    const size_t o_status = L.out(sizeof(int32_t) * n_utts);
+    const size_t o_tok = L.out(sizeof(int2) * (size_t)(tok_total > 0 ? tok_total : 1));
+    const size_t o_big = L.out(sizeof(int) * (size_t)n_utts * G_COUNT * (max_phones + 1));
+    if (devbuf_reserve(m->align_ws, L.size(), "ssw_align_batch") < 0)
+        return -1;
+    unsigned char *ws = m->align_ws.p;
+    /* utts | senid | tmatid | sf | ef | state in one copy */
+    if (stage_upload(m, ws + o_utts, L.in_bytes(), st, [&](unsigned char *hs) { L.fill(hs, 0); }) < 0)
+        return -1;
     AlignParams A;
     memset(&A, 0, sizeof(A));
     A.senscr = d_senscr;
@@ -152,7 +132,7 @@ align_batch_any(ssw_model_t *m, const int16_t *d_senscr, int32_t n_utts, const i
     hipLaunchKernelGGL(viterbi_align_any_kernel, dim3(n_utts), dim3(64), 0, st, A, ne);
     HIP_OK(hipGetLastError());
     {
-        const size_t b_status = (sizeof(int32_t) * (size_t)n_utts + 255) & ~(size_t)255;
+        const size_t b_status = align256(sizeof(int32_t) * (size_t)n_utts);
         int slot = 0;
         unsigned char *hs = stage_acquire(m, b_status + b_state, &slot);
         if (hs == NULL)
@@ -160,7 +140,8 @@ align_batch_any(ssw_model_t *m, const int16_t *d_senscr, int32_t n_utts, const i
         HIP_OK(hipMemcpyAsync(hs, ws + o_status, sizeof(int32_t) * (size_t)n_utts,
                               hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(hs + b_status, ws + o_state, b_state, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipEventRecord(m->ev_stage[slot], st));
+        if (stage_release(m, slot, st) < 0)
+            return -1;
         HIP_OK(hipStreamSynchronize(st));
         memcpy(status, hs, sizeof(int32_t) * (size_t)n_utts);
         memcpy(state_io, hs + b_status, b_state);
@@ -368,8 +349,8 @@ align_batch_impl(ssw_model_t *m, const int16_t *d_senscr, int32_t n_utts,
             return -1;
         }
         if (mwb) { /* bytes: [n_frames][64 words] tokens | [n_frames] int32 | [n_frames + 1] uint16 */
-            const long long tokb = (((long long)U.n_frames * 64 * words_all) + 255) & ~255ll;
-            tok_total += (tokb + 4ll * U.n_frames + 2ll * (U.n_frames + 1) + 255) & ~255ll;
+            const size_t tokb = align256((size_t)U.n_frames * 64 * words_all);
+            tok_total += (long long)align256(tokb + 4 * (size_t)U.n_frames + 2 * ((size_t)U.n_frames + 1));
         } else
             tok_total += (long long)U.n_frames
                 * (band_tokens ? std::min(U.n_phones * 3, band_tokens) : U.n_phones * 3);
@@ -382,37 +363,27 @@ align_batch_impl(ssw_model_t *m, const int16_t *d_senscr, int32_t n_utts,
     for (int i = 0; hbm && i < n_run; ++i)
         utts[i].ws_off = (long long)i * A_COUNT * (max_phones + 1);
     /* one grow-only device arena per model for the call's inputs, token stacks and results */
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) {
-        size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t o_utts = carve(sizeof(AlignUtt) * n_run);
-    const size_t o_senid = carve(sizeof(uint16_t) * 3 * (size_t)total_phones + 16);
-    const size_t o_tmatid = carve(sizeof(int16_t) * (size_t)total_phones + 16);
-    const size_t o_sf = carve(sizeof(int32_t) * (size_t)total_phones);
-    const size_t o_ef = carve(sizeof(int32_t) * (size_t)total_phones);
-    const size_t o_status = carve(sizeof(int32_t) * n_utts);
-    const size_t o_state = carve(sizeof(ssw_align_entry_t) * 3 * (size_t)total_phones);
-    const size_t o_tok = carve((mwb ? 1 : sizeof(int2)) * (size_t)(tok_total > 0 ? tok_total : 1));
-    const size_t o_big = carve(hbm ? sizeof(int) * (size_t)n_run * A_COUNT * (max_phones + 1) : 0);
-    const size_t o_band = carve(band_tokens ? sizeof(int) * (2 * (size_t)frame_off[n_utts] + 2 * (size_t)n_utts + 2) : 0);
+    WsLayout L;
+    const size_t o_utts = L.out(sizeof(AlignUtt) * n_run);
+    const size_t o_senid = L.out(sizeof(uint16_t) * 3 * (size_t)total_phones + 16);
+    const size_t o_tmatid = L.out(sizeof(int16_t) * (size_t)total_phones + 16);
+    const size_t o_sf = L.out(sizeof(int32_t) * (size_t)total_phones);
+    const size_t o_ef = L.out(sizeof(int32_t) * (size_t)total_phones);
+    const size_t o_status = L.out(sizeof(int32_t) * n_utts);
+    const size_t o_state = L.out(sizeof(ssw_align_entry_t) * 3 * (size_t)total_phones);
+    const size_t o_tok = L.out((mwb ? 1 : sizeof(int2)) * (size_t)(tok_total > 0 ? tok_total : 1));
+    const size_t o_big = L.out(hbm ? sizeof(int) * (size_t)n_run * A_COUNT * (max_phones + 1) : 0);
+    const size_t o_band = L.out(band_tokens ? sizeof(int) * (2 * (size_t)frame_off[n_utts] + 2 * (size_t)n_utts + 2) : 0);
     int rv = -1;
 #define TRY(expr)                                                                            \
     if ((expr) != hipSuccess) {                                                              \
         ssw_set_error("%s failed: %s", #expr, hipGetErrorString(hipGetLastError()));         \
         goto out;                                                                            \
     }
-    if (off > m->align_ws_bytes) {
-        (void)hipFree(m->d_align_ws);
-        m->d_align_ws = NULL;
-        m->align_ws_bytes = 0;
-        TRY(hipMalloc((void **)&m->d_align_ws, off));
-        m->align_ws_bytes = off;
-    }
+    if (devbuf_reserve(m->align_ws, L.size(), "ssw_align_batch") < 0)
+        goto out;
     {
-    unsigned char *ws = m->d_align_ws;
+    unsigned char *ws = m->align_ws.p;
     AlignUtt *d_utts = reinterpret_cast<AlignUtt *>(ws + o_utts);
     uint16_t *d_senid = reinterpret_cast<uint16_t *>(ws + o_senid);
     int16_t *d_tmatid = reinterpret_cast<int16_t *>(ws + o_tmatid);
@@ -452,7 +423,8 @@ align_batch_impl(ssw_model_t *m, const int16_t *d_senscr, int32_t n_utts,
             host_copy_parallel(hs + up_bytes, state_io, b_state);
             TRY(hipMemcpyAsync(d_state, hs + up_bytes, b_state, hipMemcpyHostToDevice, st));
         }
-        TRY(hipEventRecord(m->ev_stage[slot], st));
+        if (stage_release(m, slot, st) < 0)
+            goto out;
     }
     {
         AlignParams A;
@@ -520,14 +492,15 @@ align_batch_impl(ssw_model_t *m, const int16_t *d_senscr, int32_t n_utts,
         /* results: status and state entries into pinned staging, then the caller's arrays */
         const size_t b_status = sizeof(int32_t) * (size_t)n_utts;
         int slot = 0;
-        unsigned char *hs = stage_acquire(m, ((b_status + 255) & ~(size_t)255) + b_state, &slot);
+        unsigned char *hs = stage_acquire(m, align256(b_status) + b_state, &slot);
         if (hs == NULL)
             goto out;
-        unsigned char *h_state = hs + ((b_status + 255) & ~(size_t)255);
+        unsigned char *h_state = hs + align256(b_status);
         TRY(hipMemcpyAsync(hs, d_status, sizeof(int32_t) * (size_t)(only == NULL ? n_utts : n_run),
                            hipMemcpyDeviceToHost, st));
         TRY(hipMemcpyAsync(h_state, d_state, b_state, hipMemcpyDeviceToHost, st));
-        TRY(hipEventRecord(m->ev_stage[slot], st));
+        if (stage_release(m, slot, st) < 0)
+            goto out;
         TRY(hipStreamSynchronize(st));
         const int32_t *got = reinterpret_cast<const int32_t *>(hs);
         if (only == NULL)

@@ -62,27 +62,22 @@ ssw_compact_plan_create(ssw_model_t *m, int32_t n_utts, const int32_t *frame_off
         }
     p->elems = elems;
     /* one device allocation, every table at a 256-byte boundary */
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) {
-        size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
+    WsLayout L;
     const size_t nst = (size_t)p->total_phones * 3;
-    const size_t o_fo = carve(sizeof(int32_t) * ((size_t)n_utts + 1));
-    const size_t o_po = carve(sizeof(int32_t) * ((size_t)n_utts + 1));
-    const size_t o_cs = carve(sizeof(int32_t) * (size_t)n_utts);
-    const size_t o_ro = carve(sizeof(long long) * (size_t)n_utts);
-    const size_t o_uf = carve(sizeof(int32_t) * (size_t)std::max(p->n_frames, 1));
-    const size_t o_sid = carve(sizeof(uint16_t) * nst + 16);
-    const size_t o_cidx = carve(sizeof(uint16_t) * nst + 16);
-    const size_t o_cpos = carve(sizeof(uint32_t) * (size_t)n_utts * (size_t)m->slot_stride);
+    const size_t o_fo = L.out(sizeof(int32_t) * ((size_t)n_utts + 1));
+    const size_t o_po = L.out(sizeof(int32_t) * ((size_t)n_utts + 1));
+    const size_t o_cs = L.out(sizeof(int32_t) * (size_t)n_utts);
+    const size_t o_ro = L.out(sizeof(long long) * (size_t)n_utts);
+    const size_t o_uf = L.out(sizeof(int32_t) * (size_t)std::max(p->n_frames, 1));
+    const size_t o_sid = L.out(sizeof(uint16_t) * nst + 16);
+    const size_t o_cidx = L.out(sizeof(uint16_t) * nst + 16);
+    const size_t o_cpos = L.out(sizeof(uint32_t) * (size_t)n_utts * (size_t)m->slot_stride);
     hipError_t e = hipSetDevice(m->device);
     if (e == hipSuccess)
-        e = hipMalloc((void **)&p->d_mem, off);
+        e = hipMalloc((void **)&p->d_mem, L.size());
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        ssw_set_error("ssw_compact_plan_create: %zu bytes of device memory: %s", off,
+        ssw_set_error("ssw_compact_plan_create: %zu bytes of device memory: %s", L.size(),
                       hipGetErrorString(e));
         delete p;
         return NULL;
@@ -213,21 +208,15 @@ ssw_score_batch_compact(ssw_model_t *m, int scorer, const float *d_feats,
         return score_batch_impl(m, scorer, d_feats, plan->n_frames, plan->frame_off.data(),
                                 plan->n_utts, d_compact, stream, flags & SSW_SCORE_SHARE_DEVICE,
                                 NULL, NULL, NULL, NULL, plan);
-    const size_t need = (size_t)plan->n_frames * h->n_sen;
-    if (need > m->full_tmp_cap) {
-        HIP_OK(hipSetDevice(m->device));
-        (void)hipFree(m->d_full_tmp);
-        m->d_full_tmp = NULL;
-        m->full_tmp_cap = 0;
-        if (dev_alloc(&m->d_full_tmp, need) < 0)
-            return -1;
-        m->full_tmp_cap = need;
-    }
+    HIP_OK(hipSetDevice(m->device));
+    if (devbuf_reserve(m->full_tmp, sizeof(int16_t) * (size_t)plan->n_frames * h->n_sen,
+                       "ssw_score_batch_compact") < 0)
+        return -1;
     if (score_batch_impl(m, scorer, d_feats, plan->n_frames, plan->frame_off.data(), plan->n_utts,
-                         m->d_full_tmp, stream, flags & SSW_SCORE_SHARE_DEVICE, NULL, NULL) < 0)
+                         m->full_tmp.as<int16_t>(), stream, flags & SSW_SCORE_SHARE_DEVICE, NULL, NULL) < 0)
         return -1;
     CompactGatherParams G;
-    G.full = m->d_full_tmp;
+    G.full = m->full_tmp.as<int16_t>();
     G.utt_of_frame = plan->d_utt_of_frame;
     G.cutt_off = plan->d_frame_off;
     G.cstride = plan->d_cstride;

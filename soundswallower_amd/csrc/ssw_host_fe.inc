@@ -207,10 +207,8 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm, const
     memcpy(frame_off_out, foff.data(), sizeof(int32_t) * ((size_t)n_utts + 1));
     if (total == 0)
         return 0;
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    if (check_has_device(m) < 0)
         return -1;
-    }
     if (d_pcm == NULL || d_cep == NULL) {
         ssw_set_error("bad arguments to %s", who);
         return -1;
@@ -257,15 +255,10 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm, const
     /* grow-only workspace: records, offsets, groups, then the mel spectra */
     const size_t utt_bytes = sizeof(FeUtt) * (size_t)n_utts;
     const size_t int_bytes = sizeof(int) * (grp_utt.size() + grp_off.size() + (size_t)n_utts + 1);
-    const size_t off_bytes = (utt_bytes + int_bytes + 255) & ~(size_t)255;
+    const size_t off_bytes = align256(utt_bytes + int_bytes);
     const size_t ws = off_bytes + (size_t)n_frames * nfilt * sizeof(double);
-    if (ws > m->fe_ws_cap) {
-        (void)hipFree(m->d_fe_ws);
-        m->d_fe_ws = NULL;
-        m->fe_ws_cap = 0;
-        HIP_OK(hipMalloc((void **)&m->d_fe_ws, ws));
-        m->fe_ws_cap = ws;
-    }
+    if (devbuf_reserve(m->fe_ws, ws, who) < 0)
+        return -1;
     std::vector<unsigned char> stage(utt_bytes + int_bytes);
     {
         unsigned char *p = stage.data();
@@ -279,12 +272,12 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm, const
     }
     FeParams F;
     F.pcm = d_pcm;
-    F.utt = (const FeUtt *)m->d_fe_ws;
-    F.frame_off = (const int *)(m->d_fe_ws + utt_bytes);
+    F.utt = (const FeUtt *)m->fe_ws.p;
+    F.frame_off = (const int *)(m->fe_ws.p + utt_bytes);
     const int *d_grp_utt = F.frame_off + n_utts + 1;
     const int *d_grp_off = d_grp_utt + n_utts;
     F.tab = m->d_fe_tab;
-    F.mfspec = (double *)(m->d_fe_ws + off_bytes);
+    F.mfspec = (double *)(m->fe_ws.p + off_bytes);
     F.cep = d_cep;
     F.grp_utt = F.grp_off = nullptr; /* (set per spectrum launch) */
     F.n_grp = F.n_grp_frames = 0;
@@ -296,7 +289,7 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm, const
         m->fe_ev_ready = 1;
     }
     const bool timed = m->timing && m->fe_ev_ready;
-    hipError_t e = hipMemcpyAsync(m->d_fe_ws, stage.data(), stage.size(), hipMemcpyHostToDevice, st);
+    hipError_t e = hipMemcpyAsync(m->fe_ws.p, stage.data(), stage.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && timed)
         e = hipEventRecord(m->fe_ev[0], st);
     for (int o = SSW_FE_MIN_LOG2N; o <= SSW_FE_MAX_LOG2N && e == hipSuccess; ++o) {

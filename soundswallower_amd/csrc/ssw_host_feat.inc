@@ -13,24 +13,17 @@ ssw_feat_batch(ssw_model_t *m, const float *d_cep, int32_t n_frames, const int32
     hipStream_t st = (hipStream_t)stream;
     if (n_frames == 0 || n_utts == 0)
         return 0;
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    if (check_has_device(m) < 0)
         return -1;
-    }
-    if (ncep < 1 || ncep > 64 || n_frames < 0 || n_utts < 0 || utt_off == NULL || utt_off[0] != 0
-        || utt_off[n_utts] != n_frames) {
+    if (ncep < 1 || ncep > 64 || n_frames < 0 || n_utts < 0 || utt_off == NULL
+        || !utt_off_spans(utt_off, n_utts, n_frames)) {
         ssw_set_error("bad arguments to ssw_feat_batch");
         return -1;
     }
     HIP_OK(hipSetDevice(m->device));
-    if ((size_t)n_utts + 1 > m->feat_off_cap) { /* grow-only offsets buffer */
-        (void)hipFree(m->d_feat_off);
-        m->d_feat_off = NULL;
-        m->feat_off_cap = 0;
-        HIP_OK(hipMalloc((void **)&m->d_feat_off, sizeof(int) * ((size_t)n_utts + 1)));
-        m->feat_off_cap = (size_t)n_utts + 1;
-    }
-    int *d_off = m->d_feat_off;
+    if (devbuf_reserve(m->feat_off, sizeof(int) * ((size_t)n_utts + 1), "ssw_feat_batch") < 0)
+        return -1;
+    int *d_off = m->feat_off.as<int>();
     hipError_t e = hipMemcpyAsync(d_off, utt_off, sizeof(int) * ((size_t)n_utts + 1),
                                   hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {

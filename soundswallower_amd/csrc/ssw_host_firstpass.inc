@@ -53,17 +53,14 @@ ssw_first_pass_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_c
 {
     if (n_utts == 0)
         return 0;
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    if (check_has_device(m) < 0)
         return -1;
-    }
     if (n_utts < 0 || n_frames < 0 || max_seg < 1 || !utt_off || !word_off || !words || !n_seg
-        || !seg || !d || utt_off[0] != 0 || utt_off[n_utts] != n_frames) {
+        || !seg || !d || !utt_off_spans(utt_off, n_utts, n_frames)) {
         ssw_set_error("bad arguments to ssw_first_pass_batch");
         return -1;
     }
-    const double t0 = std::chrono::duration<double, std::milli>(
-                          std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t0 = now_ms();
     ssw_fp_graphs_t *g = ssw_fp_graphs_build(m, d, cfg, n_utts, word_off, words);
     if (g == NULL)
         return -1;
@@ -80,17 +77,14 @@ ssw_first_pass_run(ssw_model_t *m, const ssw_first_pass_plan_t *plan, const int1
 {
     if (plan == NULL || plan->n_utts == 0)
         return 0;
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    if (check_has_device(m) < 0)
         return -1;
-    }
-    if (n_frames < 0 || max_seg < 1 || !utt_off || !n_seg || !seg || utt_off[0] != 0
-        || utt_off[plan->n_utts] != n_frames) {
+    if (n_frames < 0 || max_seg < 1 || !utt_off || !n_seg || !seg
+        || !utt_off_spans(utt_off, plan->n_utts, n_frames)) {
         ssw_set_error("bad arguments to ssw_first_pass_run");
         return -1;
     }
-    const double t0 = std::chrono::duration<double, std::milli>(
-                          std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t0 = now_ms();
     return first_pass_run(m, plan->g, t0, d_senscr, n_frames, utt_off, plan->n_utts, max_seg, n_seg,
                           seg, stream);
 }
@@ -164,11 +158,7 @@ first_pass_run_impl(ssw_model_t *m, ssw_fp_graphs_t *g, double fp_t0, const int1
     if (n_utts == 0)
         return 0;
     const bool fp_timing = m->kn.align_timing;
-    auto fp_now = [] { return std::chrono::duration<double, std::milli>(
-                           std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double fp_t1 = fp_now();
-    /* one staging buffer -> one copy: every array at a 256-byte boundary */
-    struct piece { const void *src; size_t bytes, off; };
+    const double fp_t1 = now_ms();
     std::vector<long long> hist_off((size_t)n_utts);
     std::vector<long long> big_off((size_t)n_utts);
     size_t hist_total = 0, lds_ints = 0, max_nodes = 0, big_ints = 0;
@@ -226,55 +216,49 @@ first_pass_run_impl(ssw_model_t *m, ssw_fp_graphs_t *g, double fp_t0, const int1
      * batch through the kernel that keeps the node state in HBM; SSW_FP_KERNEL=big forces it */
     if (!big)
         big_ints = 0;
-    piece pc[] = {
-        { utt_off, sizeof(int) * ((size_t)n_utts + 1), 0 },
-        { g->node_off, sizeof(int) * ((size_t)n_utts + 1), 0 },
-        { g->leaf_off, sizeof(int) * ((size_t)n_utts + 1), 0 },
-        { g->state_off, sizeof(int) * ((size_t)n_utts + 1), 0 },
-        { g->senid, sizeof(uint16_t) * 4 * (size_t)g->n_nodes, 0 },
-        { g->pen, sizeof(int) * (size_t)g->n_nodes, 0 },
-        { g->parent, sizeof(int) * (size_t)g->n_nodes, 0 },
-        { g->info, sizeof(uint32_t) * (size_t)g->n_nodes, 0 },
-        { g->ctxt, sizeof(uint64_t) * (size_t)g->n_nodes, 0 },
-        { g->leaf_ord, sizeof(int) * (size_t)g->n_nodes, 0 },
-        { g->leaf_wid, sizeof(int) * (size_t)g->n_leaves, 0 },
-        { g->leaf_to, sizeof(int) * (size_t)g->n_leaves, 0 },
-        { g->leaf_node, sizeof(int) * (size_t)g->n_leaves, 0 },
-        { g->in_off, sizeof(int) * ((size_t)g->n_states + 1), 0 },
-        { g->in_leaf, sizeof(int) * (size_t)g->n_in, 0 },
-        { hist_off.data(), sizeof(long long) * (size_t)n_utts, 0 },
-        { g->tw, sizeof(int) * (size_t)g->n_tw, 0 },
-        { g->tw_off, sizeof(int) * ((size_t)n_utts + 1), 0 },
-        { g->twin_ref, sizeof(int) * (size_t)g->n_nodes, 0 },
-        { g->tw_rk, sizeof(int) * (size_t)n_utts, 0 },
-        { big_off.data(), sizeof(long long) * (size_t)n_utts, 0 },
-        { only.data(), sizeof(int) * only.size(), 0 },
-    };
-    const int n_pc = (int)(sizeof(pc) / sizeof(pc[0]));
-    size_t off = 0;
-    for (int i = 0; i < n_pc; ++i) {
-        pc[i].off = off;
-        off = (off + pc[i].bytes + 255) & ~(size_t)255;
-    }
-    const size_t in_bytes = off;
-    const size_t out_off = off;
-    off += ((sizeof(int) * (size_t)n_utts + 255) & ~(size_t)255);
-    const size_t seg_off = off;
-    off += ((sizeof(ssw_word_seg_t) * (size_t)n_utts * (size_t)max_seg + 255) & ~(size_t)255);
-    const size_t hist_at = off;
-    off += (sizeof(int2) * (hist_total ? hist_total : 1) + 255) & ~(size_t)255;
-    const size_t big_at = off;
-    off += sizeof(int) * big_ints;
+    /* one staging buffer -> one copy (WsLayout).  What changes from call to call comes last
+     * among the uploaded tables -- the utterance offsets and hist_off excepted, which lie ahead
+     * of the graph's: `o_call` is where the graph's tables end */
+    const size_t nU = (size_t)n_utts, nN = (size_t)g->n_nodes, nL = (size_t)g->n_leaves;
+    WsLayout L;
+    const size_t o_utt_off = L.in(utt_off, sizeof(int) * (nU + 1));
+    const size_t o_node_off = L.in(g->node_off, sizeof(int) * (nU + 1));
+    const size_t o_leaf_off = L.in(g->leaf_off, sizeof(int) * (nU + 1));
+    const size_t o_state_off = L.in(g->state_off, sizeof(int) * (nU + 1));
+    const size_t o_senid = L.in(g->senid, sizeof(uint16_t) * 4 * nN);
+    const size_t o_pen = L.in(g->pen, sizeof(int) * nN);
+    const size_t o_parent = L.in(g->parent, sizeof(int) * nN);
+    const size_t o_info = L.in(g->info, sizeof(uint32_t) * nN);
+    const size_t o_ctxt = L.in(g->ctxt, sizeof(uint64_t) * nN);
+    const size_t o_leaf_ord = L.in(g->leaf_ord, sizeof(int) * nN);
+    const size_t o_leaf_wid = L.in(g->leaf_wid, sizeof(int) * nL);
+    const size_t o_leaf_to = L.in(g->leaf_to, sizeof(int) * nL);
+    const size_t o_leaf_node = L.in(g->leaf_node, sizeof(int) * nL);
+    const size_t o_in_off = L.in(g->in_off, sizeof(int) * ((size_t)g->n_states + 1));
+    const size_t o_in_leaf = L.in(g->in_leaf, sizeof(int) * (size_t)g->n_in);
+    const size_t b_hist_off = sizeof(long long) * nU;
+    const size_t o_hist_off = L.in(hist_off.data(), b_hist_off);
+    const size_t o_tw = L.in(g->tw, sizeof(int) * (size_t)g->n_tw);
+    const size_t o_tw_off = L.in(g->tw_off, sizeof(int) * (nU + 1));
+    const size_t o_twin_ref = L.in(g->twin_ref, sizeof(int) * nN);
+    const size_t o_tw_rk = L.in(g->tw_rk, sizeof(int) * nU);
+    const size_t o_call = L.mark();
+    const size_t o_big_off = L.in(big_off.data(), sizeof(long long) * nU);
+    const size_t o_only = L.in(only.data(), sizeof(int) * only.size());
+    const size_t in_bytes = L.in_bytes();
+    const size_t out_off = L.out(sizeof(int) * nU);
+    const size_t seg_off = L.out(sizeof(ssw_word_seg_t) * nU * (size_t)max_seg);
+    const size_t hist_at = L.out(sizeof(int2) * (hist_total ? hist_total : 1));
+    const size_t big_at = L.out(sizeof(int) * big_ints);
 
     hipError_t e = hipSetDevice(m->device);
-    if (e == hipSuccess && off > m->fp_ws_cap) { /* grow-only workspace */
-        (void)hipFree(m->d_fp_ws);
-        m->d_fp_ws = NULL;
-        m->fp_ws_cap = 0;
-        m->fp_ws_uid = 0;
-        e = hipMalloc((void **)&m->d_fp_ws, off + off / 4);
-        if (e == hipSuccess)
-            m->fp_ws_cap = off + off / 4;
+    if (e == hipSuccess) {
+        bool moved = false;
+        const int got = devbuf_reserve(m->fp_ws, L.size(), "ssw_first_pass_batch", L.size() / 4, &moved);
+        if (moved) /* the cached graphs went with the old buffer */
+            m->fp_ws_uid = 0;
+        if (got < 0)
+            return -1;
     }
     /* The same graphs searched again (the rounds of ssw_first_pass_batch_active, a level's
      * leftovers, a plan run on several recordings): their tables are on the device already --
@@ -282,15 +266,13 @@ first_pass_run_impl(ssw_model_t *m, ssw_fp_graphs_t *g, double fp_t0, const int1
      * a plan's texts meet new recordings) and is all that goes up: utt_off, hist_off, big_off,
      * only.  Keyed by the graphs' uid, not their address. */
     const bool cached = m->fp_ws_uid != 0 && m->fp_ws_uid == g->uid
-        && m->fp_ws_uid_bytes == pc[20].off;
-    const size_t up_from = cached ? pc[20].off : 0; /* big_off | only */
+        && m->fp_ws_uid_bytes == o_call;
+    const size_t up_from = cached ? o_call : 0; /* big_off | only */
     std::vector<unsigned char> stage(in_bytes - up_from + 1);
     std::vector<int> all_n;
     std::vector<ssw_word_seg_t> all_seg;
     if (e == hipSuccess) {
-        for (int i = 0; i < n_pc; ++i)
-            if (pc[i].bytes && pc[i].off >= up_from)
-                memcpy(stage.data() + (pc[i].off - up_from), pc[i].src, pc[i].bytes);
+        L.fill(stage.data(), up_from);
         /* the graphs go up on a stream of their own: whatever the caller's stream still has
          * to do (ssw_align_text_batch: the scoring kernels) does not hold the copy back; the
          * search then waits for both */
@@ -300,19 +282,19 @@ first_pass_run_impl(ssw_model_t *m, ssw_fp_graphs_t *g, double fp_t0, const int1
                 e = hipEventCreateWithFlags(&m->ev_up, hipEventDisableTiming);
         }
         if (e == hipSuccess && in_bytes > up_from)
-            e = hipMemcpyAsync(m->d_fp_ws + up_from, stage.data(), in_bytes - up_from,
+            e = hipMemcpyAsync(m->fp_ws.p + up_from, stage.data(), in_bytes - up_from,
                                hipMemcpyHostToDevice, m->s_up);
         if (e == hipSuccess && cached) {
             /* the two small tables ahead of the graph's that a call may change */
-            e = hipMemcpyAsync(m->d_fp_ws + pc[0].off, utt_off, pc[0].bytes, hipMemcpyHostToDevice,
-                               m->s_up);
+            e = hipMemcpyAsync(m->fp_ws.p + o_utt_off, utt_off, sizeof(int) * (nU + 1),
+                               hipMemcpyHostToDevice, m->s_up);
             if (e == hipSuccess)
-                e = hipMemcpyAsync(m->d_fp_ws + pc[15].off, hist_off.data(), pc[15].bytes,
+                e = hipMemcpyAsync(m->fp_ws.p + o_hist_off, hist_off.data(), b_hist_off,
                                    hipMemcpyHostToDevice, m->s_up);
         }
         if (e == hipSuccess) {
             m->fp_ws_uid = g->uid;
-            m->fp_ws_uid_bytes = pc[20].off;
+            m->fp_ws_uid_bytes = o_call;
         } else
             m->fp_ws_uid = 0;
         if (e == hipSuccess)
@@ -321,36 +303,36 @@ first_pass_run_impl(ssw_model_t *m, ssw_fp_graphs_t *g, double fp_t0, const int1
             e = hipStreamWaitEvent(st, m->ev_up, 0);
     }
     if (e == hipSuccess) {
-        unsigned char *ws = m->d_fp_ws;
+        unsigned char *ws = m->fp_ws.p;
         FirstPassParams P;
         P.senscr = d_senscr;
-        P.utt_off = (const int *)(ws + pc[0].off);
-        P.node_off = (const int *)(ws + pc[1].off);
-        P.leaf_off = (const int *)(ws + pc[2].off);
-        P.state_off = (const int *)(ws + pc[3].off);
-        P.senid = (const uint16_t *)(ws + pc[4].off);
-        P.pen = (const int *)(ws + pc[5].off);
-        P.parent = (const int *)(ws + pc[6].off);
-        P.info = (const uint32_t *)(ws + pc[7].off);
-        P.ctxt = (const unsigned long long *)(ws + pc[8].off);
-        P.leaf_ord = (const int *)(ws + pc[9].off);
-        P.leaf_wid = (const int *)(ws + pc[10].off);
-        P.leaf_to = (const int *)(ws + pc[11].off);
-        P.leaf_node = (const int *)(ws + pc[12].off);
-        P.in_off = (const int *)(ws + pc[13].off);
-        P.in_leaf = (const int *)(ws + pc[14].off);
-        P.hist_off = (const long long *)(ws + pc[15].off);
-        P.tw = (const int *)(ws + pc[16].off);
-        P.tw_off = (const int *)(ws + pc[17].off);
-        P.twin_ref = (const int *)(ws + pc[18].off);
-        P.tw_rk = (const int *)(ws + pc[19].off);
-        P.big_off = (const long long *)(ws + pc[20].off);
-        P.only = only.empty() ? NULL : (const int *)(ws + pc[21].off);
-        P.big_ws = (int *)(ws + big_at);
+        P.utt_off = ws_at<const int>(ws, o_utt_off);
+        P.node_off = ws_at<const int>(ws, o_node_off);
+        P.leaf_off = ws_at<const int>(ws, o_leaf_off);
+        P.state_off = ws_at<const int>(ws, o_state_off);
+        P.senid = ws_at<const uint16_t>(ws, o_senid);
+        P.pen = ws_at<const int>(ws, o_pen);
+        P.parent = ws_at<const int>(ws, o_parent);
+        P.info = ws_at<const uint32_t>(ws, o_info);
+        P.ctxt = ws_at<const unsigned long long>(ws, o_ctxt);
+        P.leaf_ord = ws_at<const int>(ws, o_leaf_ord);
+        P.leaf_wid = ws_at<const int>(ws, o_leaf_wid);
+        P.leaf_to = ws_at<const int>(ws, o_leaf_to);
+        P.leaf_node = ws_at<const int>(ws, o_leaf_node);
+        P.in_off = ws_at<const int>(ws, o_in_off);
+        P.in_leaf = ws_at<const int>(ws, o_in_leaf);
+        P.hist_off = ws_at<const long long>(ws, o_hist_off);
+        P.tw = ws_at<const int>(ws, o_tw);
+        P.tw_off = ws_at<const int>(ws, o_tw_off);
+        P.twin_ref = ws_at<const int>(ws, o_twin_ref);
+        P.tw_rk = ws_at<const int>(ws, o_tw_rk);
+        P.big_off = ws_at<const long long>(ws, o_big_off);
+        P.only = only.empty() ? NULL : ws_at<const int>(ws, o_only);
+        P.big_ws = ws_at<int>(ws, big_at);
         P.tp = (const uint32_t *)m->d_tp;
-        P.hist = (int2 *)(ws + hist_at);
-        P.n_seg = (int *)(ws + out_off);
-        P.seg = (ssw_word_seg_t *)(ws + seg_off);
+        P.hist = ws_at<int2>(ws, hist_at);
+        P.n_seg = ws_at<int>(ws, out_off);
+        P.seg = ws_at<ssw_word_seg_t>(ws, seg_off);
         P.n_sen = m->h->n_sen;
         P.max_seg = max_seg;
         P.beam = g->beam;
@@ -455,7 +437,7 @@ first_pass_run_impl(ssw_model_t *m, ssw_fp_graphs_t *g, double fp_t0, const int1
         rc = 0;
     if (fp_timing)
         fprintf(stderr, "ssw_first_pass_batch: graphs %.2f ms (%d HMMs), upload + search + results "
-                        "%.2f ms\n", fp_t1 - fp_t0, g->n_nodes, fp_now() - fp_t1);
+                        "%.2f ms\n", fp_t1 - fp_t0, g->n_nodes, now_ms() - fp_t1);
     return rc;
 }
 
@@ -581,9 +563,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
     const ssw_host_model_t *h = m->h;
     refresh_knobs(m);
     const bool timing = m->kn.align_timing; /* SSW_ALIGN_TIMING: stderr, ms per stage */
-    auto now = [] { return std::chrono::duration<double, std::milli>(
-                        std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_a = now(), t_b, t_c, t_d;
+    double t_a = now_ms(), t_b, t_c, t_d;
     int max_words = plan ? plan->max_words : 0;
     for (int u = 0; !plan && u < n_utts; ++u)
         max_words = std::max(max_words, word_off[u + 1] - word_off[u]);
@@ -601,19 +581,8 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
     if (fpa != NULL)
         seed.assign((size_t)n_utts * nw32, 0u);
     const bool carry2 = fpa != NULL && fpa->two_pass && fpa->scorer == SSW_SCORER_PTM && n_utts > 0;
-    if (carry2) { /* history slot 1 after every utterance's first pass, [n_utts][n_cbf] */
-        const size_t ncar = (size_t)m->n_cbf * (size_t)n_utts;
-        if (ncar > m->carry_rows_cap) {
-            (void)hipFree(m->d_carry_rows);
-            m->d_carry_rows = NULL;
-            m->carry_rows_cap = 0;
-            if (hipMalloc((void **)&m->d_carry_rows, ncar * sizeof(uint32_t)) != hipSuccess) {
-                ssw_set_error("ssw_align_text_batch_active: out of device memory");
-                return NULL;
-            }
-            m->carry_rows_cap = ncar;
-        }
-    }
+    if (carry2 && carry_rows_reserve(m, n_utts, "ssw_align_text_batch_active") < 0)
+        return NULL;
     for (int attempt = 0; n_utts && attempt < 2; ++attempt) {
         seg.assign((size_t)n_utts * max_seg, ssw_word_seg_t());
         if (!plan && (attempt == 1 || fpa != NULL) && own_plan == NULL) { /* build the graphs once more only in this rare case */
@@ -626,7 +595,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
             ? first_pass_active_run(m, use->g, fpa->scorer, fpa->d_feats, n_frames, utt_off, n_utts,
                                     max_seg, n_seg.data(), seg.data(),
                                     const_cast<int16_t *>(d_senscr), false, seed.data(), NULL, stream,
-                                    carry2 ? m->d_carry_rows : NULL)
+                                    carry2 ? m->carry_rows.as<uint32_t>() : NULL)
             : use ? ssw_first_pass_run(m, use, d_senscr, n_frames, utt_off, max_seg,
                                                 n_seg.data(), seg.data(), stream)
                            : ssw_first_pass_batch(m, d, cfg, d_senscr, n_frames, utt_off, n_utts,
@@ -645,7 +614,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
         max_seg = need;
     }
     ssw_first_pass_plan_free(own_plan);
-    t_b = now();
+    t_b = now_ms();
     ssw_alignment_set_t *a = new ssw_alignment_set_t();
     a->m = m;
     a->d = d;
@@ -761,7 +730,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
         sf[i] = start[i] > 0 ? start[i] : 0; /* state_align_search_init, :464-471 */
         ef[i] = dur[i] > 0 ? start[i] + dur[i] : INT_MAX;
     }
-    t_c = now();
+    t_c = now_ms();
     /* (ssw_align_text_batch with two_pass_history: the scores are made again here, from the
      * history the first pass left, before the second pass reads them) */
     if (between != NULL && between(between_arg) < 0) {
@@ -793,7 +762,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
                                       tmat.data() + p0, sf.data() + p0, ef.data() + p0,
                                       seed.data() + (size_t)u0 * nw32, a->state_al.data() + p0 * ne,
                                       st.data(), NULL, stream,
-                                      carry2 ? m->d_carry_rows + (size_t)u0 * m->n_cbf : NULL)
+                                      carry2 ? m->carry_rows.as<uint32_t>() + (size_t)u0 * m->n_cbf : NULL)
             : ssw_align_batch(m, d_senscr + (size_t)utt_off[u0] * h->n_sen, u1 - u0, foff.data(),
                               poff.data(), a->senid.data() + p0 * ne, tmat.data() + p0,
                               sf.data() + p0, ef.data() + p0, a->state_al.data() + p0 * ne,
@@ -807,7 +776,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
                 a->status[u] = 2;
         u0 = u1;
     }
-    t_d = now();
+    t_d = now_ms();
     /* alignment_propagate: states -> phones -> words, the utterances shared out over the host
      * threads (one after the other they took 0.28 ms per 256 utterances, as long as a fifth of
      * the second pass's kernel) */
@@ -852,7 +821,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
     }
     if (timing)
         fprintf(stderr, "ssw_forced_align_batch: first pass %.2f ms, populate %.2f, second pass %.2f, "
-                        "propagate %.2f\n", t_b - t_a, t_c - t_b, t_d - t_c, now() - t_d);
+                        "propagate %.2f\n", t_b - t_a, t_c - t_b, t_d - t_c, now_ms() - t_d);
     return a;
 }
 
@@ -865,34 +834,21 @@ ssw_align_text_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_c
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    if (check_has_device(m) < 0)
         return NULL;
-    }
     if (n_frames < 0 || (n_frames > 0 && d_feats == NULL)) {
         ssw_set_error("bad arguments to ssw_align_text_batch");
         return NULL;
     }
-    const size_t need = (size_t)n_frames * (size_t)m->h->n_sen;
     if (hipSetDevice(m->device) != hipSuccess)
         return NULL;
-    if (need > m->text_scr_cap) {
-        (void)hipFree(m->d_text_scr);
-        m->d_text_scr = NULL;
-        m->text_scr_cap = 0;
-        hipError_t e = hipMalloc((void **)&m->d_text_scr, sizeof(int16_t) * need);
-        if (e != hipSuccess) {
-            ssw_set_error("ssw_align_text_batch: %s", hipGetErrorString(e));
-            return NULL;
-        }
-        m->text_scr_cap = need;
-    }
+    if (text_rows_reserve(m, n_frames, "ssw_align_text_batch") < 0)
+        return NULL;
     refresh_knobs(m);
     const bool timing = m->kn.align_timing;
-    const double t_in = std::chrono::duration<double, std::milli>(
-                            std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t_in = now_ms();
     if (n_frames > 0
-        && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, m->d_text_scr, stream) < 0)
+        && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, m->text_scr.as<int16_t>(), stream) < 0)
         return NULL;
     /* decoder_alignment's history semantics (src/decoder.c:786-793): the second pass scores
      * again after acmod_rewind, from the top-N order the first pass left (src/ptm_mgau.c:425-448;
@@ -909,20 +865,11 @@ ssw_align_text_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_c
     const bool two_pass = cfg != NULL && cfg->two_pass_history && scorer == SSW_SCORER_PTM
         && n_frames > 0 && n_utts > 0;
     if (two_pass) {
-        const size_t ncar = (size_t)m->n_cbf * (size_t)n_utts;
-        if (ncar > m->carry_rows_cap) {
-            (void)hipFree(m->d_carry_rows);
-            m->d_carry_rows = NULL;
-            m->carry_rows_cap = 0;
-            if (hipMalloc((void **)&m->d_carry_rows, ncar * sizeof(uint32_t)) != hipSuccess) {
-                ssw_set_error("ssw_align_text_batch: out of device memory");
-                return NULL;
-            }
-            m->carry_rows_cap = ncar;
-        }
+        if (carry_rows_reserve(m, n_utts, "ssw_align_text_batch") < 0)
+            return NULL;
         hipLaunchKernelGGL(gather_last_orders_kernel, dim3((unsigned)n_utts), dim3(128), 0,
                            (hipStream_t)stream, m->d_topn_cw, m->d_utt_off, m->n_cbf,
-                           (const uint32_t *)NULL, m->d_carry_rows);
+                           (const uint32_t *)NULL, m->carry_rows.as<uint32_t>());
         if (hipGetLastError() != hipSuccess) {
             ssw_set_error("ssw_align_text_batch: gather_last_orders_kernel failed to launch");
             return NULL;
@@ -931,8 +878,8 @@ ssw_align_text_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_c
     auto rescore = [](void *arg) -> int {
         rescore_t *r = static_cast<rescore_t *>(arg);
         return score_batch_impl(r->m, SSW_SCORER_PTM, r->d_feats, r->n_frames, r->utt_off,
-                                r->n_utts, r->m->d_text_scr, r->stream, 0u, NULL, NULL, NULL,
-                                r->m->d_carry_rows);
+                                r->n_utts, r->m->text_scr.as<int16_t>(), r->stream, 0u, NULL, NULL, NULL,
+                                r->m->carry_rows.as<uint32_t>());
     };
     /* the scoring kernels are in flight: the host builds the first pass's graphs meanwhile;
      * the searches then run on the same stream, after the scores */
@@ -945,15 +892,14 @@ ssw_align_text_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_c
         (void)hipStreamSynchronize((hipStream_t)stream);
         return NULL;
     }
-    ssw_alignment_set_t *a = forced_align_core(m, d, NULL, plan, m->d_text_scr, n_frames, utt_off,
+    ssw_alignment_set_t *a = forced_align_core(m, d, NULL, plan, m->text_scr.as<int16_t>(), n_frames, utt_off,
                                                plan->n_utts, NULL, NULL, stream,
                                                c.any ? &c.reject : NULL,
                                                two_pass ? +rescore : NULL, &rs);
     ssw_first_pass_plan_free(plan);
     if (timing)
         fprintf(stderr, "ssw_align_text_batch: %.2f ms in the call\n",
-                std::chrono::duration<double, std::milli>(
-                    std::chrono::steady_clock::now().time_since_epoch()).count() - t_in);
+                now_ms() - t_in);
     return a;
 }
 

@@ -55,8 +55,7 @@ fpa_fp_search(void *arg, const int16_t *rows, const std::vector<int> &only,
     m->fpa_mask = mask;
     m->fpa_act_off = d_act_off;
     m->fpa_node_cnt = d_node_cnt;
-    const double t0 = std::chrono::duration<double, std::milli>(
-                          std::chrono::steady_clock::now().time_since_epoch()).count();
+    const double t0 = now_ms();
     /* (through the levels of the long-text kernels, as ssw_first_pass_batch goes) */
     return first_pass_run(m, a.g, t0, rows, a.n_frames, a.utt_off, a.n_utts, a.max_seg, a.n_seg,
                           a.seg, a.stream, &only);
@@ -105,9 +104,7 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
     HIP_OK(hipSetDevice(m->device));
     refresh_knobs(m);
     const bool timing = m->kn.align_timing;
-    auto now = [] { return std::chrono::duration<double, std::milli>(
-                        std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_in = now();
+    const double t_in = now_ms();
     const int nw32 = (h->n_sen + 31) / 32;
     /* the exported sets: [n_frames_u][ceil(N_u / 64)] 64-bit words per utterance */
     std::vector<long long> act_off((size_t)n_utts);
@@ -134,58 +131,36 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
             return -1;
         }
     }
-    size_t off = 0;
-    auto carve = [&off](size_t bytes) {
-        size_t at = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t nf = (size_t)std::max(n_frames, 1);
-    const size_t o_ma = carve(sizeof(unsigned long long) * (size_t)std::max(mask_words, 1ll));
-    const size_t o_mb = carve(sizeof(unsigned long long) * (size_t)std::max(mask_words, 1ll));
-    const size_t o_up = off; /* uploaded in one copy: act_off | utt_off | node base, count | senid */
-    const size_t o_ao = carve(sizeof(long long) * (size_t)n_utts);
-    const size_t o_uo = carve(sizeof(int) * ((size_t)n_utts + 1));
-    const size_t o_nb = carve(sizeof(int) * (size_t)n_utts);
-    const size_t o_nc = carve(sizeof(int) * (size_t)n_utts);
-    const size_t o_sid = carve(sizeof(uint16_t) * 4 * (size_t)std::max(G.n_nodes, 1));
-    const size_t up_bytes = off - o_up;
-    const size_t o_listed = carve(sizeof(uint32_t) * nf * (size_t)nw32);
-    const size_t o_cbm = carve(sizeof(unsigned long long) * nf);
-    const size_t o_iota = carve(sizeof(int32_t) * nf);
-    const size_t o_seed = carve(sizeof(uint32_t) * (size_t)n_utts * (size_t)nw32);
-    const size_t o_diff = carve(sizeof(int32_t) * (size_t)n_utts);
-    const size_t o_only = carve(sizeof(int32_t) * (size_t)n_utts);
+    const size_t nf = (size_t)std::max(n_frames, 1), nU = (size_t)n_utts;
+    WsLayout L;
+    const size_t o_ma = L.out(sizeof(unsigned long long) * (size_t)std::max(mask_words, 1ll));
+    const size_t o_mb = L.out(sizeof(unsigned long long) * (size_t)std::max(mask_words, 1ll));
+    const size_t o_up = L.mark(); /* uploaded in one copy: act_off | utt_off | node base, count | senid */
+    const size_t o_ao = L.in(act_off.data(), sizeof(long long) * nU);
+    const size_t o_uo = L.in(utt_off, sizeof(int) * (nU + 1));
+    const size_t o_nb = L.in(G.node_base.data(), sizeof(int) * nU);
+    const size_t o_nc = L.in(G.node_cnt.data(), sizeof(int) * nU);
+    const size_t o_sid = L.in(G.senid, sizeof(uint16_t) * 4 * (size_t)G.n_nodes, 1);
+    const size_t o_listed = L.out(sizeof(uint32_t) * nf * (size_t)nw32);
+    const size_t o_cbm = L.out(sizeof(unsigned long long) * nf);
+    const size_t o_iota = L.out(sizeof(int32_t) * nf);
+    const size_t o_seed = L.out(sizeof(uint32_t) * nU * (size_t)nw32);
+    const size_t o_diff = L.out(sizeof(int32_t) * nU);
+    const size_t o_only = L.out(sizeof(int32_t) * nU);
     int max_len = 0;
     for (int u = 0; u < n_utts; ++u)
         max_len = std::max(max_len, utt_off[u + 1] - utt_off[u]);
     /* one utterance's compallsen = yes rows (the rounds over few utterances, below) */
-    const size_t o_yes = carve(sizeof(int16_t) * (size_t)std::max(max_len, 1) * (size_t)h->n_sen);
+    const size_t o_yes = L.out(sizeof(int16_t) * (size_t)std::max(max_len, 1) * (size_t)h->n_sen);
     /* (two-pass history: the whole batch's utterance-start bits, for fpa_carry_rows_kernel) */
     const size_t n_start_words = nf / 32 + 2;
-    const size_t o_start = carve(d_carry_out != NULL ? sizeof(uint32_t) * n_start_words : 0);
-    if (off > m->fpa_ws_cap) {
-        HIP_OK(hipStreamSynchronize(st));
-        (void)hipFree(m->d_fpa_ws);
-        m->d_fpa_ws = NULL;
-        m->fpa_ws_cap = 0;
-        HIP_OK(hipMalloc((void **)&m->d_fpa_ws, off));
-        m->fpa_ws_cap = off;
-    }
-    unsigned char *ws = m->d_fpa_ws;
-    {
-        int slot = 0;
-        unsigned char *hs = stage_acquire(m, up_bytes, &slot);
-        if (hs == NULL)
-            return -1;
-        memcpy(hs + (o_ao - o_up), act_off.data(), sizeof(long long) * (size_t)n_utts);
-        memcpy(hs + (o_uo - o_up), utt_off, sizeof(int) * ((size_t)n_utts + 1));
-        memcpy(hs + (o_nb - o_up), G.node_base.data(), sizeof(int) * (size_t)n_utts);
-        memcpy(hs + (o_nc - o_up), G.node_cnt.data(), sizeof(int) * (size_t)n_utts);
-        memcpy(hs + (o_sid - o_up), G.senid, sizeof(uint16_t) * 4 * (size_t)G.n_nodes);
-        HIP_OK(hipMemcpyAsync(ws + o_up, hs, up_bytes, hipMemcpyHostToDevice, st));
-        HIP_OK(hipEventRecord(m->ev_stage[slot], st));
-    }
+    const size_t o_start = L.out(d_carry_out != NULL ? sizeof(uint32_t) * n_start_words : 0);
+    if (devbuf_reserve(m->fpa_ws, L.size(), G.who) < 0)
+        return -1;
+    unsigned char *ws = m->fpa_ws.p;
+    if (stage_upload(m, ws + o_up, L.in_bytes() - o_up, st,
+                     [&](unsigned char *hs) { L.fill(hs, o_up); }) < 0)
+        return -1;
     unsigned long long *mask_x = reinterpret_cast<unsigned long long *>(ws + o_ma);
     unsigned long long *mask_y = reinterpret_cast<unsigned long long *>(ws + o_mb);
     const long long *d_act_off = reinterpret_cast<const long long *>(ws + o_ao);
@@ -209,7 +184,7 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
         return -1;
     if (G.search(G.arg, d_rows, only, mask_x, d_act_off, d_node_cnt) < 0)
         return -1;
-    const double t_spec = now();
+    const double t_spec = now_ms();
     std::vector<int32_t> rounds((size_t)n_utts, 0), diff((size_t)n_utts);
     auto plan_and_score = [&](int lo, int hi, int u_lo, int u_hi, int full) -> int {
         /* frames [lo, hi) = utterances [u_lo, u_hi), planned from mask_x and scored into d_rows */
@@ -269,7 +244,7 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
     int n_round = 0;
     for (;;) {
         ++n_round;
-        const double r0 = now();
+        const double r0 = now_ms();
         /* 2 + 3: the sets assumed (mask_x) -> listed senones and active codebooks per frame ->
          * the scores the reference would compute for them.  Few unproven utterances left: they
          * are scored one by one; else the whole batch again (the proven ones' rows come out as
@@ -299,22 +274,18 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
         }
         if (timing)
             HIP_OK(hipStreamSynchronize(st));
-        const double r1 = now();
+        const double r1 = now_ms();
         /* 4: the search over those scores, its sets into mask_y */
         if (G.search(G.arg, d_rows, only, mask_y, d_act_off, d_node_cnt) < 0)
             return -1;
-        const double r2 = now();
+        const double r2 = now_ms();
         /* 5: proven where the sets are the assumed ones */
         const int n_cmp = only.empty() ? n_utts : (int)only.size();
-        if (!only.empty()) {
-            int slot = 0;
-            unsigned char *hs = stage_acquire(m, sizeof(int32_t) * only.size(), &slot);
-            if (hs == NULL)
-                return -1;
-            memcpy(hs, only.data(), sizeof(int32_t) * only.size());
-            HIP_OK(hipMemcpyAsync(d_only, hs, sizeof(int32_t) * only.size(), hipMemcpyHostToDevice, st));
-            HIP_OK(hipEventRecord(m->ev_stage[slot], st));
-        }
+        if (!only.empty()
+            && stage_upload(m, d_only, sizeof(int32_t) * only.size(), st, [&](unsigned char *hs) {
+                   memcpy(hs, only.data(), sizeof(int32_t) * only.size());
+               }) < 0)
+            return -1;
         HIP_OK(hipMemsetAsync(d_diff, 0x7f, sizeof(int32_t) * (size_t)n_utts, st));
         /* (slices: enough workgroups for a single long utterance, few for a batch of short ones) */
         const unsigned slices = (unsigned)std::min<long long>(
@@ -343,7 +314,7 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
         if (timing)
             fprintf(stderr, "%s: round %d, %d searched, %zu not yet proven "
                             "(plan + scoring %.2f ms, search %.2f, comparison %.2f)\n",
-                    G.who, n_round, n_cmp, again.size(), r1 - r0, r2 - r1, now() - r2);
+                    G.who, n_round, n_cmp, again.size(), r1 - r0, r2 - r1, now_ms() - r2);
         if (again.empty())
             break;
         /* every round proves at least one more frame of each of them (the first differing
@@ -374,18 +345,15 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
         /* history slot 1 as every utterance's first pass leaves it (fpa_carry_rows_kernel): from
          * the features and the proven codebook masks -- d_cbm holds, for every utterance, those of
          * the last plan of its frames */
-        int slot = 0;
-        unsigned char *hs = stage_acquire(m, sizeof(uint32_t) * n_start_words, &slot);
-        if (hs == NULL)
+        uint32_t *d_start = ws_at<uint32_t>(ws, o_start);
+        if (stage_upload(m, d_start, sizeof(uint32_t) * n_start_words, st, [&](unsigned char *hs) {
+                uint32_t *bits = reinterpret_cast<uint32_t *>(hs);
+                memset(bits, 0, sizeof(uint32_t) * n_start_words);
+                for (int u = 0; u < n_utts; ++u)
+                    if (utt_off[u] < n_frames)
+                        bits[(size_t)utt_off[u] >> 5] |= 1u << (utt_off[u] & 31);
+            }) < 0)
             return -1;
-        uint32_t *bits = reinterpret_cast<uint32_t *>(hs);
-        memset(bits, 0, sizeof(uint32_t) * n_start_words);
-        for (int u = 0; u < n_utts; ++u)
-            if (utt_off[u] < n_frames)
-                bits[(size_t)utt_off[u] >> 5] |= 1u << (utt_off[u] & 31);
-        uint32_t *d_start = reinterpret_cast<uint32_t *>(ws + o_start);
-        HIP_OK(hipMemcpyAsync(d_start, bits, sizeof(uint32_t) * n_start_words, hipMemcpyHostToDevice, st));
-        HIP_OK(hipEventRecord(m->ev_stage[slot], st));
         FramesParams F;
         memset(&F, 0, sizeof(F));
         F.utt_start = d_start;
@@ -424,7 +392,7 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
         memcpy(rounds_out, rounds.data(), sizeof(int32_t) * (size_t)n_utts);
     if (timing)
         fprintf(stderr, "%s: assumption (compallsen = yes scoring + search) "
-                        "%.2f ms, %d round(s) %.2f ms\n", G.who, t_spec - t_in, n_round, now() - t_spec);
+                        "%.2f ms, %d round(s) %.2f ms\n", G.who, t_spec - t_in, n_round, now_ms() - t_spec);
     return 0;
 }
 
@@ -461,12 +429,10 @@ ssw_first_pass_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
 {
     if (n_utts == 0)
         return 0;
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    if (check_has_device(m) < 0)
         return -1;
-    }
     if (n_utts < 0 || n_frames < 0 || max_seg < 1 || !utt_off || !word_off || !words || !n_seg
-        || !seg || !d || utt_off[0] != 0 || utt_off[n_utts] != n_frames
+        || !seg || !d || !utt_off_spans(utt_off, n_utts, n_frames)
         || (n_frames > 0 && d_feats == NULL)) {
         ssw_set_error("bad arguments to ssw_first_pass_batch_active");
         return -1;
@@ -476,16 +442,10 @@ ssw_first_pass_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
         return -1;
     int16_t *rows = d_senscr;
     if (rows == NULL) { /* the model's own rows (ssw_align_text_batch's workspace) */
-        const size_t need = (size_t)n_frames * (size_t)m->h->n_sen;
         HIP_OK(hipSetDevice(m->device));
-        if (need > m->text_scr_cap) {
-            (void)hipFree(m->d_text_scr);
-            m->d_text_scr = NULL;
-            m->text_scr_cap = 0;
-            HIP_OK(hipMalloc((void **)&m->d_text_scr, sizeof(int16_t) * std::max(need, (size_t)1)));
-            m->text_scr_cap = need;
-        }
-        rows = m->d_text_scr;
+        if (text_rows_reserve(m, n_frames, "ssw_first_pass_batch_active") < 0)
+            return -1;
+        rows = m->text_scr.as<int16_t>();
     }
     ssw_fp_graphs_t *g = ssw_fp_graphs_build(m, d, cfg, n_utts, word_off, words);
     if (g == NULL)
@@ -521,29 +481,17 @@ ssw_align_text_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    if (check_has_device(m) < 0)
         return NULL;
-    }
     if (n_utts < 0 || n_frames < 0 || (n_frames > 0 && d_feats == NULL) || !utt_off || !word_off
-        || !words || !d || utt_off[0] != 0 || utt_off[n_utts] != n_frames) {
+        || !words || !d || !utt_off_spans(utt_off, n_utts, n_frames)) {
         ssw_set_error("bad arguments to ssw_align_text_batch_active");
         return NULL;
     }
-    const size_t need = (size_t)n_frames * (size_t)m->h->n_sen;
     if (hipSetDevice(m->device) != hipSuccess)
         return NULL;
-    if (need > m->text_scr_cap) {
-        (void)hipFree(m->d_text_scr);
-        m->d_text_scr = NULL;
-        m->text_scr_cap = 0;
-        hipError_t e = hipMalloc((void **)&m->d_text_scr, sizeof(int16_t) * std::max(need, (size_t)1));
-        if (e != hipSuccess) {
-            ssw_set_error("ssw_align_text_batch_active: %s", hipGetErrorString(e));
-            return NULL;
-        }
-        m->text_scr_cap = need;
-    }
+    if (text_rows_reserve(m, n_frames, "ssw_align_text_batch_active") < 0)
+        return NULL;
     checked_texts_t c;
     check_texts(d, n_utts, word_off, words, c);
     ssw_first_pass_plan_t *plan = c.any
@@ -552,7 +500,7 @@ ssw_align_text_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
     if (plan == NULL)
         return NULL;
     fpa_mode_t mode = { scorer, d_feats, cfg != NULL && cfg->two_pass_history != 0 };
-    ssw_alignment_set_t *a = forced_align_core(m, d, NULL, plan, m->d_text_scr, n_frames, utt_off,
+    ssw_alignment_set_t *a = forced_align_core(m, d, NULL, plan, m->text_scr.as<int16_t>(), n_frames, utt_off,
                                                plan->n_utts, NULL, NULL, stream,
                                                c.any ? &c.reject : NULL, NULL, NULL, &mode);
     ssw_first_pass_plan_free(plan);
@@ -570,11 +518,11 @@ ssw_first_pass_active_carry(ssw_model_t *m, int32_t n_utts, uint32_t *rows)
     if (!busy_.ok)
         return -1;
     const size_t n = (size_t)n_utts * (size_t)m->n_cbf;
-    if (n_utts < 0 || rows == NULL || m->d_carry_rows == NULL || n > m->carry_rows_cap) {
+    if (n_utts < 0 || rows == NULL || m->carry_rows.p == NULL || sizeof(uint32_t) * n > m->carry_rows.cap) {
         ssw_set_error("ssw_first_pass_active_carry: no carried orders of %d utterances", n_utts);
         return -1;
     }
     HIP_OK(hipSetDevice(m->device));
-    HIP_OK(hipMemcpy(rows, m->d_carry_rows, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(rows, m->carry_rows.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
     return 0;
 }

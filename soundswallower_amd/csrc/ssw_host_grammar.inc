@@ -361,131 +361,115 @@ grammar_run_t::begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_pl
     if (n_utts == 0)
         return 0;
 
-    /* one staging buffer -> one copy, every array at a 256-byte boundary; the graph's tables
-     * first (they stay while the plan is the last one searched), the call's after them */
-    struct piece { const void *src; size_t bytes, off; };
-    const size_t nG = (size_t)g->n_utts;
-    piece pc[] = {
-        { g->node_off, sizeof(int) * (nG + 1), 0 },                       /* 0 */
-        { g->leaf_off, sizeof(int) * (nG + 1), 0 },
-        { g->state_off, sizeof(int) * (nG + 1), 0 },
-        { g->senid, sizeof(uint16_t) * 4 * (size_t)g->n_nodes, 0 },
-        { g->pen, sizeof(int) * (size_t)g->n_nodes, 0 },
-        { g->parent, sizeof(int) * (size_t)g->n_nodes, 0 },               /* 5 */
-        { g->info, sizeof(uint32_t) * (size_t)g->n_nodes, 0 },
-        { g->ctxt, sizeof(uint64_t) * (size_t)g->n_nodes, 0 },
-        { g->leaf_ord, sizeof(int) * (size_t)g->n_nodes, 0 },
-        { g->leaf_wid, sizeof(int) * (size_t)g->n_leaves, 0 },
-        { g->leaf_node, sizeof(int) * (size_t)g->n_leaves, 0 },           /* 10 */
-        { g->leaf_lscr, sizeof(int) * (size_t)g->n_leaves, 0 },
-        { g->slot_off, sizeof(int) * ((size_t)g->n_states + 1), 0 },
-        { g->slot_leaf, sizeof(int) * (size_t)g->n_slots, 0 },
-        { g->slot_pen, sizeof(int) * (size_t)g->n_slots, 0 },
-        { g->slot_null, sizeof(int) * (size_t)g->n_slots, 0 },            /* 15 */
-        { g->slot_state, sizeof(int) * (size_t)g->n_slots, 0 },
-        { g->ls_off, sizeof(int) * ((size_t)g->n_leaves + 1), 0 },
-        { g->ls_slot, sizeof(int) * (size_t)g->n_ls, 0 },
-        { g->g_start, sizeof(int) * nG, 0 },
-        { g->g_final, sizeof(int) * nG, 0 },                              /* 20 */
-        { g->sn_off, sizeof(int) * (nG + 1), 0 },
-        { g->sn_to, sizeof(int) * (size_t)g->n_sn, 0 },
-        { g->sn_pen, sizeof(int) * (size_t)g->n_sn, 0 },
-        { g->tw, sizeof(int) * (size_t)g->n_tw, 0 },
-        { g->tw_off, sizeof(int) * (nG + 1), 0 },                         /* 25 */
-        { g->twin_ref, sizeof(int) * (size_t)g->n_nodes, 0 },
-        { g->tw_rk, sizeof(int) * nG, 0 },
-        { utt_off, sizeof(int) * ((size_t)n_utts + 1), 0 },               /* 28: the call's */
-        { fsg_of_utt, fsg_of_utt ? sizeof(int) * (size_t)n_utts : 0, 0 },
-        { hist_off.data(), sizeof(long long) * (size_t)n_utts, 0 },       /* 30 */
-        { ws_off.data(), sizeof(long long) * (size_t)n_utts, 0 },
-    };
-    enum { PC_CALL = 28 };
-    const int n_pc = (int)(sizeof(pc) / sizeof(pc[0]));
-    size_t off = 0;
-    for (int i = 0; i < n_pc; ++i) {
-        pc[i].off = off;
-        off = (off + pc[i].bytes + 255) & ~(size_t)255;
-    }
-    const size_t in_bytes = off;
-    nseg_off = off;
-    off += (sizeof(int) * (size_t)n_utts + 255) & ~(size_t)255;
-    score_off = off;
-    off += (sizeof(int) * (size_t)n_utts + 255) & ~(size_t)255;
-    only_off = off; /* (the utterances a round of the default configuration searches) */
-    off += (sizeof(int) * (size_t)n_utts + 255) & ~(size_t)255;
-    seg_off = off;
-    off += (sizeof(ssw_fsg_seg_t) * (size_t)n_utts * (size_t)max_seg + 255) & ~(size_t)255;
-    const size_t hist_at = off;
-    off += (sizeof(int2) * (hist_total ? hist_total : 1) + 255) & ~(size_t)255;
-    const size_t big_at = off;
-    off += (sizeof(int) * ws_ints + 255) & ~(size_t)255;
+    /* one staging buffer -> one copy (WsLayout); the graph's tables first (they stay while the
+     * plan is the last one searched), the call's after `o_call` */
+    const size_t nG = (size_t)g->n_utts, nU = (size_t)n_utts, nN = (size_t)g->n_nodes;
+    const size_t nL = (size_t)g->n_leaves, nS = (size_t)g->n_slots;
+    WsLayout L;
+    const size_t o_node_off = L.in(g->node_off, sizeof(int) * (nG + 1));
+    const size_t o_leaf_off = L.in(g->leaf_off, sizeof(int) * (nG + 1));
+    const size_t o_state_off = L.in(g->state_off, sizeof(int) * (nG + 1));
+    const size_t o_senid = L.in(g->senid, sizeof(uint16_t) * 4 * nN);
+    const size_t o_pen = L.in(g->pen, sizeof(int) * nN);
+    const size_t o_parent = L.in(g->parent, sizeof(int) * nN);
+    const size_t o_info = L.in(g->info, sizeof(uint32_t) * nN);
+    const size_t o_ctxt = L.in(g->ctxt, sizeof(uint64_t) * nN);
+    const size_t o_leaf_ord = L.in(g->leaf_ord, sizeof(int) * nN);
+    const size_t o_leaf_wid = L.in(g->leaf_wid, sizeof(int) * nL);
+    const size_t o_leaf_node = L.in(g->leaf_node, sizeof(int) * nL);
+    const size_t o_leaf_lscr = L.in(g->leaf_lscr, sizeof(int) * nL);
+    const size_t o_slot_off = L.in(g->slot_off, sizeof(int) * ((size_t)g->n_states + 1));
+    const size_t o_slot_leaf = L.in(g->slot_leaf, sizeof(int) * nS);
+    const size_t o_slot_pen = L.in(g->slot_pen, sizeof(int) * nS);
+    const size_t o_slot_null = L.in(g->slot_null, sizeof(int) * nS);
+    const size_t o_slot_state = L.in(g->slot_state, sizeof(int) * nS);
+    const size_t o_ls_off = L.in(g->ls_off, sizeof(int) * (nL + 1));
+    const size_t o_ls_slot = L.in(g->ls_slot, sizeof(int) * (size_t)g->n_ls);
+    const size_t o_g_start = L.in(g->g_start, sizeof(int) * nG);
+    const size_t o_g_final = L.in(g->g_final, sizeof(int) * nG);
+    const size_t o_sn_off = L.in(g->sn_off, sizeof(int) * (nG + 1));
+    const size_t o_sn_to = L.in(g->sn_to, sizeof(int) * (size_t)g->n_sn);
+    const size_t o_sn_pen = L.in(g->sn_pen, sizeof(int) * (size_t)g->n_sn);
+    const size_t o_tw = L.in(g->tw, sizeof(int) * (size_t)g->n_tw);
+    const size_t o_tw_off = L.in(g->tw_off, sizeof(int) * (nG + 1));
+    const size_t o_twin_ref = L.in(g->twin_ref, sizeof(int) * nN);
+    const size_t o_tw_rk = L.in(g->tw_rk, sizeof(int) * nG);
+    const size_t o_call = L.mark();
+    const size_t o_utt_off = L.in(utt_off, sizeof(int) * (nU + 1));
+    const size_t o_fsg_of_utt = L.in(fsg_of_utt, fsg_of_utt ? sizeof(int) * nU : 0);
+    const size_t o_hist_off = L.in(hist_off.data(), sizeof(long long) * nU);
+    const size_t o_ws_off = L.in(ws_off.data(), sizeof(long long) * nU);
+    const size_t in_bytes = L.in_bytes();
+    nseg_off = L.out(sizeof(int) * nU);
+    score_off = L.out(sizeof(int) * nU);
+    only_off = L.out(sizeof(int) * nU); /* (the utterances a round of the default configuration searches) */
+    seg_off = L.out(sizeof(ssw_fsg_seg_t) * nU * (size_t)max_seg);
+    const size_t hist_at = L.out(sizeof(int2) * (hist_total ? hist_total : 1));
+    const size_t big_at = L.out(sizeof(int) * ws_ints);
 
     hipError_t e = hipSetDevice(m->device);
-    if (e == hipSuccess && off > m->gr_ws_cap) { /* grow-only workspace */
-        (void)hipFree(m->d_gr_ws);
-        m->d_gr_ws = NULL;
-        m->gr_ws_cap = 0;
-        m->gr_ws_uid = 0;
-        e = hipMalloc((void **)&m->d_gr_ws, off + off / 4);
-        if (e == hipSuccess)
-            m->gr_ws_cap = off + off / 4;
+    if (e == hipSuccess) {
+        bool moved = false;
+        const int got = devbuf_reserve(m->gr_ws, L.size(), "ssw_grammar_search_batch", L.size() / 4, &moved);
+        if (moved) /* the cached graphs went with the old buffer */
+            m->gr_ws_uid = 0;
+        if (got < 0)
+            return -1;
     }
     const bool cached = m->gr_ws_uid != 0 && m->gr_ws_uid == g->uid;
-    const size_t up_from = cached ? pc[PC_CALL].off : 0;
+    const size_t up_from = cached ? o_call : 0;
     stage.resize(in_bytes - up_from + 1);
     if (e == hipSuccess) {
-        for (int i = 0; i < n_pc; ++i)
-            if (pc[i].bytes && pc[i].off >= up_from)
-                memcpy(stage.data() + (pc[i].off - up_from), pc[i].src, pc[i].bytes);
-        e = hipMemcpyAsync(m->d_gr_ws + up_from, stage.data(), in_bytes - up_from,
+        L.fill(stage.data(), up_from);
+        e = hipMemcpyAsync(m->gr_ws.p + up_from, stage.data(), in_bytes - up_from,
                            hipMemcpyHostToDevice, st);
         m->gr_ws_uid = e == hipSuccess ? g->uid : 0;
         uploaded = true;
     }
     if (e == hipSuccess) {
-        unsigned char *ws = m->d_gr_ws;
+        unsigned char *ws = m->gr_ws.p;
         P.senscr = NULL;
         P.only = NULL;
         P.act_mask = NULL;
         P.act_off = NULL;
-        P.node_off = (const int *)(ws + pc[0].off);
-        P.leaf_off = (const int *)(ws + pc[1].off);
-        P.state_off = (const int *)(ws + pc[2].off);
-        P.senid = (const uint16_t *)(ws + pc[3].off);
-        P.pen = (const int *)(ws + pc[4].off);
-        P.parent = (const int *)(ws + pc[5].off);
-        P.info = (const uint32_t *)(ws + pc[6].off);
-        P.ctxt = (const unsigned long long *)(ws + pc[7].off);
-        P.leaf_ord = (const int *)(ws + pc[8].off);
-        P.leaf_wid = (const int *)(ws + pc[9].off);
-        P.leaf_node = (const int *)(ws + pc[10].off);
-        P.leaf_lscr = (const int *)(ws + pc[11].off);
-        P.slot_off = (const int *)(ws + pc[12].off);
-        P.slot_leaf = (const int *)(ws + pc[13].off);
-        P.slot_pen = (const int *)(ws + pc[14].off);
-        P.slot_null = (const int *)(ws + pc[15].off);
-        P.slot_state = (const int *)(ws + pc[16].off);
-        P.ls_off = (const int *)(ws + pc[17].off);
-        P.ls_slot = (const int *)(ws + pc[18].off);
-        P.g_start = (const int *)(ws + pc[19].off);
-        P.g_final = (const int *)(ws + pc[20].off);
-        P.sn_off = (const int *)(ws + pc[21].off);
-        P.sn_to = (const int *)(ws + pc[22].off);
-        P.sn_pen = (const int *)(ws + pc[23].off);
-        P.tw = (const int *)(ws + pc[24].off);
-        P.tw_off = (const int *)(ws + pc[25].off);
-        P.twin_ref = (const int *)(ws + pc[26].off);
-        P.tw_rk = (const int *)(ws + pc[27].off);
-        P.utt_off = (const int *)(ws + pc[28].off);
-        P.fsg_of_utt = fsg_of_utt ? (const int *)(ws + pc[29].off) : NULL;
-        P.hist_off = (const long long *)(ws + pc[30].off);
-        big_ws = (int *)(ws + big_at);
-        big_ws_off = (const long long *)(ws + pc[31].off);
+        P.node_off = ws_at<const int>(ws, o_node_off);
+        P.leaf_off = ws_at<const int>(ws, o_leaf_off);
+        P.state_off = ws_at<const int>(ws, o_state_off);
+        P.senid = ws_at<const uint16_t>(ws, o_senid);
+        P.pen = ws_at<const int>(ws, o_pen);
+        P.parent = ws_at<const int>(ws, o_parent);
+        P.info = ws_at<const uint32_t>(ws, o_info);
+        P.ctxt = ws_at<const unsigned long long>(ws, o_ctxt);
+        P.leaf_ord = ws_at<const int>(ws, o_leaf_ord);
+        P.leaf_wid = ws_at<const int>(ws, o_leaf_wid);
+        P.leaf_node = ws_at<const int>(ws, o_leaf_node);
+        P.leaf_lscr = ws_at<const int>(ws, o_leaf_lscr);
+        P.slot_off = ws_at<const int>(ws, o_slot_off);
+        P.slot_leaf = ws_at<const int>(ws, o_slot_leaf);
+        P.slot_pen = ws_at<const int>(ws, o_slot_pen);
+        P.slot_null = ws_at<const int>(ws, o_slot_null);
+        P.slot_state = ws_at<const int>(ws, o_slot_state);
+        P.ls_off = ws_at<const int>(ws, o_ls_off);
+        P.ls_slot = ws_at<const int>(ws, o_ls_slot);
+        P.g_start = ws_at<const int>(ws, o_g_start);
+        P.g_final = ws_at<const int>(ws, o_g_final);
+        P.sn_off = ws_at<const int>(ws, o_sn_off);
+        P.sn_to = ws_at<const int>(ws, o_sn_to);
+        P.sn_pen = ws_at<const int>(ws, o_sn_pen);
+        P.tw = ws_at<const int>(ws, o_tw);
+        P.tw_off = ws_at<const int>(ws, o_tw_off);
+        P.twin_ref = ws_at<const int>(ws, o_twin_ref);
+        P.tw_rk = ws_at<const int>(ws, o_tw_rk);
+        P.utt_off = ws_at<const int>(ws, o_utt_off);
+        P.fsg_of_utt = fsg_of_utt ? ws_at<const int>(ws, o_fsg_of_utt) : NULL;
+        P.hist_off = ws_at<const long long>(ws, o_hist_off);
+        big_ws = ws_at<int>(ws, big_at);
+        big_ws_off = ws_at<const long long>(ws, o_ws_off);
         P.tp = (const uint32_t *)m->d_tp;
-        P.hist = (int2 *)(ws + hist_at);
-        P.n_seg = (int *)(ws + nseg_off);
-        P.score = (int *)(ws + score_off);
-        P.seg = (ssw_fsg_seg_t *)(ws + seg_off);
+        P.hist = ws_at<int2>(ws, hist_at);
+        P.n_seg = ws_at<int>(ws, nseg_off);
+        P.score = ws_at<int>(ws, score_off);
+        P.seg = ws_at<ssw_fsg_seg_t>(ws, seg_off);
         P.n_sen = m->h->n_sen;
         P.max_seg = max_seg;
         P.beam = g->beam;
@@ -509,7 +493,7 @@ grammar_run_t::launch(const int16_t *d_senscr, const std::vector<int> *only, uns
                       const long long *d_act_off, const int *d_node_cnt)
 {
     hipError_t e = hipSuccess;
-    unsigned char *ws = m->d_gr_ws;
+    unsigned char *ws = m->gr_ws.p;
     const bool exp = mask != NULL;
     const int n_run = only != NULL && !only->empty() ? (int)only->size() : n_utts;
     P.senscr = d_senscr;
@@ -615,7 +599,7 @@ grammar_run_t::finish()
     std::vector<ssw_fsg_seg_t> seg((size_t)n_utts * (size_t)max_seg);
     hipError_t e = hipSuccess;
     {
-        unsigned char *ws = m->d_gr_ws;
+        unsigned char *ws = m->gr_ws.p;
         if (e == hipSuccess)
             e = hipMemcpyAsync(n_seg.data(), ws + nseg_off, sizeof(int) * (size_t)n_utts,
                                hipMemcpyDeviceToHost, st);
@@ -692,14 +676,12 @@ ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_
                          const int32_t *utt_off, int32_t n_utts, void *stream)
 {
     if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
-        || utt_off[0] != 0 || utt_off[n_utts] != n_frames || (n_frames > 0 && d_senscr == NULL)) {
+        || !utt_off_spans(utt_off, n_utts, n_frames) || (n_frames > 0 && d_senscr == NULL)) {
         ssw_set_error("bad arguments to ssw_grammar_search_batch");
         return NULL;
     }
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    if (check_has_device(m) < 0)
         return NULL;
-    }
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
@@ -729,28 +711,16 @@ ssw_recognize_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_plan_
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    if (check_has_device(m) < 0)
         return NULL;
-    }
-    const size_t need = (size_t)n_frames * (size_t)m->h->n_sen;
     if (hipSetDevice(m->device) != hipSuccess)
         return NULL;
-    if (need > m->text_scr_cap) {
-        (void)hipFree(m->d_text_scr);
-        m->d_text_scr = NULL;
-        m->text_scr_cap = 0;
-        hipError_t e = hipMalloc((void **)&m->d_text_scr, sizeof(int16_t) * need);
-        if (e != hipSuccess) {
-            ssw_set_error("ssw_recognize_batch: %s", hipGetErrorString(e));
-            return NULL;
-        }
-        m->text_scr_cap = need;
-    }
-    if (n_frames > 0
-        && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, m->d_text_scr, stream) < 0)
+    if (text_rows_reserve(m, n_frames, "ssw_recognize_batch") < 0)
         return NULL;
-    return ssw_grammar_search_batch(m, d, plan, fsg_of_utt, m->d_text_scr, n_frames, utt_off,
+    if (n_frames > 0
+        && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, m->text_scr.as<int16_t>(), stream) < 0)
+        return NULL;
+    return ssw_grammar_search_batch(m, d, plan, fsg_of_utt, m->text_scr.as<int16_t>(), n_frames, utt_off,
                                     n_utts, stream);
 }
 
@@ -782,17 +752,15 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
                            int16_t *d_senscr, uint32_t *listed, int32_t *rounds, void *stream)
 {
     if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
-        || utt_off[0] != 0 || utt_off[n_utts] != n_frames || (n_frames > 0 && d_feats == NULL)) {
+        || !utt_off_spans(utt_off, n_utts, n_frames) || (n_frames > 0 && d_feats == NULL)) {
         ssw_set_error("bad arguments to ssw_recognize_batch_active");
         return NULL;
     }
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
-    if (m->device == SSW_DEVICE_NONE) {
-        ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    if (check_has_device(m) < 0)
         return NULL;
-    }
     if (plan->big && !plan->active) {
         ssw_set_error("grammar %d (%s) has %d phone-tree HMMs and is searched from an HBM workspace: "
                       "the default configuration (compallsen = no) holds a plan's largest grammar "
@@ -806,19 +774,9 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
         return NULL;
     int16_t *rows = d_senscr;
     if (rows == NULL) { /* the model's own rows */
-        const size_t need = (size_t)n_frames * (size_t)m->h->n_sen;
-        if (need > m->text_scr_cap) {
-            (void)hipFree(m->d_text_scr);
-            m->d_text_scr = NULL;
-            m->text_scr_cap = 0;
-            hipError_t e = hipMalloc((void **)&m->d_text_scr, sizeof(int16_t) * std::max(need, (size_t)1));
-            if (e != hipSuccess) {
-                ssw_set_error("ssw_recognize_batch_active: %s", hipGetErrorString(e));
-                return NULL;
-            }
-            m->text_scr_cap = need;
-        }
-        rows = m->d_text_scr;
+        if (text_rows_reserve(m, n_frames, "ssw_recognize_batch_active") < 0)
+            return NULL;
+        rows = m->text_scr.as<int16_t>();
     }
     grammar_run_t R;
     if (R.begin(m, d, plan, fsg_of_utt, n_frames, utt_off, n_utts, stream) < 0)

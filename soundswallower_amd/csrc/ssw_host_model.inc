@@ -139,6 +139,14 @@ struct ssw_compact_plan_s {
     uint32_t *d_cpos;
 };
 
+/* The one grow-only device buffer (devbuf_reserve below): a pointer and its capacity in bytes;
+ * all zeros = empty (ssw_model_s is memset). */
+struct DevBuf {
+    unsigned char *p;
+    size_t cap;
+    template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
+};
+
 struct ssw_model_s {
     ssw_host_model_t *h;
     Knobs kn;
@@ -166,18 +174,15 @@ struct ssw_model_s {
     short4 *d_slot_sen;
     uint32_t *d_quad_info; /* per quad: first senone id | (4 consecutive ids) << 16 | codebook << 24 */
     uint16_t *d_sen_slot;  /* slot of every senone in d_mixw's slot order */
-    unsigned char *d_act_ws; /* ssw_align_batch_active: segments, lists, scores (grow-only) */
-    size_t act_ws_cap;
+    DevBuf act_ws; /* ssw_align_batch_active: segments, lists, scores */
     int n_quads, slot_stride;
     /* scoring workspace */
     uint32_t *d_topn_cw;
     int4 *d_topn_sc;
     int *d_utt_off;
     uint32_t *d_utt_start;      /* bit per frame: first frame of an utterance */
-    uint32_t *d_carry0;         /* ssw_score_batch_ex: carried codeword orders, [n_utts][n_cbf] */
-    size_t carry_cap;
-    uint32_t *d_carry_rows;     /* ssw_align_text_batch, two_pass_history: [n_utts][n_cbf] */
-    size_t carry_rows_cap;
+    DevBuf carry0;              /* ssw_score_batch_ex: carried codeword orders, uint32 [n_utts][n_cbf] */
+    DevBuf carry_rows;          /* ssw_align_text_batch, two_pass_history: uint32 [n_utts][n_cbf] */
     unsigned long long *d_nfixed; /* exact in-wave pass: [0] running count, [1] last batch */
     size_t ws_frames, ws_utts, ws_bits, ws_utts_hint, ws_bits_hint, meta_nw;
     std::vector<int32_t> *utt_cache; /* last uploaded utterance offsets */
@@ -214,48 +219,40 @@ struct ssw_model_s {
     int timing, timing_pieced;
     hipEvent_t ev[3];
     /* utterance offsets of ssw_feat_batch */
-    int *d_feat_off;
-    size_t feat_off_cap;
+    DevBuf feat_off;
     /* the front end (ssw_host_fe.inc): its tables on the device and the configuration they were
-     * built for; the blocks that depend on the rate, by configuration and framing; a grow-only
+     * built for; the blocks that depend on the rate, by configuration and framing; a
      * workspace (offsets, mel spectra); per-kernel events */
     ssw_fe_tables_t *d_fe_tab;
     ssw_fe_config_t fe_tab_cfg;
     std::map<std::string, ssw_fe_rate_t *> *fe_rate_tab; /* (a pointer: the struct is memset) */
     int fe_nfilt, fe_noise;
-    unsigned char *d_fe_ws;
-    size_t fe_ws_cap;
+    DevBuf fe_ws;
     hipEvent_t fe_ev[4];
     int fe_ev_ready, fe_timed;
     /* alignment workspace (ssw_align_batch) */
-    unsigned char *d_align_ws;
-    unsigned char *d_fp_ws; /* first-pass workspace (grow-only) */
+    DevBuf align_ws;
+    DevBuf fp_ws;           /* first-pass workspace */
     hipStream_t s_up;       /* the first pass uploads its graphs here, beside the caller's stream */
     hipEvent_t ev_up;
-    size_t fp_ws_cap;
-    uint64_t fp_ws_uid;     /* the graphs whose tables d_fp_ws holds (ssw_fp_graphs_t::uid), 0 = none */
+    uint64_t fp_ws_uid;     /* the graphs whose tables fp_ws holds (ssw_fp_graphs_t::uid), 0 = none */
     size_t fp_ws_uid_bytes; /* and how much of the workspace they take */
     /* the default configuration's first pass as a batch (ssw_host_fpactive.inc): its workspace,
      * and -- while one of its searches runs -- where first_pass_kernel<.., EXPORT> writes the
      * sets of active HMMs (NULL otherwise) */
-    unsigned char *d_fpa_ws;
-    size_t fpa_ws_cap;
+    DevBuf fpa_ws;
     unsigned long long *fpa_mask;
     const long long *fpa_act_off;
     const int *fpa_node_cnt; /* device [n_utts]: phone-tree HMMs of every utterance's graph */
     int64_t gra_stats[4]; /* as fpa_stats, of ssw_recognize_batch_active */
     int64_t fpa_stats[4]; /* utterances, verify rounds summed over them, rounds of the last call, utterances that needed more than one */
-    int16_t *d_text_scr; /* ssw_align_text_batch's score rows (grow-only) */
-    size_t text_scr_cap;
-    /* grammar search (ssw_host_grammar.inc): workspace (grow-only) and the plan whose graphs
-     * it holds (ssw_fp_graphs_t::uid, 0 = none) */
-    unsigned char *d_gr_ws;
-    size_t gr_ws_cap;
+    DevBuf text_scr; /* ssw_align_text_batch's score rows, int16 [n_frames][n_sen] (text_rows_reserve) */
+    /* grammar search (ssw_host_grammar.inc): workspace and the plan whose graphs it holds
+     * (ssw_fp_graphs_t::uid, 0 = none) */
+    DevBuf gr_ws;
     uint64_t gr_ws_uid;
-    size_t align_ws_bytes;
-    /* ssw_score_batch_compact's fall-back: full rows of a launch that has no COMPACT instance */
-    int16_t *d_full_tmp;
-    size_t full_tmp_cap;
+    /* ssw_score_batch_compact's fall-back: full int16 rows of a launch that has no COMPACT instance */
+    DevBuf full_tmp;
 };
 
 static inline void
@@ -351,6 +348,98 @@ stage_acquire(ssw_model_s *m, size_t bytes, int *slot_out)
     }
     *slot_out = k;
     return m->h_stage[k];
+}
+
+/* what follows every use of a staging slot: the event behind the copies that read or write it.
+ * A slot whose event was not recorded is handed out again while its copy may still run. */
+static int
+stage_release(ssw_model_s *m, int slot, hipStream_t st)
+{
+    HIP_OK(hipEventRecord(m->ev_stage[slot], st));
+    return 0;
+}
+
+/* The one pinned upload: a slot of `bytes`, fill(slot) writes them, one asynchronous copy to
+ * d_dst on `st`, the slot's event behind it.  -1 with the error set. */
+template <typename F>
+static int
+stage_upload(ssw_model_s *m, void *d_dst, size_t bytes, hipStream_t st, F fill)
+{
+    int slot = 0;
+    unsigned char *hs = stage_acquire(m, bytes, &slot);
+    if (hs == NULL)
+        return -1;
+    fill(hs);
+    HIP_OK(hipMemcpyAsync(d_dst, hs, bytes, hipMemcpyHostToDevice, st));
+    return stage_release(m, slot, st);
+}
+
+/* The one grow-only device buffer.  bytes <= cap: returns at once, no HIP call (what every
+ * steady-state call takes).  Else the buffer is freed and max(bytes + slack, 1) bytes are
+ * allocated; *moved (if given) is set, for callers that key a cache on the buffer's contents.
+ * On failure the buffer is empty, HIP's sticky error is cleared, the message names `who` and
+ * the size, and -1 is returned.
+ * No caller synchronises its stream before this: hipFree performs an implicit
+ * hipDeviceSynchronize() (hip_runtime_api.h, hipFree), so nothing still reads the old buffer
+ * when it goes.  The device must be current (hipSetDevice) -- every caller has done that. */
+static int
+devbuf_reserve(DevBuf &b, size_t bytes, const char *who, size_t slack = 0, bool *moved = NULL)
+{
+    if (bytes <= b.cap)
+        return 0;
+    (void)hipFree(b.p);
+    b.p = NULL;
+    b.cap = 0;
+    if (moved != NULL)
+        *moved = true;
+    const size_t want = std::max(bytes + slack, (size_t)1);
+    const hipError_t e = hipMalloc((void **)&b.p, want);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = NULL;
+        ssw_set_error("%s: %zu bytes of device memory: %s", who, want, hipGetErrorString(e));
+        return -1;
+    }
+    b.cap = want;
+    return 0;
+}
+
+/* the model's own score rows, int16 [n_frames][n_sen] (the text and grammar entry points) */
+static int
+text_rows_reserve(ssw_model_s *m, int32_t n_frames, const char *who)
+{
+    return devbuf_reserve(m->text_scr, sizeof(int16_t) * (size_t)n_frames * (size_t)m->h->n_sen, who);
+}
+
+/* history slot 1 after every utterance's first pass, uint32 [n_utts][n_cbf] (two_pass_history) */
+static int
+carry_rows_reserve(ssw_model_s *m, int32_t n_utts, const char *who)
+{
+    return devbuf_reserve(m->carry_rows, sizeof(uint32_t) * (size_t)m->n_cbf * (size_t)n_utts, who);
+}
+
+/* the refusals the batch entry points share, once; -1 with the message set */
+static int
+check_has_device(const ssw_model_s *m)
+{
+    if (m->device != SSW_DEVICE_NONE)
+        return 0;
+    ssw_set_error("model was loaded with device = SSW_DEVICE_NONE: no GPU, no CPU fallback");
+    return -1;
+}
+
+/* utt_off starts at 0 and ends at n_frames (n_utts >= 0 and utt_off != NULL checked first) */
+static bool
+utt_off_spans(const int32_t *utt_off, int32_t n_utts, int32_t n_frames)
+{
+    return utt_off[0] == 0 && utt_off[n_utts] == n_frames;
+}
+
+static inline double
+now_ms()
+{
+    return std::chrono::duration<double, std::milli>(
+               std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 template <typename T>
@@ -657,23 +746,23 @@ ssw_model_free(ssw_model_t *m)
     (void)hipFree(m->d_exlist);
     (void)hipFree(m->d_wfrag);
     (void)hipFree(m->d_exlistm);
-    (void)hipFree(m->d_align_ws);
-    (void)hipFree(m->d_fp_ws);
-    (void)hipFree(m->d_fpa_ws);
-    (void)hipFree(m->d_gr_ws);
-    (void)hipFree(m->d_text_scr);
-    (void)hipFree(m->d_feat_off);
+    (void)hipFree(m->align_ws.p);
+    (void)hipFree(m->fp_ws.p);
+    (void)hipFree(m->fpa_ws.p);
+    (void)hipFree(m->gr_ws.p);
+    (void)hipFree(m->text_scr.p);
+    (void)hipFree(m->feat_off.p);
     (void)hipFree(m->d_fe_tab);
     if (m->fe_rate_tab)
         for (auto &kv : *m->fe_rate_tab)
             (void)hipFree(kv.second);
     delete m->fe_rate_tab;
-    (void)hipFree(m->d_fe_ws);
+    (void)hipFree(m->fe_ws.p);
     if (m->fe_ev_ready)
         for (int i = 0; i < 4; ++i)
             (void)hipEventDestroy(m->fe_ev[i]);
     (void)hipFree(m->d_sen_slot);
-    (void)hipFree(m->d_act_ws);
+    (void)hipFree(m->act_ws.p);
     (void)hipFree(m->d_mixw);
     (void)hipFree(m->d_ms_pdf);
     (void)hipFree(m->d_sen2cb);
@@ -690,8 +779,8 @@ ssw_model_free(ssw_model_t *m)
     (void)hipFree(m->d_topn_cw);
     (void)hipFree(m->d_topn_sc);
     (void)hipFree(m->d_utt_off); /* (d_utt_start lies in the same allocation) */
-    (void)hipFree(m->d_carry0);
-    (void)hipFree(m->d_carry_rows);
+    (void)hipFree(m->carry0.p);
+    (void)hipFree(m->carry_rows.p);
     (void)hipFree(m->d_nfixed);
     delete m->utt_cache;
     delete m->xcd_cuts;
@@ -715,7 +804,7 @@ ssw_model_free(ssw_model_t *m)
             (void)hipFree(m->d_pipe_out[k]);
         }
     }
-    (void)hipFree(m->d_full_tmp);
+    (void)hipFree(m->full_tmp.p);
     if (m->timing)
         for (int i = 0; i < 3; ++i)
             (void)hipEventDestroy(m->ev[i]);

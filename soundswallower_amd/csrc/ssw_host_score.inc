@@ -393,16 +393,9 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
                                   (carry_in[i] >> (8 * k)) & 0xffu, m->h->n_density);
                     return -1;
                 }
-        const size_t ncar = (size_t)m->n_cbf * (size_t)n_utts;
-        if (ncar > m->carry_cap) {
-            HIP_OK(hipStreamSynchronize(st)); /* (the old buffer may still be read) */
-            (void)hipFree(m->d_carry0);
-            m->d_carry0 = NULL;
-            m->carry_cap = 0;
-            if (dev_alloc(&m->d_carry0, ncar) < 0)
-                return -1;
-            m->carry_cap = ncar;
-        }
+        if (devbuf_reserve(m->carry0, sizeof(uint32_t) * (size_t)m->n_cbf * (size_t)n_utts,
+                           "ssw_score_batch_ex") < 0)
+            return -1;
     }
     /* the offsets rarely change between calls of one job: upload only when they do
      * (cache key: the chain flag, then the offsets) */
@@ -429,7 +422,7 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
             for (size_t i = 0; i < ncar; ++i)
                 car[i] = 0x03020100u;
             memcpy(car, carry_in, sizeof(uint32_t) * (size_t)m->n_cbf);
-            HIP_OK(hipMemcpyAsync(m->d_carry0, car, b_car, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(m->carry0.as<uint32_t>(), car, b_car, hipMemcpyHostToDevice, st));
         }
         if (new_offsets) {
             m->utt_cache->assign(1, chain ? 1 : 0);
@@ -454,7 +447,8 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
             HIP_OK(hipMemcpyAsync(m->d_utt_off, hoff, sizeof(uint32_t) * (m->ws_utts + 2 * nw),
                                   hipMemcpyHostToDevice, st));
         }
-        HIP_OK(hipEventRecord(m->ev_stage[slot], st));
+        if (stage_release(m, slot, st) < 0)
+            return -1;
     }
     const ssw_host_model_t *h = m->h;
     ChainParams P;
@@ -465,7 +459,7 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
     /* a call that continues an utterance (a piece of ssw_score_batch_host's cut): the in-utterance
      * number of its frame 0, which decides the frames a ds > 1 model re-scans on */
     P.frame_base = frame_base;
-    P.carry_pk = (carry_in != NULL && !ms) ? m->d_carry0 : NULL;
+    P.carry_pk = (carry_in != NULL && !ms) ? m->carry0.as<uint32_t>() : NULL;
     if (d_carry_rows != NULL && !ms) /* a row per utterance, already on the device */
         P.carry_pk = d_carry_rows;
     const int64_t pairs = (int64_t)n_frames * m->n_cbf;
@@ -550,7 +544,7 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
         F.topn_cw = m->d_topn_cw;
         F.topn_sc = m->d_topn_sc;
         F.utt_start = m->d_utt_start;
-        F.carry0 = (carry_in != NULL && !ms) ? m->d_carry0 : NULL;
+        F.carry0 = (carry_in != NULL && !ms) ? m->carry0.as<uint32_t>() : NULL;
         F.carry_rows = ms ? NULL : d_carry_rows;
         F.utt_off = m->d_utt_off;
         F.n_utts = n_utts;

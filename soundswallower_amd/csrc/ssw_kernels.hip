@@ -53,6 +53,14 @@
  *                        (fsg_search_start / _null_prop / _find_exit, src/fsg_search.c:543-924)
  *                        grammar_search_big_kernel: the same search from an HBM workspace, for
  *                        grammars beyond one workgroup (ssw_grammar_prepare_large)
+ *   ssw_ws_layout.inc    host, no HIP: align256 and WsLayout, the one layout of a device
+ *                        workspace (256-byte-aligned offsets in call order, the uploaded pieces
+ *                        staged by fill(); a host program can include it on its own)
+ *   ssw_host_model.inc   also the host side's three shared helpers, each holding one policy:
+ *                        devbuf_reserve (the grow-only device buffer: no HIP call unless it
+ *                        grows, hipFree's implicit synchronisation, sticky error cleared),
+ *                        WsLayout (above), stage_upload / stage_release (the pinned upload: the
+ *                        slot's event is always recorded behind its copies)
  *   ssw_host_*.inc       device model and loaders' upload, batched scoring, alignment, the
  *                        mgau_t / search-module shaped objects, features, the front end
  *                        (ssw_host_fe.inc; its tables are built in ssw_model.c), device-memory
@@ -112,6 +120,7 @@ namespace {
 
 } // namespace
 
+#include "ssw_ws_layout.inc"
 #include "ssw_host_model.inc"
 #include "ssw_host_score.inc"
 #include "ssw_host_align.inc"
