@@ -104,6 +104,8 @@ def lib() -> C.CDLL:
     L.ssw_model_info.argtypes = [vp, C.POINTER(SswModelInfo)]
     L.ssw_model_selftest_message.restype = C.c_char_p
     L.ssw_model_selftest_message.argtypes = [vp]
+    L.ssw_model_scorer.restype = C.c_int
+    L.ssw_model_scorer.argtypes = [vp]
     L.ssw_model_table.restype = vp
     L.ssw_model_table.argtypes = [vp, C.c_int, C.POINTER(sz)]
     L.ssw_score_batch.argtypes = [vp, C.c_int, vp, i32, vp, i32, vp, vp]
@@ -134,6 +136,8 @@ def lib() -> C.CDLL:
     L.ssw_ptm_mgau_init.argtypes = [vp]
     L.ssw_ms_mgau_init.restype = C.POINTER(SswMgau)
     L.ssw_ms_mgau_init.argtypes = [vp]
+    L.ssw_s2_semi_mgau_init.restype = C.POINTER(SswMgau)
+    L.ssw_s2_semi_mgau_init.argtypes = [vp]
     L.ssw_mgau_reset_hist.argtypes = [C.POINTER(SswMgau)]
     L.ssw_mgau_prescore.argtypes = [C.POINTER(SswMgau), vp, i32]
     L.ssw_align_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -17,6 +17,7 @@ from ._lib import SswAlignEntry, SswConfig, SswFeConfig, SswModelInfo
 
 SCORER_PTM = 0
 SCORER_MS = 1
+SCORER_S2_SEMI = 2
 SSW_DEVICE_NONE = -2
 INT_MAX = 2**31 - 1
 
@@ -143,6 +144,21 @@ class Model:
 
     __del__ = close
 
+    def scorer(self) -> int:
+        """ssw_model_scorer: the scorer the reference's acmod_load_am would choose for the model
+        (SCORER_PTM, SCORER_S2_SEMI for a single codebook, SCORER_MS), -1 when it has the
+        mixture weights of none."""
+        return int(self._L.ssw_model_scorer(self._m))
+
+    def pick_scorer(self, scorer=None) -> int:
+        """the scorer a call without one takes: SCORER_S2_SEMI for a single-codebook model, else
+        SCORER_PTM (SCORER_MS is asked for by name)"""
+        if scorer is not None:
+            return int(scorer)
+        if getattr(self, "_default_scorer", None) is None:
+            self._default_scorer = SCORER_S2_SEMI if self.scorer() == SCORER_S2_SEMI else SCORER_PTM
+        return self._default_scorer
+
     @property
     def tmat_n_emit(self) -> int:
         """Emitting states of the transition matrices (3 for both shipped models; 1, 2, 4 or 5
@@ -163,7 +179,7 @@ class Model:
         return np.frombuffer(buf, dtype=dtype).copy()
 
     # ---- scoring ------------------------------------------------------------------
-    def score_batch(self, feats, utt_off=None, scorer=SCORER_PTM, out=None) -> np.ndarray:
+    def score_batch(self, feats, utt_off=None, scorer=None, out=None) -> np.ndarray:
         """Score host features [n_frames][39]; returns int16 [n_frames][n_sen] (`out`, if given:
         a caller that scores batch after batch reuses one buffer instead of faulting in 10 KB
         of fresh pages per frame)."""
@@ -174,27 +190,27 @@ class Model:
         if out is None:
             out = np.zeros((n, self.n_sen), np.int16)
         assert out.dtype == np.int16 and out.shape == (n, self.n_sen) and out.flags.c_contiguous
-        _check(self._L.ssw_score_batch_host(self._m, scorer, _ptr(feats), n, _ptr(off),
+        _check(self._L.ssw_score_batch_host(self._m, self.pick_scorer(scorer), _ptr(feats), n, _ptr(off),
                                             len(off) - 1, _ptr(out)), "ssw_score_batch_host")
         return out
 
     def score_batch_device(self, d_feats, n_frames, utt_off, d_out, stream=None,
-                           scorer=SCORER_PTM, share_device=False):
+                           scorer=None, share_device=False):
         """Device pointers (ints or torch tensors); asynchronous on `stream`.  share_device:
         SSW_SCORE_SHARE_DEVICE, for callers that run another stream's kernels beside it."""
         off = np.ascontiguousarray(utt_off, np.int32)
         st = C.c_void_p(int(stream)) if stream else None
         if share_device:
-            _check(self._L.ssw_score_batch_ex(self._m, scorer, _ptr(d_feats), int(n_frames),
+            _check(self._L.ssw_score_batch_ex(self._m, self.pick_scorer(scorer), _ptr(d_feats), int(n_frames),
                                               _ptr(off), len(off) - 1, _ptr(d_out), st, 2, None,
                                               None), "ssw_score_batch_ex")
             return
-        _check(self._L.ssw_score_batch(self._m, scorer, _ptr(d_feats), int(n_frames), _ptr(off),
+        _check(self._L.ssw_score_batch(self._m, self.pick_scorer(scorer), _ptr(d_feats), int(n_frames), _ptr(off),
                                        len(off) - 1, _ptr(d_out), st),
                "ssw_score_batch")
 
     def score_batch_carry(self, feats, utt_off=None, carry_in=None, carry_utts=False,
-                          scorer=SCORER_PTM, rewind=False):
+                          scorer=None, rewind=False):
         """ssw_score_batch_ex on host features: returns (scores int16 [n][n_sen], carry_out
         uint32 [n_cb * n_feat]); carry_in = the carry_out of an earlier call (or None).
         rewind = SSW_SCORE_CARRY_OUT_REWIND: carry_out is what the NEXT utterance, or the second
@@ -213,7 +229,7 @@ class Model:
         d_in = self.to_device(feats)
         d_out = self.device_malloc(out.nbytes)
         try:
-            _check(self._L.ssw_score_batch_ex(self._m, scorer, d_in, n, _ptr(off), len(off) - 1,
+            _check(self._L.ssw_score_batch_ex(self._m, self.pick_scorer(scorer), d_in, n, _ptr(off), len(off) - 1,
                                               d_out, None, flags, _ptr(cin),
                                               _ptr(cout)), "ssw_score_batch_ex")
             _check(self._L.ssw_memcpy_d2h(_ptr(out), d_out, out.nbytes), "ssw_memcpy_d2h")
@@ -351,7 +367,7 @@ class Model:
 
     def align_batch_active(self, d_feats, frame_off, phone_off, senid, tmatid, sf=None, ef=None,
                            seed_active=None, state_init=None, d_senscr=None, stream=None,
-                           scorer=SCORER_PTM):
+                           scorer=None):
         """ssw_align_batch_active: scoring over the search's active senones (compallsen = no) +
         forced alignment; returns (states[n,3] int32, status[n_utts])."""
         frame_off = np.ascontiguousarray(frame_off, np.int32)
@@ -368,7 +384,7 @@ class Model:
         status = np.zeros(n_utts, np.int32)
         seed = None if seed_active is None else np.ascontiguousarray(seed_active, np.uint32)
         _check(self._L.ssw_align_batch_active_ex(
-            self._m, int(scorer), _ptr(d_feats), n_utts, _ptr(frame_off), _ptr(phone_off), _ptr(senid),
+            self._m, self.pick_scorer(scorer), _ptr(d_feats), n_utts, _ptr(frame_off), _ptr(phone_off), _ptr(senid),
             _ptr(tmatid), _ptr(sf), _ptr(ef), _ptr(seed), _ptr(states), _ptr(status),
             _ptr(d_senscr), C.c_void_p(int(stream)) if stream else None),
             "ssw_align_batch_active")
@@ -378,11 +394,11 @@ class Model:
     def compact_plan(self, frame_off, phone_off, senid, stream=None) -> "CompactPlan":
         return CompactPlan(self, frame_off, phone_off, senid, stream)
 
-    def score_batch_compact(self, d_feats, plan, d_compact, stream=None, scorer=SCORER_PTM,
+    def score_batch_compact(self, d_feats, plan, d_compact, stream=None, scorer=None,
                             share_device=False):
         """ssw_score_batch_compact: the plan's batch scored into rows that hold each
         utterance's own states only; asynchronous on `stream`."""
-        _check(self._L.ssw_score_batch_compact(self._m, int(scorer), _ptr(d_feats), plan._p,
+        _check(self._L.ssw_score_batch_compact(self._m, self.pick_scorer(scorer), _ptr(d_feats), plan._p,
                                                _ptr(d_compact),
                                                C.c_void_p(int(stream)) if stream else None,
                                                2 if share_device else 0), "ssw_score_batch_compact")
@@ -751,6 +767,18 @@ class MsMgau(PtmMgau):
             raise SswError("ssw_ms_mgau_init: " + _lib.last_error())
 
 
+class S2SemiMgau(PtmMgau):
+    """`mgau_t` stand-in created by ssw_s2_semi_mgau_init (the "s2_semi" scorer of a
+    single-codebook model)."""
+
+    def __init__(self, model: Model):
+        self._L = _lib.lib()
+        self.model = model
+        self._g = self._L.ssw_s2_semi_mgau_init(model._m)
+        if not self._g:
+            raise SswError("ssw_s2_semi_mgau_init: " + _lib.last_error())
+
+
 class Lexicon:
     """Pronunciation dictionary + alignment_populate on the host (ssw_dict_load,
     ssw_alignment_populate): words and their windows -> the per-phone rows the aligner takes."""
@@ -899,7 +927,7 @@ class Lexicon:
         return n_seg, seg
 
     def first_pass_active(self, d_feats, utt_off, texts, cfg=None, max_seg=None, stream=None,
-                          scorer=SCORER_PTM, d_senscr=None, want_seed=False):
+                          scorer=None, d_senscr=None, want_seed=False):
         """ssw_first_pass_batch_active: the first pass in the reference's DEFAULT configuration
         (compallsen = no) for a batch, from feature rows in HBM.  Returns (segmentations as
         first_pass does, rounds int32 [n_utts]) and, with want_seed, the uint32
@@ -919,7 +947,7 @@ class Lexicon:
         return (out, rounds, seed) if want_seed else (out, rounds)
 
     def first_pass_active_raw(self, d_feats, utt_off, texts, cfg=None, max_seg=None, stream=None,
-                              scorer=SCORER_PTM, d_senscr=None, want_seed=False):
+                              scorer=None, d_senscr=None, want_seed=False):
         """The C call alone: (n_seg, seg WORD_SEG_DTYPE [n_utts][max_seg], rounds, seed or None);
         texts: list of word lists, or a Texts."""
         off = np.ascontiguousarray(utt_off, np.int32)
@@ -933,8 +961,8 @@ class Lexicon:
         rounds = np.zeros(n_utts, np.int32)
         seed = np.zeros((n_utts, (self.model.n_sen + 31) // 32), np.uint32) if want_seed else None
         _check(self._L.ssw_first_pass_batch_active(
-            self.model._m, self._d, None if cfg is None else C.byref(cfg), int(scorer),
-            _ptr(d_feats), int(off[-1]), _ptr(off), n_utts, _ptr(tx.word_off), tx.arr, max_seg,
+            self.model._m, self._d, None if cfg is None else C.byref(cfg),
+            self.model.pick_scorer(scorer), _ptr(d_feats), int(off[-1]), _ptr(off), n_utts, _ptr(tx.word_off), tx.arr, max_seg,
             _ptr(n_seg), _ptr(seg), _ptr(seed), _ptr(d_senscr), _ptr(rounds), _ptr(stream)),
             "ssw_first_pass_batch_active")
         return n_seg, seg, rounds, seed
@@ -1082,7 +1110,7 @@ class Texts:
 
 
 def align_text_batch(model: Model, lex: Lexicon, d_feats, utt_off, texts, cfg=None,
-                     scorer=SCORER_PTM, stream=None) -> AlignmentSet:
+                     scorer=None, stream=None) -> AlignmentSet:
     """ssw_align_text_batch: feature rows in HBM + texts (list of word lists, or a Texts) ->
     alignments (scoring, first pass, populate, constrained state alignment, propagate) in one C
     call."""
@@ -1091,7 +1119,8 @@ def align_text_batch(model: Model, lex: Lexicon, d_feats, utt_off, texts, cfg=No
     tx = texts if isinstance(texts, Texts) else Texts(texts)
     assert tx.n_utts == n_utts
     L = _lib.lib()
-    h = L.ssw_align_text_batch(model._m, lex._d, None if cfg is None else C.byref(cfg), scorer,
+    h = L.ssw_align_text_batch(model._m, lex._d, None if cfg is None else C.byref(cfg),
+                               model.pick_scorer(scorer),
                                _ptr(d_feats), int(off[-1]), _ptr(off), n_utts, _ptr(tx.word_off),
                                tx.arr, _ptr(stream))
     if not h:
@@ -1100,7 +1129,7 @@ def align_text_batch(model: Model, lex: Lexicon, d_feats, utt_off, texts, cfg=No
 
 
 def align_text_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, texts, cfg=None,
-                            scorer=SCORER_PTM, stream=None) -> AlignmentSet:
+                            scorer=None, stream=None) -> AlignmentSet:
     """ssw_align_text_batch_active: align_text_batch in the reference's DEFAULT configuration
     (compallsen = no): both passes score what their searches hold active."""
     off = np.ascontiguousarray(utt_off, np.int32)
@@ -1109,15 +1138,15 @@ def align_text_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, texts,
     assert tx.n_utts == n_utts
     L = _lib.lib()
     h = L.ssw_align_text_batch_active(model._m, lex._d, None if cfg is None else C.byref(cfg),
-                                      scorer, _ptr(d_feats), int(off[-1]), _ptr(off), n_utts,
-                                      _ptr(tx.word_off), tx.arr, _ptr(stream))
+                                      model.pick_scorer(scorer), _ptr(d_feats), int(off[-1]),
+                                      _ptr(off), n_utts, _ptr(tx.word_off), tx.arr, _ptr(stream))
     if not h:
         raise SswError("ssw_align_text_batch_active: " + _lib.last_error())
     return AlignmentSet(L, h, lex)
 
 
 def align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, texts, cfg=None, active=False,
-                      fe_cfg=None, scorer=SCORER_PTM, stream=None, samprate=None) -> AlignmentSet:
+                      fe_cfg=None, scorer=None, stream=None, samprate=None) -> AlignmentSet:
     """Audio and text in, alignments out: what decoder_process_int16 over each utterance and
     decoder_alignment give (src/decoder.c:737-798), for a batch.  int16 PCM (host array or
     device tensor; utterance u = samples samp_off[u] .. samp_off[u + 1]) -> ssw_fe_batch ->
@@ -1436,13 +1465,13 @@ def grammar_search_batch(model: Model, lex: Lexicon, d_senscr, utt_off, plan: Gr
 
 
 def recognize_batch(model: Model, lex: Lexicon, d_feats, utt_off, plan: GrammarPlan,
-                    fsg_of_utt=None, scorer=SCORER_PTM, stream=None) -> RecognitionSet:
+                    fsg_of_utt=None, scorer=None, stream=None) -> RecognitionSet:
     """ssw_recognize_batch: feature rows in HBM -> all senone scores -> grammar search."""
     off = np.ascontiguousarray(utt_off, np.int32)
     n_utts = len(off) - 1
     g = _fsg_of_utt(fsg_of_utt, n_utts)
     L = _lib.lib()
-    h = L.ssw_recognize_batch(model._m, lex._d, plan._p, _ptr(g), scorer, _ptr(d_feats),
+    h = L.ssw_recognize_batch(model._m, lex._d, plan._p, _ptr(g), model.pick_scorer(scorer), _ptr(d_feats),
                               int(off[-1]), _ptr(off), n_utts, _ptr(stream))
     if not h:
         raise SswError("ssw_recognize_batch: " + _lib.last_error())
@@ -1450,7 +1479,7 @@ def recognize_batch(model: Model, lex: Lexicon, d_feats, utt_off, plan: GrammarP
 
 
 def recognize_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, plan: GrammarPlan,
-                           fsg_of_utt=None, scorer=SCORER_PTM, d_senscr=None, want_listed=False,
+                           fsg_of_utt=None, scorer=None, d_senscr=None, want_listed=False,
                            stream=None):
     """ssw_recognize_batch_active: recognition in the reference's DEFAULT configuration
     (compallsen = no) from feature rows in HBM.  Returns (RecognitionSet, rounds int32 [n_utts])
@@ -1463,7 +1492,8 @@ def recognize_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, plan: G
     rounds = np.zeros(n_utts, np.int32)
     listed = np.zeros((int(off[-1]), (model.n_sen + 31) // 32), np.uint32) if want_listed else None
     L = _lib.lib()
-    h = L.ssw_recognize_batch_active(model._m, lex._d, plan._p, _ptr(g), scorer, _ptr(d_feats),
+    h = L.ssw_recognize_batch_active(model._m, lex._d, plan._p, _ptr(g),
+                                     model.pick_scorer(scorer), _ptr(d_feats),
                                      int(off[-1]), _ptr(off), n_utts, _ptr(d_senscr),
                                      _ptr(listed), _ptr(rounds), _ptr(stream))
     if not h:
@@ -1473,7 +1503,7 @@ def recognize_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, plan: G
 
 
 def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: GrammarPlan,
-                          fsg_of_utt=None, samprate=None, fe_cfg=None, scorer=SCORER_PTM,
+                          fsg_of_utt=None, samprate=None, fe_cfg=None, scorer=None,
                           stream=None, active=False) -> RecognitionSet:
     """Audio in, hypotheses out: decoder_process_int16(full_utt) + decoder_hyp / decoder_seg_iter
     under decoder_set_fsg with compallsen = yes, for a batch.  int16 PCM (host array or device

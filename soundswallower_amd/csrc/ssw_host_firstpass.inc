@@ -861,9 +861,11 @@ ssw_align_text_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_c
         int32_t n_frames, n_utts;
         const int32_t *utt_off;
         void *stream;
-    } rs = { m, d_feats, n_frames, n_utts, utt_off, stream };
-    const bool two_pass = cfg != NULL && cfg->two_pass_history && scorer == SSW_SCORER_PTM
-        && n_frames > 0 && n_utts > 0;
+        int scorer;
+    } rs = { m, d_feats, n_frames, n_utts, utt_off, stream, scorer };
+    /* (the s2_semi scorer keeps the same ring of two slots, src/s2_semi_mgau.c:845-855) */
+    const bool two_pass = cfg != NULL && cfg->two_pass_history
+        && (scorer == SSW_SCORER_PTM || scorer == SSW_SCORER_S2_SEMI) && n_frames > 0 && n_utts > 0;
     if (two_pass) {
         if (carry_rows_reserve(m, n_utts, "ssw_align_text_batch") < 0)
             return NULL;
@@ -877,7 +879,7 @@ ssw_align_text_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_c
     }
     auto rescore = [](void *arg) -> int {
         rescore_t *r = static_cast<rescore_t *>(arg);
-        return score_batch_impl(r->m, SSW_SCORER_PTM, r->d_feats, r->n_frames, r->utt_off,
+        return score_batch_impl(r->m, r->scorer, r->d_feats, r->n_frames, r->utt_off,
                                 r->n_utts, r->m->text_scr.as<int16_t>(), r->stream, 0u, NULL, NULL, NULL,
                                 r->m->carry_rows.as<uint32_t>());
     };

@@ -419,6 +419,23 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
                    rounds_out, NULL, m->fpa_stats, stream, d_carry_out);
 }
 
+/* The s2_semi scorer in the *_active calls.  s2_semi_mgau_frame_eval evaluates every Gaussian and
+ * normalises per stream by its best density whatever the active set is (src/s2_semi_mgau.c:
+ * 841-872): compallsen = no only restricts which senones are summed, and the search reads the
+ * listed ones alone.  The default configuration's search therefore reads the very scores of the
+ * compallsen = yes rows, and these calls take that route: one search, nothing to prove.  The
+ * stats report one round per utterance and every first assumption accepted; the sets of listed
+ * senones are not made (seed_active / listed are refused), d_senscr receives whole rows. */
+static void
+semi_active_done(int64_t stats[4], int32_t n_utts, int32_t *rounds)
+{
+    stats[0] += n_utts;
+    stats[1] += n_utts;
+    stats[2] = 1;
+    for (int u = 0; rounds != NULL && u < n_utts; ++u)
+        rounds[u] = 1;
+}
+
 extern "C" int
 ssw_first_pass_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_config_t *cfg,
                             int scorer, const float *d_feats, int32_t n_frames,
@@ -446,6 +463,21 @@ ssw_first_pass_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
         if (text_rows_reserve(m, n_frames, "ssw_first_pass_batch_active") < 0)
             return -1;
         rows = m->text_scr.as<int16_t>();
+    }
+    if (scorer == SSW_SCORER_S2_SEMI) { /* the compallsen = yes route (semi_active_done) */
+        if (seed_active != NULL) {
+            ssw_set_error("ssw_first_pass_batch_active: the s2_semi scorer makes no sets of listed "
+                          "senones (seed_active)");
+            return -1;
+        }
+        if (n_frames > 0
+            && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, rows, stream) < 0)
+            return -1;
+        if (ssw_first_pass_batch(m, d, cfg, rows, n_frames, utt_off, n_utts, word_off, words, max_seg,
+                                 n_seg, seg, stream) < 0)
+            return -1;
+        semi_active_done(m->fpa_stats, n_utts, rounds);
+        return 0;
     }
     ssw_fp_graphs_t *g = ssw_fp_graphs_build(m, d, cfg, n_utts, word_off, words);
     if (g == NULL)
@@ -487,6 +519,13 @@ ssw_align_text_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
         || !words || !d || !utt_off_spans(utt_off, n_utts, n_frames)) {
         ssw_set_error("bad arguments to ssw_align_text_batch_active");
         return NULL;
+    }
+    if (scorer == SSW_SCORER_S2_SEMI) { /* the compallsen = yes route (semi_active_done) */
+        ssw_alignment_set_t *a = ssw_align_text_batch(m, d, cfg, scorer, d_feats, n_frames, utt_off,
+                                                      n_utts, word_off, words, stream);
+        if (a != NULL)
+            semi_active_done(m->fpa_stats, n_utts, NULL);
+        return a;
     }
     if (hipSetDevice(m->device) != hipSuccess)
         return NULL;

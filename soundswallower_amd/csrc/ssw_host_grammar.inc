@@ -768,6 +768,29 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
                       plan->big_name.c_str(), plan->big_nodes);
         return NULL;
     }
+    if (scorer == SSW_SCORER_S2_SEMI) { /* the compallsen = yes route (semi_active_done) */
+        if (listed != NULL) {
+            ssw_set_error("ssw_recognize_batch_active: the s2_semi scorer makes no sets of listed "
+                          "senones (listed)");
+            return NULL;
+        }
+        if (hipSetDevice(m->device) != hipSuccess)
+            return NULL;
+        int16_t *all = d_senscr;
+        if (all == NULL) {
+            if (text_rows_reserve(m, n_frames, "ssw_recognize_batch_active") < 0)
+                return NULL;
+            all = m->text_scr.as<int16_t>();
+        }
+        if (n_frames > 0
+            && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, all, stream) < 0)
+            return NULL;
+        ssw_recognition_set_t *r = ssw_grammar_search_batch(m, d, plan, fsg_of_utt, all, n_frames,
+                                                            utt_off, n_utts, stream);
+        if (r != NULL)
+            semi_active_done(m->gra_stats, n_utts, rounds);
+        return r;
+    }
     if (fpa_check_limits(m, "ssw_recognize_batch_active", scorer) < 0)
         return NULL;
     if (hipSetDevice(m->device) != hipSuccess)

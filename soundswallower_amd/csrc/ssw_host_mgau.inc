@@ -31,6 +31,10 @@ struct ssw_mgau_impl {
     /* whole-utterance cache filled by ssw_mgau_prescore */
     std::vector<int16_t> cache;
     int cache_frames;
+    /* the s2_semi scorer's ring of two slots (src/s2_semi_mgau.c:845-855), kept on the host: the
+     * packed codeword order of every stream, and the whole row the slot's lists last gave */
+    std::vector<uint32_t> sc_hist[2];
+    std::vector<int16_t> sc_row[2];
 };
 
 static int mgau_frame_eval(ssw_mgau_t *mg, int16_t *senscr, uint8_t *senone_active,
@@ -154,6 +158,88 @@ ssw_ms_mgau_init(ssw_model_t *m)
     return &g->base;
 }
 
+static void
+semi_mgau_reset(ssw_mgau_impl *g)
+{
+    for (int i = 0; i < 2; ++i) {
+        g->sc_hist[i].assign((size_t)g->m->n_cbf, 0x03020100u); /* codeword k (:993-1002) */
+        g->sc_row[i].assign((size_t)g->m->h->n_sen, 0);
+    }
+}
+
+static ssw_mgaufuncs_t g_s2_semi_funcs = { "s2_semi", mgau_frame_eval, mgau_transform, mgau_free };
+
+/* s2_semi_mgau_init(acmod_t *) (src/s2_semi_mgau.c:1014): a single-codebook model.  frame_eval
+ * scores a frame that acmod has not scored yet (frame >= frame_idx) as a batch of one, from the
+ * other slot's order, and keeps the row; an earlier frame gets its slot's row again, as the
+ * reference makes it again from the slot's lists.  With compallsen = 0 the listed senones (the
+ * delta list's bridge entries included) get their values and every other one 0: the Gaussians and
+ * the normalisation do not depend on the list (:841-872). */
+extern "C" ssw_mgau_t *
+ssw_s2_semi_mgau_init(ssw_model_t *m)
+{
+    if (check_scorer_shape(m, SSW_SCORER_S2_SEMI) < 0)
+        return NULL;
+    if (hipSetDevice(m->device) != hipSuccess) {
+        ssw_set_error("hipSetDevice failed");
+        return NULL;
+    }
+    ssw_mgau_impl *g = new ssw_mgau_impl();
+    g->base.vt = &g_s2_semi_funcs;
+    g->base.frame_idx = 0;
+    g->m = m;
+    g->scorer = SSW_SCORER_S2_SEMI;
+    g->cache_frames = 0;
+    if (dev_alloc(&g->d_feat1, (size_t)m->h->veclen_total) < 0
+        || dev_alloc(&g->d_out1, (size_t)m->h->n_sen) < 0) {
+        mgau_free(&g->base);
+        return NULL;
+    }
+    semi_mgau_reset(g);
+    return &g->base;
+}
+
+static int
+semi_mgau_frame_eval(ssw_mgau_impl *g, int16_t *senscr, const uint8_t *senone_active,
+                     int32_t n_senone_active, float **feat, int32_t frame, int32_t compallsen)
+{
+    ssw_model_s *m = g->m;
+    const ssw_host_model_t *h = m->h;
+    const int slot = frame % 2;
+    const int16_t *row = g->sc_row[slot].data();
+    if (frame < g->cache_frames) /* ssw_mgau_prescore */
+        row = g->cache.data() + (size_t)frame * h->n_sen;
+    else if (frame >= g->base.frame_idx) {
+        std::vector<float> x((size_t)h->veclen_total);
+        for (int f = 0; f < h->n_feat; ++f)
+            memcpy(x.data() + h->featoff[f], feat[f], sizeof(float) * h->veclen[f]);
+        const int32_t off[2] = { 0, 1 };
+        HIP_OK(hipMemcpy(g->d_feat1, x.data(), sizeof(float) * x.size(), hipMemcpyHostToDevice));
+        /* (frame_base: the frame's number decides whether a ds > 1 model scans the codebook) */
+        if (score_batch_impl(m, SSW_SCORER_S2_SEMI, g->d_feat1, 1, off, 1, g->d_out1, NULL, 0u,
+                             g->sc_hist[slot ^ 1].data(), g->sc_hist[slot].data(), NULL, NULL, NULL,
+                             frame) < 0)
+            return -1;
+        HIP_OK(hipMemcpy(g->sc_row[slot].data(), g->d_out1, sizeof(int16_t) * h->n_sen,
+                         hipMemcpyDeviceToHost));
+    }
+    if (compallsen) {
+        memcpy(senscr, row, sizeof(int16_t) * h->n_sen);
+        return 0;
+    }
+    memset(senscr, 0, sizeof(int16_t) * h->n_sen); /* (:841) */
+    int at = 0;
+    for (int32_t i = 0; i < n_senone_active; ++i) {
+        at += senone_active[i];
+        if (at >= h->n_sen) {
+            ssw_set_error("active list runs past the last senone (%d >= %d)", at, h->n_sen);
+            return -1;
+        }
+        senscr[at] = row[at];
+    }
+    return 0;
+}
+
 extern "C" void
 ssw_mgau_reset_hist(ssw_mgau_t *mg)
 {
@@ -161,6 +247,8 @@ ssw_mgau_reset_hist(ssw_mgau_t *mg)
     (void)hipSetDevice(g->m->device);
     if (g->scorer == SSW_SCORER_PTM)
         (void)mgau_reset_device_hist(g);
+    if (g->scorer == SSW_SCORER_S2_SEMI)
+        semi_mgau_reset(g);
     g->cache_frames = 0;
 }
 
@@ -227,6 +315,9 @@ mgau_frame_eval(ssw_mgau_t *mg, int16_t *senscr, uint8_t *senone_active,
         return 0;
     }
     HIP_OK(hipSetDevice(m->device));
+    if (g->scorer == SSW_SCORER_S2_SEMI)
+        return semi_mgau_frame_eval(g, senscr, senone_active, n_senone_active, feat, frame,
+                                    compallsen);
     std::vector<uint8_t> sen_act, cb_act; /* (the ms path's per-senone view of the list) */
     if (!compallsen && g->scorer == SSW_SCORER_MS
         && decode_active(h, senone_active, n_senone_active, sen_act, cb_act) < 0)

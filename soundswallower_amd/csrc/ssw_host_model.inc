@@ -253,6 +253,16 @@ struct ssw_model_s {
     uint64_t gr_ws_uid;
     /* ssw_score_batch_compact's fall-back: full int16 rows of a launch that has no COMPACT instance */
     DevBuf full_tmp;
+    /* the s2_semi scorer (ssw_host_semi.inc): its Gaussian table (ssw_host_model_t::sc_rec), the
+     * mixture weights [n_feat * n_density][sc_stride] in senone order (rows padded with 0 to a
+     * multiple of 16 bytes), and its workspace: every density's truncated score and tie bit per
+     * (frame, stream), and the frame's candidates */
+    float *d_sc_rec;
+    uint8_t *d_sc_mixw;
+    int sc_stride;
+    DevBuf sc_ws;
+    hipEvent_t ev_sc; /* kernel timing: between its density and chain kernels */
+    int timing_semi;  /* the last timed call was this scorer's */
 };
 
 static inline void
@@ -456,9 +466,25 @@ upload_model(ssw_model_s *m)
     const ssw_host_model_t *h = m->h;
     const int ncbf = h->n_cb * h->n_feat;
     m->n_cbf = ncbf;
+    if (h->sc_rec != NULL) { /* a single-codebook model: the s2_semi scorer's tables alone */
+        const size_t nrec = (size_t)h->n_feat * SSW_SC_ROWS * SSW_SC_MAX_DENSITY;
+        if (dev_alloc(&m->d_sc_rec, nrec) < 0)
+            return -1;
+        HIP_OK(hipMemcpy(m->d_sc_rec, h->sc_rec, nrec * sizeof(float), hipMemcpyHostToDevice));
+        if (h->ptm_mixw != NULL) {
+            const size_t rows = (size_t)h->n_feat * h->n_density;
+            m->sc_stride = (h->n_sen + 15) & ~15;
+            std::vector<uint8_t> mw(rows * (size_t)m->sc_stride, 0);
+            for (size_t r = 0; r < rows; ++r)
+                memcpy(&mw[r * (size_t)m->sc_stride], h->ptm_mixw + r * (size_t)h->n_sen,
+                       (size_t)h->n_sen);
+            HIP_OK(hipMalloc((void **)&m->d_sc_mixw, mw.size()));
+            HIP_OK(hipMemcpy(m->d_sc_mixw, mw.data(), mw.size(), hipMemcpyHostToDevice));
+        }
+    }
     /* Gaussian records and the scan's quadratic-form records, built on the host in
      * ssw_model.c:ssw_host_build_records (the error analysis lives there) */
-    {
+    if (h->rec != NULL) {
         const size_t nrec = (size_t)ncbf * h->n_density * SSW_REC_FLOATS;
         const size_t nd0 = (size_t)ncbf * SSW_REC_FLOATS, nex = (size_t)ncbf * SSW_EXLIST_STRIDE;
         m->n_exact_form = h->n_exact_form;
@@ -503,14 +529,14 @@ upload_model(ssw_model_s *m)
         HIP_OK(hipMalloc((void **)&m->d_logadd_mirror, mir.size()));
         HIP_OK(hipMemcpy(m->d_logadd_mirror, mir.data(), mir.size(), hipMemcpyHostToDevice));
     }
-    if (h->n_sen) {
+    if (h->n_sen && h->sen2cb != NULL) {
         std::vector<uint8_t> s2c((size_t)h->n_sen);
         for (int i = 0; i < h->n_sen; ++i)
             s2c[i] = (uint8_t)h->sen2cb[i];
         HIP_OK(hipMalloc((void **)&m->d_sen2cb, s2c.size()));
         HIP_OK(hipMemcpy(m->d_sen2cb, s2c.data(), s2c.size(), hipMemcpyHostToDevice));
     }
-    if (h->ptm_mixw || h->ms_pdf) {
+    if ((h->ptm_mixw || h->ms_pdf) && h->sc_rec == NULL) {
         /* slot order: senones grouped by codebook (ascending id inside a group), every group
          * padded to a multiple of 4 slots */
         std::vector<int16_t> slot_sen;
@@ -681,7 +707,8 @@ ssw_model_load(const char *mdef, const char *means, const char *variances, const
     ssw_host_model_t *h = ssw_host_model_load(mdef, means, variances, sendump, mixw, tmat, cfg);
     if (h == NULL)
         return NULL;
-    for (int f = 0; f < h->n_feat; ++f)
+    /* (ssw_host_build_records has refused it already; a single-codebook model has its own limit) */
+    for (int f = 0; f < h->n_feat && ssw_host_scorer(h) != SSW_SCORER_S2_SEMI; ++f)
         if (h->veclen[f] > SSW_MAX_VECLEN) {
             ssw_set_error("stream %d has %d dimensions; the gfx950 kernels handle <= %d", f,
                           h->veclen[f], SSW_MAX_VECLEN);
@@ -805,9 +832,14 @@ ssw_model_free(ssw_model_t *m)
         }
     }
     (void)hipFree(m->full_tmp.p);
-    if (m->timing)
+    (void)hipFree(m->d_sc_rec);
+    (void)hipFree(m->d_sc_mixw);
+    (void)hipFree(m->sc_ws.p);
+    if (m->timing) {
         for (int i = 0; i < 3; ++i)
             (void)hipEventDestroy(m->ev[i]);
+        (void)hipEventDestroy(m->ev_sc);
+    }
     ssw_host_model_free(m->h);
     delete m;
 }
@@ -847,6 +879,16 @@ ssw_model_info(const ssw_model_t *m, ssw_model_info_t *o)
     o->mfma_selftest_worst_u = m->selftest_worst_u;
     o->mfma_selftest_ms = m->selftest_ms;
     return 0;
+}
+
+extern "C" int
+ssw_model_scorer(const ssw_model_t *m)
+{
+    const ssw_host_model_t *h = m->h;
+    const int by_shape = ssw_host_scorer(h);
+    if (by_shape != SSW_SCORER_MS && h->ptm_mixw != NULL)
+        return by_shape;
+    return h->ms_pdf != NULL ? SSW_SCORER_MS : -1;
 }
 
 extern "C" const char *

@@ -57,6 +57,8 @@ check_scorer_shape(const ssw_model_s *m, int scorer)
                       "no scoring -- there is no CPU fallback");
         return -1;
     }
+    if (scorer == SSW_SCORER_S2_SEMI || h->sc_rec != NULL)
+        return semi_check_shape(m, scorer);
     if (scorer == SSW_SCORER_PTM && h->ptm_mixw == NULL) {
         ssw_set_error("model has no PTM mixture weights (sendump / mixw)");
         return -1;
@@ -333,6 +335,55 @@ ssw_score_batch_ex(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_f
                             carry_in, carry_out);
 }
 
+/* what every scoring call ends in: the counters, and carry_out read back */
+static int
+score_batch_finish(ssw_model_t *m, bool ms, int32_t n_frames, const int32_t *utt_off, int32_t n_utts,
+                   hipStream_t st, uint32_t flags, const uint32_t *carry_in, uint32_t *carry_out)
+{
+    const bool chain = (flags & SSW_SCORE_CARRY_UTTS) != 0 && !ms;
+    const int64_t pairs = (int64_t)n_frames * m->n_cbf;
+    m->last_n_frames = n_frames;
+    m->stats[1] = pairs;
+    if (carry_out != NULL) {
+        /* what the next call starts from.  Default: the last frame's final order (the next call
+         * continues the same utterance).  SSW_SCORE_CARRY_OUT_REWIND: history slot 1 of the
+         * reference's ring, which is what frame 0 of the NEXT utterance -- or of the second pass
+         * after acmod_rewind -- copies (src/ptm_mgau.c:425-437): the final order of the last
+         * odd-numbered frame of the last utterance that has two frames (in a chain; of the last
+         * utterance otherwise), else what that utterance itself started from */
+        long long row = (long long)n_frames - 1;
+        bool from_start = false; /* no frame wrote the slot: carry_in / the reset order */
+        if (flags & SSW_SCORE_CARRY_OUT_REWIND) {
+            row = -1;
+            for (int u = n_utts - 1; u >= 0 && row < 0; --u) {
+                const int T = utt_off[u + 1] - utt_off[u];
+                if (T >= 2)
+                    row = (long long)utt_off[u] + (T / 2) * 2 - 1;
+                else if (!chain) { /* utterances are independent: only the last one counts */
+                    from_start = true;
+                    for (int i = 0; i < m->n_cbf; ++i)
+                        carry_out[i] = (u == 0 && carry_in != NULL) ? carry_in[i] : 0x03020100u;
+                    break;
+                }
+            }
+            if (row < 0 && !from_start) {
+                from_start = true;
+                for (int i = 0; i < m->n_cbf; ++i)
+                    carry_out[i] = carry_in != NULL ? carry_in[i] : 0x03020100u;
+            }
+        }
+        if (ms)
+            for (int i = 0; i < m->n_cbf; ++i)
+                carry_out[i] = 0x03020100u; /* the ms scorer keeps no history */
+        else if (!from_start) {
+            HIP_OK(hipMemcpyAsync(carry_out, m->d_topn_cw + (size_t)row * m->n_cbf,
+                                  sizeof(uint32_t) * (size_t)m->n_cbf, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+        }
+    }
+    return 0;
+}
+
 static int
 score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
                  const int32_t *utt_off, int32_t n_utts, int16_t *d_out, void *stream,
@@ -528,8 +579,22 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
             hipLaunchKernelGGL(senone_active2_kernel<false>, grid, dim3(256), lds, st, A);
         return hipGetLastError();
     };
-    if (m->timing)
+    if (m->timing) {
         HIP_OK(hipEventRecord(m->ev[0], st));
+        m->timing_semi = scorer == SSW_SCORER_S2_SEMI;
+    }
+    if (scorer == SSW_SCORER_S2_SEMI) {
+        /* the same batch, history and carry semantics; its own three kernels (ssw_host_semi.inc) */
+        if (act != NULL || cp != NULL) {
+            ssw_set_error("internal error: active sets or compact rows with the s2_semi scorer");
+            return -1;
+        }
+        if (semi_launch(m, P, d_out, st) < 0)
+            return -1;
+        m->stats[0] = 0;
+        m->stats_pending = 0;
+        return score_batch_finish(m, false, n_frames, utt_off, n_utts, st, flags, carry_in, carry_out);
+    }
     if (!ms && (h->cfg.ds != 1 || m->force_exact)) {
         /* frame down-sampling makes every frame depend on its predecessor: exact chains */
         int n_chain = (chain ? 1 : n_utts) * m->n_cbf;
@@ -750,46 +815,7 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
         }
     }
 #endif
-    m->last_n_frames = n_frames;
-    m->stats[1] = pairs;
-    if (carry_out != NULL) {
-        /* what the next call starts from.  Default: the last frame's final order (the next call
-         * continues the same utterance).  SSW_SCORE_CARRY_OUT_REWIND: history slot 1 of the
-         * reference's ring, which is what frame 0 of the NEXT utterance -- or of the second pass
-         * after acmod_rewind -- copies (src/ptm_mgau.c:425-437): the final order of the last
-         * odd-numbered frame of the last utterance that has two frames (in a chain; of the last
-         * utterance otherwise), else what that utterance itself started from */
-        long long row = (long long)n_frames - 1;
-        bool from_start = false; /* no frame wrote the slot: carry_in / the reset order */
-        if (flags & SSW_SCORE_CARRY_OUT_REWIND) {
-            row = -1;
-            for (int u = n_utts - 1; u >= 0 && row < 0; --u) {
-                const int T = utt_off[u + 1] - utt_off[u];
-                if (T >= 2)
-                    row = (long long)utt_off[u] + (T / 2) * 2 - 1;
-                else if (!chain) { /* utterances are independent: only the last one counts */
-                    from_start = true;
-                    for (int i = 0; i < m->n_cbf; ++i)
-                        carry_out[i] = (u == 0 && carry_in != NULL) ? carry_in[i] : 0x03020100u;
-                    break;
-                }
-            }
-            if (row < 0 && !from_start) {
-                from_start = true;
-                for (int i = 0; i < m->n_cbf; ++i)
-                    carry_out[i] = carry_in != NULL ? carry_in[i] : 0x03020100u;
-            }
-        }
-        if (ms)
-            for (int i = 0; i < m->n_cbf; ++i)
-                carry_out[i] = 0x03020100u; /* the ms scorer keeps no history */
-        else if (!from_start) {
-            HIP_OK(hipMemcpyAsync(carry_out, m->d_topn_cw + (size_t)row * m->n_cbf,
-                                  sizeof(uint32_t) * (size_t)m->n_cbf, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-        }
-    }
-    return 0;
+    return score_batch_finish(m, ms, n_frames, utt_off, n_utts, st, flags, carry_in, carry_out);
 }
 
 /* Measurement aid (DESIGN.md section 7, the first pass in the default configuration): `reps`
@@ -1067,10 +1093,12 @@ ssw_set_kernel_timing(ssw_model_t *m, int enable)
     if (enable && !m->timing) {
         for (int i = 0; i < 3; ++i)
             HIP_OK(hipEventCreate(&m->ev[i]));
+        HIP_OK(hipEventCreate(&m->ev_sc));
         m->timing = 1;
     } else if (!enable && m->timing) {
         for (int i = 0; i < 3; ++i)
             (void)hipEventDestroy(m->ev[i]);
+        (void)hipEventDestroy(m->ev_sc);
         m->timing = 0;
     }
     return 0;
@@ -1094,6 +1122,10 @@ ssw_get_kernel_timing(ssw_model_t *m, float *ms, int n)
     int k = 0;
     for (; k < 2 && k < n; ++k)
         HIP_OK(hipEventElapsedTime(&ms[k], m->ev[k], m->ev[k + 1]));
+    if (m->timing_semi && n >= 3) { /* the s2_semi scorer: the chain kernel's share of ms[0] */
+        HIP_OK(hipEventElapsedTime(&ms[2], m->ev_sc, m->ev[1]));
+        k = 3;
+    }
     return k;
 }
 

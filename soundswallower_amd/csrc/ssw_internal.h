@@ -26,6 +26,13 @@ extern "C" {
 /* matrix-core scan: binary16 values per (codebook, stream) in wfrag */
 #define SSW_WFRAG_PER_CBF (4 * 2 * 2 * 64 * 8)
 
+/* s2_semi scorer (ssw_k10_semi.inc): one codebook, streams of up to 32 dimensions, up to 256
+ * densities; its Gaussian table holds SSW_SC_ROWS rows of SSW_SC_MAX_DENSITY floats per stream */
+#define SSW_SC_MAX_VECLEN 32
+#define SSW_SC_MAX_DENSITY 256
+#define SSW_SC_MAX_TOPN 4
+#define SSW_SC_ROWS (2 * SSW_SC_MAX_VECLEN + 1)
+
 /* MFCC front end (ssw_model.c, ssw_k8_fe.inc, ssw_host_fe.inc): ssw_fe_batch's one framing,
  * 16 kHz, 100 frames/s, 25.625 ms window, 512-point FFT; ssw_fe_batch_ex frames at any rate
  * with FFTs of SSW_FE_MIN_NFFT .. SSW_FE_MAX_NFFT points */
@@ -138,7 +145,13 @@ typedef struct ssw_host_model_s {
     int32_t *pid_memo;
     int32_t logadd8_size;   /* entries produced by logmath_init (>= 256) */
     int32_t zero8;          /* logmath zero at shift 10 */
+    /* single-codebook models (the s2_semi scorer): sc_rec [n_feat][SSW_SC_ROWS]
+     * [SSW_SC_MAX_DENSITY], see build_semi_records; NULL otherwise */
+    float *sc_rec;
 } ssw_host_model_t;
+
+/* the scorer acmod_load_am would choose for the model's shape (enum ssw_scorer) */
+int ssw_host_scorer(const ssw_host_model_t *h);
 
 ssw_host_model_t *ssw_host_model_load(const char *mdef, const char *means,
                                       const char *variances, const char *sendump,

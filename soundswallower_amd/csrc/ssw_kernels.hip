@@ -53,6 +53,10 @@
  *                        (fsg_search_start / _null_prop / _find_exit, src/fsg_search.c:543-924)
  *                        grammar_search_big_kernel: the same search from an HBM workspace, for
  *                        grammars beyond one workgroup (ssw_grammar_prepare_large)
+ *   ssw_k10_semi.inc     the s2_semi scorer of single-codebook models: semi_density_kernel (every
+ *                        density exactly, the frame's candidates), semi_chain_kernel (eval_topn and
+ *                        eval_cb over them, one wave per utterance and stream), semi_senone_kernel
+ *                        (mgau_norm + get_scores_8b_feat_all), src/s2_semi_mgau.c:68-202, :425-443
  *   ssw_ws_layout.inc    host, no HIP: align256 and WsLayout, the one layout of a device
  *                        workspace (256-byte-aligned offsets in call order, the uploaded pieces
  *                        staged by fill(); a host program can include it on its own)
@@ -117,11 +121,13 @@ namespace {
 #include "ssw_k7_fpactive.inc"
 #include "ssw_k8_fe.inc"
 #include "ssw_k9_grammar.inc"
+#include "ssw_k10_semi.inc"
 
 } // namespace
 
 #include "ssw_ws_layout.inc"
 #include "ssw_host_model.inc"
+#include "ssw_host_semi.inc"
 #include "ssw_host_score.inc"
 #include "ssw_host_align.inc"
 #include "ssw_host_compact.inc"

@@ -1219,6 +1219,10 @@ load_sendump(ssw_host_model_t *h, const char *path)
             for (s = 0; s < sens; ++s) {
                 int packed = src[s / 2];
                 int code = (packed & 1) ? packed >> 4 : packed & 0x0f;
+                /* the s2_semi scorer takes the nibble by the senone's parity instead
+                 * (src/s2_semi_mgau.c:809-810) */
+                if (ssw_host_scorer(h) == SSW_SCORER_S2_SEMI)
+                    code = (s & 1) ? packed >> 4 : packed & 0x0f;
                 dst[s] = codebook[code];
             }
         }
@@ -1762,6 +1766,13 @@ ssw_host_build_records(ssw_host_model_t *h)
                       SSW_EXLIST_STRIDE - 1);
         return -1;
     }
+    /* before any record is written: a record has SSW_MAX_VECLEN slots per table */
+    for (f = 0; f < h->n_feat; ++f)
+        if (h->veclen[f] > SSW_MAX_VECLEN) {
+            ssw_set_error("stream %d has %d dimensions; the gfx950 kernels handle <= %d", f,
+                          h->veclen[f], SSW_MAX_VECLEN);
+            return -1;
+        }
     h->rec = (float *)calloc(nrec * SSW_REC_FLOATS, sizeof(float));
     h->recq = (float *)calloc(nrec * SSW_REC_FLOATS, sizeof(float));
     h->recd0 = (float *)calloc((size_t)ncbf * SSW_REC_FLOATS, sizeof(float));
@@ -1826,6 +1837,72 @@ ssw_host_build_records(ssw_host_model_t *h)
 }
 
 
+/* The scorer acmod_load_am would choose without senmgau (src/acmod.c:101-119: ptm, then
+ * s2_semi, then ms): PTM when the codebooks number the CI phones and are at most 256
+ * (src/ptm_mgau.c:760-768), else S2_SEMI for a single codebook (src/s2_semi_mgau.c:942), else
+ * MS.  Before the mixture weights are read only the shape decides. */
+int
+ssw_host_scorer(const ssw_host_model_t *h)
+{
+    if (h->n_cb == h->n_ciphone && h->n_cb <= 256)
+        return SSW_SCORER_PTM;
+    if (h->n_cb == 1)
+        return SSW_SCORER_S2_SEMI;
+    return SSW_SCORER_MS;
+}
+
+/* The s2_semi kernels' Gaussian table (ssw_k10_semi.inc): per stream SSW_SC_ROWS rows of
+ * SSW_SC_MAX_DENSITY floats, density-minor so that a wave's lanes read neighbouring densities:
+ *   row j < 32  mean of dimension j     row 32 + j  scale 1 / (2 var) of dimension j     row 64  det
+ * Unused dimensions and densities are 0.0f (the kernels walk veclen dimensions and n_density
+ * densities only). */
+static int
+build_semi_records(ssw_host_model_t *h)
+{
+    const float *mp = h->mean, *vp = h->var;
+    /* (the loader takes a topn outside 1 .. n_density for n_density) */
+    const int topn = h->cfg.topn < 1 || h->cfg.topn > h->n_density ? h->n_density : h->cfg.topn;
+    int f, d, j;
+
+    if (topn > SSW_SC_MAX_TOPN) {
+        ssw_set_error("s2_semi scorer: topn %d, at most %d is supported", topn, SSW_SC_MAX_TOPN);
+        return -1;
+    }
+    if (h->n_density > SSW_SC_MAX_DENSITY) {
+        ssw_set_error("s2_semi scorer: %d densities, at most %d are supported", h->n_density,
+                      SSW_SC_MAX_DENSITY);
+        return -1;
+    }
+    if (h->n_feat > SSW_MAX_FEAT) {
+        ssw_set_error("s2_semi scorer: %d streams, at most %d are supported", h->n_feat,
+                      SSW_MAX_FEAT);
+        return -1;
+    }
+    for (f = 0; f < h->n_feat; ++f)
+        if (h->veclen[f] > SSW_SC_MAX_VECLEN) {
+            ssw_set_error("s2_semi scorer: stream %d has %d dimensions, at most %d are supported",
+                          f, h->veclen[f], SSW_SC_MAX_VECLEN);
+            return -1;
+        }
+    h->sc_rec = (float *)calloc((size_t)h->n_feat * SSW_SC_ROWS * SSW_SC_MAX_DENSITY, sizeof(float));
+    if (h->sc_rec == NULL) {
+        ssw_set_error("out of memory building the s2_semi records");
+        return -1;
+    }
+    for (f = 0; f < h->n_feat; ++f) {
+        float *r = h->sc_rec + (size_t)f * SSW_SC_ROWS * SSW_SC_MAX_DENSITY;
+        for (d = 0; d < h->n_density; ++d) {
+            for (j = 0; j < h->veclen[f]; ++j) {
+                r[(size_t)j * SSW_SC_MAX_DENSITY + d] = *mp++;
+                r[(size_t)(SSW_SC_MAX_VECLEN + j) * SSW_SC_MAX_DENSITY + d] = *vp++;
+            }
+            r[(size_t)(2 * SSW_SC_MAX_VECLEN) * SSW_SC_MAX_DENSITY + d]
+                = h->det[(size_t)f * h->n_density + d];
+        }
+    }
+    return 0;
+}
+
 ssw_host_model_t *
 ssw_host_model_load(const char *mdef, const char *means, const char *variances,
                     const char *sendump, const char *mixw, const char *tmat,
@@ -1863,7 +1940,12 @@ ssw_host_model_load(const char *mdef, const char *means, const char *variances,
         goto bad;
     if (load_gaussians(h, &lb, means, variances) < 0)
         goto bad;
-    if (ssw_host_build_records(h) < 0)
+    /* a single-codebook model is the s2_semi scorer's: its own table, none of the PTM scan's
+     * (records of 15 dimensions, at most 131 densities), no senone-to-codebook map */
+    if (ssw_host_scorer(h) == SSW_SCORER_S2_SEMI) {
+        if (build_semi_records(h) < 0)
+            goto bad;
+    } else if (ssw_host_build_records(h) < 0)
         goto bad;
     if (tmat && load_tmat(h, &lb, tmat) < 0)
         goto bad;
@@ -1881,7 +1963,7 @@ ssw_host_model_load(const char *mdef, const char *means, const char *variances,
         ssw_set_error("senone to codebook map needs the mdef");
         goto bad;
     }
-    for (i = 0; i < h->n_sen; ++i)
+    for (i = 0; i < h->n_sen && ssw_host_scorer(h) != SSW_SCORER_S2_SEMI; ++i)
         if (h->sen2cb[i] < 0 || h->sen2cb[i] >= h->n_cb) {
             /* PTM needs one codebook per CI phone (src/ptm_mgau.c:760-764) */
             ssw_set_error("senone %d maps to codebook %d of %d", i, h->sen2cb[i], h->n_cb);
@@ -1932,6 +2014,7 @@ ssw_host_model_free(ssw_host_model_t *h)
     free(h->exlistm);
     free(h->wfrag);
     free(h->rec28);
+    free(h->sc_rec);
     free(h->sseq);
     free(h->sen2cb);
     free(h->phone_ssid);
