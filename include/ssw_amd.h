@@ -29,6 +29,11 @@
  * compiled on x86).  ms scorer: infinities likewise; with a NaN the reference's compute_dist
  * (src/ms_gauden.c:397-420) leaves its top-N entries as they were, i.e. reads the PREVIOUS
  * frame's ids from its buffer -- a result no batch can reproduce and none is claimed.
+ * ms scorer on a continuous-density model (one codebook per senone, ssw_model_is_continuous):
+ * equality with the reference is claimed for finite features under which every codebook takes
+ * at least topn densities (every density scores >= (float)INT32_MIN: any real cepstral input).
+ * Otherwise the reference again reads stale ids from its persistent buffer; the result here is
+ * a deterministic row (an entry no density filled counts as density 0 at WORST_DIST) and no fault.
  * Range: any finite feature gives the reference's scores, but the fast path of the scoring
  * kernels (the matrix-core scan, binary16 operands) only trusts frames whose features lie
  * within +-255 -- cepstral features of the shipped front end are a tenth of that; a frame
@@ -151,6 +156,17 @@ enum ssw_scorer { SSW_SCORER_PTM = 0, SSW_SCORER_MS = 1, SSW_SCORER_S2_SEMI = 2 
  * loaded; else S2_SEMI for a single codebook with such weights; else MS when a mixture_weights
  * file gave its table; else -1 */
 int ssw_model_scorer(const ssw_model_t *m);
+/* 1 for a continuous-density model: its codebooks number its senones (and are neither one nor
+ * the CI phones) and a mixture_weights file was given.  Such a model is the ms scorer's with the
+ * reference's .cont. map, sen2cb[s] = s (src/ms_senone.c:238-250): ssw_model_scorer answers
+ * SSW_SCORER_MS.  Limits, refused at load by name: <= 8 streams of <= 64 dimensions, <= 64
+ * densities, topn <= 8 or >= the densities (then all of them, in index order, no selection), no
+ * sendump, <= 32767 senones.  It is scored in whole rows (compallsen = yes): ssw_score_batch(_ex,
+ * _host), the ms drop-in, ssw_forced_align_batch, ssw_align_text_batch, ssw_first_pass_batch and
+ * ssw_recognize_batch take it (flags, carry_in, carry_out and ds are ignored, as for ms); the
+ * *_active entry points, the compact-row calls, ssw_score_batch_topn, the ssw_debug_scan_* calls
+ * and SSW_SCAN / SSW_SCAN_AUDIT settings are refused by name. */
+int ssw_model_is_continuous(const ssw_model_t *m);
 
 /* device pointers, asynchronous on `stream` (a hipStream_t, NULL = default stream) */
 int ssw_score_batch(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,

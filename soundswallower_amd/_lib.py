@@ -106,6 +106,8 @@ def lib() -> C.CDLL:
     L.ssw_model_selftest_message.argtypes = [vp]
     L.ssw_model_scorer.restype = C.c_int
     L.ssw_model_scorer.argtypes = [vp]
+    L.ssw_model_is_continuous.restype = C.c_int
+    L.ssw_model_is_continuous.argtypes = [vp]
     L.ssw_model_table.restype = vp
     L.ssw_model_table.argtypes = [vp, C.c_int, C.POINTER(sz)]
     L.ssw_score_batch.argtypes = [vp, C.c_int, vp, i32, vp, i32, vp, vp]

@@ -151,13 +151,20 @@ class Model:
         return int(self._L.ssw_model_scorer(self._m))
 
     def pick_scorer(self, scorer=None) -> int:
-        """the scorer a call without one takes: SCORER_S2_SEMI for a single-codebook model, else
-        SCORER_PTM (SCORER_MS is asked for by name)"""
+        """the scorer a call without one takes: SCORER_S2_SEMI for a single-codebook model,
+        SCORER_MS for a continuous one, else SCORER_PTM (where SCORER_MS is asked for by name)"""
         if scorer is not None:
             return int(scorer)
         if getattr(self, "_default_scorer", None) is None:
-            self._default_scorer = SCORER_S2_SEMI if self.scorer() == SCORER_S2_SEMI else SCORER_PTM
+            self._default_scorer = (SCORER_S2_SEMI if self.scorer() == SCORER_S2_SEMI
+                                    else SCORER_MS if self.continuous else SCORER_PTM)
         return self._default_scorer
+
+    @property
+    def continuous(self) -> bool:
+        """ssw_model_is_continuous: one codebook per senone (the reference's `.cont.` map); the
+        model is scored with SCORER_MS, in whole rows."""
+        return bool(self._L.ssw_model_is_continuous(self._m))
 
     @property
     def tmat_n_emit(self) -> int:

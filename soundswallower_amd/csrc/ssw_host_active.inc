@@ -264,7 +264,8 @@ align_batch_active_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_
         return -1;
     const ssw_host_model_t *h = m->h;
     hipStream_t st = (hipStream_t)stream;
-    if (semi_refuse(scorer, "ssw_align_batch_active") < 0)
+    if (semi_refuse(scorer, "ssw_align_batch_active") < 0
+        || cont_refuse(m, "ssw_align_batch_active") < 0)
         return -1;
     if (n_utts <= 0)
         return 0;

@@ -22,6 +22,8 @@ ssw_compact_plan_create(ssw_model_t *m, int32_t n_utts, const int32_t *frame_off
     }
     if (h->sc_rec != NULL && semi_refuse(SSW_SCORER_S2_SEMI, "ssw_compact_plan_create") < 0)
         return NULL; /* a single-codebook model */
+    if (cont_refuse(m, "ssw_compact_plan_create") < 0)
+        return NULL;
     if (h->n_emit_state != 3 || m->d_sen_slot == NULL) {
         ssw_set_error("ssw_compact_plan_create: 3-state models with mixture weights only");
         return NULL;
@@ -171,7 +173,8 @@ ssw_score_batch_compact(ssw_model_t *m, int scorer, const float *d_feats,
                         const ssw_compact_plan_t *plan, int16_t *d_compact, void *stream,
                         uint32_t flags)
 {
-    if (semi_refuse(scorer, "ssw_score_batch_compact") < 0)
+    if (semi_refuse(scorer, "ssw_score_batch_compact") < 0
+        || cont_refuse(m, "ssw_score_batch_compact") < 0)
         return -1;
     if (plan == NULL || plan->m != m) {
         ssw_set_error("ssw_score_batch_compact: the plan belongs to another model");

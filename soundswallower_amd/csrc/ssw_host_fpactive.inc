@@ -454,6 +454,8 @@ ssw_first_pass_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
         ssw_set_error("bad arguments to ssw_first_pass_batch_active");
         return -1;
     }
+    if (cont_refuse(m, "ssw_first_pass_batch_active") < 0)
+        return -1;
     ModelBusy busy_(m);
     if (!busy_.ok)
         return -1;
@@ -520,6 +522,8 @@ ssw_align_text_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
         ssw_set_error("bad arguments to ssw_align_text_batch_active");
         return NULL;
     }
+    if (cont_refuse(m, "ssw_align_text_batch_active") < 0)
+        return NULL;
     if (scorer == SSW_SCORER_S2_SEMI) { /* the compallsen = yes route (semi_active_done) */
         ssw_alignment_set_t *a = ssw_align_text_batch(m, d, cfg, scorer, d_feats, n_frames, utt_off,
                                                       n_utts, word_off, words, stream);

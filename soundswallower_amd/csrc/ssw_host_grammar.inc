@@ -761,6 +761,8 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
         return NULL;
     if (check_has_device(m) < 0)
         return NULL;
+    if (cont_refuse(m, "ssw_recognize_batch_active") < 0)
+        return NULL;
     if (plan->big && !plan->active) {
         ssw_set_error("grammar %d (%s) has %d phone-tree HMMs and is searched from an HBM workspace: "
                       "the default configuration (compallsen = no) holds a plan's largest grammar "

@@ -322,7 +322,7 @@ mgau_frame_eval(ssw_mgau_t *mg, int16_t *senscr, uint8_t *senone_active,
     if (!compallsen && g->scorer == SSW_SCORER_MS
         && decode_active(h, senone_active, n_senone_active, sen_act, cb_act) < 0)
         return -1;
-    float row[SSW_MAX_FEAT * SSW_MAX_VECLEN];
+    float row[SSW_MAX_FEAT * SSW_CONT_MAX_VECLEN]; /* (the widest model the loader accepts) */
     for (int f = 0; f < h->n_feat; ++f)
         memcpy(row + h->featoff[f], feat[f], sizeof(float) * h->veclen[f]);
 

@@ -263,6 +263,12 @@ struct ssw_model_s {
     DevBuf sc_ws;
     hipEvent_t ev_sc; /* kernel timing: between its density and chain kernels */
     int timing_semi;  /* the last timed call was this scorer's */
+    /* continuous-density models (ssw_host_cont.inc): the table (ssw_host_model_t::cont_rec), the
+     * mixture weights [n_sen][n_feat][n_density] as the host holds them, and the workspace: raw
+     * rows and a minimum per frame */
+    float *d_cont_rec;
+    uint8_t *d_cont_pdf;
+    DevBuf cont_ws;
 };
 
 static inline void
@@ -482,6 +488,14 @@ upload_model(ssw_model_s *m)
             HIP_OK(hipMemcpy(m->d_sc_mixw, mw.data(), mw.size(), hipMemcpyHostToDevice));
         }
     }
+    if (h->cont_rec != NULL) { /* a continuous-density model: its own two tables alone */
+        const size_t npdf = (size_t)h->n_sen * h->n_feat * h->n_density;
+        if (dev_alloc(&m->d_cont_rec, h->cont_floats) < 0 || dev_alloc(&m->d_cont_pdf, npdf) < 0)
+            return -1;
+        HIP_OK(hipMemcpy(m->d_cont_rec, h->cont_rec, h->cont_floats * sizeof(float),
+                         hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(m->d_cont_pdf, h->ms_pdf, npdf, hipMemcpyHostToDevice));
+    }
     /* Gaussian records and the scan's quadratic-form records, built on the host in
      * ssw_model.c:ssw_host_build_records (the error analysis lives there) */
     if (h->rec != NULL) {
@@ -529,14 +543,14 @@ upload_model(ssw_model_s *m)
         HIP_OK(hipMalloc((void **)&m->d_logadd_mirror, mir.size()));
         HIP_OK(hipMemcpy(m->d_logadd_mirror, mir.data(), mir.size(), hipMemcpyHostToDevice));
     }
-    if (h->n_sen && h->sen2cb != NULL) {
+    if (h->n_sen && h->sen2cb != NULL && h->cont_rec == NULL) {
         std::vector<uint8_t> s2c((size_t)h->n_sen);
         for (int i = 0; i < h->n_sen; ++i)
             s2c[i] = (uint8_t)h->sen2cb[i];
         HIP_OK(hipMalloc((void **)&m->d_sen2cb, s2c.size()));
         HIP_OK(hipMemcpy(m->d_sen2cb, s2c.data(), s2c.size(), hipMemcpyHostToDevice));
     }
-    if ((h->ptm_mixw || h->ms_pdf) && h->sc_rec == NULL) {
+    if ((h->ptm_mixw || h->ms_pdf) && h->sc_rec == NULL && h->cont_rec == NULL) {
         /* slot order: senones grouped by codebook (ascending id inside a group), every group
          * padded to a multiple of 4 slots */
         std::vector<int16_t> slot_sen;
@@ -708,7 +722,7 @@ ssw_model_load(const char *mdef, const char *means, const char *variances, const
     if (h == NULL)
         return NULL;
     /* (ssw_host_build_records has refused it already; a single-codebook model has its own limit) */
-    for (int f = 0; f < h->n_feat && ssw_host_scorer(h) != SSW_SCORER_S2_SEMI; ++f)
+    for (int f = 0; f < h->n_feat && ssw_host_scorer(h) != SSW_SCORER_S2_SEMI && !h->continuous; ++f)
         if (h->veclen[f] > SSW_MAX_VECLEN) {
             ssw_set_error("stream %d has %d dimensions; the gfx950 kernels handle <= %d", f,
                           h->veclen[f], SSW_MAX_VECLEN);
@@ -835,6 +849,9 @@ ssw_model_free(ssw_model_t *m)
     (void)hipFree(m->d_sc_rec);
     (void)hipFree(m->d_sc_mixw);
     (void)hipFree(m->sc_ws.p);
+    (void)hipFree(m->d_cont_rec);
+    (void)hipFree(m->d_cont_pdf);
+    (void)hipFree(m->cont_ws.p);
     if (m->timing) {
         for (int i = 0; i < 3; ++i)
             (void)hipEventDestroy(m->ev[i]);
@@ -889,6 +906,12 @@ ssw_model_scorer(const ssw_model_t *m)
     if (by_shape != SSW_SCORER_MS && h->ptm_mixw != NULL)
         return by_shape;
     return h->ms_pdf != NULL ? SSW_SCORER_MS : -1;
+}
+
+extern "C" int
+ssw_model_is_continuous(const ssw_model_t *m)
+{
+    return m->h->continuous ? 1 : 0;
 }
 
 extern "C" const char *

@@ -57,6 +57,8 @@ check_scorer_shape(const ssw_model_s *m, int scorer)
                       "no scoring -- there is no CPU fallback");
         return -1;
     }
+    if (h->continuous)
+        return cont_check_shape(m, scorer);
     if (scorer == SSW_SCORER_S2_SEMI || h->sc_rec != NULL)
         return semi_check_shape(m, scorer);
     if (scorer == SSW_SCORER_PTM && h->ptm_mixw == NULL) {
@@ -421,6 +423,27 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
         return -1;
     }
     HIP_OK(hipSetDevice(m->device));
+    if (m->h->continuous) {
+        /* no history, no utterance boundaries, none of the PTM scan's workspaces: its own two
+         * kernels (ssw_host_cont.inc); flags, carry_in and ds are ignored as for ms */
+        if (act != NULL || cp != NULL) {
+            ssw_set_error("internal error: active sets or compact rows with a continuous model");
+            return -1;
+        }
+        if (m->timing) {
+            HIP_OK(hipEventRecord(m->ev[0], st));
+            m->timing_semi = 0;
+        }
+        if (cont_launch(m, d_feats, n_frames, d_out, st) < 0)
+            return -1;
+        m->stats[0] = 0;
+        m->stats_pending = 0;
+        m->last_n_frames = 0; /* (no top-N block: ssw_score_batch_topn has nothing to show) */
+        m->stats[1] = (int64_t)n_frames * m->n_cbf;
+        for (int i = 0; carry_out != NULL && i < m->n_cbf; ++i)
+            carry_out[i] = 0x03020100u; /* the ms scorer keeps no history */
+        return 0;
+    }
     /* history carried from utterance to utterance (the reference never resets it after
      * start-up, src/acmod.c:367): the batch is one chain, only its first frame is a start.  The
      * chain follows the reference's two-slot ring (src/ptm_mgau.c:425-437): frame numbers restart
@@ -990,7 +1013,7 @@ ssw_score_batch_host(ssw_model_t *m, int scorer, const float *feats, int32_t n_f
     std::vector<int32_t> off;
     /* the top-N workspace holds the WHOLE call (the debug view ssw_score_batch_topn speaks of
      * the last call): every sub-batch scores into its own stretch of it */
-    if (ensure_score_ws(m, n_frames, n_utts) < 0)
+    if (!h->continuous && ensure_score_ws(m, n_frames, n_utts) < 0)
         return -1;
     uint32_t *const topn_cw0 = m->d_topn_cw;
     int4 *const topn_sc0 = m->d_topn_sc;
@@ -1031,8 +1054,10 @@ ssw_score_batch_host(ssw_model_t *m, int scorer, const float *feats, int32_t n_f
                                   hipMemcpyHostToDevice, m->s_pipe));
             /* the device rows of this slot were downloaded by sub-batch k - 2 */
             HIP_OK(hipStreamWaitEvent(m->s_pipe, m->ev_down[slot], 0));
-            m->d_topn_cw = topn_cw0 + (size_t)f0 * m->n_cbf;
-            m->d_topn_sc = topn_sc0 + (size_t)f0 * m->n_cbf;
+            if (!h->continuous) {
+                m->d_topn_cw = topn_cw0 + (size_t)f0 * m->n_cbf;
+                m->d_topn_sc = topn_sc0 + (size_t)f0 * m->n_cbf;
+            }
             /* (carry_out makes the piece's call synchronous: a long utterance's pieces do not
              * overlap their scoring with the copies -- they are 16 K frames each) */
             const int rc = score_batch_impl(m, scorer, m->d_pipe_feat[slot], nf, off.data(), u1 - u0,
@@ -1073,6 +1098,8 @@ ssw_score_batch_topn(ssw_model_t *m, int32_t n_frames, uint8_t *cw, int32_t *sco
 {
     ModelBusy busy_(m);
     if (!busy_.ok)
+        return -1;
+    if (cont_refuse(m, "ssw_score_batch_topn") < 0)
         return -1;
     if (n_frames > m->last_n_frames) {
         ssw_set_error("only %d frames were scored", m->last_n_frames);
@@ -1172,6 +1199,8 @@ ssw_debug_scan_keys(ssw_model_t *m, const float *d_feats, int32_t n_frames, int3
     if (!busy_.ok)
         return -1;
     const ssw_host_model_t *h = m->h;
+    if (cont_refuse(m, "ssw_debug_scan_keys") < 0)
+        return -1;
     if (m->device == SSW_DEVICE_NONE || m->d_wfrag == NULL) {
         ssw_set_error("no matrix-core scan tables for this model (or no device)");
         return -1;
@@ -1203,6 +1232,8 @@ ssw_debug_scan_top5(ssw_model_t *m, const float *keys, int32_t n_frames, int32_t
 {
     ModelBusy busy_(m);
     if (!busy_.ok)
+        return -1;
+    if (cont_refuse(m, "ssw_debug_scan_top5") < 0)
         return -1;
     if (m->device == SSW_DEVICE_NONE || n_frames <= 0 || !keys || !idx || !top) {
         ssw_set_error("ssw_debug_scan_top5: no device or bad arguments");

@@ -33,6 +33,12 @@ extern "C" {
 #define SSW_SC_MAX_TOPN 4
 #define SSW_SC_ROWS (2 * SSW_SC_MAX_VECLEN + 1)
 
+/* continuous-density models (one codebook per senone, ssw_k11_cont.inc): streams of up to 64
+ * dimensions, up to 64 densities, topn up to 8 or every density */
+#define SSW_CONT_MAX_VECLEN 64
+#define SSW_CONT_MAX_DENSITY 64
+#define SSW_CONT_MAX_TOPN 8
+
 /* MFCC front end (ssw_model.c, ssw_k8_fe.inc, ssw_host_fe.inc): ssw_fe_batch's one framing,
  * 16 kHz, 100 frames/s, 25.625 ms window, 512-point FFT; ssw_fe_batch_ex frames at any rate
  * with FFTs of SSW_FE_MIN_NFFT .. SSW_FE_MAX_NFFT points */
@@ -148,6 +154,12 @@ typedef struct ssw_host_model_s {
     /* single-codebook models (the s2_semi scorer): sc_rec [n_feat][SSW_SC_ROWS]
      * [SSW_SC_MAX_DENSITY], see build_semi_records; NULL otherwise */
     float *sc_rec;
+    /* continuous-density models (n_cb == n_sen, the ms scorer with sen2cb the identity): the
+     * table of ssw_k11_cont.inc, see build_cont_records; NULL otherwise.  cont_sp = n_sen rounded
+     * up to 64, cont_off[f] = floats before stream f's part, cont_floats = all of them */
+    float *cont_rec;
+    int32_t continuous, cont_sp;
+    size_t cont_off[SSW_MAX_FEAT], cont_floats;
 } ssw_host_model_t;
 
 /* the scorer acmod_load_am would choose for the model's shape (enum ssw_scorer) */

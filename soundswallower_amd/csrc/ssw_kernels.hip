@@ -57,6 +57,10 @@
  *                        density exactly, the frame's candidates), semi_chain_kernel (eval_topn and
  *                        eval_cb over them, one wave per utterance and stream), semi_senone_kernel
  *                        (mgau_norm + get_scores_8b_feat_all), src/s2_semi_mgau.c:68-202, :425-443
+ *   ssw_k11_cont.inc     the ms scorer on continuous-density models (one codebook per senone):
+ *                        cont_score_kernel (compute_dist + senone_eval, a lane per senone),
+ *                        cont_norm_kernel (the frame's minimum), src/ms_gauden.c:349-432,
+ *                        src/ms_senone.c:314-362, src/ms_mgau.c:299-321
  *   ssw_ws_layout.inc    host, no HIP: align256 and WsLayout, the one layout of a device
  *                        workspace (256-byte-aligned offsets in call order, the uploaded pieces
  *                        staged by fill(); a host program can include it on its own)
@@ -122,12 +126,20 @@ namespace {
 #include "ssw_k8_fe.inc"
 #include "ssw_k9_grammar.inc"
 #include "ssw_k10_semi.inc"
+#include "ssw_k11_cont.inc"
 
 } // namespace
 
 #include "ssw_ws_layout.inc"
 #include "ssw_host_model.inc"
 #include "ssw_host_semi.inc"
+/* ssw_host_cont.inc comes LAST: kernels are emitted in the order the host code first launches
+ * them, and the continuous-model kernels behind every other one leave the code object's layout
+ * ahead of them -- the placement of the PTM kernels -- as it was */
+static int cont_check_shape(const ssw_model_s *m, int scorer);
+static int cont_refuse(const ssw_model_s *m, const char *who);
+static int cont_launch(ssw_model_s *m, const float *d_feats, int32_t n_frames, int16_t *d_out,
+                       hipStream_t st);
 #include "ssw_host_score.inc"
 #include "ssw_host_align.inc"
 #include "ssw_host_compact.inc"
@@ -141,3 +153,4 @@ namespace {
 #include "ssw_host_grammar.inc"
 #include "ssw_host_devmem.inc"
 #include "ssw_host_comm.inc"
+#include "ssw_host_cont.inc"

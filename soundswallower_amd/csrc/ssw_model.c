@@ -1903,6 +1903,90 @@ build_semi_records(ssw_host_model_t *h)
     return 0;
 }
 
+/* n_sen of a mixture-weights file's header (a model without an mdef), 0 when it cannot be read:
+ * load_mixw reports why */
+static int32_t
+peek_mixw_senones(const char *path)
+{
+    rd_t r;
+    int32_t dims[4] = { 0, 0, 0, 0 };
+
+    if (rd_open(&r, path) < 0)
+        return 0;
+    if (rd_s3_header(&r) < 0 || rd_words(&r, dims, 4) < 0)
+        dims[0] = 0;
+    rd_close(&r);
+    return dims[0] > 0 ? dims[0] : 0;
+}
+
+/* The table of ssw_k11_cont.inc, senone-minor so that a wave's lanes (one per senone) read
+ * neighbouring addresses.  Stream f starts cont_off[f] floats in; its density d takes
+ * 2 veclen[f] + 1 rows of cont_sp floats:
+ *   rows 2 j, 2 j + 1  (mean, scale 1 / (2 var)) of dimension j as pairs, [cont_sp][2]
+ *   row 2 veclen[f]    det, [cont_sp]
+ * Senones past n_sen are 0.0f (no lane reads them). */
+static int
+build_cont_records(ssw_host_model_t *h)
+{
+    /* (the loader takes a topn outside 1 .. n_density for n_density: every density, no selection) */
+    const int topn = h->cfg.topn < 1 || h->cfg.topn > h->n_density ? h->n_density : h->cfg.topn;
+    const size_t sp = ((size_t)h->n_cb + 63) & ~(size_t)63;
+    const float *mp = h->mean, *vp = h->var, *dp = h->det;
+    size_t total = 0;
+    int c, f, d, j;
+
+    if (h->n_cb > 32767) {
+        ssw_set_error("continuous model: %d senones, at most 32767 are supported", h->n_cb);
+        return -1;
+    }
+    if (h->n_feat > SSW_MAX_FEAT) {
+        ssw_set_error("continuous model: %d streams, at most %d are supported", h->n_feat,
+                      SSW_MAX_FEAT);
+        return -1;
+    }
+    for (f = 0; f < h->n_feat; ++f)
+        if (h->veclen[f] > SSW_CONT_MAX_VECLEN) {
+            ssw_set_error("continuous model: stream %d has %d dimensions, at most %d are supported",
+                          f, h->veclen[f], SSW_CONT_MAX_VECLEN);
+            return -1;
+        }
+    if (h->n_density > SSW_CONT_MAX_DENSITY) {
+        ssw_set_error("continuous model: %d densities, at most %d are supported", h->n_density,
+                      SSW_CONT_MAX_DENSITY);
+        return -1;
+    }
+    if (topn > SSW_CONT_MAX_TOPN && topn < h->n_density) {
+        ssw_set_error("continuous model: topn %d, at most %d or all %d densities are supported",
+                      topn, SSW_CONT_MAX_TOPN, h->n_density);
+        return -1;
+    }
+    for (f = 0; f < h->n_feat; ++f) {
+        h->cont_off[f] = total;
+        total += sp * (size_t)h->n_density * (2 * (size_t)h->veclen[f] + 1);
+    }
+    h->cont_sp = (int32_t)sp;
+    h->cont_floats = total;
+    h->cont_rec = (float *)calloc(total, sizeof(float));
+    if (h->cont_rec == NULL) {
+        ssw_set_error("out of memory building the continuous model's table (%zu bytes)",
+                      total * sizeof(float));
+        return -1;
+    }
+    for (c = 0; c < h->n_cb; ++c)
+        for (f = 0; f < h->n_feat; ++f) {
+            const size_t vl = (size_t)h->veclen[f];
+            for (d = 0; d < h->n_density; ++d) {
+                float *r = h->cont_rec + h->cont_off[f] + (size_t)d * (2 * vl + 1) * sp;
+                for (j = 0; j < h->veclen[f]; ++j) {
+                    r[2 * ((size_t)j * sp + (size_t)c)] = *mp++;
+                    r[2 * ((size_t)j * sp + (size_t)c) + 1] = *vp++;
+                }
+                r[2 * vl * sp + (size_t)c] = *dp++;
+            }
+        }
+    return 0;
+}
+
 ssw_host_model_t *
 ssw_host_model_load(const char *mdef, const char *means, const char *variances,
                     const char *sendump, const char *mixw, const char *tmat,
@@ -1911,6 +1995,7 @@ ssw_host_model_load(const char *mdef, const char *means, const char *variances,
     ssw_host_model_t *h = (ssw_host_model_t *)calloc(1, sizeof(*h));
     lbase_t lb;
     int i, n;
+    int32_t n_sen_known;
 
     if (h == NULL)
         return NULL;
@@ -1940,9 +2025,40 @@ ssw_host_model_load(const char *mdef, const char *means, const char *variances,
         goto bad;
     if (load_gaussians(h, &lb, means, variances) < 0)
         goto bad;
+    /* the senones: the mdef's, or without one the mixture-weights file's */
+    n_sen_known = h->n_sen;
+    if (n_sen_known == 0 && mixw != NULL)
+        n_sen_known = peek_mixw_senones(mixw);
+    /* The codebooks number the senones, and are neither one nor the CI phones (those shapes are
+     * s2_semi's and PTM's, as the order of attempts in acmod_load_am makes them, src/acmod.c:
+     * 101-119): a continuous-density model, the ms scorer with the .cont. map (src/ms_senone.c:
+     * 238-250).  It needs its mixture_weights file (src/ms_mgau.c:208-212). */
+    if (ssw_host_scorer(h) == SSW_SCORER_MS && n_sen_known > 0) {
+        if (h->n_cb == n_sen_known && mixw != NULL) {
+            if (sendump != NULL) {
+                ssw_set_error("continuous model (%d codebooks for %d senones): a sendump cannot be "
+                              "used, the ms scorer reads mixture_weights", h->n_cb, n_sen_known);
+                goto bad;
+            }
+            h->continuous = 1;
+        } else if (h->n_cb > n_sen_known) {
+            ssw_set_error("%d codebooks for %d senones: more codebooks than senones", h->n_cb,
+                          n_sen_known);
+            goto bad;
+        } else if (h->n_cb < n_sen_known) {
+            ssw_set_error("%d codebooks for %d senones: fewer codebooks than senones, and neither "
+                          "one codebook nor one per CI phone (%d)", h->n_cb, n_sen_known,
+                          h->n_ciphone);
+            goto bad;
+        }
+    }
     /* a single-codebook model is the s2_semi scorer's: its own table, none of the PTM scan's
-     * (records of 15 dimensions, at most 131 densities), no senone-to-codebook map */
-    if (ssw_host_scorer(h) == SSW_SCORER_S2_SEMI) {
+     * (records of 15 dimensions, at most 131 densities), no senone-to-codebook map; a continuous
+     * model likewise has its own */
+    if (h->continuous) {
+        if (build_cont_records(h) < 0)
+            goto bad;
+    } else if (ssw_host_scorer(h) == SSW_SCORER_S2_SEMI) {
         if (build_semi_records(h) < 0)
             goto bad;
     } else if (ssw_host_build_records(h) < 0)
@@ -1957,8 +2073,18 @@ ssw_host_model_load(const char *mdef, const char *means, const char *variances,
         if (load_sendump(h, sendump) < 0)
             goto bad;
     }
-    if (mixw && load_mixw(h, &lb, mixw, sendump == NULL) < 0)
+    if (mixw && load_mixw(h, &lb, mixw, sendump == NULL && !h->continuous) < 0)
         goto bad;
+    if (h->continuous) { /* the .cont. map: senone s has codebook s (src/ms_senone.c:238-250) */
+        int16_t *map = (int16_t *)realloc(h->sen2cb, sizeof(int16_t) * (size_t)h->n_sen);
+        if (map == NULL) {
+            ssw_set_error("out of memory");
+            goto bad;
+        }
+        h->sen2cb = map;
+        for (i = 0; i < h->n_sen; ++i)
+            h->sen2cb[i] = (int16_t)i;
+    }
     if (h->sen2cb == NULL && h->n_sen) {
         ssw_set_error("senone to codebook map needs the mdef");
         goto bad;
@@ -2015,6 +2141,7 @@ ssw_host_model_free(ssw_host_model_t *h)
     free(h->wfrag);
     free(h->rec28);
     free(h->sc_rec);
+    free(h->cont_rec);
     free(h->sseq);
     free(h->sen2cb);
     free(h->phone_ssid);
