@@ -960,6 +960,80 @@ int ssw_feat_batch(ssw_model_t *m, const float *d_cep, int32_t n_frames,
                    void *stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Dynamic features as the model's feat_params.json says: every configuration that          */
+/* feat_init_s3file accepts and feat_s2mfc2feat_block_utt computes for whole utterances     */
+/* (src/feat.c:732-927, :977-1008; src/cmn.c:159-224; src/cmn_live.c:60-134;                */
+/* src/lda.c:84-144).  Bit-exact float32.  Streaming calls (an utterance in pieces), an     */
+/* LDA over several streams and AGC (the reference has none) are out of scope.              */
+/* ------------------------------------------------------------------------------------ */
+enum ssw_cmn { SSW_CMN_NONE = 0, SSW_CMN_BATCH = 1, SSW_CMN_LIVE = 2 };
+/* the settings of config_defs.h FEAT_OPTIONS (include/soundswallower/config_defs.h:418-450);
+ * defaults are the reference's.  An empty string is an unset (NULL) setting. */
+typedef struct ssw_feat_config_s {
+    char feat[64];      /* "feat"     1s_c_d_dd */
+    int32_t ceplen;     /* "ceplen"   13 (0 reads as 13, src/feat.c:741-742) */
+    int32_t cmn;        /* "cmn"      live (enum ssw_cmn; batch = current, live = prior) */
+    int32_t varnorm;    /* "varnorm"  no */
+    int32_t ldadim;     /* "ldadim"   0 = every row of the matrix */
+    int32_t from_file;  /* ssw_model_feat_config: 1 when feat_params.json was read */
+    char cmninit[512];  /* "cmninit"  40,3,-1 */
+    char lda[1024];     /* "lda"      path of the feature transform; ssw_model_feat_config: unset =
+                         *            the file feature_transform beside the means file, if there
+                         *            is one (src/decoder.c:90-119) */
+    char svspec[512];   /* "svspec"   e.g. 24,0-11/25,12-23/26-38 */
+} ssw_feat_config_t;
+void ssw_feat_config_defaults(ssw_feat_config_t *cfg);
+/* the FEAT_OPTIONS keys of a feat_params.json over *cfg (which holds the defaults): 0 read,
+ * 1 no such file, -1 unusable (ssw_last_error: bad JSON, an unknown cmn, a value of the
+ * wrong type) */
+int ssw_feat_config_read(const char *path, ssw_feat_config_t *cfg);
+/* What ssw_model_load read from the model directory's feat_params.json, over the defaults
+ * (from_file says whether there was one).  0, or -1 on NULL. */
+int ssw_model_feat_config(const ssw_model_t *m, ssw_feat_config_t *out);
+
+/* A resolved configuration with its device tables (feature recipe, LDA matrix, subvector
+ * gather).  cfg NULL = the model's own.  The type is resolved by feat_init_s3file's chain of
+ * comparisons, in its order: s2_4x; s3_1x39 / 1s_12c_12d_3p_12dd; the prefixes 1s_c_d_dd,
+ * 1s_c_d_ld_dd, cep_dcep / 1s_c_d, cep / 1s_c, 1s_3c / 1s_4c; else the generic
+ * "n,n,...[:window]".  Refused by name, before anything is uploaded, with the reference's own
+ * reason where it has one: LDA or svspec with more than one stream; a matrix whose width is not
+ * the stream's; varnorm with cmn = live; s2_4x / s3_1x39 with ceplen != 13; a malformed generic
+ * type or svspec; an unreadable or corrupt matrix file; and this implementation's limits:
+ * ceplen 1..64, window <= 8, at most 8 streams, at most 256 LDA rows, svspec dimensions below
+ * the raw dimension.  NULL on error (ssw_last_error). */
+typedef struct ssw_feat_s ssw_feat_t;
+ssw_feat_t *ssw_feat_create(ssw_model_t *m, const ssw_feat_config_t *cfg);
+void ssw_feat_free(ssw_feat_t *f);
+int32_t ssw_feat_out_dim(const ssw_feat_t *f);  /* floats per output row */
+int32_t ssw_feat_raw_dim(const ssw_feat_t *f);  /* before LDA and svspec: the stream lengths' sum */
+int32_t ssw_feat_window(const ssw_feat_t *f);
+int32_t ssw_feat_n_streams(const ssw_feat_t *f); /* feat_dimension1: subvectors, else streams */
+/* feat_dimension2 of stream i (the LDA's rows, a subvector's length, the stream's); -1 */
+int32_t ssw_feat_stream_len(const ssw_feat_t *f, int32_t i);
+int32_t ssw_feat_tile_frames(const ssw_feat_t *f); /* frames one workgroup computes */
+/* live CMN's running estimate (cmn_t: cmn_mean, sum, nframe), host memory */
+typedef struct ssw_cmn_state_s {
+    float mean[64], sum[64];
+    int32_t nframe;
+} ssw_cmn_state_t;
+/* the state of a fresh decoder: cmninit as cmn_set_repr reads it (src/cmn.c:112-140; values
+ * beyond the list stay 0, nframe 500), all zeros without a cmninit or with cmn = none */
+int ssw_feat_cmn_prior(const ssw_feat_t *f, ssw_cmn_state_t *out);
+/* d_cep [n_frames][ncep] (ncep must be the configuration's ceplen) -> d_out
+ * [n_frames][ssw_feat_out_dim], utterance u = frames utt_off[u] .. utt_off[u + 1] (host int32
+ * [n_utts + 1], non-decreasing from 0 to n_frames).  cmn_state, with cmn = live only:
+ *   NULL      every utterance is the first of a fresh decoder (the prior is cmninit);
+ *   non-NULL  in/out: the batch's utterances are one decoder's, in order -- after each come
+ *             cmn_live's shift (nframe > 800, src/cmn_live.c:131-133) and cmn_live_update
+ *             (src/feat.c:944-945; an empty utterance gets the update alone).
+ * With cmn = batch or none the state is neither read nor written.  feat NULL = a
+ * configuration the model builds once from its own settings and keeps.  Synchronous on
+ * `stream`; 0, or -1 (ssw_last_error). */
+int ssw_feat_batch_ex(ssw_model_t *m, ssw_feat_t *feat, const float *d_cep, int32_t n_frames,
+                      const int32_t *utt_off, int32_t n_utts, int32_t ncep, float *d_out,
+                      ssw_cmn_state_t *cmn_state, void *stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* MFCC front end on the device: 16-bit PCM -> cepstra for  */
 /* whole utterances, as fe_start + fe_process_int16 over all samples + fe_end compute them */
 /* (src/fe_interface.c:86-330, :560-690; src/fe_sigproc.c:70-738; src/fe_noise.c:111-327). */
@@ -994,7 +1068,8 @@ typedef struct ssw_fe_config_s {
 void ssw_fe_config_defaults(ssw_fe_config_t *cfg);
 /* What ssw_model_load read from feat_params.json beside the `means` file (the model
  * directory; acmod reads the same file, src/config.c:441-510 parses it), over the defaults;
- * keys the front end does not use (feat, cmn, svspec, ...) are ignored.  0, or -1 on NULL. */
+ * the feature stage's keys (feat, ceplen, cmn, cmninit, varnorm, lda, ldadim, svspec) are left
+ * to ssw_model_feat_config, every other unknown key is ignored.  0, or -1 on NULL. */
 int ssw_model_fe_config(const ssw_model_t *m, ssw_fe_config_t *out);
 /* Frames the front end makes of n_samples samples at 16 kHz (fe_process_int16 + fe_end,
  * src/fe_interface.c:560-690): 0 for 0 samples, 1 below one window (410 samples), else

@@ -43,6 +43,18 @@ class SswFeConfig(C.Structure):
                                  "from_file")]
 
 
+class SswFeatConfig(C.Structure):
+    """ssw_feat_config_t: the feature stage's settings (config_defs.h FEAT_OPTIONS)"""
+    _fields_ = [("feat", C.c_char * 64), ("ceplen", C.c_int32), ("cmn", C.c_int32),
+                ("varnorm", C.c_int32), ("ldadim", C.c_int32), ("from_file", C.c_int32),
+                ("cmninit", C.c_char * 512), ("lda", C.c_char * 1024), ("svspec", C.c_char * 512)]
+
+
+class SswCmnState(C.Structure):
+    """ssw_cmn_state_t: live CMN's running estimate"""
+    _fields_ = [("mean", C.c_float * 64), ("sum", C.c_float * 64), ("nframe", C.c_int32)]
+
+
 class SswAlignEntry(C.Structure):
     _fields_ = [("start", C.c_int32), ("duration", C.c_int32), ("score", C.c_int32)]
 
@@ -299,6 +311,23 @@ def lib() -> C.CDLL:
     L.ssw_recognition_set_free.argtypes = [vp]
     L.ssw_recognition_set_free.restype = None
     L.ssw_feat_batch.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
+    if hasattr(L, "ssw_feat_create"):   # (an older build loaded through SSW_AMD_LIB has none)
+        L.ssw_feat_config_defaults.argtypes = [C.POINTER(SswFeatConfig)]
+        L.ssw_feat_config_defaults.restype = None
+        L.ssw_feat_config_read.argtypes = [C.c_char_p, C.POINTER(SswFeatConfig)]
+        L.ssw_model_feat_config.argtypes = [vp, C.POINTER(SswFeatConfig)]
+        L.ssw_feat_create.restype = vp
+        L.ssw_feat_create.argtypes = [vp, C.POINTER(SswFeatConfig)]
+        L.ssw_feat_free.argtypes = [vp]
+        L.ssw_feat_free.restype = None
+        for fn in (L.ssw_feat_out_dim, L.ssw_feat_raw_dim, L.ssw_feat_window, L.ssw_feat_n_streams,
+                   L.ssw_feat_tile_frames):
+            fn.restype = i32
+            fn.argtypes = [vp]
+        L.ssw_feat_stream_len.restype = i32
+        L.ssw_feat_stream_len.argtypes = [vp, i32]
+        L.ssw_feat_cmn_prior.argtypes = [vp, C.POINTER(SswCmnState)]
+        L.ssw_feat_batch_ex.argtypes = [vp, vp, vp, i32, vp, i32, i32, vp, C.POINTER(SswCmnState), vp]
     L.ssw_fe_config_defaults.argtypes = [C.POINTER(SswFeConfig)]
     L.ssw_fe_config_defaults.restype = None
     L.ssw_model_fe_config.argtypes = [vp, C.POINTER(SswFeConfig)]

@@ -13,7 +13,8 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import SswAlignEntry, SswConfig, SswFeConfig, SswModelInfo
+from ._lib import (SswAlignEntry, SswCmnState, SswConfig, SswFeatConfig, SswFeConfig,
+                   SswModelInfo)
 
 SCORER_PTM = 0
 SCORER_MS = 1
@@ -38,6 +39,50 @@ class SswError(RuntimeError):
 
 FE_TRANSFORMS = {"legacy": 0, "dct": 1, "htk": 2}
 FE_FRAME, FE_SHIFT, FE_NCEP = 410, 160, 13
+
+
+CMN_TYPES = {"none": 0, "batch": 1, "current": 1, "live": 2, "prior": 2}
+
+
+class FeatConfig(SswFeatConfig):
+    """ssw_feat_config_t: feat, ceplen, cmn, cmninit, varnorm, lda, ldadim, svspec."""
+
+    def update(self, **settings) -> "FeatConfig":
+        names = dict(SswFeatConfig._fields_)
+        for k, v in settings.items():
+            if k not in names or k == "from_file":
+                raise SswError(f"unknown feature setting {k!r}")
+            if k == "cmn" and isinstance(v, str):
+                if v not in CMN_TYPES:
+                    raise SswError(f"Unknown CMN type {v!r}")
+                v = CMN_TYPES[v]
+            if k == "cmninit" and v is not None and not isinstance(v, (str, bytes)):
+                v = ",".join(repr(float(x)) for x in v)
+            if k in ("feat", "cmninit", "lda", "svspec"):
+                v = b"" if v is None else os.fsencode(v)
+                if len(v) >= C.sizeof(names[k]):
+                    raise SswError(f"feature setting {k!r} is too long")
+            setattr(self, k, int(v) if isinstance(v, bool) else v)
+        return self
+
+    @classmethod
+    def read(cls, path, **settings) -> "FeatConfig":
+        """The reference's defaults, a feat_params.json's keys over them (ssw_feat_config_read),
+        then `settings`."""
+        L = _lib.lib()
+        c = cls()
+        L.ssw_feat_config_defaults(C.byref(c))
+        if path is not None:
+            _check(L.ssw_feat_config_read(os.fsencode(path), C.byref(c)), "ssw_feat_config_read")
+        return c.update(**settings)
+
+    def as_dict(self) -> dict:
+        inv = {0: "none", 1: "batch", 2: "live"}
+        return {"feat": self.feat.decode(), "ceplen": int(self.ceplen),
+                "cmn": inv.get(int(self.cmn), int(self.cmn)),
+                "cmninit": self.cmninit.decode() or None, "varnorm": bool(self.varnorm),
+                "lda": os.fsdecode(self.lda) or None, "ldadim": int(self.ldadim),
+                "svspec": self.svspec.decode() or None, "from_file": bool(self.from_file)}
 
 
 def fe_frame_counts(n_samples) -> np.ndarray:
@@ -139,6 +184,9 @@ class Model:
 
     def close(self):
         if getattr(self, "_m", None):
+            if getattr(self, "_feat0", None) is not None:
+                self._feat0.free()
+                self._feat0 = None
             self._L.ssw_model_free(self._m)
             self._m = None
 
@@ -465,6 +513,105 @@ class Model:
             self._L.ssw_device_free(d_out)
         return out
 
+    # ---- dynamic features of every configuration ---------------------------------------
+    def feat_config(self, **overrides) -> "FeatConfig":
+        """The feature stage's settings the model loaded from its feat_params.json (reference
+        defaults for missing keys; `lda` unset = the model directory's feature_transform, if it
+        has one), with `overrides` applied: feat, ceplen, cmn ("none", "batch" / "current",
+        "live" / "prior"), cmninit (a string or numbers), varnorm, lda (a path), ldadim, svspec.
+        None unsets a string setting."""
+        c = FeatConfig()
+        _check(self._L.ssw_model_feat_config(self._m, C.byref(c)), "ssw_model_feat_config")
+        return c.update(**overrides)
+
+    def feat(self, **overrides) -> "Feat":
+        """ssw_feat_create: the model's feature configuration (with overrides, or cfg=FeatConfig)
+        resolved, checked and with its tables on the device."""
+        cfg = overrides.pop("cfg", None)
+        if cfg is not None and overrides:
+            raise SswError("feat(): give cfg or overrides, not both")
+        if cfg is None and overrides:
+            cfg = self.feat_config(**overrides)
+        return Feat(self, cfg)
+
+    def _own_feat(self) -> "Feat":
+        if getattr(self, "_feat0", None) is None:
+            self._feat0 = Feat(self, None)
+        return self._feat0
+
+    def feat_plain(self) -> bool:
+        """Whether the helpers that go from audio compute this model's features with
+        ssw_feat_batch: it read no feat_params.json, or its configuration is the plain one
+        (1s_c_d_dd of 13 cepstra, batch CMN, no varnorm, no LDA, svspec absent or
+        0-12/13-25/26-38).  Everything else goes through ssw_feat_batch_ex."""
+        if getattr(self, "_feat_plain", None) is None:
+            c = self.feat_config()
+            if not c.from_file:
+                try:                      # a feat_params.json that is there but cannot be used
+                    Feat(self, None).free()   # is an error here, as it is for the front end
+                except SswError as e:
+                    if "feat_params.json cannot be used" in str(e):
+                        raise
+            self._feat_plain = (not c.from_file) or (
+                c.feat == b"1s_c_d_dd" and c.ceplen in (0, 13) and c.cmn == CMN_TYPES["batch"]
+                and not c.varnorm and not c.lda and c.svspec in (b"", b"0-12/13-25/26-38"))
+        return self._feat_plain
+
+    def feat_batch_ex_device(self, d_cep, n_frames, utt_off, d_out, feat=None, cmn_state=None,
+                             stream=None, ncep=None):
+        """ssw_feat_batch_ex on device buffers: d_cep float32 [n_frames][ceplen] -> d_out
+        [n_frames][feat.out_dim].  feat None: the model's own configuration.  cmn_state: an
+        SswCmnState, read and written with cmn = live."""
+        feat = feat if feat is not None else self._own_feat()
+        off = np.ascontiguousarray(utt_off, np.int32)
+        _check(self._L.ssw_feat_batch_ex(self._m, feat._h, _ptr(d_cep), n_frames, _ptr(off),
+                                         len(off) - 1, feat.ceplen if ncep is None else ncep,
+                                         _ptr(d_out),
+                                         None if cmn_state is None else C.byref(cmn_state),
+                                         _ptr(stream)), "ssw_feat_batch_ex")
+
+    def feat_batch_ex(self, cep, utt_off=None, feat=None, cmn_state=None) -> np.ndarray:
+        """Dynamic features as the model's (or `feat`'s) configuration says, on the GPU: host
+        cepstra [n][ceplen] -> host features [n][out_dim]."""
+        feat = feat if feat is not None else self._own_feat()
+        cep = np.ascontiguousarray(cep, np.float32)
+        n, ncep = cep.shape
+        off = (np.array([0, n], np.int32) if utt_off is None
+               else np.ascontiguousarray(utt_off, np.int32))
+        out = np.zeros((n, feat.out_dim), np.float32)
+        d_in = self.to_device(cep) if n else None
+        d_out = _check(self._L.ssw_device_malloc(out.nbytes), "ssw_device_malloc") if n else None
+        try:
+            self.feat_batch_ex_device(d_in, n, off, d_out, feat, cmn_state, ncep=ncep)
+            if n:
+                _check(self._L.ssw_memcpy_d2h(_ptr(out), d_out, out.nbytes), "ssw_memcpy_d2h")
+        finally:
+            if n:
+                self._L.ssw_device_free(d_in)
+                self._L.ssw_device_free(d_out)
+        return out
+
+    def _audio_feat_width(self) -> int:
+        """Floats per feature row of the audio helpers: 39 for the plain configuration
+        (feat_plain), else the configuration's out_dim, which must be the width of the model's
+        streams together."""
+        if self.feat_plain():
+            return 3 * FE_NCEP
+        feat = self._own_feat()
+        if feat.out_dim != self.veclen_total:
+            raise SswError(f"the model's feature configuration makes rows of {feat.out_dim} floats, "
+                           f"but its Gaussians' streams are {self.veclen_total} wide together")
+        return feat.out_dim
+
+    def _audio_feats(self, d_cep, n_frames, fo, d_feat, stream):
+        """The feature rows of the audio helpers: the plain configuration through ssw_feat_batch,
+        as ever; any other through ssw_feat_batch_ex."""
+        if self.feat_plain():
+            _check(self._L.ssw_feat_batch(self._m, d_cep, n_frames, _ptr(fo), len(fo) - 1,
+                                          FE_NCEP, d_feat, _ptr(stream)), "ssw_feat_batch")
+        else:
+            self.feat_batch_ex_device(d_cep, n_frames, fo, d_feat, None, None, stream, ncep=FE_NCEP)
+
     # ---- MFCC front end ----------------------------------------------------------------
     def fe_config(self, **overrides) -> SswFeConfig:
         """The front-end settings the model loaded from its feat_params.json (reference defaults
@@ -620,6 +767,39 @@ class Model:
 
     def device_free(self, p):
         self._L.ssw_device_free(p)
+
+
+class Feat:
+    """An ssw_feat_t: a feature configuration resolved as feat_init_s3file resolves it, with its
+    tables on the device (Model.feat)."""
+
+    def __init__(self, model: Model, cfg=None):
+        self._L = model._L
+        self._model = model
+        self._h = self._L.ssw_feat_create(model._m, None if cfg is None else C.byref(cfg))
+        if not self._h:
+            raise SswError("ssw_feat_create: " + _lib.last_error())
+        L, h = self._L, self._h
+        self.out_dim = int(L.ssw_feat_out_dim(h))
+        self.raw_dim = int(L.ssw_feat_raw_dim(h))
+        self.window = int(L.ssw_feat_window(h))
+        self.tile_frames = int(L.ssw_feat_tile_frames(h))
+        self.stream_lens = [int(L.ssw_feat_stream_len(h, i))
+                            for i in range(int(L.ssw_feat_n_streams(h)))]
+        self.ceplen = int((cfg if cfg is not None else model.feat_config()).ceplen) or 13
+
+    def cmn_prior(self) -> SswCmnState:
+        """ssw_feat_cmn_prior: the state of a fresh decoder (cmninit)."""
+        s = SswCmnState()
+        _check(self._L.ssw_feat_cmn_prior(self._h, C.byref(s)), "ssw_feat_cmn_prior")
+        return s
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._L.ssw_feat_free(self._h)
+            self._h = None
+
+    __del__ = free
 
 
 class CompactPlan:
@@ -1157,11 +1337,13 @@ def align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, texts, cfg=None
     """Audio and text in, alignments out: what decoder_process_int16 over each utterance and
     decoder_alignment give (src/decoder.c:737-798), for a batch.  int16 PCM (host array or
     device tensor; utterance u = samples samp_off[u] .. samp_off[u + 1]) -> ssw_fe_batch ->
-    ssw_feat_batch -> ssw_align_text_batch, or ssw_align_text_batch_active when active=True (the
+    ssw_feat_batch (ssw_feat_batch_ex when the model's feat_params.json asks for anything but
+    the plain features, Model.feat_plain) -> ssw_align_text_batch, or ssw_align_text_batch_active when active=True (the
     reference's default compallsen = no).  cfg: FirstPassConfig; fe_cfg: front-end settings
     (None = the model's feat_params.json).  samprate None: 16 kHz audio through ssw_fe_batch;
     a number, or one per utterance: the cepstra at that rate through ssw_fe_batch_ex, as the
     reference computes them at the rate the audio has."""
+    width = model._audio_feat_width()
     off = np.ascontiguousarray(samp_off, np.int64)
     n_frames = int(fe_frame_counts(np.diff(off)).sum() if samprate is None else
                    model.fe_frame_counts_rates(np.diff(off), samprate, fe_cfg).sum())
@@ -1169,7 +1351,7 @@ def align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, texts, cfg=None
     d_pcm = pcm if on_device else (model.to_device(np.ascontiguousarray(pcm, np.int16))
                                    if off[-1] > 0 else None)
     d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
-    d_feat = model.device_malloc(n_frames * 3 * FE_NCEP * 4) if n_frames else None
+    d_feat = model.device_malloc(n_frames * width * 4) if n_frames else None
     try:
         if samprate is None:
             _, fo = model.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, fe_cfg, stream)
@@ -1177,8 +1359,7 @@ def align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, texts, cfg=None
             _, fo = model.fe_batch_rates_device(d_pcm, off, samprate, d_cep if d_cep else 0,
                                                 fe_cfg, stream)
         if n_frames:
-            _check(model._L.ssw_feat_batch(model._m, d_cep, n_frames, _ptr(fo), len(fo) - 1,
-                                           FE_NCEP, d_feat, _ptr(stream)), "ssw_feat_batch")
+            model._audio_feats(d_cep, n_frames, fo, d_feat, stream)
         fn = align_text_batch_active if active else align_text_batch
         return fn(model, lex, d_feat if d_feat else 0, fo, texts, cfg=cfg, scorer=scorer,
                   stream=stream)
@@ -1515,8 +1696,10 @@ def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: Gramm
     """Audio in, hypotheses out: decoder_process_int16(full_utt) + decoder_hyp / decoder_seg_iter
     under decoder_set_fsg with compallsen = yes, for a batch.  int16 PCM (host array or device
     tensor; utterance u = samples samp_off[u] .. samp_off[u + 1]) -> ssw_fe_batch (samprate None:
-    16 kHz) or ssw_fe_batch_ex -> ssw_feat_batch -> ssw_recognize_batch, or
+    16 kHz) or ssw_fe_batch_ex -> ssw_feat_batch (ssw_feat_batch_ex when the model's
+    feat_params.json asks for anything but the plain features) -> ssw_recognize_batch, or
     ssw_recognize_batch_active when active=True (the reference's default compallsen = no)."""
+    width = model._audio_feat_width()
     off = np.ascontiguousarray(samp_off, np.int64)
     n_frames = int(fe_frame_counts(np.diff(off)).sum() if samprate is None else
                    model.fe_frame_counts_rates(np.diff(off), samprate, fe_cfg).sum())
@@ -1524,7 +1707,7 @@ def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: Gramm
     d_pcm = pcm if on_device else (model.to_device(np.ascontiguousarray(pcm, np.int16))
                                    if off[-1] > 0 else None)
     d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
-    d_feat = model.device_malloc(n_frames * 3 * FE_NCEP * 4) if n_frames else None
+    d_feat = model.device_malloc(n_frames * width * 4) if n_frames else None
     try:
         if samprate is None:
             _, fo = model.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, fe_cfg, stream)
@@ -1532,8 +1715,7 @@ def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: Gramm
             _, fo = model.fe_batch_rates_device(d_pcm, off, samprate, d_cep if d_cep else 0,
                                                 fe_cfg, stream)
         if n_frames:
-            _check(model._L.ssw_feat_batch(model._m, d_cep, n_frames, _ptr(fo), len(fo) - 1,
-                                           FE_NCEP, d_feat, _ptr(stream)), "ssw_feat_batch")
+            model._audio_feats(d_cep, n_frames, fo, d_feat, stream)
         if active:
             return recognize_batch_active(model, lex, d_feat if d_feat else 0, fo, plan,
                                           fsg_of_utt, scorer=scorer, stream=stream)[0]

@@ -269,6 +269,11 @@ struct ssw_model_s {
     float *d_cont_rec;
     uint8_t *d_cont_pdf;
     DevBuf cont_ws;
+    /* dynamic features of every configuration (ssw_host_featex.inc): the model's own
+     * configuration, built by the first ssw_feat_batch_ex call that passes none, and the
+     * workspace: tile table, utterance offsets, means, scales, the CMN state */
+    ssw_feat_t *own_feat;
+    DevBuf featex_ws;
 };
 
 static inline void
@@ -775,11 +780,13 @@ ssw_model_free(ssw_model_t *m)
 {
     if (m == NULL)
         return;
+    ssw_feat_free(m->own_feat);
     if (m->device == SSW_DEVICE_NONE) {
         ssw_host_model_free(m->h);
         delete m;
         return;
     }
+    (void)hipFree(m->featex_ws.p);
     (void)hipFree(m->d_rec);
     (void)hipFree(m->d_rec28);
     (void)hipFree(m->d_recq);

@@ -93,9 +93,47 @@ ssw_fe_rate_t *ssw_fe_rate_build(const ssw_fe_config_t *c, const ssw_fe_framing_
 int64_t ssw_fe_frames_of(int64_t n_samples);
 int64_t ssw_fe_frames_at(const ssw_fe_framing_t *f, int64_t n_samples);
 
+/* Dynamic features (ssw_model.c, ssw_k12_feat.inc, ssw_host_featex.inc): a configuration as
+ * feat_init_s3file resolves it (src/feat.c:732-927). */
+#define SSW_FEAT_MAX_CEP 64
+#define SSW_FEAT_MAX_WIN 8
+#define SSW_FEAT_MAX_LDA_ROWS 256
+/* one float of the raw feature vector (the streams back to back, before LDA and svspec) as the
+ * reference's compute_feat functions form it (src/feat.c:437-712), packed into 32 bits:
+ *   bits 0..1   op: 0  c[t+o0][i]                      (memcpy, feat_copy)
+ *                   1  c[t+o0][i] - c[t+o1][i]          (a delta)
+ *                   2  (c[t+o0][i] - c[t+o1][i]) - (c[t+o2][i] - c[t+o3][i])   (d1 - d2)
+ *   bits 2..7   i, the cepstral dimension
+ *   bits 8..27  o0..o3, each + SSW_FEAT_MAX_WIN in 5 bits */
+#define SSW_FEAT_RECIPE(op, i, o0, o1, o2, o3)                                               \
+    ((uint32_t)(op) | (uint32_t)(i) << 2 | (uint32_t)((o0) + SSW_FEAT_MAX_WIN) << 8           \
+     | (uint32_t)((o1) + SSW_FEAT_MAX_WIN) << 13 | (uint32_t)((o2) + SSW_FEAT_MAX_WIN) << 18  \
+     | (uint32_t)((o3) + SSW_FEAT_MAX_WIN) << 23)
+typedef struct ssw_feat_plan_s {
+    int32_t cepsize, window, n_stream, stream_len[SSW_MAX_FEAT], raw_dim;
+    int32_t cmn, varnorm;      /* enum ssw_cmn */
+    int32_t lda_rows;          /* rows used (feat->out_dim after feat_read_lda_s3file), 0 = no LDA */
+    int32_t n_sv, sv_len[SSW_MAX_FEAT], sv_dim; /* svspec: subvectors, 0 = none */
+    int32_t out_dim;           /* floats per output row: sv_dim, else lda_rows, else raw_dim */
+    uint32_t *recipe;          /* [raw_dim] */
+    float *lda_t;              /* [raw_dim][lda_rows]: matrix 0 of the file, transposed */
+    int32_t *sv;               /* [sv_dim] dimensions gathered, in output order */
+    float prior_mean[SSW_FEAT_MAX_CEP], prior_sum[SSW_FEAT_MAX_CEP]; /* cmn_set_repr(cmninit) */
+    int32_t prior_nframe;
+} ssw_feat_plan_t;
+/* 0, or -1 and ssw_set_error; on success the caller owns the plan's arrays */
+int ssw_feat_plan_build(const ssw_feat_config_t *c, ssw_feat_plan_t *p);
+void ssw_feat_plan_free(ssw_feat_plan_t *p);
+/* feat_params.json's FEAT_OPTIONS keys over *c: 0 read, 1 no such file, -1 unusable (err) */
+int ssw_feat_config_read_err(const char *path, ssw_feat_config_t *c, char *err, size_t err_len);
+
 /* Host-side model: every table derived exactly as the reference derives it. */
 typedef struct ssw_host_model_s {
     ssw_config_t cfg;
+    /* the feature stage's settings from the same feat_params.json, and why they could not be
+     * read ("" when they could) */
+    ssw_feat_config_t feat;
+    char feat_err[256];
     /* front end: feat_params.json beside the means file (ssw_model.c); fe_err holds why that file
      * could not be used ("" when it could, or when there is none) */
     ssw_fe_config_t fe;

@@ -61,6 +61,12 @@
  *                        cont_score_kernel (compute_dist + senone_eval, a lane per senone),
  *                        cont_norm_kernel (the frame's minimum), src/ms_gauden.c:349-432,
  *                        src/ms_senone.c:314-362, src/ms_mgau.c:299-321
+ *   ssw_k12_feat.inc     dynamic features of every type feat_init_s3file accepts, with batch or
+ *                        live CMN, varnorm, an LDA and a subvector gather: feat_stats_kernel /
+ *                        feat_chain_kernel (the utterances' means and scales, live CMN's state)
+ *                        and feat_tile_kernel (frame-parallel), src/feat.c:437-712, :977-1008,
+ *                        src/cmn.c:159-224, src/cmn_live.c:60-134, src/lda.c:124-144
+ *   ssw_feat_tiles.inc   host, no HIP: the tile table and tile size of ssw_feat_batch_ex
  *   ssw_ws_layout.inc    host, no HIP: align256 and WsLayout, the one layout of a device
  *                        workspace (256-byte-aligned offsets in call order, the uploaded pieces
  *                        staged by fill(); a host program can include it on its own)
@@ -127,10 +133,12 @@ namespace {
 #include "ssw_k9_grammar.inc"
 #include "ssw_k10_semi.inc"
 #include "ssw_k11_cont.inc"
+#include "ssw_k12_feat.inc"
 
 } // namespace
 
 #include "ssw_ws_layout.inc"
+#include "ssw_feat_tiles.inc"
 #include "ssw_host_model.inc"
 #include "ssw_host_semi.inc"
 /* ssw_host_cont.inc comes LAST: kernels are emitted in the order the host code first launches
@@ -154,3 +162,5 @@ static int cont_launch(ssw_model_s *m, const float *d_feats, int32_t n_frames, i
 #include "ssw_host_devmem.inc"
 #include "ssw_host_comm.inc"
 #include "ssw_host_cont.inc"
+/* ... and the feature kernels of every configuration behind those, for the same reason */
+#include "ssw_host_featex.inc"

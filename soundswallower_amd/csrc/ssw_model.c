@@ -218,11 +218,15 @@ fe_set_key(ssw_fe_config_t *c, const char *key, const char *v, int is_string)
     return 0;
 }
 
-int
-ssw_fe_config_read(const char *path, ssw_fe_config_t *c, char *err, size_t err_len)
+/* a flat JSON object: set(ctx, key, value, is_string) for every pair, which returns -1 for a
+ * value it cannot use.  0 read, 1 no such file, -1 unusable (message in err) */
+typedef int (*json_key_fn)(void *ctx, const char *key, const char *val, int is_string);
+
+static int
+json_object_read(const char *path, json_key_fn set, void *ctx, char *err, size_t err_len)
 {
     FILE *f = fopen(path, "rb");
-    char *buf = NULL, key[128], val[512];
+    char *buf = NULL, key[128], val[1100];
     const char *p;
     long len;
     int is_string, rv = -1;
@@ -259,7 +263,7 @@ ssw_fe_config_read(const char *path, ssw_fe_config_t *c, char *err, size_t err_l
             snprintf(err, err_len, "%s: bad value of \"%s\"", path, key);
             goto done;
         }
-        if (fe_set_key(c, key, val, is_string) < 0) {
+        if (set(ctx, key, val, is_string) < 0) {
             snprintf(err, err_len, "%s: cannot use \"%s\" as the value of \"%s\"", path, val, key);
             goto done;
         }
@@ -272,11 +276,25 @@ ssw_fe_config_read(const char *path, ssw_fe_config_t *c, char *err, size_t err_l
             goto done;
         }
     }
-    c->from_file = 1;
     rv = 0;
 done:
     free(buf);
     fclose(f);
+    return rv;
+}
+
+static int
+fe_set_key_cb(void *ctx, const char *key, const char *v, int is_string)
+{
+    return fe_set_key((ssw_fe_config_t *)ctx, key, v, is_string);
+}
+
+int
+ssw_fe_config_read(const char *path, ssw_fe_config_t *c, char *err, size_t err_len)
+{
+    const int rv = json_object_read(path, fe_set_key_cb, c, err, err_len);
+    if (rv == 0)
+        c->from_file = 1;
     return rv;
 }
 
@@ -820,6 +838,496 @@ rd_s3_finish(rd_t *r)
         return -1;
     }
     return 0;
+}
+
+/* ---------------------------------------------------------------------------------- */
+/* Dynamic features: the FEAT_OPTIONS keys of feat_params.json (include/soundswallower/ */
+/* config_defs.h:418-450) and the configuration feat_init_s3file makes of them          */
+/* (src/feat.c:732-927).  The kernels (ssw_k12_feat.inc) only read the tables.          */
+/* ---------------------------------------------------------------------------------- */
+void
+ssw_feat_config_defaults(ssw_feat_config_t *c)
+{
+    memset(c, 0, sizeof(*c));
+    strcpy(c->feat, "1s_c_d_dd");
+    c->ceplen = 13;
+    c->cmn = SSW_CMN_LIVE;
+    strcpy(c->cmninit, "40,3,-1");
+}
+
+/* a string setting: null = unset */
+static int
+feat_set_str(char *dst, size_t cap, const char *v, int is_string)
+{
+    if (!is_string && !strcmp(v, "null"))
+        v = "";
+    if (strlen(v) >= cap)
+        return -1;
+    strcpy(dst, v);
+    return 0;
+}
+
+static int
+feat_set_key(void *ctx, const char *key, const char *v, int is_string)
+{
+    ssw_feat_config_t *c = (ssw_feat_config_t *)ctx;
+    if (key[0] == '-') /* command-line spelling */
+        ++key;
+    if (!strcmp(key, "feat"))
+        return v[0] == '\0' ? -1 : feat_set_str(c->feat, sizeof(c->feat), v, 1);
+    if (!strcmp(key, "ceplen"))
+        return parse_int(v, &c->ceplen);
+    if (!strcmp(key, "ldadim"))
+        return parse_int(v, &c->ldadim);
+    if (!strcmp(key, "varnorm"))
+        return parse_bool(v, &c->varnorm);
+    if (!strcmp(key, "cmninit"))
+        return feat_set_str(c->cmninit, sizeof(c->cmninit), v, is_string);
+    if (!strcmp(key, "lda"))
+        return feat_set_str(c->lda, sizeof(c->lda), v, is_string);
+    if (!strcmp(key, "svspec"))
+        return feat_set_str(c->svspec, sizeof(c->svspec), v, is_string);
+    if (!strcmp(key, "cmn")) {
+        /* cmn_type_from_str, src/cmn.c:55-79: "Unknown CMN type" is fatal there */
+        if (!strcmp(v, "none"))
+            c->cmn = SSW_CMN_NONE;
+        else if (!strcmp(v, "batch") || !strcmp(v, "current"))
+            c->cmn = SSW_CMN_BATCH;
+        else if (!strcmp(v, "live") || !strcmp(v, "prior"))
+            c->cmn = SSW_CMN_LIVE;
+        else
+            return -1;
+        return 0;
+    }
+    return 0;
+}
+
+int
+ssw_feat_config_read_err(const char *path, ssw_feat_config_t *c, char *err, size_t err_len)
+{
+    const int rv = json_object_read(path, feat_set_key, c, err, err_len);
+    if (rv == 0)
+        c->from_file = 1;
+    return rv;
+}
+
+int
+ssw_feat_config_read(const char *path, ssw_feat_config_t *c)
+{
+    char err[600];
+    int rv;
+    if (path == NULL || c == NULL) {
+        ssw_set_error("bad arguments to ssw_feat_config_read");
+        return -1;
+    }
+    rv = ssw_feat_config_read_err(path, c, err, sizeof(err));
+    if (rv < 0)
+        ssw_set_error("%s", err);
+    return rv;
+}
+
+void
+ssw_feat_plan_free(ssw_feat_plan_t *p)
+{
+    free(p->recipe);
+    free(p->lda_t);
+    free(p->sv);
+    p->recipe = NULL;
+    p->lda_t = NULL;
+    p->sv = NULL;
+}
+
+/* the generic type "n,n,...[:window]" as src/feat.c:827-884 scans it: commas between the first
+ * and the last character become blanks, a colon there ends the list and atoi reads the window
+ * behind it, every blank-separated word is a stream width read with %u */
+static int
+feat_plan_generic(const char *type, int32_t ceplen, ssw_feat_plan_t *p)
+{
+    char mtype[64], wd[64];
+    const size_t len = strlen(type);
+    const char *strp;
+    size_t i;
+    int k = 0, n = 0, l;
+    long long cepsize = 0;
+
+    if (len == 0 || len >= sizeof(mtype))
+        goto bad;
+    strcpy(mtype, type);
+    for (i = 1; i + 1 < len; ++i) {
+        if (mtype[i] == ',') {
+            mtype[i] = ' ';
+            ++k;
+        } else if (mtype[i] == ':') {
+            mtype[i] = '\0';
+            p->window = atoi(mtype + i + 1);
+            break;
+        }
+    }
+    ++k;
+    if (p->window < 0 || p->window > SSW_FEAT_MAX_WIN) {
+        ssw_set_error("feat = %s: a window of %d frames (supported: 0..%d)", type, p->window,
+                      SSW_FEAT_MAX_WIN);
+        return -1;
+    }
+    if (k > SSW_MAX_FEAT) {
+        ssw_set_error("feat = %s: %d streams (supported: at most %d)", type, k, SSW_MAX_FEAT);
+        return -1;
+    }
+    p->n_stream = k;
+    strp = mtype;
+    while (sscanf(strp, "%63s%n", wd, &l) == 1) {
+        unsigned int w;
+        strp += l;
+        if (n >= k || sscanf(wd, "%u", &w) != 1 || w == 0 || w > SSW_FEAT_MAX_CEP)
+            goto bad;
+        cepsize += w;
+        p->stream_len[n++] = (int32_t)w * (2 * p->window + 1);
+    }
+    if (n != k || cepsize != ceplen)
+        goto bad;
+    p->cepsize = ceplen;
+    return 0;
+bad:
+    ssw_set_error("feat = %s: Bad feature type argument (ceplen %d)", type, ceplen);
+    return -1;
+}
+
+/* feat_read_lda_s3file, src/lda.c:84-122: a 3-d float array of which matrix 0 is used, its
+ * checksum verified, as wide as the stream; dim <= 0 or beyond the rows = every row.  The used
+ * rows go into p->lda_t transposed, [column][row]. */
+static int
+feat_plan_read_lda(const char *path, int32_t dim, ssw_feat_plan_t *p)
+{
+    rd_t r;
+    int32_t dims[3], total, rows, j, k;
+    float *data = NULL;
+
+    if (rd_open(&r, path) < 0)
+        return -1;
+    if (rd_s3_header(&r) < 0 || rd_words(&r, dims, 3) < 0 || rd_i32(&r, &total) < 0)
+        goto bad;
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || dims[1] > (1 << 20) || dims[2] > (1 << 20)
+        || (int64_t)total != (int64_t)dims[0] * dims[1] * dims[2] || total > (1 << 26)) {
+        ssw_set_error("%s: %d values do not make a %d x %d x %d transform", path, total, dims[0],
+                      dims[1], dims[2]);
+        goto bad;
+    }
+    data = (float *)malloc(sizeof(float) * (size_t)total);
+    if (data == NULL) {
+        ssw_set_error("out of memory");
+        goto bad;
+    }
+    if (rd_words(&r, data, (size_t)total) < 0 || rd_s3_finish(&r) < 0)
+        goto bad;
+    if (dims[2] != p->stream_len[0]) {
+        ssw_set_error("%s: LDA matrix dimension %d doesn't match feature stream size %d", path,
+                      dims[2], p->stream_len[0]);
+        goto bad;
+    }
+    rows = (dim > dims[1] || dim <= 0) ? dims[1] : dim;
+    if (rows > SSW_FEAT_MAX_LDA_ROWS) {
+        ssw_set_error("%s: %d rows of the LDA matrix are used (supported: at most %d)", path, rows,
+                      SSW_FEAT_MAX_LDA_ROWS);
+        goto bad;
+    }
+    p->lda_t = (float *)malloc(sizeof(float) * (size_t)rows * (size_t)dims[2]);
+    if (p->lda_t == NULL) {
+        ssw_set_error("out of memory");
+        goto bad;
+    }
+    for (j = 0; j < rows; ++j)
+        for (k = 0; k < dims[2]; ++k)
+            p->lda_t[(size_t)k * rows + j] = data[(size_t)j * dims[2] + k];
+    p->lda_rows = rows;
+    free(data);
+    rd_close(&r);
+    return 0;
+bad:
+    free(data);
+    rd_close(&r);
+    return -1;
+}
+
+/* parse_subvecs and feat_set_subvecs, src/feat.c:181-341: subvectors apart by '/', in each a
+ * comma-separated list of dimensions or ranges a-b; a dimension may not come twice in one
+ * subvector.  `pre` is feat_dimension (the LDA's rows, else the stream's length). */
+static int
+feat_plan_svspec(const char *str, int32_t pre, ssw_feat_plan_t *p)
+{
+    const char *s = str;
+    /* (a subvector starts with at most `pre` <= raw_dim entries before it and adds at most
+     * raw_dim distinct ones before the total is checked) */
+    int32_t *sv = (int32_t *)malloc(sizeof(int32_t) * (size_t)(2 * p->raw_dim + 1));
+    int n_sv = 0, n_dim = 0, first = 0;
+
+    if (sv == NULL) {
+        ssw_set_error("out of memory");
+        return -1;
+    }
+    for (;;) {
+        int n, n2, l, q;
+        if (sscanf(s, "%d%n", &n, &l) != 1) {
+            ssw_set_error("svspec '%s': Couldn't read int32 @pos %d", str, (int)(s - str));
+            goto bad;
+        }
+        s += l;
+        n2 = n;
+        if (*s == '-') {
+            ++s;
+            if (sscanf(s, "%d%n", &n2, &l) != 1) {
+                ssw_set_error("svspec '%s': Couldn't read int32 @pos %d", str, (int)(s - str));
+                goto bad;
+            }
+            s += l;
+        }
+        if (n < 0 || n > n2) {
+            ssw_set_error("svspec '%s': Bad subrange spec ending @pos %d", str, (int)(s - str));
+            goto bad;
+        }
+        if (n2 >= p->raw_dim) {
+            /* (the reference reads past the frame's row here) */
+            ssw_set_error("svspec '%s': dimension %d ending @pos %d is beyond the %d the stream has",
+                          str, n2, (int)(s - str), p->raw_dim);
+            goto bad;
+        }
+        for (; n <= n2; ++n) {
+            for (q = first; q < n_dim; ++q)
+                if (sv[q] == n) {
+                    ssw_set_error("svspec '%s': Duplicate dimension ending @pos %d", str,
+                                  (int)(s - str));
+                    goto bad;
+                }
+            sv[n_dim++] = n; /* (no duplicates in a subvector: at most raw_dim entries each) */
+        }
+        if (*s == ',') {
+            ++s;
+            continue;
+        }
+        if (*s != '\0' && *s != '/') {
+            ssw_set_error("svspec '%s': Bad delimiter @pos %d", str, (int)(s - str));
+            goto bad;
+        }
+        if (n_sv >= SSW_MAX_FEAT) {
+            ssw_set_error("svspec '%s': more than %d subvectors", str, SSW_MAX_FEAT);
+            goto bad;
+        }
+        p->sv_len[n_sv++] = n_dim - first;
+        first = n_dim;
+        if (n_dim > pre) {
+            ssw_set_error("svspec '%s': Total dimensionality of subvector specification %d "
+                          "> feature dimensionality %d", str, n_dim, pre);
+            goto bad;
+        }
+        if (*s == '\0')
+            break;
+        ++s;
+    }
+    p->sv = sv;
+    p->n_sv = n_sv;
+    p->sv_dim = n_dim;
+    return 0;
+bad:
+    free(sv);
+    return -1;
+}
+
+int
+ssw_feat_plan_build(const ssw_feat_config_t *c, ssw_feat_plan_t *p)
+{
+    const char *type = c->feat;
+    int32_t cepsize = c->ceplen == 0 ? 13 : c->ceplen; /* src/feat.c:741-742 */
+    int32_t kind, i, j, k, w, C;
+    uint32_t *r;
+    enum { K_S2_4X, K_S3_1X39, K_C_D_DD, K_C_D_LD_DD, K_C_D, K_C, K_COPY };
+
+    memset(p, 0, sizeof(*p));
+    if (memchr(c->feat, '\0', sizeof(c->feat)) == NULL || memchr(c->cmninit, '\0', sizeof(c->cmninit)) == NULL
+        || memchr(c->lda, '\0', sizeof(c->lda)) == NULL || memchr(c->svspec, '\0', sizeof(c->svspec)) == NULL) {
+        ssw_set_error("feature configuration: a string setting is not terminated");
+        return -1;
+    }
+    if (cepsize < 1 || cepsize > SSW_FEAT_MAX_CEP) {
+        ssw_set_error("feature configuration: ceplen %d (supported: 1..%d)", cepsize, SSW_FEAT_MAX_CEP);
+        return -1;
+    }
+    if (c->cmn != SSW_CMN_NONE && c->cmn != SSW_CMN_BATCH && c->cmn != SSW_CMN_LIVE) {
+        ssw_set_error("feature configuration: Unknown CMN type %d", c->cmn);
+        return -1;
+    }
+    /* the reference's chain of comparisons, in its order (src/feat.c:749-884) */
+    p->n_stream = 1;
+    p->cepsize = cepsize;
+    if (strcmp(type, "s2_4x") == 0) {
+        if (cepsize != 13) {
+            ssw_set_error("feat = s2_4x: s2_4x features require cepsize == 13 (ceplen is %d)", cepsize);
+            return -1;
+        }
+        kind = K_S2_4X;
+        p->n_stream = 4;
+        p->stream_len[0] = 12;
+        p->stream_len[1] = 24;
+        p->stream_len[2] = 3;
+        p->stream_len[3] = 12;
+        p->window = 4;
+    } else if (strcmp(type, "s3_1x39") == 0 || strcmp(type, "1s_12c_12d_3p_12dd") == 0) {
+        if (cepsize != 13) {
+            ssw_set_error("feat = %s: s3_1x39 features require cepsize == 13 (ceplen is %d)", type,
+                          cepsize);
+            return -1;
+        }
+        kind = K_S3_1X39;
+        p->stream_len[0] = 39;
+        p->window = 3;
+    } else if (strncmp(type, "1s_c_d_dd", 9) == 0) {
+        kind = K_C_D_DD;
+        p->stream_len[0] = cepsize * 3;
+        p->window = 3; /* FEAT_DCEP_WIN + 1 */
+    } else if (strncmp(type, "1s_c_d_ld_dd", 12) == 0) {
+        kind = K_C_D_LD_DD;
+        p->stream_len[0] = cepsize * 4;
+        p->window = 4; /* FEAT_DCEP_WIN * 2 */
+    } else if (strncmp(type, "cep_dcep", 8) == 0 || strncmp(type, "1s_c_d", 6) == 0) {
+        kind = K_C_D;
+        p->stream_len[0] = cepsize * 2;
+        p->window = 2;
+    } else if (strncmp(type, "cep", 3) == 0 || strncmp(type, "1s_c", 4) == 0) {
+        kind = K_C;
+        p->stream_len[0] = cepsize;
+        p->window = 0;
+    } else if (strncmp(type, "1s_3c", 5) == 0 || strncmp(type, "1s_4c", 5) == 0) {
+        kind = K_COPY;
+        p->window = strncmp(type, "1s_3c", 5) == 0 ? 3 : 4;
+        p->stream_len[0] = cepsize * (2 * p->window + 1);
+    } else {
+        kind = K_COPY;
+        if (feat_plan_generic(type, cepsize, p) < 0)
+            return -1;
+    }
+    for (j = 0; j < p->n_stream; ++j)
+        p->raw_dim += p->stream_len[j];
+    p->cmn = c->cmn;
+    p->varnorm = c->varnorm != 0;
+    if (p->cmn == SSW_CMN_LIVE && p->varnorm) {
+        /* cmn_live, src/cmn_live.c:114-115: fatal at the first utterance */
+        ssw_set_error("feature configuration: Variance normalization not implemented in live mode "
+                      "decode (varnorm with cmn = live)");
+        return -1;
+    }
+    /* cmn_set_repr, src/cmn.c:112-140 */
+    if (p->cmn != SSW_CMN_NONE && c->cmninit[0]) {
+        char vals[sizeof(c->cmninit)], *s = vals, *cc;
+        int nvals = 0;
+        strcpy(vals, c->cmninit);
+        while (nvals < cepsize && (cc = strchr(s, ',')) != NULL) {
+            *cc = '\0';
+            p->prior_mean[nvals] = (float)atof(s);
+            p->prior_sum[nvals] = p->prior_mean[nvals] * 500; /* CMN_WIN */
+            s = cc + 1;
+            ++nvals;
+        }
+        if (nvals < cepsize && *s != '\0') {
+            p->prior_mean[nvals] = (float)atof(s);
+            p->prior_sum[nvals] = p->prior_mean[nvals] * 500;
+        }
+        p->prior_nframe = 500;
+    }
+    /* the recipe of every raw dimension, as the compute_feat functions write them
+     * (src/feat.c:437-712) */
+    r = p->recipe = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)p->raw_dim);
+    if (r == NULL) {
+        ssw_set_error("out of memory");
+        return -1;
+    }
+    C = cepsize;
+#define COPY(i, o) SSW_FEAT_RECIPE(0, i, o, 0, 0, 0)
+#define DELTA(i, o) SSW_FEAT_RECIPE(1, i, o, -(o), 0, 0)
+#define DDELTA(i) SSW_FEAT_RECIPE(2, i, 3, -1, 1, -3)
+    switch (kind) {
+    case K_S2_4X: /* cep 1..12 | short and long delta | c0, its delta and delta-delta | dd */
+        for (i = 0; i < 12; ++i) {
+            r[i] = COPY(i + 1, 0);
+            r[12 + i] = DELTA(i + 1, 2);
+            r[24 + i] = DELTA(i + 1, 4);
+            r[39 + i] = DDELTA(i + 1);
+        }
+        r[36] = COPY(0, 0);
+        r[37] = DELTA(0, 2);
+        r[38] = DDELTA(0);
+        break;
+    case K_S3_1X39: /* cep 1..12 | delta | c0, its delta and delta-delta | dd */
+        for (i = 0; i < 12; ++i) {
+            r[i] = COPY(i + 1, 0);
+            r[12 + i] = DELTA(i + 1, 2);
+            r[27 + i] = DDELTA(i + 1);
+        }
+        r[24] = COPY(0, 0);
+        r[25] = DELTA(0, 2);
+        r[26] = DDELTA(0);
+        break;
+    case K_C_D_DD:
+        for (i = 0; i < C; ++i) {
+            r[i] = COPY(i, 0);
+            r[C + i] = DELTA(i, 2);
+            r[2 * C + i] = DDELTA(i);
+        }
+        break;
+    case K_C_D_LD_DD:
+        for (i = 0; i < C; ++i) {
+            r[i] = COPY(i, 0);
+            r[C + i] = DELTA(i, 2);
+            r[2 * C + i] = DELTA(i, 4);
+            r[3 * C + i] = DDELTA(i);
+        }
+        break;
+    case K_C_D:
+        for (i = 0; i < C; ++i) {
+            r[i] = COPY(i, 0);
+            r[C + i] = DELTA(i, 2);
+        }
+        break;
+    case K_C:
+        for (i = 0; i < C; ++i)
+            r[i] = COPY(i, 0);
+        break;
+    default: /* feat_copy: frames -window .. window of every stream's part, side by side */
+        for (j = 0, k = 0, i = 0; j < p->n_stream; ++j) {
+            const int32_t sl = p->stream_len[j] / (2 * p->window + 1);
+            int32_t e;
+            for (w = -p->window; w <= p->window; ++w)
+                for (e = 0; e < sl; ++e)
+                    r[k++] = COPY(i + e, w);
+            i += sl;
+        }
+        break;
+    }
+#undef COPY
+#undef DELTA
+#undef DDELTA
+    p->out_dim = p->raw_dim;
+    if (c->lda[0]) {
+        if (p->n_stream != 1) {
+            ssw_set_error("feature configuration: LDA incompatible with multi-stream features "
+                          "(n_stream = %d)", p->n_stream);
+            goto bad;
+        }
+        if (feat_plan_read_lda(c->lda, c->ldadim, p) < 0)
+            goto bad;
+        p->out_dim = p->lda_rows;
+    }
+    if (c->svspec[0]) {
+        if (p->n_stream != 1) {
+            ssw_set_error("feature configuration: Subvector specifications require single-stream "
+                          "features! (n_stream = %d)", p->n_stream);
+            goto bad;
+        }
+        if (feat_plan_svspec(c->svspec, p->out_dim, p) < 0)
+            goto bad;
+        p->out_dim = p->sv_dim;
+    }
+    return 0;
+bad:
+    ssw_feat_plan_free(p);
+    return -1;
 }
 
 /* ---------------------------------------------------------------------------------- */
@@ -2114,6 +2622,22 @@ ssw_host_model_load(const char *mdef, const char *means, const char *variances,
         if (ssw_fe_config_read(path, &h->fe, h->fe_err, sizeof(h->fe_err)) < 0) {
             ssw_fe_config_defaults(&h->fe);
             h->fe.from_file = 0;
+        }
+        /* the feature stage's keys of the same file; `lda` unset = the directory's
+         * feature_transform, if there is one (expand_file_config, src/decoder.c:90-119) */
+        ssw_feat_config_defaults(&h->feat);
+        if (ssw_feat_config_read_err(path, &h->feat, h->feat_err, sizeof(h->feat_err)) < 0) {
+            ssw_feat_config_defaults(&h->feat);
+            h->feat.from_file = 0;
+        }
+        if (h->feat.lda[0] == '\0' && dir + sizeof("feature_transform") <= sizeof(h->feat.lda)) {
+            FILE *lf;
+            memcpy(h->feat.lda, means, dir);
+            strcpy(h->feat.lda + dir, "feature_transform");
+            if ((lf = fopen(h->feat.lda, "rb")) != NULL)
+                fclose(lf);
+            else
+                h->feat.lda[0] = '\0';
         }
         free(path);
     }
