@@ -948,6 +948,60 @@ int32_t ssw_recognition_set_json(const ssw_recognition_set_t *r, int32_t utt, do
                                  int32_t frate, char *out, int32_t out_len);
 void ssw_recognition_set_free(ssw_recognition_set_t *r);
 
+/* decoder_result_json(d, start, 1 or 2) after a grammar: decoder_alignment (src/decoder.c:737-798)
+ * for every utterance of a recognition set.  The best path's entries are walked in order
+ * (decoder_seg_iter); an entry whose word is no dictionary word ("(NULL)", wid < 0) is skipped
+ * (:759-761); every other one, fillers and alternate pronunciations included, is
+ * alignment_add_word(wid, sf, ef - sf + 1), the windows as they are (the contiguity assert of
+ * :763 is compiled out of a release build); then alignment_populate (:769), the state alignment
+ * constrained to those windows (state_align_search_init / step / finish, :777-795) and
+ * alignment_propagate.  The set is read with the ssw_alignment_set_* calls; per utterance:
+ *   0  aligned
+ *   1  no hypothesis (decoder_seg_iter NULL, :753-755; recognition status 1 or 2): the
+ *      recognition set's message, e.g. "Final result does not match the grammar in frame N"
+ *   2  alignment_populate or the second pass failed; also a path without a dictionary word on it
+ *      (null transitions only), with a message saying so -- no equality with the reference is
+ *      claimed for that one
+ * and the other utterances of the batch are aligned all the same.  ssw_alignment_set_json of
+ * such a set prints decoder_hyp's text -- the recognition set's hypothesis, which follows the
+ * GRAMMAR's filler marking -- as the top-level "t".
+ *
+ * ssw_recognition_set_align: over whole rows in HBM (d_senscr int16 [n_frames][n_sen], the rows
+ * the search read: compallsen = yes); follows ssw_grammar_search_batch or ssw_recognize_batch.
+ * NULL with a message for a set made with another model or frame counts that are not the set's. */
+ssw_alignment_set_t *ssw_recognition_set_align(ssw_model_t *m, const ssw_recognition_set_t *r,
+                                               const int16_t *d_senscr, int32_t n_frames,
+                                               const int32_t *utt_off, void *stream);
+/* ssw_recognize_batch, then ssw_recognition_set_align over the same rows.  two_pass_history (PTM
+ * and s2_semi scorers): the rows are made again between the two searches from the top-N order
+ * every utterance's own search left, as ssw_align_text_batch does (src/decoder.c:786-793,
+ * src/ptm_mgau.c:425-448).  rec_out: NULL, or receives the recognition set, equal in every
+ * accessor to ssw_recognize_batch's for the same input; the caller frees both sets. */
+ssw_alignment_set_t *ssw_recognize_align_batch(ssw_model_t *m, const ssw_dict_t *d,
+                                               const ssw_grammar_plan_t *plan,
+                                               const int32_t *fsg_of_utt, int scorer,
+                                               const float *d_feats, int32_t n_frames,
+                                               const int32_t *utt_off, int32_t n_utts,
+                                               int32_t two_pass_history,
+                                               ssw_recognition_set_t **rec_out, void *stream);
+/* The same in the reference's DEFAULT configuration (compallsen = no): ssw_recognize_batch_active,
+ * then the second pass scoring for itself as ssw_align_batch_active_ex does, its active set
+ * seeded with acmod's flags after the grammar search's last frame (no bridges) and only growing
+ * from there (src/state_align_search.c:186-189); with two_pass_history (PTM) it starts from the
+ * orders the search left in history slot 1.  The s2_semi scorer takes the whole-rows route, as
+ * in every *_active call; a continuous model is refused by name.  Limits and refusals as
+ * ssw_recognize_batch_active (a plan with a grammar beyond one workgroup must come from
+ * ssw_grammar_prepare_large_active) and ssw_align_batch_active_ex, reported under this name.
+ * rounds as ssw_recognize_batch_active's. */
+ssw_alignment_set_t *ssw_recognize_align_batch_active(ssw_model_t *m, const ssw_dict_t *d,
+                                                      const ssw_grammar_plan_t *plan,
+                                                      const int32_t *fsg_of_utt, int scorer,
+                                                      const float *d_feats, int32_t n_frames,
+                                                      const int32_t *utt_off, int32_t n_utts,
+                                                      int32_t two_pass_history,
+                                                      ssw_recognition_set_t **rec_out,
+                                                      int32_t *rounds, void *stream);
+
 /* ------------------------------------------------------------------------------------ */
 /* Dynamic features on the device: feat_s2mfc2feat_live for whole    */
 /* utterances with feat = 1s_c_d_dd, cmn = batch ("current"), no varnorm / agc / lda       */

@@ -310,6 +310,14 @@ def lib() -> C.CDLL:
     L.ssw_recognition_set_json.argtypes = [vp, i32, C.c_double, i32, C.c_char_p, i32]
     L.ssw_recognition_set_free.argtypes = [vp]
     L.ssw_recognition_set_free.restype = None
+    L.ssw_recognition_set_align.restype = vp
+    L.ssw_recognition_set_align.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.ssw_recognize_align_batch.restype = vp
+    L.ssw_recognize_align_batch.argtypes = [vp, vp, vp, vp, C.c_int, vp, i32, vp, i32, i32,
+                                            C.POINTER(vp), vp]
+    L.ssw_recognize_align_batch_active.restype = vp
+    L.ssw_recognize_align_batch_active.argtypes = [vp, vp, vp, vp, C.c_int, vp, i32, vp, i32, i32,
+                                                   C.POINTER(vp), vp, vp]
     L.ssw_feat_batch.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
     if hasattr(L, "ssw_feat_create"):   # (an older build loaded through SSW_AMD_LIB has none)
         L.ssw_feat_config_defaults.argtypes = [C.POINTER(SswFeatConfig)]

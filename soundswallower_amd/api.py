@@ -1621,6 +1621,21 @@ class RecognitionSet:
                "ssw_recognition_set_json")
         return buf.value.decode()
 
+    def align(self, model: "Model", d_senscr, utt_off, stream=None) -> "AlignmentSet":
+        """ssw_recognition_set_align: decoder_alignment (src/decoder.c:737-798) for every
+        utterance of this set over whole rows in HBM -- the rows the search read (d_senscr device
+        int16 [n_frames][n_sen]).  Status per utterance: 0 aligned, 1 no hypothesis (this set's
+        message), 2 populate or the second pass failed."""
+        off = np.ascontiguousarray(utt_off, np.int32)
+        if len(off) - 1 != self.n_utts:
+            raise SswError("ssw_recognition_set_align: utt_off is for %d utterances, the set has %d"
+                           % (len(off) - 1, self.n_utts))
+        h = self._L.ssw_recognition_set_align(model._m, self._r, _ptr(d_senscr), int(off[-1]),
+                                              _ptr(off), _ptr(stream))
+        if not h:
+            raise SswError("ssw_recognition_set_align: " + _lib.last_error())
+        return AlignmentSet(self._L, h, self._lex)
+
     def free(self):
         if getattr(self, "_r", None):
             self._L.ssw_recognition_set_free(self._r)
@@ -1721,6 +1736,84 @@ def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: Gramm
                                           fsg_of_utt, scorer=scorer, stream=stream)[0]
         return recognize_batch(model, lex, d_feat if d_feat else 0, fo, plan, fsg_of_utt,
                                scorer=scorer, stream=stream)
+    finally:
+        if d_pcm is not None and not on_device:
+            model.device_free(d_pcm)
+        for p in (d_cep, d_feat):
+            if p:
+                model.device_free(p)
+
+
+def recognize_align_batch(model: Model, lex: Lexicon, d_feats, utt_off, plan: GrammarPlan,
+                          fsg_of_utt=None, scorer=None, two_pass_history=False, stream=None):
+    """ssw_recognize_align_batch: recognize_batch, then decoder_alignment (src/decoder.c:737-798)
+    of what was recognised, over the same rows (compallsen = yes) -- what decoder_result_json
+    prints at align_level 1 and 2 after a grammar.  two_pass_history: the rows are made again
+    between the two searches from the top-N order each utterance's search left.  Returns
+    (RecognitionSet, AlignmentSet); the recognition set is recognize_batch's."""
+    off = np.ascontiguousarray(utt_off, np.int32)
+    n_utts = len(off) - 1
+    g = _fsg_of_utt(fsg_of_utt, n_utts)
+    rec = C.c_void_p()
+    L = _lib.lib()
+    h = L.ssw_recognize_align_batch(model._m, lex._d, plan._p, _ptr(g), model.pick_scorer(scorer),
+                                    _ptr(d_feats), int(off[-1]), _ptr(off), n_utts,
+                                    int(bool(two_pass_history)), C.byref(rec), _ptr(stream))
+    if not h:
+        raise SswError("ssw_recognize_align_batch: " + _lib.last_error())
+    return RecognitionSet(L, rec, lex, n_utts), AlignmentSet(L, h, lex)
+
+
+def recognize_align_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, plan: GrammarPlan,
+                                 fsg_of_utt=None, scorer=None, two_pass_history=False,
+                                 stream=None):
+    """ssw_recognize_align_batch_active: recognize_align_batch in the reference's DEFAULT
+    configuration (compallsen = no): the second pass scores for itself, its active set seeded
+    with what the grammar search's last frame left.  Returns (RecognitionSet, AlignmentSet,
+    rounds int32 [n_utts]); set and rounds are recognize_batch_active's."""
+    off = np.ascontiguousarray(utt_off, np.int32)
+    n_utts = len(off) - 1
+    g = _fsg_of_utt(fsg_of_utt, n_utts)
+    rounds = np.zeros(n_utts, np.int32)
+    rec = C.c_void_p()
+    L = _lib.lib()
+    h = L.ssw_recognize_align_batch_active(model._m, lex._d, plan._p, _ptr(g),
+                                           model.pick_scorer(scorer), _ptr(d_feats), int(off[-1]),
+                                           _ptr(off), n_utts, int(bool(two_pass_history)),
+                                           C.byref(rec), _ptr(rounds), _ptr(stream))
+    if not h:
+        raise SswError("ssw_recognize_align_batch_active: " + _lib.last_error())
+    return RecognitionSet(L, rec, lex, n_utts), AlignmentSet(L, h, lex), rounds
+
+
+def recognize_align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: GrammarPlan,
+                                fsg_of_utt=None, samprate=None, fe_cfg=None, scorer=None,
+                                stream=None, active=False, two_pass_history=False):
+    """Audio in, hypotheses with phone and state times out: recognize_audio_batch followed by
+    decoder_alignment, i.e. decoder_result_json(d, start, 1 or 2) after decoder_set_fsg /
+    decoder_set_jsgf_*, for a batch.  The front end is recognize_audio_batch's; then
+    ssw_recognize_align_batch, or ssw_recognize_align_batch_active when active=True (the
+    reference's default compallsen = no).  Returns (RecognitionSet, AlignmentSet)."""
+    width = model._audio_feat_width()
+    off = np.ascontiguousarray(samp_off, np.int64)
+    n_frames = int(fe_frame_counts(np.diff(off)).sum() if samprate is None else
+                   model.fe_frame_counts_rates(np.diff(off), samprate, fe_cfg).sum())
+    on_device = hasattr(pcm, "data_ptr") and getattr(pcm, "is_cuda", False)
+    d_pcm = pcm if on_device else (model.to_device(np.ascontiguousarray(pcm, np.int16))
+                                   if off[-1] > 0 else None)
+    d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
+    d_feat = model.device_malloc(n_frames * width * 4) if n_frames else None
+    try:
+        if samprate is None:
+            _, fo = model.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, fe_cfg, stream)
+        else:
+            _, fo = model.fe_batch_rates_device(d_pcm, off, samprate, d_cep if d_cep else 0,
+                                                fe_cfg, stream)
+        if n_frames:
+            model._audio_feats(d_cep, n_frames, fo, d_feat, stream)
+        fn = recognize_align_batch_active if active else recognize_align_batch
+        return fn(model, lex, d_feat if d_feat else 0, fo, plan, fsg_of_utt, scorer=scorer,
+                  two_pass_history=two_pass_history, stream=stream)[:2]
     finally:
         if d_pcm is not None and not on_device:
             model.device_free(d_pcm)

@@ -451,6 +451,9 @@ struct ssw_alignment_set_s {
     int32_t n_utts;
     std::vector<int32_t> status, word_off, phone_off;
     std::vector<std::string> message; /* per utterance: why its text was rejected (status 3) */
+    /* empty, or per utterance decoder_hyp's text as the grammar search built it: the sets of
+     * ssw_recognition_set_align and its kin, for ssw_alignment_set_json's top-level "t" */
+    std::vector<std::string> hyp;
     std::vector<int32_t> wid, cipid, parent;
     std::vector<uint16_t> senid;
     std::vector<ssw_align_entry_t> word_al, phone_al, state_al;
@@ -478,6 +481,23 @@ static ssw_alignment_set_t *forced_align_core(ssw_model_t *m, const ssw_dict_t *
                                               const std::vector<std::string> *reject = NULL,
                                               int (*between)(void *) = NULL, void *between_arg = NULL,
                                               const fpa_mode_t *fpa = NULL);
+
+/* decoder_alignment from alignment_add_word on (src/decoder.c:765-797), for a batch whose word
+ * windows are known: forced_align_core's second half, and what follows a grammar search
+ * (ssw_host_grammar.inc).  Utterance u has n_seg[u] words at seg + u * max_seg; n_seg[u] < 0: none,
+ * reported with status pre_status[u] (NULL: 1) and message[u].  fpa: the default configuration,
+ * with `seed` (host [n_utts][(n_sen + 31) / 32]) and d_carry (NULL, or device [n_utts][n_cbf]);
+ * else the second pass reads d_senscr.  between: NULL, or called once before the second pass.
+ * first_ms: for SSW_ALIGN_TIMING's line, the time the caller's first pass took. */
+static ssw_alignment_set_t *align_word_segments(ssw_model_t *m, const ssw_dict_t *d,
+                                                const int16_t *d_senscr, const int32_t *utt_off,
+                                                int32_t n_utts, const int32_t *n_seg,
+                                                const ssw_word_seg_t *seg, int32_t max_seg,
+                                                const int32_t *pre_status,
+                                                std::vector<std::string> &message,
+                                                const fpa_mode_t *fpa, const uint32_t *seed,
+                                                const uint32_t *d_carry, int (*between)(void *),
+                                                void *between_arg, void *stream, double first_ms);
 
 /* decoder_set_align_text fails for the one utterance whose text has a word the dictionary does
  * not know (src/decoder.c:699-703); in a batch the others must still be aligned.  The texts are
@@ -562,8 +582,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
         return NULL;
     const ssw_host_model_t *h = m->h;
     refresh_knobs(m);
-    const bool timing = m->kn.align_timing; /* SSW_ALIGN_TIMING: stderr, ms per stage */
-    double t_a = now_ms(), t_b, t_c, t_d;
+    const double t_a = now_ms();
     int max_words = plan ? plan->max_words : 0;
     for (int u = 0; !plan && u < n_utts; ++u)
         max_words = std::max(max_words, word_off[u + 1] - word_off[u]);
@@ -614,7 +633,37 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
         max_seg = need;
     }
     ssw_first_pass_plan_free(own_plan);
-    t_b = now_ms();
+    std::vector<std::string> message((size_t)n_utts);
+    std::vector<int32_t> pre_status((size_t)n_utts, 1);
+    if (reject != NULL) /* these were searched as empty texts: no alignment for them */
+        for (int u = 0; u < n_utts; ++u)
+            if (!(*reject)[u].empty()) {
+                message[u] = (*reject)[u];
+                pre_status[u] = 3;
+                n_seg[u] = -1;
+            }
+    return align_word_segments(m, d, d_senscr, utt_off, n_utts, n_seg.data(), seg.data(), max_seg,
+                               pre_status.data(), message, fpa, seed.data(),
+                               carry2 ? m->carry_rows.as<uint32_t>() : NULL, between, between_arg,
+                               stream, now_ms() - t_a);
+}
+
+static ssw_alignment_set_t *
+align_word_segments(ssw_model_t *m, const ssw_dict_t *d, const int16_t *d_senscr,
+                    const int32_t *utt_off, int32_t n_utts, const int32_t *n_seg,
+                    const ssw_word_seg_t *seg, int32_t max_seg, const int32_t *pre_status,
+                    std::vector<std::string> &message, const fpa_mode_t *fpa, const uint32_t *seed,
+                    const uint32_t *d_carry, int (*between)(void *), void *between_arg, void *stream,
+                    double first_ms)
+{
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return NULL;
+    const ssw_host_model_t *h = m->h;
+    refresh_knobs(m);
+    const bool timing = m->kn.align_timing; /* SSW_ALIGN_TIMING: stderr, ms per stage */
+    const size_t nw32 = ((size_t)h->n_sen + 31) / 32;
+    double t_b = now_ms(), t_c, t_d;
     ssw_alignment_set_t *a = new ssw_alignment_set_t();
     a->m = m;
     a->d = d;
@@ -622,13 +671,8 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
     for (int u = 0; u < n_utts; ++u)
         a->n_frames.push_back(utt_off[u + 1] - utt_off[u]);
     a->status.assign((size_t)n_utts, 0);
-    a->message.assign((size_t)n_utts, std::string());
-    if (reject != NULL) /* these were searched as empty texts: no alignment for them */
-        for (int u = 0; u < n_utts; ++u)
-            if (!(*reject)[u].empty()) {
-                a->message[u] = (*reject)[u];
-                n_seg[u] = -1;
-            }
+    a->message.swap(message);
+    a->message.resize((size_t)n_utts);
     a->word_off.assign((size_t)n_utts + 1, 0);
     a->phone_off.assign((size_t)n_utts + 1, 0);
     /* alignment_add_word + alignment_populate per utterance, with the first pass's windows;
@@ -648,7 +692,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
         for (int u = u0; u < u1; ++u) {
             if (n_seg[u] < 0)
                 continue;
-            const ssw_word_seg_t *sg = seg.data() + (size_t)u * max_seg;
+            const ssw_word_seg_t *sg = seg + (size_t)u * max_seg;
             wstr.clear();
             wstart.clear();
             wdur.clear();
@@ -691,7 +735,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
         a->word_off[u] = (int32_t)a->wid.size();
         a->phone_off[u] = (int32_t)a->cipid.size();
         if (n_seg[u] < 0) {
-            a->status[u] = a->message[u].empty() ? 1 : 3;
+            a->status[u] = pre_status != NULL ? pre_status[u] : 1;
             continue;
         }
         const piece_t &pc = piece[u];
@@ -699,7 +743,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
             a->status[u] = 2;
             continue;
         }
-        const ssw_word_seg_t *sg = seg.data() + (size_t)u * max_seg;
+        const ssw_word_seg_t *sg = seg + (size_t)u * max_seg;
         for (int i = 0; i < n_seg[u]; ++i)
             a->wid.push_back(sg[i].wid);
         a->cipid.insert(a->cipid.end(), pc.ci.begin(), pc.ci.end());
@@ -760,9 +804,9 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
                                       fpa->d_feats + (size_t)utt_off[u0] * h->veclen_total, u1 - u0,
                                       foff.data(), poff.data(), a->senid.data() + p0 * ne,
                                       tmat.data() + p0, sf.data() + p0, ef.data() + p0,
-                                      seed.data() + (size_t)u0 * nw32, a->state_al.data() + p0 * ne,
+                                      seed + (size_t)u0 * nw32, a->state_al.data() + p0 * ne,
                                       st.data(), NULL, stream,
-                                      carry2 ? m->carry_rows.as<uint32_t>() + (size_t)u0 * m->n_cbf : NULL)
+                                      d_carry != NULL ? d_carry + (size_t)u0 * m->n_cbf : NULL)
             : ssw_align_batch(m, d_senscr + (size_t)utt_off[u0] * h->n_sen, u1 - u0, foff.data(),
                               poff.data(), a->senid.data() + p0 * ne, tmat.data() + p0,
                               sf.data() + p0, ef.data() + p0, a->state_al.data() + p0 * ne,
@@ -821,7 +865,7 @@ forced_align_core(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_conf
     }
     if (timing)
         fprintf(stderr, "ssw_forced_align_batch: first pass %.2f ms, populate %.2f, second pass %.2f, "
-                        "propagate %.2f\n", t_b - t_a, t_c - t_b, t_d - t_c, now_ms() - t_d);
+                        "propagate %.2f\n", first_ms, t_c - t_b, t_d - t_c, now_ms() - t_d);
     return a;
 }
 
@@ -981,6 +1025,8 @@ ssw_alignment_set_json(const ssw_alignment_set_t *a, int32_t utt, double utt_sta
             hyp += ssw_dict_word(a->d, ssw_dict_base_id(a->d, wid));
         }
     }
+    if (!a->hyp.empty()) /* (the grammar's filler marking, not the dictionary's) */
+        hyp = a->hyp[(size_t)utt];
     return ssw_alignment_json(a->m, hyp.c_str(), 0, utt_start, frate, a->n_frames[utt] + 1, nw,
                               wstr.data(), a->word_al.data() + w0, np, a->cipid.data() + p0,
                               a->parent.data() + p0, a->phone_al.data() + p0,

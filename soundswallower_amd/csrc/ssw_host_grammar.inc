@@ -1,5 +1,6 @@
 /* ssw_host_grammar.inc -- host: ssw_grammar_prepare(_large, _large_active), ssw_grammar_search_batch,
- * ssw_recognize_batch, ssw_recognize_batch_active and the recognition set.
+ * ssw_recognize_batch, ssw_recognize_batch_active, the recognition set, and decoder_alignment of
+ * what was recognised: ssw_recognition_set_align, ssw_recognize_align_batch(_active).
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 /* ---------------------------------------------------------------------------------- */
 /* recognition against word FSGs (decoder_set_fsg; ssw_k9_grammar.inc)                  */
@@ -299,10 +300,12 @@ struct grammar_run_t {
     int *big_ws;            /* grammar_search_big_kernel's workspaces and their offsets */
     const long long *big_ws_off;
     bool uploaded;
+    const char *who; /* the default configuration's entry point, for the loop's messages */
 
     grammar_run_t() : m(NULL), d(NULL), plan(NULL), fsg_of_utt(NULL), n_utts(0), st(NULL), r(NULL),
                       max_seg(1), nseg_off(0), score_off(0), seg_off(0), only_off(0), big_ws(NULL),
-                      big_ws_off(NULL), uploaded(false) {}
+                      big_ws_off(NULL), uploaded(false),
+                      who("ssw_recognize_batch_active") {}
     ~grammar_run_t()
     {
         if (uploaded)
@@ -734,7 +737,7 @@ grammar_active_search(void *arg, const int16_t *rows, const std::vector<int> &on
     const hipError_t e = R.launch(rows, &only, mask, d_act_off, d_node_cnt);
     if (e != hipSuccess) {
         R.m->gr_ws_uid = 0;
-        ssw_set_error("ssw_recognize_batch_active: %s", hipGetErrorString(e));
+        ssw_set_error("%s: %s", R.who, hipGetErrorString(e));
         return -1;
     }
     return 0;
@@ -825,6 +828,273 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
                 rounds, listed, m->gra_stats, stream, NULL) < 0)
         return NULL;
     return R.finish();
+}
+
+/* ---------------------------------------------------------------------------------- */
+/* decoder_alignment after a grammar search (src/decoder.c:737-798)                     */
+/* ---------------------------------------------------------------------------------- */
+/* The best path's entries as alignment_add_word takes them (:758-768): every entry whose word is
+ * a dictionary word -- fillers and alternate pronunciations included, "(NULL)" left out -- with
+ * sf and ef - sf + 1, the windows as they are (the contiguity assert of :763 is compiled out of
+ * a release build).  n_seg[u] = -1 and a status for an utterance that has no alignment. */
+struct rec_word_segs_t {
+    int32_t max_seg;
+    std::vector<int32_t> n_seg, pre_status;
+    std::vector<ssw_word_seg_t> seg;
+    std::vector<std::string> message;
+};
+
+static void
+recognition_word_segs(const ssw_recognition_set_t *r, rec_word_segs_t &w)
+{
+    const int n_utts = r->n_utts;
+    w.max_seg = 1;
+    for (int u = 0; u < n_utts; ++u)
+        w.max_seg = std::max(w.max_seg, r->n_seg[(size_t)u]);
+    w.n_seg.assign((size_t)n_utts, -1);
+    w.pre_status.assign((size_t)n_utts, 1);
+    w.message.assign((size_t)n_utts, std::string());
+    w.seg.assign((size_t)n_utts * (size_t)w.max_seg, ssw_word_seg_t());
+    for (int u = 0; u < n_utts; ++u) {
+        if (r->status[(size_t)u] != 0) { /* decoder_seg_iter NULL: no alignment (:753-755) */
+            w.message[(size_t)u] = r->message[(size_t)u];
+            continue;
+        }
+        const ssw_fsg_seg_t *sg = r->seg.data() + r->seg_off[(size_t)u];
+        ssw_word_seg_t *out = w.seg.data() + (size_t)u * (size_t)w.max_seg;
+        int n = 0;
+        for (int i = 0; i < r->n_seg[(size_t)u]; ++i) {
+            if (sg[i].wid < 0)
+                continue;
+            out[n].wid = sg[i].wid;
+            out[n].start = sg[i].sf;
+            out[n].duration = sg[i].ef - sg[i].sf + 1;
+            ++n;
+        }
+        if (n == 0) {
+            w.pre_status[(size_t)u] = 2;
+            w.message[(size_t)u] = "The best path holds no dictionary word (null transitions only): "
+                                   "nothing to align";
+            continue;
+        }
+        w.n_seg[(size_t)u] = n;
+    }
+}
+
+static int
+recognition_set_check(const char *who, const ssw_model_t *m, const ssw_recognition_set_t *r,
+                      int32_t n_frames, const int32_t *utt_off)
+{
+    if (m == NULL || r == NULL || n_frames < 0 || utt_off == NULL
+        || !utt_off_spans(utt_off, r->n_utts, n_frames)) {
+        ssw_set_error("bad arguments to %s", who);
+        return -1;
+    }
+    if (r->m != m) {
+        ssw_set_error("%s: the recognition set was made with another model", who);
+        return -1;
+    }
+    for (int u = 0; u < r->n_utts; ++u)
+        if (utt_off[u + 1] - utt_off[u] != r->n_frames[(size_t)u]) {
+            ssw_set_error("%s: utterance %d has %d frames in utt_off and %d in the recognition set",
+                          who, u, utt_off[u + 1] - utt_off[u], r->n_frames[(size_t)u]);
+            return -1;
+        }
+    return 0;
+}
+
+/* the second half for a recognition set; `who` has checked the set */
+static ssw_alignment_set_t *
+recognition_align(ssw_model_t *m, const ssw_recognition_set_t *r, const int16_t *d_senscr,
+                  const int32_t *utt_off, const fpa_mode_t *fpa, const uint32_t *seed,
+                  const uint32_t *d_carry, void *stream)
+{
+    rec_word_segs_t w;
+    recognition_word_segs(r, w);
+    ssw_alignment_set_t *a = align_word_segments(m, r->d, d_senscr, utt_off, r->n_utts,
+                                                 w.n_seg.data(), w.seg.data(), w.max_seg,
+                                                 w.pre_status.data(), w.message, fpa, seed, d_carry,
+                                                 NULL, NULL, stream, 0.0);
+    if (a != NULL)
+        a->hyp = r->hyp; /* decoder_hyp's text, for the JSON line's "t" */
+    return a;
+}
+
+extern "C" ssw_alignment_set_t *
+ssw_recognition_set_align(ssw_model_t *m, const ssw_recognition_set_t *r, const int16_t *d_senscr,
+                          int32_t n_frames, const int32_t *utt_off, void *stream)
+{
+    if (recognition_set_check("ssw_recognition_set_align", m, r, n_frames, utt_off) < 0)
+        return NULL;
+    if (n_frames > 0 && d_senscr == NULL) {
+        ssw_set_error("bad arguments to ssw_recognition_set_align");
+        return NULL;
+    }
+    if (check_has_device(m) < 0)
+        return NULL;
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return NULL;
+    return recognition_align(m, r, d_senscr, utt_off, NULL, NULL, NULL, stream);
+}
+
+/* ssw_recognize_batch, then decoder_alignment over the same rows; with two_pass_history (PTM and
+ * s2_semi) the rows are made again in between from the order every utterance's own search left,
+ * as ssw_align_text_batch does (src/decoder.c:786-793, src/ptm_mgau.c:425-448) */
+static ssw_alignment_set_t *
+recognize_align_rows(const char *who, ssw_model_t *m, const ssw_dict_t *d,
+                     const ssw_grammar_plan_t *plan, const int32_t *fsg_of_utt, int scorer,
+                     const float *d_feats, int32_t n_frames, const int32_t *utt_off, int32_t n_utts,
+                     int32_t two_pass_history, ssw_recognition_set_t **rec_out, void *stream)
+{
+    if (rec_out != NULL)
+        *rec_out = NULL;
+    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
+        || !utt_off_spans(utt_off, n_utts, n_frames) || (n_frames > 0 && d_feats == NULL)) {
+        ssw_set_error("bad arguments to %s", who);
+        return NULL;
+    }
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return NULL;
+    if (check_has_device(m) < 0)
+        return NULL;
+    if (hipSetDevice(m->device) != hipSuccess)
+        return NULL;
+    if (text_rows_reserve(m, n_frames, who) < 0)
+        return NULL;
+    int16_t *rows = m->text_scr.as<int16_t>();
+    if (n_frames > 0 && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, rows, stream) < 0)
+        return NULL;
+    const bool two_pass = two_pass_history != 0
+        && (scorer == SSW_SCORER_PTM || scorer == SSW_SCORER_S2_SEMI) && n_frames > 0 && n_utts > 0;
+    if (two_pass) { /* set aside while the first scoring's top-N block is still in the workspace */
+        if (carry_rows_reserve(m, n_utts, who) < 0)
+            return NULL;
+        hipLaunchKernelGGL(gather_last_orders_kernel, dim3((unsigned)n_utts), dim3(128), 0,
+                           (hipStream_t)stream, m->d_topn_cw, m->d_utt_off, m->n_cbf,
+                           (const uint32_t *)NULL, m->carry_rows.as<uint32_t>());
+        if (hipGetLastError() != hipSuccess) {
+            ssw_set_error("%s: gather_last_orders_kernel failed to launch", who);
+            return NULL;
+        }
+    }
+    ssw_recognition_set_t *r = ssw_grammar_search_batch(m, d, plan, fsg_of_utt, rows, n_frames,
+                                                        utt_off, n_utts, stream);
+    if (r == NULL)
+        return NULL;
+    ssw_alignment_set_t *a = NULL;
+    if (!two_pass
+        || score_batch_impl(m, scorer, d_feats, n_frames, utt_off, n_utts, rows, stream, 0u, NULL,
+                            NULL, NULL, m->carry_rows.as<uint32_t>()) >= 0)
+        a = recognition_align(m, r, rows, utt_off, NULL, NULL, NULL, stream);
+    if (a != NULL && rec_out != NULL)
+        *rec_out = r;
+    else
+        ssw_recognition_set_free(r);
+    return a;
+}
+
+extern "C" ssw_alignment_set_t *
+ssw_recognize_align_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_plan_t *plan,
+                          const int32_t *fsg_of_utt, int scorer, const float *d_feats,
+                          int32_t n_frames, const int32_t *utt_off, int32_t n_utts,
+                          int32_t two_pass_history, ssw_recognition_set_t **rec_out, void *stream)
+{
+    return recognize_align_rows("ssw_recognize_align_batch", m, d, plan, fsg_of_utt, scorer, d_feats,
+                                n_frames, utt_off, n_utts, two_pass_history, rec_out, stream);
+}
+
+/* the same in the reference's default configuration (compallsen = no): ssw_recognize_batch_active,
+ * then the second pass as ssw_align_batch_active_ex runs it, seeded with acmod's flags after the
+ * grammar search's last frame (they only grow from there, src/state_align_search.c:186-189) and,
+ * with two_pass_history and PTM, started from the orders the search left in history slot 1 */
+extern "C" ssw_alignment_set_t *
+ssw_recognize_align_batch_active(ssw_model_t *m, const ssw_dict_t *d,
+                                 const ssw_grammar_plan_t *plan, const int32_t *fsg_of_utt,
+                                 int scorer, const float *d_feats, int32_t n_frames,
+                                 const int32_t *utt_off, int32_t n_utts, int32_t two_pass_history,
+                                 ssw_recognition_set_t **rec_out, int32_t *rounds, void *stream)
+{
+    const char *who = "ssw_recognize_align_batch_active";
+    if (rec_out != NULL)
+        *rec_out = NULL;
+    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
+        || !utt_off_spans(utt_off, n_utts, n_frames) || (n_frames > 0 && d_feats == NULL)) {
+        ssw_set_error("bad arguments to %s", who);
+        return NULL;
+    }
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return NULL;
+    if (check_has_device(m) < 0)
+        return NULL;
+    if (cont_refuse(m, who) < 0)
+        return NULL;
+    if (plan->big && !plan->active) {
+        ssw_set_error("%s: grammar %d (%s) has %d phone-tree HMMs and is searched from an HBM "
+                      "workspace: the default configuration (compallsen = no) takes such a plan "
+                      "from ssw_grammar_prepare_large_active only; use ssw_recognize_align_batch",
+                      who, plan->big_fsg, plan->big_name.c_str(), plan->big_nodes);
+        return NULL;
+    }
+    if (scorer == SSW_SCORER_S2_SEMI) { /* the compallsen = yes route (semi_active_done) */
+        ssw_alignment_set_t *a = recognize_align_rows(who, m, d, plan, fsg_of_utt, scorer, d_feats,
+                                                      n_frames, utt_off, n_utts, two_pass_history,
+                                                      rec_out, stream);
+        if (a != NULL)
+            semi_active_done(m->gra_stats, n_utts, rounds);
+        return a;
+    }
+    if (fpa_check_limits(m, who, scorer) < 0)
+        return NULL;
+    if (hipSetDevice(m->device) != hipSuccess)
+        return NULL;
+    if (text_rows_reserve(m, n_frames, who) < 0)
+        return NULL;
+    int16_t *rows = m->text_scr.as<int16_t>();
+    const bool carry2 = two_pass_history != 0 && scorer == SSW_SCORER_PTM && n_utts > 0;
+    if (carry2 && carry_rows_reserve(m, n_utts, who) < 0)
+        return NULL;
+    const uint32_t *d_carry = carry2 ? m->carry_rows.as<uint32_t>() : NULL;
+    const size_t nw32 = ((size_t)m->h->n_sen + 31) / 32;
+    std::vector<uint32_t> seed((size_t)n_utts * nw32, 0u); /* acmod's set after the last frame */
+    ssw_recognition_set_t *r = NULL;
+    {
+        grammar_run_t R;
+        R.who = who;
+        if (R.begin(m, d, plan, fsg_of_utt, n_frames, utt_off, n_utts, stream) < 0)
+            return NULL;
+        if (n_utts > 0) {
+            const ssw_fp_graphs_t *g = plan->g;
+            fpa_graph_t G;
+            G.who = who;
+            G.n_nodes = g->n_nodes;
+            G.senid = g->senid;
+            G.max_nodes = plan->max_nodes;
+            for (int u = 0; u < n_utts; ++u) {
+                const int gi = fsg_of_utt ? fsg_of_utt[u] : 0; /* (checked by begin) */
+                G.node_base.push_back(g->node_off[gi]);
+                G.node_cnt.push_back(g->node_off[gi + 1] - g->node_off[gi]);
+            }
+            G.search = grammar_active_search;
+            G.arg = &R;
+            if (fpa_run(m, G, scorer, d_feats, n_frames, utt_off, n_utts, rows, false, seed.data(),
+                        rounds, NULL, m->gra_stats, stream,
+                        carry2 ? m->carry_rows.as<uint32_t>() : NULL) < 0)
+                return NULL;
+        }
+        r = R.finish();
+    }
+    if (r == NULL)
+        return NULL;
+    fpa_mode_t mode = { scorer, d_feats, two_pass_history != 0 };
+    ssw_alignment_set_t *a = recognition_align(m, r, rows, utt_off, &mode, seed.data(), d_carry, stream);
+    if (a != NULL && rec_out != NULL)
+        *rec_out = r;
+    else
+        ssw_recognition_set_free(r);
+    return a;
 }
 
 /* [0] utterances searched by ssw_recognize_batch_active since the model was loaded, [1] their

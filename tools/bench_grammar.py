@@ -36,6 +36,20 @@ the one-workgroup kernel with eight HMMs per thread), each at 1, 16 and 256 copi
 recording; per figure the number of history groups the call is searched in, and `ratio_400_200`.
 
     python tools/bench_grammar.py --large [--reps 10] [--warmup 2] [--out FILE]
+
+With --recognize-align it times phone and state times for recognised speech, from feature rows,
+on the goforward plan and writes profiles/recognize_align_bench.json: the same 256 copies,
+
+    goforward         ssw_recognize_batch: all senones scored, one search (words only)
+    recognize_align   ssw_recognize_align_batch: the same, then decoder_alignment of the result
+    align_text        ssw_align_text_batch of the words "go forward ten meters": scoring, first
+                      pass over the text's graphs, decoder_alignment
+
+and the three in the default configuration (compallsen = no: ssw_recognize_batch_active,
+ssw_recognize_align_batch_active, ssw_align_text_batch_active) as `*_active`; alternating, the
+median of --reps calls after --warmup.
+
+    python tools/bench_grammar.py --recognize-align [--utts 256] [--reps 10] [--warmup 2] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -116,6 +130,96 @@ def active(a):
     print(json.dumps(out))
 
 
+def recognize_align(a):
+    import torch
+
+    import soundswallower_amd as ssw
+    from tests import fsg_common as G
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_grammar: no GPU; nothing is measured without one")
+    mdir = ssw.model_dir("en-us")
+    m = ssw.Model(mdir)
+    lex = ssw.Lexicon(m, os.path.join(mdir, "dict.txt"), os.path.join(mdir, "noisedict.txt"))
+    cep, _ = m.fe_batch(G.pcm("goforward.raw", 0))
+    feats = np.ascontiguousarray(m.feat_batch(cep), np.float32)
+    T, n = len(feats), a.utts
+    d = torch.from_numpy(np.ascontiguousarray(np.tile(feats, (n, 1)))).cuda()
+    off = (np.arange(n + 1) * T).astype(np.int32)
+    plan = lex.grammar_plan(ssw.Fsg.read(m, lex, G.fsg_path("goforward")))
+    texts = ssw.Texts(["go forward ten meters".split()] * n)
+    last = {}
+
+    def free(*sets):
+        for s in sets:
+            s.free()
+
+    def run_goforward():
+        r = ssw.recognize_batch(m, lex, d, off, plan)
+        last["goforward"] = (r.hyp(n - 1), r.score(n - 1))
+        free(r)
+
+    def run_recognize_align():
+        r, al = ssw.recognize_align_batch(m, lex, d, off, plan)
+        last["recognize_align"] = (r.hyp(n - 1), r.score(n - 1), al.status(n - 1))
+        free(r, al)
+
+    def run_align_text():
+        al = ssw.align_text_batch(m, lex, d, off, texts)
+        last["align_text"] = al.status(n - 1)
+        free(al)
+
+    def run_goforward_active():
+        r, _ = ssw.recognize_batch_active(m, lex, d, off, plan)
+        last["goforward_active"] = (r.hyp(n - 1), r.score(n - 1))
+        free(r)
+
+    def run_recognize_align_active():
+        r, al, _ = ssw.recognize_align_batch_active(m, lex, d, off, plan)
+        last["recognize_align_active"] = (r.hyp(n - 1), r.score(n - 1), al.status(n - 1))
+        free(r, al)
+
+    def run_align_text_active():
+        al = ssw.align_text_batch_active(m, lex, d, off, texts)
+        last["align_text_active"] = al.status(n - 1)
+        free(al)
+
+    calls = {"goforward": run_goforward, "recognize_align": run_recognize_align,
+             "align_text": run_align_text, "goforward_active": run_goforward_active,
+             "recognize_align_active": run_recognize_align_active,
+             "align_text_active": run_align_text_active}
+    times = {k: [] for k in calls}
+    for i in range(a.warmup + a.reps):
+        for k, fn in calls.items():          # alternating: the calls share whatever the box does
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            dt = (time.perf_counter() - t0) * 1e3
+            if i >= a.warmup:
+                times[k].append(dt)
+    out = {
+        "what": "recognition with phone and state times (ssw_recognize_align_batch[_active]) next "
+                "to recognition alone (ssw_recognize_batch[_active]) and to text alignment of the "
+                "same words (ssw_align_text_batch[_active]), from feature rows, host clock around "
+                "one synchronous call, ms; measured on the GPU named below",
+        "device": torch.cuda.get_device_name(0),
+        "utterances": n, "frames_per_utterance": T, "reps": a.reps, "warmup": a.warmup,
+        "hmms": plan.hmms(), "results_of_the_last_utterance": last,
+        "ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4),
+                   "max": round(max(v), 4)} for k, v in times.items()},
+    }
+    med = {k: out["ms"][k]["median"] for k in times}
+    out["ratio_to_goforward"] = round(med["recognize_align"] / med["goforward"], 3)
+    out["ratio_to_align_text"] = round(med["recognize_align"] / med["align_text"], 3)
+    out["ratio_to_goforward_active"] = round(med["recognize_align_active"] / med["goforward_active"], 3)
+    out["ratio_to_align_text_active"] = round(med["recognize_align_active"] / med["align_text_active"], 3)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 def large(a):
     import torch
 
@@ -187,15 +291,21 @@ def main():
                     help="time ssw_recognize_batch_active next to ssw_recognize_batch instead")
     ap.add_argument("--large", action="store_true",
                     help="time grammars beyond one workgroup (ssw_grammar_prepare_large) instead")
+    ap.add_argument("--recognize-align", action="store_true", dest="recognize_align",
+                    help="time ssw_recognize_align_batch next to ssw_recognize_batch and "
+                         "ssw_align_text_batch instead")
     ap.add_argument("--utts", type=int, default=256)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "grammar_large_bench.json" if a.large
+        a.out = os.path.join(ROOT, "profiles", "recognize_align_bench.json" if a.recognize_align
+                             else "grammar_large_bench.json" if a.large
                              else "grammar_active_bench.json" if a.active
                              else "grammar_bench.json")
+    if a.recognize_align:
+        return recognize_align(a)
     if a.active:
         return active(a)
     if a.large:
