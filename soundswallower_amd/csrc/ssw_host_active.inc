@@ -409,8 +409,17 @@ align_batch_active_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_
         act.seg_cbmask = A.seg_cbmask;
         act.a2 = &A;
         act.ls = NULL;
-        if (score_batch_impl(m, scorer, d_feats, n_frames, frame_off, n_utts, d_compact, stream,
-                             0u, NULL, NULL, &act, d_carry_rows) < 0)
+        ScoreReq R{};
+        R.scorer = scorer;
+        R.d_feats = d_feats;
+        R.n_frames = n_frames;
+        R.utt_off = frame_off;
+        R.n_utts = n_utts;
+        R.d_out = d_compact;
+        R.stream = stream;
+        R.act = &act;
+        R.d_carry_rows = d_carry_rows;
+        if (score_batch_impl(m, R) < 0)
             return -1;
     }
     return align_batch_levels(m, d_compact, n_utts, frame_off, phone_off, senid, tmatid, sf, ef,

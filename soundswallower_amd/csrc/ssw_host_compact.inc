@@ -211,16 +211,25 @@ ssw_score_batch_compact(ssw_model_t *m, int scorer, const float *d_feats,
         }
         direct = ms_takes_packed_kernel(m, least);
     }
-    if (direct)
-        return score_batch_impl(m, scorer, d_feats, plan->n_frames, plan->frame_off.data(),
-                                plan->n_utts, d_compact, stream, flags & SSW_SCORE_SHARE_DEVICE,
-                                NULL, NULL, NULL, NULL, plan);
+    ScoreReq R{};
+    R.scorer = scorer;
+    R.d_feats = d_feats;
+    R.n_frames = plan->n_frames;
+    R.utt_off = plan->frame_off.data();
+    R.n_utts = plan->n_utts;
+    R.stream = stream;
+    R.flags = flags & SSW_SCORE_SHARE_DEVICE;
+    if (direct) {
+        R.d_out = d_compact;
+        R.cp = plan;
+        return score_batch_impl(m, R);
+    }
     HIP_OK(hipSetDevice(m->device));
     if (devbuf_reserve(m->full_tmp, sizeof(int16_t) * (size_t)plan->n_frames * h->n_sen,
                        "ssw_score_batch_compact") < 0)
         return -1;
-    if (score_batch_impl(m, scorer, d_feats, plan->n_frames, plan->frame_off.data(), plan->n_utts,
-                         m->full_tmp.as<int16_t>(), stream, flags & SSW_SCORE_SHARE_DEVICE, NULL, NULL) < 0)
+    R.d_out = m->full_tmp.as<int16_t>();
+    if (score_batch_impl(m, R) < 0)
         return -1;
     CompactGatherParams G;
     G.full = m->full_tmp.as<int16_t>();

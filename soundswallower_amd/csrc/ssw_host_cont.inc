@@ -101,16 +101,16 @@ cont_launch(ssw_model_s *m, const float *d_feats, int32_t n_frames, int16_t *d_o
     }
 #undef SSW_CONT_LAUNCH
     HIP_OK(hipGetLastError());
-    if (m->timing)
-        HIP_OK(hipEventRecord(m->ev[1], st));
+    if (m->sw.timing)
+        HIP_OK(hipEventRecord(m->sw.ev[1], st));
     if (m->ms_raw)
         hipLaunchKernelGGL(cont_norm_kernel<true>, dim3((unsigned)n_frames), dim3(256), 0, st, P);
     else
         hipLaunchKernelGGL(cont_norm_kernel<false>, dim3((unsigned)n_frames), dim3(256), 0, st, P);
     HIP_OK(hipGetLastError());
-    if (m->timing) {
-        HIP_OK(hipEventRecord(m->ev[2], st));
-        m->timing_pieced = 0;
+    if (m->sw.timing) {
+        HIP_OK(hipEventRecord(m->sw.ev[2], st));
+        m->sw.timing_pieced = 0;
     }
     return 0;
 }

@@ -283,12 +283,12 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm, const
     F.n_grp = F.n_grp_frames = 0;
     F.n_utts = n_utts;
     F.n_frames = n_frames;
-    if (m->timing && !m->fe_ev_ready) {
+    if (m->sw.timing && !m->fe_ev_ready) {
         for (int i = 0; i < 4; ++i)
             HIP_OK(hipEventCreate(&m->fe_ev[i]));
         m->fe_ev_ready = 1;
     }
-    const bool timed = m->timing && m->fe_ev_ready;
+    const bool timed = m->sw.timing && m->fe_ev_ready;
     hipError_t e = hipMemcpyAsync(m->fe_ws.p, stage.data(), stage.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && timed)
         e = hipEventRecord(m->fe_ev[0], st);

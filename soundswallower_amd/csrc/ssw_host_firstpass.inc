@@ -914,7 +914,7 @@ ssw_align_text_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_c
         if (carry_rows_reserve(m, n_utts, "ssw_align_text_batch") < 0)
             return NULL;
         hipLaunchKernelGGL(gather_last_orders_kernel, dim3((unsigned)n_utts), dim3(128), 0,
-                           (hipStream_t)stream, m->d_topn_cw, m->d_utt_off, m->n_cbf,
+                           (hipStream_t)stream, m->sw.cw(), m->sw.utt_off(), m->n_cbf,
                            (const uint32_t *)NULL, m->carry_rows.as<uint32_t>());
         if (hipGetLastError() != hipSuccess) {
             ssw_set_error("ssw_align_text_batch: gather_last_orders_kernel failed to launch");
@@ -923,9 +923,16 @@ ssw_align_text_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pass_c
     }
     auto rescore = [](void *arg) -> int {
         rescore_t *r = static_cast<rescore_t *>(arg);
-        return score_batch_impl(r->m, r->scorer, r->d_feats, r->n_frames, r->utt_off,
-                                r->n_utts, r->m->text_scr.as<int16_t>(), r->stream, 0u, NULL, NULL, NULL,
-                                r->m->carry_rows.as<uint32_t>());
+        ScoreReq R{};
+        R.scorer = r->scorer;
+        R.d_feats = r->d_feats;
+        R.n_frames = r->n_frames;
+        R.utt_off = r->utt_off;
+        R.n_utts = r->n_utts;
+        R.d_out = r->m->text_scr.as<int16_t>();
+        R.stream = r->stream;
+        R.d_carry_rows = r->m->carry_rows.as<uint32_t>();
+        return score_batch_impl(r->m, R);
     };
     /* the scoring kernels are in flight: the host builds the first pass's graphs meanwhile;
      * the searches then run on the same stream, after the scores */

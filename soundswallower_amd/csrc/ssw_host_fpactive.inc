@@ -179,8 +179,7 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
     /* 0: the assumption -- the trajectory of the search over the compallsen = yes scores */
     std::vector<int> only; /* empty = every utterance */
     if (n_frames > 0
-        && score_batch_impl(m, scorer, d_feats, n_frames, utt_off, n_utts, d_rows, stream, 0u, NULL,
-                            NULL) < 0)
+        && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, d_rows, stream) < 0)
         return -1;
     if (G.search(G.arg, d_rows, only, mask_x, d_act_off, d_node_cnt) < 0)
         return -1;
@@ -236,8 +235,16 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
                 sub.push_back(utt_off[u] - lo);
             uo = sub.data();
         }
-        return score_batch_impl(m, scorer, d_feats + (size_t)lo * h->veclen_total, hi - lo, uo,
-                                u_hi - u_lo, d_rows, stream, 0u, NULL, NULL, &act);
+        ScoreReq R{};
+        R.scorer = scorer;
+        R.d_feats = d_feats + (size_t)lo * h->veclen_total;
+        R.n_frames = hi - lo;
+        R.utt_off = uo;
+        R.n_utts = u_hi - u_lo;
+        R.d_out = d_rows;
+        R.stream = stream;
+        R.act = &act;
+        return score_batch_impl(m, R);
     };
     /* (iota must hold 0 .. n for any sub-batch: the whole batch's plan writes iota[t] = t once;
      * a sub-batch's plan writes the same values at the same places) */
@@ -265,8 +272,8 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
                 if (b <= a)
                     continue;
                 const int32_t uo[2] = { 0, b - a };
-                if (score_batch_impl(m, scorer, d_feats + (size_t)a * h->veclen_total, b - a, uo, 1,
-                                     d_yes, stream, 0u, NULL, NULL) < 0)
+                if (ssw_score_batch(m, scorer, d_feats + (size_t)a * h->veclen_total, b - a, uo, 1,
+                                    d_yes, stream) < 0)
                     return -1;
                 if (plan_and_score(a, b, u, u + 1, 2) < 0)
                     return -1;

@@ -972,7 +972,7 @@ recognize_align_rows(const char *who, ssw_model_t *m, const ssw_dict_t *d,
         if (carry_rows_reserve(m, n_utts, who) < 0)
             return NULL;
         hipLaunchKernelGGL(gather_last_orders_kernel, dim3((unsigned)n_utts), dim3(128), 0,
-                           (hipStream_t)stream, m->d_topn_cw, m->d_utt_off, m->n_cbf,
+                           (hipStream_t)stream, m->sw.cw(), m->sw.utt_off(), m->n_cbf,
                            (const uint32_t *)NULL, m->carry_rows.as<uint32_t>());
         if (hipGetLastError() != hipSuccess) {
             ssw_set_error("%s: gather_last_orders_kernel failed to launch", who);
@@ -984,9 +984,16 @@ recognize_align_rows(const char *who, ssw_model_t *m, const ssw_dict_t *d,
     if (r == NULL)
         return NULL;
     ssw_alignment_set_t *a = NULL;
-    if (!two_pass
-        || score_batch_impl(m, scorer, d_feats, n_frames, utt_off, n_utts, rows, stream, 0u, NULL,
-                            NULL, NULL, m->carry_rows.as<uint32_t>()) >= 0)
+    ScoreReq R{}; /* the second pass: every utterance from its first pass's history */
+    R.scorer = scorer;
+    R.d_feats = d_feats;
+    R.n_frames = n_frames;
+    R.utt_off = utt_off;
+    R.n_utts = n_utts;
+    R.d_out = rows;
+    R.stream = stream;
+    R.d_carry_rows = m->carry_rows.as<uint32_t>();
+    if (!two_pass || score_batch_impl(m, R) >= 0)
         a = recognition_align(m, r, rows, utt_off, NULL, NULL, NULL, stream);
     if (a != NULL && rec_out != NULL)
         *rec_out = r;

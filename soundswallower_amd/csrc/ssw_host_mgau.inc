@@ -215,10 +215,17 @@ semi_mgau_frame_eval(ssw_mgau_impl *g, int16_t *senscr, const uint8_t *senone_ac
             memcpy(x.data() + h->featoff[f], feat[f], sizeof(float) * h->veclen[f]);
         const int32_t off[2] = { 0, 1 };
         HIP_OK(hipMemcpy(g->d_feat1, x.data(), sizeof(float) * x.size(), hipMemcpyHostToDevice));
-        /* (frame_base: the frame's number decides whether a ds > 1 model scans the codebook) */
-        if (score_batch_impl(m, SSW_SCORER_S2_SEMI, g->d_feat1, 1, off, 1, g->d_out1, NULL, 0u,
-                             g->sc_hist[slot ^ 1].data(), g->sc_hist[slot].data(), NULL, NULL, NULL,
-                             frame) < 0)
+        ScoreReq R{};
+        R.scorer = SSW_SCORER_S2_SEMI;
+        R.d_feats = g->d_feat1;
+        R.n_frames = 1;
+        R.utt_off = off;
+        R.n_utts = 1;
+        R.d_out = g->d_out1;
+        R.carry_in = g->sc_hist[slot ^ 1].data();
+        R.carry_out = g->sc_hist[slot].data();
+        R.frame_base = frame; /* (the frame's number decides whether a ds > 1 model scans the codebook) */
+        if (score_batch_impl(m, R) < 0)
             return -1;
         HIP_OK(hipMemcpy(g->sc_row[slot].data(), g->d_out1, sizeof(int16_t) * h->n_sen,
                          hipMemcpyDeviceToHost));

@@ -147,6 +147,39 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+/* The scoring workspace: what score_batch_impl (ssw_host_score.inc) keeps on the device from call
+ * to call, and what the last call left for the debug views.  ensure_score_ws sizes the buffers. */
+struct ScoreWs {
+    /* the top-N block, [rows][n_cbf]: codeword orders (uint32) and scores (int4); grow-only, of
+     * exactly the rows the largest call asked for */
+    DevBuf topn_cw, topn_sc;
+    /* utterance offsets, start bits and skip bits share ONE buffer, laid out so that a call
+     * uploads them with one copy: [offsets: ws_utts words][start bits: nw][skip bits: nw], nw =
+     * the words THIS batch's bits take (meta_nw, kept with the cached offsets) */
+    DevBuf meta;
+    size_t ws_utts, ws_bits, ws_utts_hint, ws_bits_hint, meta_nw;
+    std::vector<int32_t> *utt_cache; /* last uploaded utterance offsets (a pointer: the struct is memset) */
+    std::map<int, std::array<int, 10>> *xcd_cuts; /* matrix-core scan: XCD chunks per shape */
+    unsigned long long *d_nfixed; /* exact in-wave pass: [0] running count, [1] last batch */
+    hipStream_t last_stream;      /* the stream of the last call, if there was one */
+    int have_last_stream;
+    int stats_pending;
+    int stats_accumulate; /* ssw_score_batch_host: this launch's exact-pass count is ADDED to the
+                           * last batch's (a call scored as several sub-batches) */
+    int last_n_frames;
+    int64_t stats[2];
+    /* optional per-kernel event timing */
+    int timing, timing_pieced;
+    int timing_semi;  /* the last timed call was the s2_semi scorer's */
+    hipEvent_t ev[3];
+    hipEvent_t ev_sc; /* s2_semi: between its density and chain kernels */
+
+    uint32_t *cw() const { return topn_cw.as<uint32_t>(); }
+    int4 *sc() const { return topn_sc.as<int4>(); }
+    int *utt_off() const { return meta.as<int>(); }
+    uint32_t *utt_start() const { return meta.as<uint32_t>() + ws_utts; } /* bit per frame: first frame of an utterance */
+};
+
 struct ssw_model_s {
     ssw_host_model_t *h;
     Knobs kn;
@@ -176,16 +209,10 @@ struct ssw_model_s {
     uint16_t *d_sen_slot;  /* slot of every senone in d_mixw's slot order */
     DevBuf act_ws; /* ssw_align_batch_active: segments, lists, scores */
     int n_quads, slot_stride;
-    /* scoring workspace */
-    uint32_t *d_topn_cw;
-    int4 *d_topn_sc;
-    int *d_utt_off;
-    uint32_t *d_utt_start;      /* bit per frame: first frame of an utterance */
+    int logadd_max; /* the largest log-add entry (upload_model) */
+    ScoreWs sw;     /* scoring workspace */
     DevBuf carry0;              /* ssw_score_batch_ex: carried codeword orders, uint32 [n_utts][n_cbf] */
     DevBuf carry_rows;          /* ssw_align_text_batch, two_pass_history: uint32 [n_utts][n_cbf] */
-    unsigned long long *d_nfixed; /* exact in-wave pass: [0] running count, [1] last batch */
-    size_t ws_frames, ws_utts, ws_bits, ws_utts_hint, ws_bits_hint, meta_nw;
-    std::vector<int32_t> *utt_cache; /* last uploaded utterance offsets */
     /* Round 5: what a scoring call uploads (utterance offsets, start / skip bits, carried orders)
      * goes through PINNED staging, two slots used in turn, and hipMemcpyAsync on the caller's
      * stream -- ordered behind the launches that still read the old contents, no
@@ -195,8 +222,6 @@ struct ssw_model_s {
     size_t h_stage_cap[2];
     hipEvent_t ev_stage[2];
     int stage_next;
-    hipStream_t last_score_stream;
-    int have_last_score_stream;
     /* ssw_score_batch_host's pipeline (ssw_host_score.inc): scoring stream, download stream,
      * two slots of pinned staging and device rows */
     hipStream_t s_pipe, s_copy;
@@ -205,19 +230,10 @@ struct ssw_model_s {
     float *d_pipe_feat[2];
     int16_t *d_pipe_out[2];
     size_t pipe_feat_cap, pipe_out_cap;
-    std::map<int, std::array<int, 10>> *xcd_cuts; /* matrix-core scan: XCD chunks per shape */
     int force_exact;            /* SSW_PTM_EXACT=1: always run the sequential chain kernel */
     int ms_raw;                 /* next ms launch leaves its scores un-normalised */
-    int stats_pending;
-    int stats_accumulate; /* ssw_score_batch_host: this launch's exact-pass count is ADDED to the
-                           * last batch's (a call scored as several sub-batches) */
-    int last_n_frames;
-    int64_t stats[2];
     int64_t align_stats[2]; /* ssw_align_stats */
     int align_state_out_only; /* SSW_ALIGN_STATE_OUT_ONLY of the call in progress */
-    /* optional per-kernel event timing */
-    int timing, timing_pieced;
-    hipEvent_t ev[3];
     /* utterance offsets of ssw_feat_batch */
     DevBuf feat_off;
     /* the front end (ssw_host_fe.inc): its tables on the device and the configuration they were
@@ -261,8 +277,6 @@ struct ssw_model_s {
     uint8_t *d_sc_mixw;
     int sc_stride;
     DevBuf sc_ws;
-    hipEvent_t ev_sc; /* kernel timing: between its density and chain kernels */
-    int timing_semi;  /* the last timed call was this scorer's */
     /* continuous-density models (ssw_host_cont.inc): the table (ssw_host_model_t::cont_rec), the
      * mixture weights [n_sen][n_feat][n_density] as the host holds them, and the workspace: raw
      * rows and a minimum per frame */
@@ -536,6 +550,7 @@ upload_model(ssw_model_s *m)
         int T = 0;
         for (int i = 0; i < 256; ++i)
             T = h->logadd8[i] > T ? h->logadd8[i] : T;
+        m->logadd_max = T; /* (launch_senone and ms_takes_packed_kernel read it) */
         std::vector<uint8_t> mir((size_t)3 * SSW_LOGADD_MIRROR);
         for (int part = 0; part < 2; ++part) {
             const int size = (part + 1) * SSW_LOGADD_MIRROR, mid = size / 2;
@@ -824,14 +839,14 @@ ssw_model_free(ssw_model_t *m)
     (void)hipFree(m->d_logadd8);
     (void)hipFree(m->d_logadd_mirror);
     (void)hipFree(m->d_tp);
-    (void)hipFree(m->d_topn_cw);
-    (void)hipFree(m->d_topn_sc);
-    (void)hipFree(m->d_utt_off); /* (d_utt_start lies in the same allocation) */
+    (void)hipFree(m->sw.topn_cw.p);
+    (void)hipFree(m->sw.topn_sc.p);
+    (void)hipFree(m->sw.meta.p);
     (void)hipFree(m->carry0.p);
     (void)hipFree(m->carry_rows.p);
-    (void)hipFree(m->d_nfixed);
-    delete m->utt_cache;
-    delete m->xcd_cuts;
+    (void)hipFree(m->sw.d_nfixed);
+    delete m->sw.utt_cache;
+    delete m->sw.xcd_cuts;
     for (int k = 0; k < 2; ++k) {
         if (m->h_stage[k] != NULL) {
             (void)hipHostFree(m->h_stage[k]);
@@ -859,10 +874,10 @@ ssw_model_free(ssw_model_t *m)
     (void)hipFree(m->d_cont_rec);
     (void)hipFree(m->d_cont_pdf);
     (void)hipFree(m->cont_ws.p);
-    if (m->timing) {
+    if (m->sw.timing) {
         for (int i = 0; i < 3; ++i)
-            (void)hipEventDestroy(m->ev[i]);
-        (void)hipEventDestroy(m->ev_sc);
+            (void)hipEventDestroy(m->sw.ev[i]);
+        (void)hipEventDestroy(m->sw.ev_sc);
     }
     ssw_host_model_free(m->h);
     delete m;

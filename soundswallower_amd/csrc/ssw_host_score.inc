@@ -1,49 +1,40 @@
 /* ssw_host_score.inc -- host: batched scoring entry points.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 /* ---------------------------------------------------------------------------------- */
+/* The scoring workspace for `rows` rows of the top-N block and a batch of n_utts utterances in
+ * them.  Grow-only: the top-N pair of exactly `rows` rows, the meta buffer of the largest
+ * utterance count and bit count seen (the *_hint maxima).  Refuses a block whose index does not
+ * fit 32 bits before anything is allocated; forgets the cached offsets when the meta buffer moves. */
 static int
-ensure_score_ws(ssw_model_s *m, int n_frames, int n_utts)
+ensure_score_ws(ssw_model_s *m, size_t rows, int n_utts)
 {
-    if ((size_t)n_frames > m->ws_frames) {
-        (void)hipFree(m->d_topn_cw);
-        (void)hipFree(m->d_topn_sc);
-        m->d_topn_cw = NULL;
-        m->d_topn_sc = NULL;
-        m->ws_frames = 0;
-        if ((uint64_t)n_frames * (uint64_t)m->n_cbf > 0xffffffffull) {
-            ssw_set_error("batch of %d frames is too large (frames x codebooks x streams must fit 32 bits)",
-                          n_frames);
-            return -1;
-        }
-        if (dev_alloc(&m->d_topn_cw, (size_t)n_frames * m->n_cbf) < 0
-            || dev_alloc(&m->d_topn_sc, (size_t)n_frames * m->n_cbf) < 0)
-            return -1;
-        m->ws_frames = (size_t)n_frames;
+    ScoreWs &w = m->sw;
+    const uint64_t pairs = (uint64_t)rows * (uint64_t)m->n_cbf;
+    if (pairs > 0xffffffffull) {
+        ssw_set_error("batch of %d frames is too large (frames x codebooks x streams must fit 32 bits)",
+                      (int)rows);
+        return -1;
     }
-    if (m->d_nfixed == NULL) {
-        if (dev_alloc(&m->d_nfixed, 4) < 0)
+    if (devbuf_reserve(w.topn_cw, sizeof(uint32_t) * (size_t)pairs, "ssw_score_batch") < 0
+        || devbuf_reserve(w.topn_sc, sizeof(int4) * (size_t)pairs, "ssw_score_batch") < 0)
+        return -1;
+    if (w.d_nfixed == NULL) {
+        if (dev_alloc(&w.d_nfixed, 4) < 0)
             return -1;
-        HIP_OK(hipMemset(m->d_nfixed, 0, 4 * sizeof(unsigned long long)));
+        HIP_OK(hipMemset(w.d_nfixed, 0, 4 * sizeof(unsigned long long)));
     }
-    /* utterance offsets, start bits and skip bits share ONE buffer, laid out so that a call
-     * uploads them with one copy: [offsets: ws_utts words][start bits: nw][skip bits: nw], nw =
-     * the words THIS batch's bits take (meta_nw, kept with the cached offsets) */
-    const size_t need_bits = 2 * (((size_t)n_frames + 31) / 32 + 2);
-    if ((size_t)n_utts + 1 > m->ws_utts || need_bits > m->ws_bits) {
-        (void)hipFree(m->d_utt_off);
-        m->d_utt_off = NULL;
-        m->d_utt_start = NULL;
-        m->ws_utts = m->ws_bits = 0;
-        if (m->utt_cache)
-            m->utt_cache->clear(); /* everything has to be uploaded again */
-        const size_t wu = std::max((size_t)n_utts + 1, m->ws_utts_hint), wb = std::max(need_bits, m->ws_bits_hint);
-        uint32_t *meta = NULL;
-        if (dev_alloc(&meta, wu + wb) < 0)
+    const size_t need_bits = 2 * ((rows + 31) / 32 + 2);
+    if ((size_t)n_utts + 1 > w.ws_utts || need_bits > w.ws_bits) {
+        const size_t wu = std::max((size_t)n_utts + 1, w.ws_utts_hint), wb = std::max(need_bits, w.ws_bits_hint);
+        bool moved = false; /* (always, here: wu + wb is more than the buffer holds) */
+        w.ws_utts = w.ws_bits = 0;
+        const int rc = devbuf_reserve(w.meta, sizeof(uint32_t) * (wu + wb), "ssw_score_batch", 0, &moved);
+        if (moved && w.utt_cache)
+            w.utt_cache->clear(); /* everything has to be uploaded again */
+        if (rc < 0)
             return -1;
-        m->d_utt_off = reinterpret_cast<int *>(meta);
-        m->d_utt_start = meta + wu;
-        m->ws_utts = m->ws_utts_hint = wu;
-        m->ws_bits = m->ws_bits_hint = wb;
+        w.ws_utts = w.ws_utts_hint = wu;
+        w.ws_bits = w.ws_bits_hint = wb;
     }
     return 0;
 }
@@ -92,6 +83,7 @@ check_scorer_shape(const ssw_model_s *m, int scorer)
     return 0;
 }
 
+/* the model's part of a chain kernel's parameters; the caller names the top-N rows it writes */
 static void
 fill_chain_params(const ssw_model_s *m, ChainParams &P, const float *d_feats)
 {
@@ -99,9 +91,7 @@ fill_chain_params(const ssw_model_s *m, ChainParams &P, const float *d_feats)
     memset(&P, 0, sizeof(P));
     P.rec = m->d_rec;
     P.feats = d_feats;
-    P.utt_off = m->d_utt_off;
-    P.topn_cw = m->d_topn_cw;
-    P.topn_sc = m->d_topn_sc;
+    P.utt_off = m->sw.utt_off();
     P.n_cbf = m->n_cbf;
     P.n_feat = h->n_feat;
     P.featdim = h->veclen_total;
@@ -117,26 +107,76 @@ static bool
 ms_takes_packed_kernel(const ssw_model_s *m, int n_frames)
 {
     const ssw_host_model_t *h = m->h;
-    int tab_max = 0;
-    for (int i = 0; i < 256; ++i)
-        tab_max = h->logadd8[i] > tab_max ? h->logadd8[i] : tab_max;
     return h->cfg.aw == 1 && !m->ms_raw && n_frames >= 4 * 512 && h->n_cb <= 64
-        && 255 + 640 + 6 * tab_max < SSW_LOGADD_MIRROR && !m->kn.ms_senone_old;
+        && 255 + 640 + 6 * m->logadd_max < SSW_LOGADD_MIRROR && !m->kn.ms_senone_old;
 }
 
-/* cp != NULL: compact rows (ssw_host_compact.inc) -- d_out is then the compact buffer and
- * frame_base the batch frame number of this launch's first frame; only for launches that take
- * the persistent kernel (the caller checks senone_compact_ok) */
+/* per-frame active sets of a compallsen = no batch (device pointers; ssw_host_active.inc) */
+struct ActiveSets {
+    const int32_t *seg_of_frame;
+    const unsigned long long *seg_cbmask;
+    SenoneActive2Params *a2; /* filled by the caller but for the top-N block and the model's tables */
+    /* or (a2 == NULL): a listed set per frame as a bitmap, ssw_k7_fpactive.inc -- listed, cbmask,
+     * out, full, cap are the caller's, the rest is filled here */
+    const SenoneListedParams *ls;
+};
+
+/* One scoring call.  `ScoreReq R{}` is all zeros; a caller names what it sets. */
+struct ScoreReq {
+    int scorer;
+    const float *d_feats;    /* device, [n_frames][veclen_total] */
+    int32_t n_frames;
+    const int32_t *utt_off;  /* host, [n_utts + 1] */
+    int32_t n_utts;
+    int16_t *d_out;          /* device rows, [n_frames][n_sen]; with cp: the compact buffer */
+    void *stream;
+    uint32_t flags;          /* SSW_SCORE_* */
+    const uint32_t *carry_in; /* host [n_cbf] or NULL: the history the first utterance starts from */
+    uint32_t *carry_out;      /* host [n_cbf] or NULL: read back, which makes the call synchronous */
+    const ActiveSets *act;    /* compallsen = no: score the active sets only */
+    const uint32_t *d_carry_rows; /* device [n_utts][n_cbf]: a history row per utterance */
+    /* compact rows (ssw_host_compact.inc): only for launches that take the persistent senone
+     * kernel (the caller checks senone_compact_ok) */
+    const ssw_compact_plan_s *cp;
+    /* a call that continues an utterance (a piece of ssw_score_batch_host's cut): the in-utterance
+     * number of its frame 0, which decides the frames a ds > 1 model re-scans on */
+    int frame_base;
+    /* the row of the model's top-N workspace that frame 0 writes: 0, but in the pieces of
+     * ssw_score_batch_host, whose workspace holds the whole call */
+    int topn_row0;
+};
+
+/* What the steps of one call share: the request and what score_batch_impl derives from it once. */
+struct ScoreCall {
+    ssw_model_s *m;
+    const ScoreReq &R;
+    hipStream_t st;
+    bool ms;      /* the ms scorer: no history, no chain */
+    /* history carried from utterance to utterance (the reference never resets it after
+     * start-up, src/acmod.c:367): the batch is one chain, only its first frame is a start.  The
+     * chain follows the reference's two-slot ring (src/ptm_mgau.c:425-437): frame numbers restart
+     * with every utterance and its frame 0 copies slot 1, so the last frame of an utterance of odd
+     * length is off the chain (`skip` bits in score_upload_meta; a one-frame utterance entirely) */
+    bool chain;
+    uint32_t *cw; /* the top-N rows of frame 0: the workspace's + topn_row0 rows */
+    int4 *sc;
+};
+
+/* The senone kernel of frames [lo, hi) of the call, from their top-N rows.  With R.cp the rows
+ * are compact: d_out is the compact buffer and lo goes to the kernel as the batch frame number of
+ * the launch's first frame.  move_stats: the launch moves the exact pass's count to d_nfixed[1]. */
 static int
-launch_senone(ssw_model_s *m, int scorer, int n_frames, const uint32_t *cw, const int4 *sc,
-              int16_t *d_out, bool move_stats, hipStream_t st, bool share_device = false,
-              const ssw_compact_plan_s *cp = NULL, int frame_base = 0)
+launch_senone(const ScoreCall &C, int lo, int hi, bool move_stats)
 {
+    ssw_model_s *m = C.m;
     const ssw_host_model_t *h = m->h;
+    const int scorer = C.R.scorer, n_frames = hi - lo;
+    const ssw_compact_plan_s *cp = C.R.cp;
+    hipStream_t st = C.st;
     SenoneParams S;
     memset(&S, 0, sizeof(S));
-    S.topn_cw = cw;
-    S.topn_sc = sc;
+    S.topn_cw = C.cw + (size_t)lo * m->n_cbf;
+    S.topn_sc = C.sc + (size_t)lo * m->n_cbf;
     S.mixw = scorer == SSW_SCORER_MS ? m->d_ms_pdf : m->d_mixw;
     S.aw = h->cfg.aw;
     S.zero = h->zero8;
@@ -146,16 +186,16 @@ launch_senone(ssw_model_s *m, int scorer, int n_frames, const uint32_t *cw, cons
     S.slot_sen = m->d_slot_sen;
     S.logadd8 = m->d_logadd8;
     S.logadd_mirror = m->d_logadd_mirror + (scorer == SSW_SCORER_MS ? SSW_LOGADD_MIRROR : 0);
-    S.nfixed = move_stats ? m->d_nfixed : NULL;
-    S.nfixed_acc = m->stats_accumulate;
-    S.out = d_out;
+    S.nfixed = move_stats ? m->sw.d_nfixed : NULL;
+    S.nfixed_acc = m->sw.stats_accumulate;
+    S.out = cp != NULL ? C.R.d_out : C.R.d_out + (size_t)lo * h->n_sen;
     if (cp != NULL) {
         S.utt_of_frame = cp->d_utt_of_frame;
         S.cutt_off = cp->d_frame_off;
         S.cstride = cp->d_cstride;
         S.crow_off = cp->d_crow_off;
         S.cpos = cp->d_cpos;
-        S.frame_base = frame_base;
+        S.frame_base = lo;
     }
     S.n_frames = n_frames;
     S.n_cb = h->n_cb;
@@ -164,9 +204,7 @@ launch_senone(ssw_model_s *m, int scorer, int n_frames, const uint32_t *cw, cons
     S.n_sen = h->n_sen;
     S.slot_stride = m->slot_stride;
     S.n_quads = m->n_quads;
-    S.tab_max = 0;
-    for (int i = 0; i < 256; ++i)
-        S.tab_max = h->logadd8[i] > S.tab_max ? h->logadd8[i] : S.tab_max;
+    S.tab_max = m->logadd_max;
     /* the PTM kernel indexes a 512-entry table with |x - y|, x >= -3 tab_max, y <= 255 + 96 */
     if (scorer != SSW_SCORER_MS && 255 + SSW_MAX_NEG_ASCR + 3 * S.tab_max >= SSW_LOGADD_LDS) {
         ssw_set_error("unsupported log-add table (largest entry %d)", S.tab_max);
@@ -249,7 +287,7 @@ launch_senone(ssw_model_s *m, int scorer, int n_frames, const uint32_t *cw, cons
      * stream (the alignment of the previous chunk, jobs.py) gets wave slots every ~100 us
      * instead of waiting for a whole 256,000-frame launch to drain (config 5 on one GPU: 56-59
      * -> 53-57 ms; alone, the shorter stay costs 3 % at 65,536 frames) */
-    if (share_device && groups < (n_units + 7) / 8)
+    if ((C.R.flags & SSW_SCORE_SHARE_DEVICE) != 0 && groups < (n_units + 7) / 8)
         groups = (n_units + 7) / 8;
     if (kn.sen_groups >= 0)
         groups = kn.sen_groups > 0 ? kn.sen_groups : n_units;
@@ -297,440 +335,163 @@ launch_senone(ssw_model_s *m, int scorer, int n_frames, const uint32_t *cw, cons
     return 0;
 }
 
-/* per-frame active sets of a compallsen = no batch (device pointers; ssw_host_active.inc) */
-struct ActiveSets {
-    const int32_t *seg_of_frame;
-    const unsigned long long *seg_cbmask;
-    SenoneActive2Params *a2; /* filled by the caller but for the top-N block and the model's tables */
-    /* or (a2 == NULL): a listed set per frame as a bitmap, ssw_k7_fpactive.inc -- listed, cbmask,
-     * out, full, cap are the caller's, the rest is filled here */
-    const SenoneListedParams *ls;
-};
-
-/* batches from this many frames take the matrix-core scan.  Rounds 2-3: 2,049, where the bf16
- * form caught up with the vector-unit scan; the binary16 form of round 4 is ahead at every
- * size measured -- 256 frames: 15.7 against 27.6 us, 1,024: 17.9 against 30.4, 2,048: 23.2
- * against 44.4 (DESIGN.md section 5) -- so every batch takes it; SSW_SCAN=fma or a larger
- * SSW_MFMA_MIN_FRAMES keep the vector-unit scan (tests, A/B) */
-#define SSW_MFMA_MIN_FRAMES_DEFAULT 1
-static int
-score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
-                 const int32_t *utt_off, int32_t n_utts, int16_t *d_out, void *stream,
-                 uint32_t flags, const uint32_t *carry_in, uint32_t *carry_out,
-                 const ActiveSets *act = NULL, const uint32_t *d_carry_rows = NULL,
-                 const ssw_compact_plan_s *cp = NULL, int frame_base = 0);
-
-extern "C" int
-ssw_score_batch(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
-                const int32_t *utt_off, int32_t n_utts, int16_t *d_out, void *stream)
+/* what SenoneListedParams and SenoneActive2Params share: the top-N rows of frames [lo, hi) and
+ * the model's tables */
+template <typename Params>
+static void
+fill_active_common(const ScoreCall &C, Params &A, int lo, int hi)
 {
-    return score_batch_impl(m, scorer, d_feats, n_frames, utt_off, n_utts, d_out, stream, 0u, NULL,
-                            NULL);
-}
-
-extern "C" int
-ssw_score_batch_ex(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
-                   const int32_t *utt_off, int32_t n_utts, int16_t *d_out, void *stream,
-                   uint32_t flags, const uint32_t *carry_in, uint32_t *carry_out)
-{
-    return score_batch_impl(m, scorer, d_feats, n_frames, utt_off, n_utts, d_out, stream, flags,
-                            carry_in, carry_out);
-}
-
-/* what every scoring call ends in: the counters, and carry_out read back */
-static int
-score_batch_finish(ssw_model_t *m, bool ms, int32_t n_frames, const int32_t *utt_off, int32_t n_utts,
-                   hipStream_t st, uint32_t flags, const uint32_t *carry_in, uint32_t *carry_out)
-{
-    const bool chain = (flags & SSW_SCORE_CARRY_UTTS) != 0 && !ms;
-    const int64_t pairs = (int64_t)n_frames * m->n_cbf;
-    m->last_n_frames = n_frames;
-    m->stats[1] = pairs;
-    if (carry_out != NULL) {
-        /* what the next call starts from.  Default: the last frame's final order (the next call
-         * continues the same utterance).  SSW_SCORE_CARRY_OUT_REWIND: history slot 1 of the
-         * reference's ring, which is what frame 0 of the NEXT utterance -- or of the second pass
-         * after acmod_rewind -- copies (src/ptm_mgau.c:425-437): the final order of the last
-         * odd-numbered frame of the last utterance that has two frames (in a chain; of the last
-         * utterance otherwise), else what that utterance itself started from */
-        long long row = (long long)n_frames - 1;
-        bool from_start = false; /* no frame wrote the slot: carry_in / the reset order */
-        if (flags & SSW_SCORE_CARRY_OUT_REWIND) {
-            row = -1;
-            for (int u = n_utts - 1; u >= 0 && row < 0; --u) {
-                const int T = utt_off[u + 1] - utt_off[u];
-                if (T >= 2)
-                    row = (long long)utt_off[u] + (T / 2) * 2 - 1;
-                else if (!chain) { /* utterances are independent: only the last one counts */
-                    from_start = true;
-                    for (int i = 0; i < m->n_cbf; ++i)
-                        carry_out[i] = (u == 0 && carry_in != NULL) ? carry_in[i] : 0x03020100u;
-                    break;
-                }
-            }
-            if (row < 0 && !from_start) {
-                from_start = true;
-                for (int i = 0; i < m->n_cbf; ++i)
-                    carry_out[i] = carry_in != NULL ? carry_in[i] : 0x03020100u;
-            }
-        }
-        if (ms)
-            for (int i = 0; i < m->n_cbf; ++i)
-                carry_out[i] = 0x03020100u; /* the ms scorer keeps no history */
-        else if (!from_start) {
-            HIP_OK(hipMemcpyAsync(carry_out, m->d_topn_cw + (size_t)row * m->n_cbf,
-                                  sizeof(uint32_t) * (size_t)m->n_cbf, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-        }
-    }
-    return 0;
-}
-
-static int
-score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
-                 const int32_t *utt_off, int32_t n_utts, int16_t *d_out, void *stream,
-                 uint32_t flags, const uint32_t *carry_in, uint32_t *carry_out,
-                 const ActiveSets *act, const uint32_t *d_carry_rows, const ssw_compact_plan_s *cp,
-                 int frame_base)
-{
-    ModelBusy busy_(m);
-    if (!busy_.ok)
-        return -1;
-    refresh_knobs(m); /* tests: knobs flipped between calls on one model */
-    const Knobs &kn = m->kn;
-    hipStream_t st = (hipStream_t)stream;
-    if (carry_out != NULL && (n_frames == 0 || n_utts == 0)) { /* nothing scored: state unchanged */
-        for (int i = 0; i < m->n_cbf; ++i)
-            carry_out[i] = carry_in ? carry_in[i] : 0x03020100u;
-    }
-    if (n_frames == 0 || n_utts == 0)
-        return 0;
-    if (n_frames < 0 || n_utts < 0 || utt_off == NULL || utt_off[0] != 0
-        || utt_off[n_utts] != n_frames) {
-        ssw_set_error("bad utterance offsets");
-        return -1;
-    }
-    for (int u = 0; u < n_utts; ++u)
-        if (utt_off[u + 1] < utt_off[u]) {
-            ssw_set_error("utterance offsets must be non-decreasing");
-            return -1;
-        }
-    if (check_scorer_shape(m, scorer) < 0)
-        return -1;
-    const bool ms = scorer == SSW_SCORER_MS;
-    if (act != NULL && (m->h->cfg.ds != 1 || m->force_exact)) { /* (before anything is launched) */
-        ssw_set_error("active-set batches: ds = 1 only");
-        return -1;
-    }
-    HIP_OK(hipSetDevice(m->device));
-    if (m->h->continuous) {
-        /* no history, no utterance boundaries, none of the PTM scan's workspaces: its own two
-         * kernels (ssw_host_cont.inc); flags, carry_in and ds are ignored as for ms */
-        if (act != NULL || cp != NULL) {
-            ssw_set_error("internal error: active sets or compact rows with a continuous model");
-            return -1;
-        }
-        if (m->timing) {
-            HIP_OK(hipEventRecord(m->ev[0], st));
-            m->timing_semi = 0;
-        }
-        if (cont_launch(m, d_feats, n_frames, d_out, st) < 0)
-            return -1;
-        m->stats[0] = 0;
-        m->stats_pending = 0;
-        m->last_n_frames = 0; /* (no top-N block: ssw_score_batch_topn has nothing to show) */
-        m->stats[1] = (int64_t)n_frames * m->n_cbf;
-        for (int i = 0; carry_out != NULL && i < m->n_cbf; ++i)
-            carry_out[i] = 0x03020100u; /* the ms scorer keeps no history */
-        return 0;
-    }
-    /* history carried from utterance to utterance (the reference never resets it after
-     * start-up, src/acmod.c:367): the batch is one chain, only its first frame is a start.  The
-     * chain follows the reference's two-slot ring (src/ptm_mgau.c:425-437): frame numbers restart
-     * with every utterance and its frame 0 copies slot 1, so the last frame of an utterance of odd
-     * length is off the chain (`skip` bits below; a one-frame utterance entirely) */
-    const bool chain = (flags & SSW_SCORE_CARRY_UTTS) != 0 && !ms;
-    if (ensure_score_ws(m, n_frames, n_utts) < 0)
-        return -1;
-    /* a caller that moves from one stream to another: the uploads below are only ordered behind
-     * the launches of THIS stream */
-    if (m->have_last_score_stream && m->last_score_stream != st)
-        HIP_OK(hipDeviceSynchronize()); /* (not the old stream itself: it may be gone) */
-    m->last_score_stream = st;
-    m->have_last_score_stream = 1;
-    const bool want_carry = carry_in != NULL && !ms;
-    if (want_carry) {
-        for (int i = 0; i < m->n_cbf; ++i)
-            for (int k = 0; k < 4; ++k)
-                if (((carry_in[i] >> (8 * k)) & 0xffu) >= (uint32_t)m->h->n_density) {
-                    ssw_set_error("carry_in[%d] names codeword %u of %d", i,
-                                  (carry_in[i] >> (8 * k)) & 0xffu, m->h->n_density);
-                    return -1;
-                }
-        if (devbuf_reserve(m->carry0, sizeof(uint32_t) * (size_t)m->n_cbf * (size_t)n_utts,
-                           "ssw_score_batch_ex") < 0)
-            return -1;
-    }
-    /* the offsets rarely change between calls of one job: upload only when they do
-     * (cache key: the chain flag, then the offsets) */
-    if (m->utt_cache == NULL)
-        m->utt_cache = new std::vector<int32_t>();
-    const bool new_offsets = m->utt_cache->size() != (size_t)n_utts + 2
-        || (*m->utt_cache)[0] != (chain ? 1 : 0)
-        || memcmp(m->utt_cache->data() + 1, utt_off, sizeof(int32_t) * ((size_t)n_utts + 1)) != 0;
-    if (want_carry || new_offsets) {
-        /* one pinned slot for everything this call uploads: [carry rows][offsets][starts][skip] */
-        const size_t ncar = want_carry ? (size_t)m->n_cbf * (size_t)n_utts : 0;
-        const size_t nw = ((size_t)n_frames + 31) / 32 + 1;
-        const size_t b_car = sizeof(uint32_t) * ncar;
-        const size_t b_off = new_offsets ? sizeof(int32_t) * ((size_t)n_utts + 1) : 0;
-        const size_t b_bits = new_offsets ? sizeof(uint32_t) * nw : 0;
-        int slot = 0;
-        unsigned char *hs = stage_acquire(m, b_car + sizeof(uint32_t) * m->ws_utts + 2 * b_bits + 64, &slot);
-        if (hs == NULL)
-            return -1;
-        if (want_carry) {
-            /* [n_utts][n_cbf]: the first utterance starts from carry_in, the others from the
-             * reset history (the chain kernel reads a row per utterance, the scans only row 0) */
-            uint32_t *car = reinterpret_cast<uint32_t *>(hs);
-            for (size_t i = 0; i < ncar; ++i)
-                car[i] = 0x03020100u;
-            memcpy(car, carry_in, sizeof(uint32_t) * (size_t)m->n_cbf);
-            HIP_OK(hipMemcpyAsync(m->carry0.as<uint32_t>(), car, b_car, hipMemcpyHostToDevice, st));
-        }
-        if (new_offsets) {
-            m->utt_cache->assign(1, chain ? 1 : 0);
-            m->utt_cache->insert(m->utt_cache->end(), utt_off, utt_off + n_utts + 1);
-            /* staged as it lies on the device: offsets (ws_utts words), start bits, skip bits */
-            int32_t *hoff = reinterpret_cast<int32_t *>(hs + b_car);
-            uint32_t *starts = reinterpret_cast<uint32_t *>(hoff + m->ws_utts);
-            uint32_t *skip = starts + nw;
-            memcpy(hoff, utt_off, b_off);
-            memset(starts, 0, 2 * b_bits);
-            if (chain)
-                starts[0] = 1u;
-            for (int u = 0; u < n_utts; ++u) {
-                if (!chain && utt_off[u] < n_frames)
-                    starts[(size_t)utt_off[u] >> 5] |= 1u << (utt_off[u] & 31);
-                if (chain && ((utt_off[u + 1] - utt_off[u]) & 1)) {
-                    const int t = utt_off[u + 1] - 1;
-                    skip[(size_t)t >> 5] |= 1u << (t & 31);
-                }
-            }
-            m->meta_nw = nw;
-            HIP_OK(hipMemcpyAsync(m->d_utt_off, hoff, sizeof(uint32_t) * (m->ws_utts + 2 * nw),
-                                  hipMemcpyHostToDevice, st));
-        }
-        if (stage_release(m, slot, st) < 0)
-            return -1;
-    }
+    const ssw_model_s *m = C.m;
     const ssw_host_model_t *h = m->h;
-    ChainParams P;
-    fill_chain_params(m, P, d_feats);
-    P.n_utts = n_utts;
-    P.n_frames = n_frames;
-    P.chain_utts = chain ? 1 : 0;
-    /* a call that continues an utterance (a piece of ssw_score_batch_host's cut): the in-utterance
-     * number of its frame 0, which decides the frames a ds > 1 model re-scans on */
-    P.frame_base = frame_base;
-    P.carry_pk = (carry_in != NULL && !ms) ? m->carry0.as<uint32_t>() : NULL;
-    if (d_carry_rows != NULL && !ms) /* a row per utterance, already on the device */
-        P.carry_pk = d_carry_rows;
-    const int64_t pairs = (int64_t)n_frames * m->n_cbf;
-    bool pieced = false;
-    /* compallsen = no: the senone kernel of frames [lo, hi) (ssw_host_active.inc filled the
-     * segment tables; four frames per workgroup, a wave each) */
-    auto launch_active = [&](int lo, int hi) -> hipError_t {
-        if (act->a2 == NULL) {
-            SenoneListedParams L = *act->ls;
-            L.topn_cw = m->d_topn_cw + (size_t)lo * m->n_cbf;
-            L.topn_sc = m->d_topn_sc + (size_t)lo * m->n_cbf;
-            L.mixw = ms ? m->d_ms_pdf : m->d_mixw;
-            L.logadd8 = m->d_logadd8;
-            L.sen2cb = m->d_sen2cb;
-            L.sen_slot = m->d_sen_slot;
-            L.n_frames = hi - lo;
-            L.frame_base = lo;
-            L.n_cb = h->n_cb;
-            L.n_feat = h->n_feat;
-            L.n_density = h->n_density;
-            L.n_sen = h->n_sen;
-            L.slot_stride = m->slot_stride;
-            L.nw32 = (h->n_sen + 31) / 32;
-            L.zero = h->zero8;
-            L.aw = h->cfg.aw;
-            if (L.cap <= 0 || L.cap > h->n_sen)
-                L.cap = h->n_sen; /* (the caller's bound on a frame's listed entries) */
-            const size_t per_wave = ((ms ? 0 : 8 * (size_t)m->n_cbf) + 4 * (size_t)((L.cap + 1) & ~1)
-                                     + 16 + 15) & ~(size_t)15;
-            const size_t lds = 4 * per_wave;
-            const dim3 grid((unsigned)((hi - lo + 3) / 4));
-            if (lds > 48 * 1024) {
-                const hipError_t ea = hipFuncSetAttribute(
-                    ms ? (const void *)senone_listed_kernel<true> : (const void *)senone_listed_kernel<false>,
-                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (ea != hipSuccess)
-                    return ea;
-            }
-            if (ms)
-                hipLaunchKernelGGL(senone_listed_kernel<true>, grid, dim3(256), lds, st, L);
-            else
-                hipLaunchKernelGGL(senone_listed_kernel<false>, grid, dim3(256), lds, st, L);
-            return hipGetLastError();
+    A.topn_cw = C.cw + (size_t)lo * m->n_cbf;
+    A.topn_sc = C.sc + (size_t)lo * m->n_cbf;
+    A.mixw = C.ms ? m->d_ms_pdf : m->d_mixw;
+    A.logadd8 = m->d_logadd8;
+    A.n_frames = hi - lo;
+    A.frame_base = lo;
+    A.n_cb = h->n_cb;
+    A.n_feat = h->n_feat;
+    A.n_density = h->n_density;
+    A.n_sen = h->n_sen;
+    A.slot_stride = m->slot_stride;
+    A.zero = h->zero8;
+    A.aw = h->cfg.aw;
+}
+
+/* compallsen = no: the senone kernel of frames [lo, hi) over R.act's sets (ssw_host_active.inc /
+ * ssw_host_fpactive.inc filled the segment tables; four frames per workgroup, a wave each).
+ * Reads the frames' top-N rows; the kernels write where the caller's parameter block says. */
+static hipError_t
+launch_active(const ScoreCall &C, int lo, int hi)
+{
+    const ssw_model_s *m = C.m;
+    const ssw_host_model_t *h = m->h;
+    const ActiveSets *act = C.R.act;
+    const bool ms = C.ms;
+    hipStream_t st = C.st;
+    const dim3 grid((unsigned)((hi - lo + 3) / 4));
+    if (act->a2 == NULL) {
+        SenoneListedParams L = *act->ls;
+        fill_active_common(C, L, lo, hi);
+        L.sen2cb = m->d_sen2cb;
+        L.sen_slot = m->d_sen_slot;
+        L.nw32 = (h->n_sen + 31) / 32;
+        if (L.cap <= 0 || L.cap > h->n_sen)
+            L.cap = h->n_sen; /* (the caller's bound on a frame's listed entries) */
+        const size_t per_wave = ((ms ? 0 : 8 * (size_t)m->n_cbf) + 4 * (size_t)((L.cap + 1) & ~1)
+                                 + 16 + 15) & ~(size_t)15;
+        const size_t lds = 4 * per_wave;
+        if (lds > 48 * 1024) {
+            const hipError_t ea = hipFuncSetAttribute(
+                ms ? (const void *)senone_listed_kernel<true> : (const void *)senone_listed_kernel<false>,
+                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (ea != hipSuccess)
+                return ea;
         }
-        SenoneActive2Params A = *act->a2;
-        A.zero = h->zero8;
-        A.aw = h->cfg.aw;
-        A.topn_cw = m->d_topn_cw + (size_t)lo * m->n_cbf;
-        A.topn_sc = m->d_topn_sc + (size_t)lo * m->n_cbf;
-        A.mixw = ms ? m->d_ms_pdf : m->d_mixw;
-        A.logadd8 = m->d_logadd8;
-        A.n_frames = hi - lo;
-        A.frame_base = lo;
-        A.n_cb = h->n_cb;
-        A.n_feat = h->n_feat;
-        A.n_density = h->n_density;
-        A.n_sen = h->n_sen;
-        A.slot_stride = m->slot_stride;
-        const size_t per_wave = (ms ? 0 : 8 * (size_t)m->n_cbf) + 2 * (size_t)((A.cap + 1) & ~1)
-            + (A.out_full != NULL ? 2 * (size_t)((h->n_sen + 1) & ~1) : 0);
-        const size_t lds = 4 * ((per_wave + 15) & ~(size_t)15);
-        const dim3 grid((unsigned)((hi - lo + 3) / 4));
         if (ms)
-            hipLaunchKernelGGL(senone_active2_kernel<true>, grid, dim3(256), lds, st, A);
+            hipLaunchKernelGGL(senone_listed_kernel<true>, grid, dim3(256), lds, st, L);
         else
-            hipLaunchKernelGGL(senone_active2_kernel<false>, grid, dim3(256), lds, st, A);
+            hipLaunchKernelGGL(senone_listed_kernel<false>, grid, dim3(256), lds, st, L);
         return hipGetLastError();
-    };
-    if (m->timing) {
-        HIP_OK(hipEventRecord(m->ev[0], st));
-        m->timing_semi = scorer == SSW_SCORER_S2_SEMI;
     }
-    if (scorer == SSW_SCORER_S2_SEMI) {
-        /* the same batch, history and carry semantics; its own three kernels (ssw_host_semi.inc) */
-        if (act != NULL || cp != NULL) {
-            ssw_set_error("internal error: active sets or compact rows with the s2_semi scorer");
-            return -1;
-        }
-        if (semi_launch(m, P, d_out, st) < 0)
-            return -1;
-        m->stats[0] = 0;
-        m->stats_pending = 0;
-        return score_batch_finish(m, false, n_frames, utt_off, n_utts, st, flags, carry_in, carry_out);
+    SenoneActive2Params A = *act->a2;
+    fill_active_common(C, A, lo, hi);
+    const size_t per_wave = (ms ? 0 : 8 * (size_t)m->n_cbf) + 2 * (size_t)((A.cap + 1) & ~1)
+        + (A.out_full != NULL ? 2 * (size_t)((h->n_sen + 1) & ~1) : 0);
+    const size_t lds = 4 * ((per_wave + 15) & ~(size_t)15);
+    if (ms)
+        hipLaunchKernelGGL(senone_active2_kernel<true>, grid, dim3(256), lds, st, A);
+    else
+        hipLaunchKernelGGL(senone_active2_kernel<false>, grid, dim3(256), lds, st, A);
+    return hipGetLastError();
+}
+
+/* The sequential top-N scan: frame down-sampling (and SSW_PTM_EXACT) makes every frame depend on
+ * its predecessor, so a wave walks each chain exactly.  Writes the call's top-N rows. */
+static hipError_t
+launch_scan_chain(const ScoreCall &C, const ChainParams &P)
+{
+    const int n_chain = (C.chain ? 1 : C.R.n_utts) * C.m->n_cbf;
+    hipLaunchKernelGGL((ptm_topn_chain_kernel<13, 2, 4>), dim3((n_chain + 3) / 4), dim3(256), 0, C.st, P);
+    return hipGetLastError();
+}
+
+/* what both frame-parallel scans read: the call's top-N rows, the uploaded offsets and bits, the
+ * carried rows; frame_lo, n_frames and tile_groups are the launch's */
+static void
+fill_frames_params(const ScoreCall &C, FramesParams &F)
+{
+    const ssw_model_s *m = C.m;
+    const ssw_host_model_t *h = m->h;
+    const ScoreReq &R = C.R;
+    memset(&F, 0, sizeof(F));
+    F.topn_cw = C.cw;
+    F.topn_sc = C.sc;
+    F.utt_start = m->sw.utt_start();
+    F.carry0 = (R.carry_in != NULL && !C.ms) ? m->carry0.as<uint32_t>() : NULL;
+    F.carry_rows = C.ms ? NULL : R.d_carry_rows;
+    F.utt_off = m->sw.utt_off();
+    F.n_utts = R.n_utts;
+    F.chain_skip = C.chain ? m->sw.utt_start() + m->sw.meta_nw : NULL;
+    F.seg_of_frame = R.act ? R.act->seg_of_frame : NULL;
+    F.seg_cbmask = R.act ? R.act->seg_cbmask : NULL;
+    F.n_fixed = m->sw.d_nfixed;
+    F.n_frames = R.n_frames;
+    F.n_cbf = m->n_cbf;
+    F.n_feat = h->n_feat;
+    F.featdim = h->veclen_total;
+    for (int f = 0; f < h->n_feat; ++f)
+        F.featoff[f] = h->featoff[f];
+}
+
+/* The matrix-core scan of frames [lo, hi) (one wave = 64 frames of one codebook x stream).  The
+ * scan of a piece takes absolute frame numbers (its exact pass may walk back into the piece
+ * before).  Sets F's frame_lo, n_frames, tile_groups, xcd_lo and audit_k. */
+static hipError_t
+launch_scan_mfma(const ScoreCall &C, FramesParams &F, int lo, int hi)
+{
+    ssw_model_s *m = C.m;
+    const Knobs &kn = m->kn;
+    const bool ms = C.ms;
+    const float *d_feats = C.R.d_feats;
+    hipStream_t st = C.st;
+    /* 64-frame steps per wave: one, or -- from 8,192 frames per launch -- two (half the
+     * workgroups and half the LDS fills: +1.2 % at 8,192 frames, +1.3 % at 16,384, +1-2 %
+     * at 65,536).  At 4,096 frames (1,008 workgroups for the chip's 1,280 slots) two steps
+     * gave +2 % on one of the pool's slower boxes and -0.5 % on the faster ones; below
+     * that one step is the faster form (39 against 43 us per call at 2,048 frames).
+     * SSW_MFMA_STEPS = "1" / "2" overrides (PTM instance only) */
+    const int nstep = ms ? 1
+        : kn.mfma_steps != 0 ? kn.mfma_steps
+                             : (hi - lo >= 8192 ? 2 : 1);
+    F.frame_lo = lo;
+    F.n_frames = hi;
+    F.tile_groups = (hi - lo + 256 * nstep - 1) / (256 * nstep);
+    /* the cut into one chunk per XCD (xcd_cut, ssw_xcd_cut.inc) depends on the number of tile
+     * groups only: computed once per shape (round 5: it used to be recomputed on every launch) */
+    const int key = F.tile_groups * 2 + (kn.mfma_balance ? 1 : 0);
+    if (m->sw.xcd_cuts == NULL)
+        m->sw.xcd_cuts = new std::map<int, std::array<int, 10>>();
+    auto it = m->sw.xcd_cuts->find(key);
+    if (it == m->sw.xcd_cuts->end()) {
+        if (m->sw.xcd_cuts->size() > 64)
+            m->sw.xcd_cuts->clear();
+        it = m->sw.xcd_cuts->emplace(key, xcd_cut(m->n_cbf, F.tile_groups, m->h->exlistm,
+                                                  SSW_EXLIST_STRIDE, kn.mfma_balance)).first;
     }
-    if (!ms && (h->cfg.ds != 1 || m->force_exact)) {
-        /* frame down-sampling makes every frame depend on its predecessor: exact chains */
-        int n_chain = (chain ? 1 : n_utts) * m->n_cbf;
-        hipLaunchKernelGGL((ptm_topn_chain_kernel<13, 2, 4>), dim3((n_chain + 3) / 4),
-                           dim3(256), 0, st, P);
-        HIP_OK(hipGetLastError());
-        m->stats[0] = pairs;
-        m->stats_pending = 0;
-    } else {
-        FramesParams F;
-        memset(&F, 0, sizeof(F));
-        F.topn_cw = m->d_topn_cw;
-        F.topn_sc = m->d_topn_sc;
-        F.utt_start = m->d_utt_start;
-        F.carry0 = (carry_in != NULL && !ms) ? m->carry0.as<uint32_t>() : NULL;
-        F.carry_rows = ms ? NULL : d_carry_rows;
-        F.utt_off = m->d_utt_off;
-        F.n_utts = n_utts;
-        F.chain_skip = chain ? m->d_utt_start + m->meta_nw : NULL;
-        F.seg_of_frame = act ? act->seg_of_frame : NULL;
-        F.seg_cbmask = act ? act->seg_cbmask : NULL;
-        F.n_fixed = m->d_nfixed;
-        F.n_frames = n_frames;
-        F.n_cbf = m->n_cbf;
-        F.n_feat = h->n_feat;
-        F.featdim = h->veclen_total;
-        for (int f = 0; f < h->n_feat; ++f)
-            F.featoff[f] = h->featoff[f];
-        /* large batches of either scorer: the scan's multiply-adds go to the matrix cores (one
-         * wave = 64 frames of one codebook x stream; SSW_SCAN=fma keeps the vector-unit scan) */
-        /* (SSW_MFMA_MIN_FRAMES: tuning -- the smallest batch that takes the matrix-core scan;
-         * d_wfrag is NULL on a device that failed the load-time self-test, ssw_host_model.inc) */
-        const bool mfma = m->d_wfrag != NULL && h->n_feat * 13 == h->veclen_total
-            && n_frames >= kn.mfma_min_frames && !kn.scan_fma;
-        /* Large batches go through the two kernels in PIECES of ~16 K frames (round 3): measured
-         * per frame, scan + senone cost 19.7 ns at 4,096 frames per launch (ramp and tail), 16.3
-         * at 16,384, 17.3 at 65,536 and 18.3 at 262,144 -- a piece's top-N block (41 MB) is read
-         * back by its senone launch while the memory-side cache still holds it, a whole batch's
-         * (660 MB at 262,144 frames) is not.  The scan of a piece takes absolute frame numbers
-         * (its exact pass may walk back into the piece before); the senone kernel has no
-         * dependency between frames and gets offset pointers.  SSW_SCORE_PIECE = frames per
-         * piece (a multiple of 256; 0 = never cut). */
-        const int piece = kn.score_piece;
-        const bool pieces = mfma && piece > 0 && n_frames >= 2 * piece;
-        auto launch_scan = [&](int lo, int hi) {
-            /* 64-frame steps per wave: one, or -- from 8,192 frames per launch -- two (half the
-             * workgroups and half the LDS fills: +1.2 % at 8,192 frames, +1.3 % at 16,384, +1-2 %
-             * at 65,536).  At 4,096 frames (1,008 workgroups for the chip's 1,280 slots) two steps
-             * gave +2 % on one of the pool's slower boxes and -0.5 % on the faster ones; below
-             * that one step is the faster form (39 against 43 us per call at 2,048 frames).
-             * SSW_MFMA_STEPS = "1" / "2" overrides (PTM instance only) */
-            const int nstep = ms ? 1
-                : kn.mfma_steps != 0 ? kn.mfma_steps
-                                     : (hi - lo >= 8192 ? 2 : 1);
-            F.frame_lo = lo;
-            F.n_frames = hi;
-            F.tile_groups = (hi - lo + 256 * nstep - 1) / (256 * nstep);
-            /* eight contiguous chunks of (codebook x stream, tile group) pairs, one per XCD,
-             * equal in COST: ~1,400 vector instructions per wave and 64-frame step plus ~45 per
-             * density its codebook leaves to the exact form (SSW_MFMA_BALANCE=0: equal counts).
-             * The cut depends on the number of tile groups only: computed once per shape
-             * (round 5: it used to be recomputed on every launch) */
-            int max_len = 0;
-            {
-                const int key = F.tile_groups * 2 + (kn.mfma_balance ? 1 : 0);
-                if (m->xcd_cuts == NULL)
-                    m->xcd_cuts = new std::map<int, std::array<int, 10>>();
-                auto it = m->xcd_cuts->find(key);
-                if (it == m->xcd_cuts->end()) {
-                    const bool by_cost = kn.mfma_balance;
-                    const int n_pairs = m->n_cbf * F.tile_groups;
-                    std::array<int, 10> cut;
-                    double total = 0.0;
-                    for (int c = 0; c < m->n_cbf; ++c)
-                        total += (1400.0 + (by_cost ? 45.0 * h->exlistm[(size_t)c * SSW_EXLIST_STRIDE] : 0.0))
-                            * F.tile_groups;
-                    double acc = 0.0;
-                    int x = 1;
-                    cut[0] = 0;
-                    for (int c = 0; c < m->n_cbf; ++c) {
-                        const double w = 1400.0
-                            + (by_cost ? 45.0 * h->exlistm[(size_t)c * SSW_EXLIST_STRIDE] : 0.0);
-                        for (int g = 0; g < F.tile_groups; ++g) {
-                            /* the pair goes to the chunk its middle falls into */
-                            while (x < 8 && acc + 0.5 * w >= total * x / 8.0)
-                                cut[x++] = c * F.tile_groups + g;
-                            acc += w;
-                        }
-                    }
-                    while (x <= 8)
-                        cut[x++] = n_pairs;
-                    cut[9] = 0;
-                    for (int k = 0; k < 8; ++k)
-                        if (cut[k + 1] - cut[k] > cut[9])
-                            cut[9] = cut[k + 1] - cut[k];
-                    if (m->xcd_cuts->size() > 64)
-                        m->xcd_cuts->clear();
-                    it = m->xcd_cuts->emplace(key, cut).first;
-                }
-                for (int k = 0; k < 9; ++k)
-                    F.xcd_lo[k] = it->second[k];
-                max_len = it->second[9];
-            }
-            dim3 mgrid((unsigned)(8 * max_len));
-            /* tuning aid: extra (unused) LDS per workgroup caps the workgroups per CU: the kernel
-             * holds 32 KB and 94 VGPRs, i.e. five workgroups per CU; 8192 makes it four */
-            const size_t dyn = (size_t)(kn.mfma_lds_pad > 0 ? kn.mfma_lds_pad : 0);
-            /* SSW_SCAN_AUDIT=k: the AUDIT instances redo every frame of every k-th wave exactly
-             * and count the pairs where a PROVEN scan result differs (ssw_scan_audit_stats) */
-            F.audit_k = kn.scan_audit;
-            /* masked batches (compallsen = no): the instances whose exact pass steps over the frames
-             * a codebook is not scanned in (ssw_k1a_frames.inc, carried_order_masked) */
-            const bool masked = act != NULL && !ms && kn.scan_audit <= 0;
+    for (int k = 0; k < 9; ++k)
+        F.xcd_lo[k] = it->second[k];
+    const int max_len = it->second[9];
+    dim3 mgrid((unsigned)(8 * max_len));
+    /* tuning aid: extra (unused) LDS per workgroup caps the workgroups per CU: the kernel
+     * holds 32 KB and 94 VGPRs, i.e. five workgroups per CU; 8192 makes it four */
+    const size_t dyn = (size_t)(kn.mfma_lds_pad > 0 ? kn.mfma_lds_pad : 0);
+    /* SSW_SCAN_AUDIT=k: the AUDIT instances redo every frame of every k-th wave exactly
+     * and count the pairs where a PROVEN scan result differs (ssw_scan_audit_stats) */
+    F.audit_k = kn.scan_audit;
+    /* masked batches (compallsen = no): the instances whose exact pass steps over the frames
+     * a codebook is not scanned in (ssw_k1a_frames.inc, carried_order_masked) */
+    const bool masked = C.R.act != NULL && !ms && kn.scan_audit <= 0;
 #define SSW_MFMA_LAUNCH(MSV, NS)                                                             \
     if (masked)                                                                              \
         hipLaunchKernelGGL((ptm_topn_mfma_kernel<13, false, NS, false, true>), mgrid, dim3(256), dyn, st, \
@@ -741,86 +502,201 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
     else                                                                                     \
         hipLaunchKernelGGL((ptm_topn_mfma_kernel<13, MSV, NS, false>), mgrid, dim3(256), dyn, st, \
                            m->d_rec28, m->d_wfrag, m->d_recmax, m->d_exlistm, d_feats, F)
-            if (nstep == 2) {
-                SSW_MFMA_LAUNCH(false, 2);
-            } else if (ms) {
-                SSW_MFMA_LAUNCH(true, 1);
-            } else {
-                SSW_MFMA_LAUNCH(false, 1);
-            }
-#undef SSW_MFMA_LAUNCH
-            return hipGetLastError();
-        };
-        if (pieces) {
-            const int n_pieces = (n_frames + piece / 2) / piece; /* the remainder joins a piece */
-            const int len = ((n_frames + n_pieces - 1) / n_pieces + 255) / 256 * 256;
-            for (int lo = 0; lo < n_frames; lo += len) {
-                const int hi = lo + len < n_frames ? lo + len : n_frames;
-                HIP_OK(launch_scan(lo, hi));
-                if (act != NULL) {
-                    HIP_OK(launch_active(lo, hi));
-                } else if (launch_senone(m, scorer, hi - lo, m->d_topn_cw + (size_t)lo * m->n_cbf,
-                                  m->d_topn_sc + (size_t)lo * m->n_cbf,
-                                  cp != NULL ? d_out : d_out + (size_t)lo * h->n_sen,
-                                  hi == n_frames, st, (flags & SSW_SCORE_SHARE_DEVICE) != 0, cp,
-                                  lo) < 0)
-                    return -1;
-            }
-            F.n_frames = n_frames;
-            pieced = true;
-        } else if (mfma)
-            HIP_OK(launch_scan(0, n_frames));
-        F.frame_lo = 0;
-        F.n_frames = n_frames;
-        /* two frames per lane once that still fills the chip with >= 4 waves per SIMD */
-        const bool two = (int64_t)((n_frames + 127) / 128) * m->n_cbf >= 2048;
-        const int fpl = two ? 2 : 1;
-        const int tiles = (n_frames + 64 * fpl - 1) / (64 * fpl);
-        F.tile_groups = (tiles + 3) / 4;
-        dim3 grid((unsigned)((((int64_t)F.tile_groups * m->n_cbf + 7) / 8) * 8));
-        if (mfma)
-            ;
-        else if (two && ms)
-            hipLaunchKernelGGL((ptm_topn_frames_kernel<13, 2, true>), grid, dim3(256), 0, st,
-                               m->d_rec, m->d_recq, m->d_recmax, m->d_exlist, d_feats, F);
-        else if (two && act != NULL)
-            hipLaunchKernelGGL((ptm_topn_frames_kernel<13, 2, false, true>), grid, dim3(256), 0, st,
-                               m->d_rec, m->d_recq, m->d_recmax, m->d_exlist, d_feats, F);
-        else if (two)
-            hipLaunchKernelGGL((ptm_topn_frames_kernel<13, 2, false>), grid, dim3(256), 0, st,
-                               m->d_rec, m->d_recq, m->d_recmax, m->d_exlist, d_feats, F);
-        else if (ms)
-            hipLaunchKernelGGL((ptm_topn_frames_kernel<13, 1, true>), grid, dim3(256), 0, st,
-                               m->d_rec, m->d_recq, m->d_recmax, m->d_exlist, d_feats, F);
-        else if (act != NULL)
-            hipLaunchKernelGGL((ptm_topn_frames_kernel<13, 1, false, true>), grid, dim3(256), 0, st,
-                               m->d_rec, m->d_recq, m->d_recmax, m->d_exlist, d_feats, F);
-        else
-            hipLaunchKernelGGL((ptm_topn_frames_kernel<13, 1, false>), grid, dim3(256), 0, st,
-                               m->d_rec, m->d_recq, m->d_recmax, m->d_exlist, d_feats, F);
-        HIP_OK(hipGetLastError());
-        m->stats_pending = 1;
+    if (nstep == 2) {
+        SSW_MFMA_LAUNCH(false, 2);
+    } else if (ms) {
+        SSW_MFMA_LAUNCH(true, 1);
+    } else {
+        SSW_MFMA_LAUNCH(false, 1);
     }
-    if (m->timing && !pieced)
-        HIP_OK(hipEventRecord(m->ev[1], st));
-    if (pieced)
-        ; /* scan and senone launches of every piece are on the stream */
-    else if (act != NULL) {
-        if (cp != NULL) {
-            ssw_set_error("internal error: compact rows with an active set");
+#undef SSW_MFMA_LAUNCH
+    return hipGetLastError();
+}
+
+/* The vector-unit scan of the whole call (SSW_SCAN=fma, a device that failed the matrix-core
+ * self-test, streams that are not 13-dimensional).  Sets F's frame_lo, n_frames, tile_groups. */
+static hipError_t
+launch_scan_frames(const ScoreCall &C, FramesParams &F)
+{
+    const ssw_model_s *m = C.m;
+    const int n_frames = C.R.n_frames;
+    const bool ms = C.ms, act = C.R.act != NULL;
+    const float *d_feats = C.R.d_feats;
+    hipStream_t st = C.st;
+    F.frame_lo = 0;
+    F.n_frames = n_frames;
+    /* two frames per lane once that still fills the chip with >= 4 waves per SIMD */
+    const bool two = (int64_t)((n_frames + 127) / 128) * m->n_cbf >= 2048;
+    const int fpl = two ? 2 : 1;
+    const int tiles = (n_frames + 64 * fpl - 1) / (64 * fpl);
+    F.tile_groups = (tiles + 3) / 4;
+    dim3 grid((unsigned)((((int64_t)F.tile_groups * m->n_cbf + 7) / 8) * 8));
+#define SSW_FRAMES_LAUNCH(...)                                                               \
+    hipLaunchKernelGGL((ptm_topn_frames_kernel<13, __VA_ARGS__>), grid, dim3(256), 0, st,    \
+                       m->d_rec, m->d_recq, m->d_recmax, m->d_exlist, d_feats, F)
+    if (two && ms)
+        SSW_FRAMES_LAUNCH(2, true);
+    else if (two && act)
+        SSW_FRAMES_LAUNCH(2, false, true);
+    else if (two)
+        SSW_FRAMES_LAUNCH(2, false);
+    else if (ms)
+        SSW_FRAMES_LAUNCH(1, true);
+    else if (act)
+        SSW_FRAMES_LAUNCH(1, false, true);
+    else
+        SSW_FRAMES_LAUNCH(1, false);
+#undef SSW_FRAMES_LAUNCH
+    return hipGetLastError();
+}
+
+/* batches from this many frames take the matrix-core scan.  Rounds 2-3: 2,049, where the bf16
+ * form caught up with the vector-unit scan; the binary16 form of round 4 is ahead at every
+ * size measured -- 256 frames: 15.7 against 27.6 us, 1,024: 17.9 against 30.4, 2,048: 23.2
+ * against 44.4 (DESIGN.md section 5) -- so every batch takes it; SSW_SCAN=fma or a larger
+ * SSW_MFMA_MIN_FRAMES keep the vector-unit scan (tests, A/B) */
+#define SSW_MFMA_MIN_FRAMES_DEFAULT 1
+
+/* The offsets of a batch: utt_off[0 .. n_utts] runs from 0 to n_frames and never falls.  `bad` is
+ * the caller's message for anything but a falling offset.  Reads host memory only. */
+static int
+score_check_batch(const int32_t *utt_off, int32_t n_utts, int32_t n_frames, const char *bad)
+{
+    if (n_frames < 0 || n_utts < 0 || utt_off == NULL || !utt_off_spans(utt_off, n_utts, n_frames)) {
+        ssw_set_error("%s", bad);
+        return -1;
+    }
+    for (int u = 0; u < n_utts; ++u)
+        if (utt_off[u + 1] < utt_off[u]) {
+            ssw_set_error("utterance offsets must be non-decreasing");
             return -1;
         }
-        HIP_OK(launch_active(0, n_frames));
-    } else if (launch_senone(m, scorer, n_frames, m->d_topn_cw, m->d_topn_sc, d_out,
-                             m->stats_pending != 0, st, (flags & SSW_SCORE_SHARE_DEVICE) != 0,
-                             cp, 0) < 0)
+    return 0;
+}
+
+/* carry_in names codewords of the model, and the device has room for a row per utterance
+ * (m->carry0, which score_upload_meta fills) */
+static int
+score_check_carry(const ScoreCall &C)
+{
+    ssw_model_s *m = C.m;
+    const uint32_t *carry_in = C.R.carry_in;
+    for (int i = 0; i < m->n_cbf; ++i)
+        for (int k = 0; k < 4; ++k)
+            if (((carry_in[i] >> (8 * k)) & 0xffu) >= (uint32_t)m->h->n_density) {
+                ssw_set_error("carry_in[%d] names codeword %u of %d", i,
+                              (carry_in[i] >> (8 * k)) & 0xffu, m->h->n_density);
+                return -1;
+            }
+    return devbuf_reserve(m->carry0, sizeof(uint32_t) * (size_t)m->n_cbf * (size_t)C.R.n_utts,
+                          "ssw_score_batch_ex");
+}
+
+/* What the call uploads, on its stream: the carried rows (want_carry: m->carry0, a row per
+ * utterance) and -- when they differ from the last call's -- the offsets, start bits and skip
+ * bits (the meta buffer; m->sw.utt_cache and meta_nw then describe it).  One pinned slot, at most
+ * two copies, the slot's event behind them. */
+static int
+score_upload_meta(const ScoreCall &C, bool want_carry)
+{
+    ssw_model_s *m = C.m;
+    ScoreWs &w = m->sw;
+    const int32_t *utt_off = C.R.utt_off;
+    const int n_utts = C.R.n_utts, n_frames = C.R.n_frames;
+    const bool chain = C.chain;
+    /* the offsets rarely change between calls of one job: upload only when they do
+     * (cache key: the chain flag, then the offsets) */
+    if (w.utt_cache == NULL)
+        w.utt_cache = new std::vector<int32_t>();
+    const bool new_offsets = w.utt_cache->size() != (size_t)n_utts + 2
+        || (*w.utt_cache)[0] != (chain ? 1 : 0)
+        || memcmp(w.utt_cache->data() + 1, utt_off, sizeof(int32_t) * ((size_t)n_utts + 1)) != 0;
+    if (!want_carry && !new_offsets)
+        return 0;
+    /* one pinned slot for everything this call uploads: [carry rows][offsets][starts][skip] */
+    const size_t ncar = want_carry ? (size_t)m->n_cbf * (size_t)n_utts : 0;
+    const size_t nw = ((size_t)n_frames + 31) / 32 + 1;
+    const size_t b_car = sizeof(uint32_t) * ncar;
+    const size_t b_off = new_offsets ? sizeof(int32_t) * ((size_t)n_utts + 1) : 0;
+    const size_t b_bits = new_offsets ? sizeof(uint32_t) * nw : 0;
+    int slot = 0;
+    unsigned char *hs = stage_acquire(m, b_car + sizeof(uint32_t) * w.ws_utts + 2 * b_bits + 64, &slot);
+    if (hs == NULL)
         return -1;
-    if (m->timing && pieced) /* scan and senone launches alternate: no split, ms[0] = the call */
-        HIP_OK(hipEventRecord(m->ev[1], st));
-    if (m->timing) {
-        HIP_OK(hipEventRecord(m->ev[2], st));
-        m->timing_pieced = pieced ? 1 : 0;
+    if (want_carry) {
+        /* [n_utts][n_cbf]: the first utterance starts from carry_in, the others from the
+         * reset history (the chain kernel reads a row per utterance, the scans only row 0) */
+        uint32_t *car = reinterpret_cast<uint32_t *>(hs);
+        for (size_t i = 0; i < ncar; ++i)
+            car[i] = 0x03020100u;
+        memcpy(car, C.R.carry_in, sizeof(uint32_t) * (size_t)m->n_cbf);
+        HIP_OK(hipMemcpyAsync(m->carry0.as<uint32_t>(), car, b_car, hipMemcpyHostToDevice, C.st));
     }
+    if (new_offsets) {
+        w.utt_cache->assign(1, chain ? 1 : 0);
+        w.utt_cache->insert(w.utt_cache->end(), utt_off, utt_off + n_utts + 1);
+        /* staged as it lies on the device: offsets (ws_utts words), start bits, skip bits */
+        int32_t *hoff = reinterpret_cast<int32_t *>(hs + b_car);
+        uint32_t *starts = reinterpret_cast<uint32_t *>(hoff + w.ws_utts);
+        uint32_t *skip = starts + nw;
+        memcpy(hoff, utt_off, b_off);
+        memset(starts, 0, 2 * b_bits);
+        if (chain)
+            starts[0] = 1u;
+        for (int u = 0; u < n_utts; ++u) {
+            if (!chain && utt_off[u] < n_frames)
+                starts[(size_t)utt_off[u] >> 5] |= 1u << (utt_off[u] & 31);
+            if (chain && ((utt_off[u + 1] - utt_off[u]) & 1)) {
+                const int t = utt_off[u + 1] - 1;
+                skip[(size_t)t >> 5] |= 1u << (t & 31);
+            }
+        }
+        w.meta_nw = nw;
+        HIP_OK(hipMemcpyAsync(w.utt_off(), hoff, sizeof(uint32_t) * (w.ws_utts + 2 * nw),
+                              hipMemcpyHostToDevice, C.st));
+    }
+    return stage_release(m, slot, C.st);
+}
+
+/* the senone kernel of frames [lo, hi): over the active sets, or all senones */
+static int
+launch_senone_or_active(const ScoreCall &C, int lo, int hi, bool move_stats)
+{
+    if (C.R.act == NULL)
+        return launch_senone(C, lo, hi, move_stats);
+    HIP_OK(launch_active(C, lo, hi));
+    return 0;
+}
+
+/* Large batches go through the two kernels in PIECES of ~16 K frames (round 3): measured
+ * per frame, scan + senone cost 19.7 ns at 4,096 frames per launch (ramp and tail), 16.3
+ * at 16,384, 17.3 at 65,536 and 18.3 at 262,144 -- a piece's top-N block (41 MB) is read
+ * back by its senone launch while the memory-side cache still holds it, a whole batch's
+ * (660 MB at 262,144 frames) is not.  The scan of a piece takes absolute frame numbers
+ * (its exact pass may walk back into the piece before); the senone kernel has no
+ * dependency between frames and gets offset pointers.  `piece` = SSW_SCORE_PIECE = frames per
+ * piece (a multiple of 256).  Leaves scan and senone launches of every piece on the stream; the
+ * last piece's senone launch moves the exact pass's count. */
+static int
+score_pieces(const ScoreCall &C, FramesParams &F, int piece)
+{
+    const int n_frames = C.R.n_frames;
+    const int n_pieces = (n_frames + piece / 2) / piece; /* the remainder joins a piece */
+    const int len = ((n_frames + n_pieces - 1) / n_pieces + 255) / 256 * 256;
+    for (int lo = 0; lo < n_frames; lo += len) {
+        const int hi = lo + len < n_frames ? lo + len : n_frames;
+        HIP_OK(launch_scan_mfma(C, F, lo, hi));
+        if (launch_senone_or_active(C, lo, hi, hi == n_frames) < 0)
+            return -1;
+    }
+    return 0;
+}
+
+/* development builds (make timeline): the kernels' time stamps to the file SSW_TIMELINE_OUT names;
+ * synchronises the stream */
+static int
+score_timeline_dump(hipStream_t st)
+{
 #if defined(SSW_TIMELINE) || defined(SSW_TIMELINE_SEN)
     if (getenv("SSW_TIMELINE_OUT")) {
         std::vector<unsigned long long> tl(16384 * 6);
@@ -837,8 +713,238 @@ score_batch_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_fra
             fclose(fp);
         }
     }
+#else
+    (void)st;
 #endif
-    return score_batch_finish(m, ms, n_frames, utt_off, n_utts, st, flags, carry_in, carry_out);
+    return 0;
+}
+
+/* What every scoring call ends in, for every scorer family: the counters, what the debug view
+ * may show, and carry_out.
+ *   exact_pairs: the (frame, codebook x stream) pairs the exact form took, counted on the host
+ *     (0, or all of them under the chain kernel); < 0: the scans counted them on the device and
+ *     the senone launch moved the count (ssw_score_batch_stats fetches it)
+ *   history: the family keeps one (PTM, s2_semi); the others hand back the reset order
+ *   topn: the call left a top-N block for ssw_score_batch_topn (all but continuous models)
+ * Reads carry_out from the top-N rows, which makes such a call synchronous. */
+static int
+score_batch_finish(const ScoreCall &C, int64_t exact_pairs, bool history, bool topn)
+{
+    ssw_model_s *m = C.m;
+    const ScoreReq &R = C.R;
+    const int32_t n_frames = R.n_frames, n_utts = R.n_utts;
+    const int32_t *utt_off = R.utt_off;
+    const uint32_t *carry_in = R.carry_in;
+    uint32_t *carry_out = R.carry_out;
+    if (exact_pairs >= 0)
+        m->sw.stats[0] = exact_pairs;
+    m->sw.stats_pending = exact_pairs < 0;
+    m->sw.last_n_frames = topn ? n_frames : 0;
+    m->sw.stats[1] = (int64_t)n_frames * m->n_cbf;
+    if (carry_out == NULL)
+        return 0;
+    if (!history) {
+        for (int i = 0; i < m->n_cbf; ++i)
+            carry_out[i] = 0x03020100u; /* the ms scorer keeps no history */
+        return 0;
+    }
+    /* what the next call starts from.  Default: the last frame's final order (the next call
+     * continues the same utterance).  SSW_SCORE_CARRY_OUT_REWIND: history slot 1 of the
+     * reference's ring, which is what frame 0 of the NEXT utterance -- or of the second pass
+     * after acmod_rewind -- copies (src/ptm_mgau.c:425-437): the final order of the last
+     * odd-numbered frame of the last utterance that has two frames (in a chain; of the last
+     * utterance otherwise), else what that utterance itself started from */
+    long long row = (long long)n_frames - 1;
+    bool from_start = false; /* no frame wrote the slot: carry_in / the reset order */
+    if (R.flags & SSW_SCORE_CARRY_OUT_REWIND) {
+        row = -1;
+        for (int u = n_utts - 1; u >= 0 && row < 0; --u) {
+            const int T = utt_off[u + 1] - utt_off[u];
+            if (T >= 2)
+                row = (long long)utt_off[u] + (T / 2) * 2 - 1;
+            else if (!C.chain) { /* utterances are independent: only the last one counts */
+                from_start = true;
+                for (int i = 0; i < m->n_cbf; ++i)
+                    carry_out[i] = (u == 0 && carry_in != NULL) ? carry_in[i] : 0x03020100u;
+                break;
+            }
+        }
+        if (row < 0 && !from_start) {
+            from_start = true;
+            for (int i = 0; i < m->n_cbf; ++i)
+                carry_out[i] = carry_in != NULL ? carry_in[i] : 0x03020100u;
+        }
+    }
+    if (from_start)
+        return 0;
+    HIP_OK(hipMemcpyAsync(carry_out, C.cw + (size_t)row * m->n_cbf,
+                          sizeof(uint32_t) * (size_t)m->n_cbf, hipMemcpyDeviceToHost, C.st));
+    HIP_OK(hipStreamSynchronize(C.st));
+    return 0;
+}
+
+/* The PTM and ms scorers: a top-N scan (the chain kernel, or the matrix-core or vector-unit scan)
+ * and the senone kernel, as one launch pair or in pieces, with the timing events around them.
+ * P: the batch as fill_chain_params and score_batch_impl describe it. */
+static int
+score_ptm_ms(const ScoreCall &C, const ChainParams &P)
+{
+    ssw_model_s *m = C.m;
+    const ssw_host_model_t *h = m->h;
+    const ScoreReq &R = C.R;
+    const Knobs &kn = m->kn;
+    const int n_frames = R.n_frames;
+    const bool exact = !C.ms && (h->cfg.ds != 1 || m->force_exact);
+    bool pieced = false;
+    if (exact) {
+        HIP_OK(launch_scan_chain(C, P));
+    } else {
+        FramesParams F;
+        fill_frames_params(C, F);
+        /* large batches of either scorer: the scan's multiply-adds go to the matrix cores (one
+         * wave = 64 frames of one codebook x stream; SSW_SCAN=fma keeps the vector-unit scan) */
+        /* (SSW_MFMA_MIN_FRAMES: tuning -- the smallest batch that takes the matrix-core scan;
+         * d_wfrag is NULL on a device that failed the load-time self-test, ssw_host_model.inc) */
+        const bool mfma = m->d_wfrag != NULL && h->n_feat * 13 == h->veclen_total
+            && n_frames >= kn.mfma_min_frames && !kn.scan_fma;
+        /* (SSW_SCORE_PIECE = 0: never cut) */
+        pieced = mfma && kn.score_piece > 0 && n_frames >= 2 * kn.score_piece;
+        if (pieced) {
+            if (score_pieces(C, F, kn.score_piece) < 0)
+                return -1;
+        } else if (mfma)
+            HIP_OK(launch_scan_mfma(C, F, 0, n_frames));
+        else
+            HIP_OK(launch_scan_frames(C, F));
+    }
+    if (m->sw.timing && !pieced)
+        HIP_OK(hipEventRecord(m->sw.ev[1], C.st));
+    if (!pieced) { /* (else scan and senone launches of every piece are on the stream) */
+        if (R.act != NULL && R.cp != NULL) {
+            ssw_set_error("internal error: compact rows with an active set");
+            return -1;
+        }
+        if (launch_senone_or_active(C, 0, n_frames, !exact) < 0)
+            return -1;
+    }
+    if (m->sw.timing && pieced) /* scan and senone launches alternate: no split, ms[0] = the call */
+        HIP_OK(hipEventRecord(m->sw.ev[1], C.st));
+    if (m->sw.timing) {
+        HIP_OK(hipEventRecord(m->sw.ev[2], C.st));
+        m->sw.timing_pieced = pieced ? 1 : 0;
+    }
+    if (score_timeline_dump(C.st) < 0)
+        return -1;
+    return score_batch_finish(C, exact ? (int64_t)n_frames * m->n_cbf : -1, !C.ms, true);
+}
+
+/* Every scoring entry point ends here: check, pick the scorer family, call its steps, finish. */
+static int
+score_batch_impl(ssw_model_t *m, const ScoreReq &R)
+{
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return -1;
+    refresh_knobs(m); /* tests: knobs flipped between calls on one model */
+    if (R.carry_out != NULL && (R.n_frames == 0 || R.n_utts == 0)) { /* nothing scored: state unchanged */
+        for (int i = 0; i < m->n_cbf; ++i)
+            R.carry_out[i] = R.carry_in ? R.carry_in[i] : 0x03020100u;
+    }
+    if (R.n_frames == 0 || R.n_utts == 0)
+        return 0;
+    if (score_check_batch(R.utt_off, R.n_utts, R.n_frames, "bad utterance offsets") < 0
+        || check_scorer_shape(m, R.scorer) < 0)
+        return -1;
+    if (R.act != NULL && (m->h->cfg.ds != 1 || m->force_exact)) { /* (before anything is launched) */
+        ssw_set_error("active-set batches: ds = 1 only");
+        return -1;
+    }
+    HIP_OK(hipSetDevice(m->device));
+    const bool ms = R.scorer == SSW_SCORER_MS;
+    ScoreCall C{ m, R, (hipStream_t)R.stream, ms, (R.flags & SSW_SCORE_CARRY_UTTS) != 0 && !ms, NULL, NULL };
+    if (m->h->continuous) {
+        /* no history, no utterance boundaries, none of the PTM scan's workspaces: its own two
+         * kernels (ssw_host_cont.inc); flags, carry_in and ds are ignored as for ms */
+        if (R.act != NULL || R.cp != NULL) {
+            ssw_set_error("internal error: active sets or compact rows with a continuous model");
+            return -1;
+        }
+        if (m->sw.timing) {
+            HIP_OK(hipEventRecord(m->sw.ev[0], C.st));
+            m->sw.timing_semi = 0;
+        }
+        if (cont_launch(m, R.d_feats, R.n_frames, R.d_out, C.st) < 0)
+            return -1;
+        /* (no top-N block: ssw_score_batch_topn has nothing to show) */
+        return score_batch_finish(C, 0, false, false);
+    }
+    if (ensure_score_ws(m, (size_t)R.topn_row0 + (size_t)R.n_frames, R.n_utts) < 0)
+        return -1;
+    C.cw = m->sw.cw() + (size_t)R.topn_row0 * m->n_cbf;
+    C.sc = m->sw.sc() + (size_t)R.topn_row0 * m->n_cbf;
+    /* a caller that moves from one stream to another: the uploads below are only ordered behind
+     * the launches of THIS stream */
+    if (m->sw.have_last_stream && m->sw.last_stream != C.st)
+        HIP_OK(hipDeviceSynchronize()); /* (not the old stream itself: it may be gone) */
+    m->sw.last_stream = C.st;
+    m->sw.have_last_stream = 1;
+    const bool want_carry = R.carry_in != NULL && !ms;
+    if (want_carry && score_check_carry(C) < 0)
+        return -1;
+    if (score_upload_meta(C, want_carry) < 0)
+        return -1;
+    ChainParams P;
+    fill_chain_params(m, P, R.d_feats);
+    P.topn_cw = C.cw;
+    P.topn_sc = C.sc;
+    P.n_utts = R.n_utts;
+    P.n_frames = R.n_frames;
+    P.chain_utts = C.chain ? 1 : 0;
+    P.frame_base = R.frame_base;
+    P.carry_pk = want_carry ? m->carry0.as<uint32_t>() : NULL;
+    if (R.d_carry_rows != NULL && !ms) /* a row per utterance, already on the device */
+        P.carry_pk = R.d_carry_rows;
+    if (m->sw.timing) {
+        HIP_OK(hipEventRecord(m->sw.ev[0], C.st));
+        m->sw.timing_semi = R.scorer == SSW_SCORER_S2_SEMI;
+    }
+    if (R.scorer != SSW_SCORER_S2_SEMI)
+        return score_ptm_ms(C, P);
+    /* the same batch, history and carry semantics; its own three kernels (ssw_host_semi.inc) */
+    if (R.act != NULL || R.cp != NULL) {
+        ssw_set_error("internal error: active sets or compact rows with the s2_semi scorer");
+        return -1;
+    }
+    if (semi_launch(m, P, R.d_out, C.st) < 0)
+        return -1;
+    return score_batch_finish(C, 0, true, true);
+}
+
+extern "C" int
+ssw_score_batch(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
+                const int32_t *utt_off, int32_t n_utts, int16_t *d_out, void *stream)
+{
+    return ssw_score_batch_ex(m, scorer, d_feats, n_frames, utt_off, n_utts, d_out, stream, 0u, NULL,
+                              NULL);
+}
+
+extern "C" int
+ssw_score_batch_ex(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
+                   const int32_t *utt_off, int32_t n_utts, int16_t *d_out, void *stream,
+                   uint32_t flags, const uint32_t *carry_in, uint32_t *carry_out)
+{
+    ScoreReq R{};
+    R.scorer = scorer;
+    R.d_feats = d_feats;
+    R.n_frames = n_frames;
+    R.utt_off = utt_off;
+    R.n_utts = n_utts;
+    R.d_out = d_out;
+    R.stream = stream;
+    R.flags = flags;
+    R.carry_in = carry_in;
+    R.carry_out = carry_out;
+    return score_batch_impl(m, R);
 }
 
 /* Measurement aid (DESIGN.md section 7, the first pass in the default configuration): `reps`
@@ -851,8 +957,7 @@ ssw_debug_score_loop(ssw_model_t *m, int scorer, const float *d_feats, int32_t n
                      void *stream)
 {
     for (int r = 0; r < reps; ++r)
-        if (score_batch_impl(m, scorer, d_feats, n_frames, utt_off, n_utts, d_out, stream, 0u, NULL,
-                             NULL) < 0)
+        if (ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, d_out, stream) < 0)
             return -1;
     HIP_OK(hipStreamSynchronize((hipStream_t)stream));
     return 0;
@@ -954,16 +1059,12 @@ ssw_score_batch_host(ssw_model_t *m, int scorer, const float *feats, int32_t n_f
         return 0;
     if (check_scorer_shape(m, scorer) < 0)
         return -1;
-    if (feats == NULL || out == NULL || utt_off == NULL || n_utts <= 0 || utt_off[0] != 0
-        || utt_off[n_utts] != n_frames) {
+    if (feats == NULL || out == NULL || n_utts <= 0) {
         ssw_set_error("ssw_score_batch_host: bad arguments");
         return -1;
     }
-    for (int u = 0; u < n_utts; ++u)
-        if (utt_off[u + 1] < utt_off[u]) {
-            ssw_set_error("utterance offsets must be non-decreasing");
-            return -1;
-        }
+    if (score_check_batch(utt_off, n_utts, n_frames, "ssw_score_batch_host: bad arguments") < 0)
+        return -1;
     HIP_OK(hipSetDevice(m->device));
     refresh_knobs(m);
     /* sub-batches: whole utterances, closed once they hold SSW_HOST_PIPE_FRAMES frames; an
@@ -1012,26 +1113,21 @@ ssw_score_batch_host(ssw_model_t *m, int scorer, const float *feats, int32_t n_f
     const int n_sub = (int)subs.size();
     std::vector<int32_t> off;
     /* the top-N workspace holds the WHOLE call (the debug view ssw_score_batch_topn speaks of
-     * the last call): every sub-batch scores into its own stretch of it */
-    if (!h->continuous && ensure_score_ws(m, n_frames, n_utts) < 0)
+     * the last call): every sub-batch scores into its own stretch of it (ScoreReq::topn_row0),
+     * reserved here, so that no sub-batch grows it */
+    if (!h->continuous && ensure_score_ws(m, (size_t)n_frames, n_utts) < 0)
         return -1;
-    uint32_t *const topn_cw0 = m->d_topn_cw;
-    int4 *const topn_sc0 = m->d_topn_sc;
     struct Restore {
         ssw_model_s *m;
-        uint32_t *cw;
-        int4 *sc;
         int total;
         ~Restore()
         {
-            m->d_topn_cw = cw;
-            m->d_topn_sc = sc;
-            m->last_n_frames = total;
-            m->stats_accumulate = 0; /* (also on the early returns: the next call counts afresh) */
+            m->sw.last_n_frames = total;
+            m->sw.stats_accumulate = 0; /* (also on the early returns: the next call counts afresh) */
         }
-    } restore_{ m, topn_cw0, topn_sc0, n_frames };
+    } restore_{ m, n_frames };
     int64_t sum_flagged = 0, sum_pairs = 0; /* ssw_score_batch_stats speaks of the whole call */
-    m->stats_accumulate = 0;
+    m->sw.stats_accumulate = 0;
     auto land = [&](int k) -> int { /* stage 3 of sub-batch k: pinned staging -> the caller's rows */
         const int slot = k & 1;
         const int f0 = subs[(size_t)k].f0, f1 = subs[(size_t)k].f1;
@@ -1054,26 +1150,27 @@ ssw_score_batch_host(ssw_model_t *m, int scorer, const float *feats, int32_t n_f
                                   hipMemcpyHostToDevice, m->s_pipe));
             /* the device rows of this slot were downloaded by sub-batch k - 2 */
             HIP_OK(hipStreamWaitEvent(m->s_pipe, m->ev_down[slot], 0));
-            if (!h->continuous) {
-                m->d_topn_cw = topn_cw0 + (size_t)f0 * m->n_cbf;
-                m->d_topn_sc = topn_sc0 + (size_t)f0 * m->n_cbf;
-            }
+            ScoreReq R{};
+            R.scorer = scorer;
+            R.d_feats = m->d_pipe_feat[slot];
+            R.n_frames = nf;
+            R.utt_off = off.data();
+            R.n_utts = u1 - u0;
+            R.d_out = m->d_pipe_out[slot];
+            R.stream = m->s_pipe;
             /* (carry_out makes the piece's call synchronous: a long utterance's pieces do not
              * overlap their scoring with the copies -- they are 16 K frames each) */
-            const int rc = score_batch_impl(m, scorer, m->d_pipe_feat[slot], nf, off.data(), u1 - u0,
-                                            m->d_pipe_out[slot], m->s_pipe, 0u,
-                                            S.cont ? carry.data() : NULL, S.more ? carry.data() : NULL,
-                                            NULL, NULL, NULL,
-                                            /* a continuing piece keeps its utterance's frame
-                                             * numbers (the ds phase); grouped utterances start at 0 */
-                                            S.cont ? f0 - utt_off[u0] : 0);
-            m->d_topn_cw = topn_cw0;
-            m->d_topn_sc = topn_sc0;
-            if (rc < 0)
+            R.carry_in = S.cont ? carry.data() : NULL;
+            R.carry_out = S.more ? carry.data() : NULL;
+            /* a continuing piece keeps its utterance's frame numbers (the ds phase); grouped
+             * utterances start at 0 */
+            R.frame_base = S.cont ? f0 - utt_off[u0] : 0;
+            R.topn_row0 = f0;
+            if (score_batch_impl(m, R) < 0)
                 return -1;
-            sum_pairs += m->stats[1];
-            sum_flagged += m->stats_pending ? 0 : m->stats[0]; /* (the chain kernel: counted on the host) */
-            m->stats_accumulate = 1; /* the next sub-batch's count joins this one's on the device */
+            sum_pairs += m->sw.stats[1];
+            sum_flagged += m->sw.stats_pending ? 0 : m->sw.stats[0]; /* (the chain kernel: counted on the host) */
+            m->sw.stats_accumulate = 1; /* the next sub-batch's count joins this one's on the device */
             HIP_OK(hipEventRecord(m->ev_piece[slot], m->s_pipe));
             HIP_OK(hipStreamWaitEvent(m->s_copy, m->ev_piece[slot], 0));
             HIP_OK(hipMemcpyAsync(m->h_pipe_out[slot], m->d_pipe_out[slot], (size_t)nf * row_out,
@@ -1083,13 +1180,13 @@ ssw_score_batch_host(ssw_model_t *m, int scorer, const float *feats, int32_t n_f
         if (k > 0 && land(k - 1) < 0)
             return -1;
     }
-    m->stats_accumulate = 0;
+    m->sw.stats_accumulate = 0;
     if (land(n_sub - 1) < 0)
         return -1;
     HIP_OK(hipStreamSynchronize(m->s_pipe));
-    m->stats[1] = sum_pairs;
-    if (!m->stats_pending)
-        m->stats[0] = sum_flagged;
+    m->sw.stats[1] = sum_pairs;
+    if (!m->sw.stats_pending)
+        m->sw.stats[0] = sum_flagged;
     return 0;
 }
 
@@ -1101,14 +1198,14 @@ ssw_score_batch_topn(ssw_model_t *m, int32_t n_frames, uint8_t *cw, int32_t *sco
         return -1;
     if (cont_refuse(m, "ssw_score_batch_topn") < 0)
         return -1;
-    if (n_frames > m->last_n_frames) {
-        ssw_set_error("only %d frames were scored", m->last_n_frames);
+    if (n_frames > m->sw.last_n_frames) {
+        ssw_set_error("only %d frames were scored", m->sw.last_n_frames);
         return -1;
     }
     HIP_OK(hipSetDevice(m->device));
     HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(cw, m->d_topn_cw, (size_t)n_frames * m->n_cbf * 4, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(score, m->d_topn_sc, (size_t)n_frames * m->n_cbf * 16,
+    HIP_OK(hipMemcpy(cw, m->sw.cw(), (size_t)n_frames * m->n_cbf * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(score, m->sw.sc(), (size_t)n_frames * m->n_cbf * 16,
                      hipMemcpyDeviceToHost));
     return 0;
 }
@@ -1117,16 +1214,16 @@ extern "C" int
 ssw_set_kernel_timing(ssw_model_t *m, int enable)
 {
     HIP_OK(hipSetDevice(m->device));
-    if (enable && !m->timing) {
+    if (enable && !m->sw.timing) {
         for (int i = 0; i < 3; ++i)
-            HIP_OK(hipEventCreate(&m->ev[i]));
-        HIP_OK(hipEventCreate(&m->ev_sc));
-        m->timing = 1;
-    } else if (!enable && m->timing) {
+            HIP_OK(hipEventCreate(&m->sw.ev[i]));
+        HIP_OK(hipEventCreate(&m->sw.ev_sc));
+        m->sw.timing = 1;
+    } else if (!enable && m->sw.timing) {
         for (int i = 0; i < 3; ++i)
-            (void)hipEventDestroy(m->ev[i]);
-        (void)hipEventDestroy(m->ev_sc);
-        m->timing = 0;
+            (void)hipEventDestroy(m->sw.ev[i]);
+        (void)hipEventDestroy(m->sw.ev_sc);
+        m->sw.timing = 0;
     }
     return 0;
 }
@@ -1134,23 +1231,23 @@ ssw_set_kernel_timing(ssw_model_t *m, int enable)
 extern "C" int
 ssw_get_kernel_timing(ssw_model_t *m, float *ms, int n)
 {
-    if (!m->timing) {
+    if (!m->sw.timing) {
         ssw_set_error("kernel timing is off");
         return -1;
     }
-    HIP_OK(hipEventSynchronize(m->ev[2]));
-    if (m->timing_pieced) { /* one number: the whole call (scan and senone launches alternate) */
+    HIP_OK(hipEventSynchronize(m->sw.ev[2]));
+    if (m->sw.timing_pieced) { /* one number: the whole call (scan and senone launches alternate) */
         if (n >= 1)
-            HIP_OK(hipEventElapsedTime(&ms[0], m->ev[0], m->ev[2]));
+            HIP_OK(hipEventElapsedTime(&ms[0], m->sw.ev[0], m->sw.ev[2]));
         if (n >= 2)
             ms[1] = 0.0f;
         return n >= 1 ? 1 : 0;
     }
     int k = 0;
     for (; k < 2 && k < n; ++k)
-        HIP_OK(hipEventElapsedTime(&ms[k], m->ev[k], m->ev[k + 1]));
-    if (m->timing_semi && n >= 3) { /* the s2_semi scorer: the chain kernel's share of ms[0] */
-        HIP_OK(hipEventElapsedTime(&ms[2], m->ev_sc, m->ev[1]));
+        HIP_OK(hipEventElapsedTime(&ms[k], m->sw.ev[k], m->sw.ev[k + 1]));
+    if (m->sw.timing_semi && n >= 3) { /* the s2_semi scorer: the chain kernel's share of ms[0] */
+        HIP_OK(hipEventElapsedTime(&ms[2], m->sw.ev_sc, m->sw.ev[1]));
         k = 3;
     }
     return k;
@@ -1159,16 +1256,16 @@ ssw_get_kernel_timing(ssw_model_t *m, float *ms, int n)
 extern "C" int
 ssw_score_batch_stats(ssw_model_t *m, int64_t stats[2])
 {
-    if (m->stats_pending) {
+    if (m->sw.stats_pending) {
         unsigned long long n = 0;
         HIP_OK(hipSetDevice(m->device));
         HIP_OK(hipDeviceSynchronize());
-        HIP_OK(hipMemcpy(&n, m->d_nfixed + 1, sizeof(n), hipMemcpyDeviceToHost));
-        m->stats[0] = (int64_t)n; /* moved there by the last batch's senone kernel */
-        m->stats_pending = 0;
+        HIP_OK(hipMemcpy(&n, m->sw.d_nfixed + 1, sizeof(n), hipMemcpyDeviceToHost));
+        m->sw.stats[0] = (int64_t)n; /* moved there by the last batch's senone kernel */
+        m->sw.stats_pending = 0;
     }
-    stats[0] = m->stats[0];
-    stats[1] = m->stats[1];
+    stats[0] = m->sw.stats[0];
+    stats[1] = m->sw.stats[1];
     return 0;
 }
 
@@ -1180,12 +1277,12 @@ extern "C" int
 ssw_scan_audit_stats(ssw_model_t *m, int64_t stats[2])
 {
     stats[0] = stats[1] = 0;
-    if (m->device == SSW_DEVICE_NONE || m->d_nfixed == NULL)
+    if (m->device == SSW_DEVICE_NONE || m->sw.d_nfixed == NULL)
         return 0;
     unsigned long long n[2] = { 0, 0 };
     HIP_OK(hipSetDevice(m->device));
     HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(n, m->d_nfixed + 2, sizeof(n), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(n, m->sw.d_nfixed + 2, sizeof(n), hipMemcpyDeviceToHost));
     stats[0] = (int64_t)n[0];
     stats[1] = (int64_t)n[1];
     return 0;

@@ -95,8 +95,8 @@ semi_launch(ssw_model_s *m, const ChainParams &C, int16_t *d_out, hipStream_t st
     }
     hipLaunchKernelGGL(semi_density_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, P);
     HIP_OK(hipGetLastError());
-    if (m->timing)
-        HIP_OK(hipEventRecord(m->ev_sc, st));
+    if (m->sw.timing)
+        HIP_OK(hipEventRecord(m->sw.ev_sc, st));
     const dim3 chains((unsigned)((C.chain_utts ? 1 : C.n_utts) * h->n_feat));
     switch (P.topn) {
     case 1: hipLaunchKernelGGL(semi_chain_kernel<1>, chains, dim3(64), 0, st, P); break;
@@ -105,13 +105,13 @@ semi_launch(ssw_model_s *m, const ChainParams &C, int16_t *d_out, hipStream_t st
     default: hipLaunchKernelGGL(semi_chain_kernel<4>, chains, dim3(64), 0, st, P); break;
     }
     HIP_OK(hipGetLastError());
-    if (m->timing)
-        HIP_OK(hipEventRecord(m->ev[1], st));
+    if (m->sw.timing)
+        HIP_OK(hipEventRecord(m->sw.ev[1], st));
     hipLaunchKernelGGL(semi_senone_kernel, dim3((unsigned)sen_blocks), dim3(256), 0, st, P);
     HIP_OK(hipGetLastError());
-    if (m->timing) {
-        HIP_OK(hipEventRecord(m->ev[2], st));
-        m->timing_pieced = 0;
+    if (m->sw.timing) {
+        HIP_OK(hipEventRecord(m->sw.ev[2], st));
+        m->sw.timing_pieced = 0;
     }
     return 0;
 }

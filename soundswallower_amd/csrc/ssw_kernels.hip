@@ -70,6 +70,8 @@
  *   ssw_ws_layout.inc    host, no HIP: align256 and WsLayout, the one layout of a device
  *                        workspace (256-byte-aligned offsets in call order, the uploaded pieces
  *                        staged by fill(); a host program can include it on its own)
+ *   ssw_xcd_cut.inc      host, no HIP: xcd_cut, the matrix-core scan's (codebook x stream, tile
+ *                        group) pairs cut into eight chunks of equal cost, one per XCD
  *   ssw_host_model.inc   also the host side's three shared helpers, each holding one policy:
  *                        devbuf_reserve (the grow-only device buffer: no HIP call unless it
  *                        grows, hipFree's implicit synchronisation, sticky error cleared),
@@ -138,6 +140,7 @@ namespace {
 } // namespace
 
 #include "ssw_ws_layout.inc"
+#include "ssw_xcd_cut.inc"
 #include "ssw_feat_tiles.inc"
 #include "ssw_host_model.inc"
 #include "ssw_host_semi.inc"
