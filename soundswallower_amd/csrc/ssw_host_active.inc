@@ -287,24 +287,15 @@ align_batch_active_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_
     }
     HIP_OK(hipSetDevice(m->device));
     const int n_frames = frame_off[n_utts];
-    /* slot of every senone (the device table's host twin, rebuilt here: a few K entries) */
-    std::vector<uint16_t> sen_slot((size_t)h->n_sen, 0);
-    {
-        std::vector<int> next((size_t)h->n_cb + 1, 0);
-        for (int i = 0; i < h->n_sen; ++i)
-            ++next[(size_t)h->sen2cb[i] + 1];
-        for (int c = 0; c < h->n_cb; ++c) /* groups padded to a multiple of 4 slots */
-            next[(size_t)c + 1] = next[(size_t)c] + ((next[(size_t)c + 1] + 3) & ~3);
-        for (int i = 0; i < h->n_sen; ++i)
-            sen_slot[(size_t)i] = (uint16_t)next[(size_t)h->sen2cb[i]]++;
-    }
+    /* slot of every senone: the device table's host twin (upload_model) */
+    const uint16_t *sen_slot = m->h_sen_slot;
     /* segments (runs of frames that share their active set), utterance by utterance on the
      * host threads, then laid end to end */
     std::vector<ActiveUtt> per_utt((size_t)n_utts);
     {
         ActiveJob J;
         J.h = h;
-        J.sen_slot = sen_slot.data();
+        J.sen_slot = sen_slot;
         J.n_utts = n_utts;
         J.frame_off = frame_off;
         J.phone_off = phone_off;

@@ -14,6 +14,8 @@ struct Knobs {
     int sen_r;            /* SSW_SEN_R: 1..4; 0 = by model */
     int sen_groups;       /* SSW_SEN_GROUPS: > 0 groups, 0 = one per unit; -1 = by device */
     bool sen_generic;     /* SSW_SEN_GENERIC: run-time stream count instances */
+    bool slot_dense;      /* SSW_SLOT_LAYOUT=dense: the dense slot layout whatever the model (read
+                             when the model is uploaded: tests, A/B; ssw_slot_layout.inc) */
     bool ms_senone_old;   /* SSW_MS_SENONE=old */
     bool scan_fma;        /* SSW_SCAN=fma: the vector-unit scan */
     int mfma_min_frames;  /* SSW_MFMA_MIN_FRAMES */
@@ -76,6 +78,7 @@ load_knobs(Knobs &k)
     e = getenv("SSW_SEN_GROUPS");
     k.sen_groups = e != NULL ? (atoi(e) > 0 ? atoi(e) : 0) : -1;
     k.sen_generic = getenv("SSW_SEN_GENERIC") != NULL;
+    k.slot_dense = env_is("SSW_SLOT_LAYOUT", "dense");
     k.ms_senone_old = env_is("SSW_MS_SENONE", "old");
     k.scan_fma = env_is("SSW_SCAN", "fma");
     k.mfma_min_frames = env_int("SSW_MFMA_MIN_FRAMES", 1);
@@ -205,8 +208,12 @@ struct ssw_model_s {
     int n_exact_form;
     uint8_t *d_mixw, *d_ms_pdf, *d_sen2cb, *d_logadd8, *d_logadd_mirror, *d_tp, *d_quad_cb;
     short4 *d_slot_sen;
-    uint32_t *d_quad_info; /* per quad: first senone id | (4 consecutive ids) << 16 | codebook << 24 */
+    /* per quad: first senone id | (4 consecutive ids) << 16 | n << 17 (its first n slots hold n
+     * consecutive ids, padding behind them; 0 = not of that form) | codebook << 24 */
+    uint32_t *d_quad_info;
     uint16_t *d_sen_slot;  /* slot of every senone in d_mixw's slot order */
+    uint16_t *h_sen_slot;  /* its host twin (ssw_align_batch_active builds its lists from it) */
+    int slot_prefix;       /* the slot layout in use: 1 = prefix runs, 0 = dense (ssw_slot_layout.inc) */
     DevBuf act_ws; /* ssw_align_batch_active: segments, lists, scores */
     int n_quads, slot_stride;
     int logadd_max; /* the largest log-add entry (upload_model) */
@@ -571,28 +578,30 @@ upload_model(ssw_model_s *m)
         HIP_OK(hipMemcpy(m->d_sen2cb, s2c.data(), s2c.size(), hipMemcpyHostToDevice));
     }
     if ((h->ptm_mixw || h->ms_pdf) && h->sc_rec == NULL && h->cont_rec == NULL) {
-        /* slot order: senones grouped by codebook (ascending id inside a group), every group
-         * padded to a multiple of 4 slots */
-        std::vector<int16_t> slot_sen;
-        std::vector<uint8_t> quad_cb;
-        for (int c = 0; c < h->n_cb; ++c) {
-            size_t start = slot_sen.size();
-            for (int i = 0; i < h->n_sen; ++i)
-                if (h->sen2cb[i] == c)
-                    slot_sen.push_back((int16_t)i);
-            while ((slot_sen.size() - start) % 4)
-                slot_sen.push_back(-1);
-            for (size_t q = start / 4; q < slot_sen.size() / 4; ++q)
-                quad_cb.push_back((uint8_t)c);
+        /* slot order: senones grouped by codebook (ascending id inside a group), every run of
+         * consecutive ids padded to a multiple of 4 slots -- or, for a model whose ids are so
+         * scattered that this would cost the senone kernels a larger workgroup, and with
+         * SSW_SLOT_LAYOUT=dense, every group padded at its end only (ssw_slot_layout.inc) */
+        SlotLayout lay = slot_layout(h->sen2cb, h->n_sen, h->n_cb, false);
+        m->slot_prefix = 0;
+        if (!m->kn.slot_dense) {
+            SlotLayout pre = slot_layout(h->sen2cb, h->n_sen, h->n_cb, true);
+            if (slot_layout_prefix_fits((int)lay.quad_cb.size(), (int)pre.quad_cb.size(),
+                                        SEN_MAX_THREADS)) {
+                lay = std::move(pre);
+                m->slot_prefix = 1;
+            }
         }
+        const std::vector<int16_t> &slot_sen = lay.slot_sen;
+        const std::vector<uint8_t> &quad_cb = lay.quad_cb;
         m->n_quads = (int)quad_cb.size();
         m->slot_stride = ((int)slot_sen.size() + 127) & ~127;
         m->sen_stride = m->slot_stride;
         const size_t rows = (size_t)h->n_feat * h->n_density;
         if (h->ptm_mixw) {
             /* padding slots repeat the weights of their quad's first slot (always a senone:
-             * groups are padded at the end), so that ptm_senone_kernel can take the frame's
-             * best score over all slots without testing for padding */
+             * padding only ever follows a senone, in both layouts), so that ptm_senone_kernel
+             * can take the frame's best score over all slots without testing for padding */
             std::vector<uint8_t> mw(rows * m->slot_stride, 0);
             for (size_t r = 0; r < rows; ++r)
                 for (size_t sl = 0; sl < slot_sen.size(); ++sl) {
@@ -619,11 +628,9 @@ upload_model(ssw_model_s *m)
         {
             std::vector<uint32_t> qi(quad_cb.size());
             for (size_t q = 0; q < qi.size(); ++q) {
-                const int16_t *sj = &slot_sen[4 * q];
-                const bool run4 = sj[0] >= 0 && sj[1] == sj[0] + 1 && sj[2] == sj[0] + 2
-                    && sj[3] == sj[0] + 3;
-                qi[q] = ((uint32_t)sj[0] & 0xffffu) | ((uint32_t)run4 << 16)
-                    | ((uint32_t)quad_cb[q] << 24);
+                const uint32_t n = lay.quad_n[q];
+                qi[q] = ((uint32_t)lay.quad_s0[q] & 0xffffu) | ((uint32_t)(n == 4) << 16)
+                    | (n << 17) | ((uint32_t)quad_cb[q] << 24);
             }
             HIP_OK(hipMalloc((void **)&m->d_quad_info, qi.size() * sizeof(uint32_t)));
             HIP_OK(hipMemcpy(m->d_quad_info, qi.data(), qi.size() * sizeof(uint32_t),
@@ -639,6 +646,12 @@ upload_model(ssw_model_s *m)
             HIP_OK(hipMalloc((void **)&m->d_sen_slot, sen_slot.size() * sizeof(uint16_t) + 16));
             HIP_OK(hipMemcpy(m->d_sen_slot, sen_slot.data(), sen_slot.size() * sizeof(uint16_t),
                              hipMemcpyHostToDevice));
+            m->h_sen_slot = (uint16_t *)malloc(sen_slot.size() * sizeof(uint16_t));
+            if (m->h_sen_slot == NULL) {
+                ssw_set_error("out of memory");
+                return -1;
+            }
+            memcpy(m->h_sen_slot, sen_slot.data(), sen_slot.size() * sizeof(uint16_t));
         }
         HIP_OK(hipMalloc((void **)&m->d_slot_sen, slot_sen.size() * sizeof(int16_t)));
         HIP_OK(hipMemcpy(m->d_slot_sen, slot_sen.data(), slot_sen.size() * sizeof(int16_t),
@@ -825,6 +838,7 @@ ssw_model_free(ssw_model_t *m)
         for (int i = 0; i < 4; ++i)
             (void)hipEventDestroy(m->fe_ev[i]);
     (void)hipFree(m->d_sen_slot);
+    free(m->h_sen_slot);
     (void)hipFree(m->act_ws.p);
     (void)hipFree(m->d_mixw);
     (void)hipFree(m->d_ms_pdf);

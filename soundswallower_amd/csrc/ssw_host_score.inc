@@ -222,21 +222,17 @@ launch_senone(const ScoreCall &C, int lo, int hi, bool move_stats)
     if (kn.sen_fpb != 0 && n_frames >= 4 * 512)
         fpb = kn.sen_fpb;
     size_t lds = 0; /* set once fpb is final */
-    int R = (m->n_quads + SEN_MAX_THREADS - 1) / SEN_MAX_THREADS;
     const bool ms_packed = !ptm && ms_takes_packed_kernel(m, n_frames);
     if (cp != NULL && !ptm && !ms_packed) {
         ssw_set_error("internal error: compact rows asked of the un-packed ms senone kernel");
         return -1;
     }
-    if ((ptm || ms_packed) && fpb == 2 && R < 4) { /* about seven waves per group */
-        const int r7 = (m->n_quads + 447) / 448;
-        R = r7 > R ? (r7 > 4 ? 4 : r7) : R;
-    }
-    if (kn.sen_r != 0)
-        R = kn.sen_r;
-    int threads = ((m->n_quads + R - 1) / R + 63) & ~63;
-    if (threads < 256)
-        threads = 256; /* the prologue copies the 256-entry table with the first 256 threads */
+    /* (about seven waves per group at two frames; at least 256 threads: the prologue copies the
+     * 256-entry table with the first 256 -- senone_shape, ssw_slot_layout.inc, which the choice of
+     * the slot layout evaluates as well) */
+    const SenoneShape shape = senone_shape(m->n_quads, fpb, ptm || ms_packed, kn.sen_r,
+                                           SEN_MAX_THREADS);
+    const int R = shape.R, threads = shape.threads;
     if (threads > SEN_MAX_THREADS || (scorer == SSW_SCORER_MS && threads < m->n_cbf)) {
         ssw_set_error("unsupported senone/codebook shape (%d quads, %d codebook x stream)",
                       m->n_quads, m->n_cbf);
@@ -275,7 +271,7 @@ launch_senone(const ScoreCall &C, int lo, int hi, bool move_stats)
         + 3 * 4 * (size_t)(ms_packed ? ((h->n_cb + 7) & ~7) : SSW_MAX_FEAT) * fpb + 16 * sizeof(int)
         + 2 * 32 * (size_t)m->n_cbf * fpb
         + 20 * (size_t)((fpb * m->n_cbf + 63) & ~63) /* DMA staging: scores + codewords */
-        + 8 * (size_t)R * threads + 16;             /* senone ids of every quad */
+        + 16;
     /* persistent groups: as many as the chip holds at once (32 wave slots per CU), each taking
      * the units (fpb frames) g, g + grid, ...; SSW_SEN_GROUPS overrides (tuning: 0 = one group
      * per unit, the round-2 form) */

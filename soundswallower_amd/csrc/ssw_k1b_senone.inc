@@ -10,7 +10,11 @@ struct SenoneParams {
     const uint8_t *mixw;     /* [n_feat][n_density][slot_stride], slot order */
     const uint8_t *quad_cb;  /* [n_quads] codebook of slots 4q..4q+3 */
     const short4 *slot_sen;  /* [n_quads] senone ids of the 4 slots, -1 = padding */
-    const uint32_t *quad_info; /* [n_quads] first senone id | 4 consecutive ids << 16 | codebook << 24 */
+    /* [n_quads] first senone id s0 | 4 consecutive ids << 16 | n << 17 | codebook << 24: the
+     * quad's first n slots hold s0 .. s0 + n - 1 and the others are padding (every quad of the
+     * prefix layout, ssw_slot_layout.inc); n = 0: it has no such form, its slots' ids are read
+     * from slot_sen */
+    const uint32_t *quad_info;
     const uint8_t *logadd8;  /* [256] */
     const uint8_t *logadd_mirror; /* the batch kernels' LDS table, ready-made (ssw_host_model.inc) */
     unsigned long long *nfixed; /* optional: [0] running count of the frames kernel's exact
@@ -65,6 +69,7 @@ fast_logadd(int x, int y, const uint8_t *tab)
 
 typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
 typedef uint32_t uint2u __attribute__((ext_vector_type(2), aligned(2))); /* 2-byte aligned 8 bytes */
+typedef uint32_t uint1u __attribute__((aligned(2)));                     /* 2-byte aligned 4 bytes */
 
 __device__ __forceinline__ uint32_t
 pk_min_u16(uint32_t a, uint32_t b)
@@ -81,7 +86,8 @@ pk_max_u16(uint32_t a, uint32_t b)
 }
 
 /* One workgroup per FPB consecutive frames.  Senones are visited in "slot" order: grouped by
- * codebook, each group padded to a multiple of 4, so one lane owns 4 consecutive slots that
+ * codebook, each run of consecutive ids (dense layout: each group) padded to a multiple of 4
+ * (ssw_slot_layout.inc), so one lane owns 4 consecutive slots that
  * share their top-N block and fetches the 4 mixture weights of a (stream, codeword) row with one
  * dword load.  R = quads per thread.  Several frames per workgroup amortise the prologue, the
  * barriers and the launch of 704-thread groups, which is what bounded the one-frame version.
@@ -343,7 +349,7 @@ ptm_senone_kernel(SenoneParams P)
      * 351 + 3 T >= 512).  It holds T - tab[|s|] mirrored around LDS address 512 (this kernel has
      * no static LDS: its dynamic LDS starts at 0, which is what the look-ups' asm assumes).
      * Carve: tab[1024] | norm[3][FPB][8] | red[3][FPB] (+ pad) | item[2][n_cbf][FPB] 32 B |
-     * stage_sc[pad64(FPB n_cbf)] int4 | stage_cw[..] | sen4[R nthr] short4.  norm / red have three slots (unit i uses slot i % 3): a slot
+     * stage_sc[pad64(FPB n_cbf)] int4 | stage_cw[..].  norm / red have three slots (unit i uses slot i % 3): a slot
      * is re-armed two barriers after its last reader and two before its next writer. */
     uint8_t *s_tab = smem;
     /* norm: PTM [3][FPB][8] per-stream normalisers; MS [3][FPB][NORM_W] sums of fden_0 per codebook */
@@ -359,12 +365,10 @@ ptm_senone_kernel(SenoneParams P)
     uint4 *s_item = reinterpret_cast<uint4 *>(s_red + 16);
     /* the next unit's raw items, fetched by LDS-DMA while the main loop runs (no registers, no
      * round trip to memory between two main loops): scores [FPB * n_cbf] int4, codewords
-     * [FPB * n_cbf] (padded to whole waves); then the senone ids of every quad's slots, staged
-     * once per group */
+     * [FPB * n_cbf] (padded to whole waves) */
     const int n_item_pad = (FPB * n_cbf + 63) & ~63;
     int4 *s_stage_sc = reinterpret_cast<int4 *>(s_item + 2 * 2 * n_cbf * FPB);
     uint32_t *s_stage_cw = reinterpret_cast<uint32_t *>(s_stage_sc + n_item_pad);
-    short4 *s_sen4 = reinterpret_cast<short4 *>(s_stage_cw + n_item_pad);
 
     const int tid = threadIdx.x;
     const int nthr = blockDim.x;
@@ -504,12 +508,10 @@ ptm_senone_kernel(SenoneParams P)
     fetch_item(u);
     /* (the quads' constants travel in the same round trip; they are settled further down) */
     uint32_t qi_ld[R];
-    short4 sen4_ld[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int q = r * nthr + tid;
         qi_ld[r] = q < P.n_quads ? P.quad_info[q] : 0u;
-        sen4_ld[r] = q < P.n_quads ? P.slot_sen[q] : make_short4(-1, -1, -1, -1);
     }
     /* the mirrored table comes ready-made (entry e = T - tab[|e - MID|]): nthr >= 256, one or
      * two dwords per thread */
@@ -549,16 +551,16 @@ ptm_senone_kernel(SenoneParams P)
         const_cast<uint8_t *>(P.mixw)
             + (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)tid & ~63u) * 4),
         (short)4, 64, (int)(1u << 23));
-    /* per quad: byte offset of its codebook's staged items within a half | bit 0: its four
-     * senone ids are consecutive (from quad_info: first senone id | that flag << 16 |
-     * codebook << 24).  Settled here, so that no load is pending when the loop starts. */
+    /* per quad, in one register (from quad_info): its first senone id s0 << 17 | byte offset of
+     * its codebook's staged items within a half (a multiple of 32 below 2^15: an item is 32 bytes
+     * and every thread of the group, 1,024 at the most, has one of its own) |
+     * bits 0..2: n, the quad's first n slots hold s0 .. s0 + n - 1 (0 = no such form).  Settled
+     * here, so that no load is pending when the loop starts. */
     uint32_t qoff[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int q = r * nthr + tid;
         const uint32_t qi = qi_ld[r];
-        qoff[r] = (qi >> 24) * (uint32_t)(n_feat * FPB * 32) | ((qi >> 16) & 1u);
-        s_sen4[q] = sen4_ld[r];
+        qoff[r] = (qi >> 24) * (uint32_t)(n_feat * FPB * 32) | ((qi >> 17) & 7u) | (qi << 17);
     }
 
     for (int it = 0;; ++it) {
@@ -585,7 +587,7 @@ ptm_senone_kernel(SenoneParams P)
             }
             if (q < P.n_quads) {
                 const uint4 *item_cb = reinterpret_cast<const uint4 *>(
-                    reinterpret_cast<const unsigned char *>(item_b) + (qoff[r] & ~1u));
+                    reinterpret_cast<const unsigned char *>(item_b) + (qoff[r] & 0x1ffe0u));
                 /* + 2 * (f * FPB + fr): immediate offsets */
                 if (MS) {
 #pragma unroll
@@ -657,14 +659,10 @@ ptm_senone_kernel(SenoneParams P)
         }
         STL(2)
         __builtin_amdgcn_s_setprio(3);
-        /* the next unit's item (in LDS by now) and the senone ids of this unit's output: no
-         * registers held across the main loop, no round trip to memory here */
+        /* the next unit's item (in LDS by now): no registers held across the main loop, no
+         * round trip to memory here */
         if (has_next)
             take_item_dma(u_next);
-        short4 sen4[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-            sen4[r] = s_sen4[r * nthr + tid];
         /* COMPACT: where this unit's scores go -- the utterance of each of its frames (wave-
          * uniform) and, per quad, the four slots' byte offsets in that utterance's compact row
          * (8 bytes, neighbouring lanes read neighbouring quads; the table is the same for all
@@ -765,29 +763,66 @@ ptm_senone_kernel(SenoneParams P)
         for (int r = 0; r < R; ++r) {
             const int q = r * nthr + tid;
             if (q < P.n_quads) {
-                /* 4 consecutive senone ids (19 quads in 20): one 8-byte store per frame,
-                 * neighbouring lanes write neighbouring chunks */
-                const bool run4 = qoff[r] & 1u;
-                const int sj[4] = { sen4[r].x, sen4[r].y, sen4[r].z, sen4[r].w };
+                /* The quad's first n slots hold the senones s0 .. s0 + n - 1 (prefix layout:
+                 * every quad).  n = 4 (19 quads in 20): one 8-byte store per frame, neighbouring
+                 * lanes write neighbouring chunks; n < 4 (the end of a run of ids): a 4-byte
+                 * store for n & 2, a 2-byte store for n & 1 -- two exec-masked stores at the
+                 * most, no per-slot test and no per-slot id.  n = 0 (dense layout only: a quad
+                 * that straddles two runs): a store per slot, ids from global memory. */
+                /* (what the stores derive from a quad's constants -- offsets, flags, the index
+                 * of its ids -- is worked out HERE, every unit: left to the compiler it is
+                 * hoisted out of the unit loop and held in registers across the main loop) */
+                uint32_t qo = qoff[r];
+                asm volatile("" : "+v"(qo));
+                const uint32_t n = qo & 7u;
+                const uint32_t boff = (qo >> 16) & 0xfffeu; /* 2 s0: bytes into the frame's row */
+                /* score - best (src/ptm_mgau.c:394-400; both < 2^15 here, so the int16
+                 * arithmetic of the reference cannot wrap); the frames' rows are wave-uniform
+                 * addresses, + a 32-bit offset per lane */
+                uint2u pk[FPB];
+                unsigned char *orow[FPB];
 #pragma unroll
                 for (int fr = 0; fr < FPB; ++fr) {
-                    if (fr < nfr) {
-                        /* score - best (src/ptm_mgau.c:394-400; both < 2^15 here, so the int16
-                         * arithmetic of the reference cannot wrap) */
-                        const uint32_t b2 = (uint32_t)best[fr] * 0x10001u;
-                        int16_t *orow = P.out + (size_t)(t0 + fr) * P.n_sen;
-                        uint2u pk;
-                        pk.x = asc2[r][fr][0] - b2;
-                        pk.y = asc2[r][fr][1] - b2;
-                        if (run4) {
-                            *reinterpret_cast<uint2u *>(orow + sj[0]) = pk;
-                        } else {
-                            const int16_t v[4] = { (int16_t)(pk.x & 0xffffu), (int16_t)(pk.x >> 16),
-                                                   (int16_t)(pk.y & 0xffffu), (int16_t)(pk.y >> 16) };
+                    const uint32_t b2 = (uint32_t)best[fr] * 0x10001u;
+                    pk[fr].x = asc2[r][fr][0] - b2;
+                    pk[fr].y = asc2[r][fr][1] - b2;
+                    orow[fr] = reinterpret_cast<unsigned char *>(P.out + (size_t)(t0 + fr) * P.n_sen);
+                }
+                if (n == 4) {
+#pragma unroll
+                    for (int fr = 0; fr < FPB; ++fr)
+                        if (fr < nfr)
+                            *reinterpret_cast<uint2u *>(orow[fr] + boff) = pk[fr];
+                } else if (n != 0) {
+                    if (n & 2u) {
+#pragma unroll
+                        for (int fr = 0; fr < FPB; ++fr)
+                            if (fr < nfr)
+                                *reinterpret_cast<uint1u *>(orow[fr] + boff) = pk[fr].x;
+                    }
+                    if (n & 1u) {
+                        const uint32_t boff1 = boff + 2 * (n & 2u);
+#pragma unroll
+                        for (int fr = 0; fr < FPB; ++fr)
+                            if (fr < nfr)
+                                *reinterpret_cast<uint16_t *>(orow[fr] + boff1)
+                                    = (uint16_t)(((n & 2u) ? pk[fr].y : pk[fr].x) & 0xffffu);
+                    }
+                } else {
+                    uint32_t lane = (uint32_t)tid;
+                    asm volatile("" : "+v"(lane));
+                    const short4 s4 = P.slot_sen[(uint32_t)(r * nthr) + lane];
+                    const int sj[4] = { s4.x, s4.y, s4.z, s4.w };
+#pragma unroll
+                    for (int fr = 0; fr < FPB; ++fr) {
+                        if (fr < nfr) {
+                            const int16_t v[4]
+                                = { (int16_t)(pk[fr].x & 0xffffu), (int16_t)(pk[fr].x >> 16),
+                                    (int16_t)(pk[fr].y & 0xffffu), (int16_t)(pk[fr].y >> 16) };
 #pragma unroll
                             for (int j = 0; j < 4; ++j)
                                 if (sj[j] >= 0)
-                                    orow[sj[j]] = v[j];
+                                    reinterpret_cast<int16_t *>(orow[fr])[sj[j]] = v[j];
                         }
                     }
                 }

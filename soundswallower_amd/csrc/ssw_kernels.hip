@@ -72,6 +72,9 @@
  *                        staged by fill(); a host program can include it on its own)
  *   ssw_xcd_cut.inc      host, no HIP: xcd_cut, the matrix-core scan's (codebook x stream, tile
  *                        group) pairs cut into eight chunks of equal cost, one per XCD
+ *   ssw_slot_layout.inc  host, no HIP: slot_layout (the senone kernels' slot order: by codebook,
+ *                        every run of consecutive ids padded to whole quads), senone_shape (their
+ *                        workgroups' shape) and the rule that chooses between the two layouts
  *   ssw_host_model.inc   also the host side's three shared helpers, each holding one policy:
  *                        devbuf_reserve (the grow-only device buffer: no HIP call unless it
  *                        grows, hipFree's implicit synchronisation, sticky error cleared),
@@ -141,6 +144,7 @@ namespace {
 
 #include "ssw_ws_layout.inc"
 #include "ssw_xcd_cut.inc"
+#include "ssw_slot_layout.inc"
 #include "ssw_feat_tiles.inc"
 #include "ssw_host_model.inc"
 #include "ssw_host_semi.inc"
