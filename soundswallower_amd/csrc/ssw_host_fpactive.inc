@@ -25,11 +25,10 @@ struct fpa_graph_t {
     void *arg;
 };
 
-/* the first pass's: first_pass_run_impl with the export switched on; `only` as it takes it */
+/* the first pass's: first_pass_run with an FpExport; `only` as it takes it */
 struct fpa_fp_search_t {
     ssw_model_t *m;
     ssw_fp_graphs_t *g;
-    int32_t n_frames;
     const int32_t *utt_off;
     int32_t n_utts, max_seg;
     int32_t *n_seg;
@@ -42,23 +41,20 @@ fpa_fp_search(void *arg, const int16_t *rows, const std::vector<int> &only,
               unsigned long long *mask, const long long *d_act_off, const int *d_node_cnt)
 {
     const fpa_fp_search_t &a = *static_cast<const fpa_fp_search_t *>(arg);
-    ssw_model_t *m = a.m;
-    struct Export {
-        ssw_model_s *m;
-        ~Export()
-        {
-            m->fpa_mask = NULL;
-            m->fpa_act_off = NULL;
-            m->fpa_node_cnt = NULL;
-        }
-    } export_{ m };
-    m->fpa_mask = mask;
-    m->fpa_act_off = d_act_off;
-    m->fpa_node_cnt = d_node_cnt;
-    const double t0 = now_ms();
+    FpReq R{};
+    R.g = a.g;
+    R.d_senscr = rows;
+    R.utt_off = a.utt_off;
+    R.n_utts = a.n_utts;
+    R.max_seg = a.max_seg;
+    R.n_seg = a.n_seg;
+    R.seg = a.seg;
+    R.stream = a.stream;
+    R.t0 = now_ms();
+    R.subset = &only;
+    R.exp = FpExport{ mask, d_act_off, d_node_cnt };
     /* (through the levels of the long-text kernels, as ssw_first_pass_batch goes) */
-    return first_pass_run(m, a.g, t0, rows, a.n_frames, a.utt_off, a.n_utts, a.max_seg, a.n_seg,
-                          a.seg, a.stream, &only);
+    return first_pass_run(a.m, R);
 }
 
 /* what the loop serves: refused with a message before anything is uploaded or launched */
@@ -410,7 +406,7 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
                       int32_t *n_seg, ssw_word_seg_t *seg, int16_t *d_rows, bool full_rows,
                       uint32_t *seed_out, int32_t *rounds_out, void *stream, uint32_t *d_carry_out)
 {
-    fpa_fp_search_t a = { m, g, n_frames, utt_off, n_utts, max_seg, n_seg, seg, stream };
+    fpa_fp_search_t a = { m, g, utt_off, n_utts, max_seg, n_seg, seg, stream };
     fpa_graph_t G;
     G.who = "ssw_first_pass_batch_active";
     G.n_nodes = g->n_nodes;
@@ -550,9 +546,17 @@ ssw_align_text_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
     if (plan == NULL)
         return NULL;
     fpa_mode_t mode = { scorer, d_feats, cfg != NULL && cfg->two_pass_history != 0 };
-    ssw_alignment_set_t *a = forced_align_core(m, d, NULL, plan, m->text_scr.as<int16_t>(), n_frames, utt_off,
-                                               plan->n_utts, NULL, NULL, stream,
-                                               c.any ? &c.reject : NULL, NULL, NULL, &mode);
+    ForcedAlignReq F{};
+    F.d = d;
+    F.plan = plan;
+    F.d_senscr = m->text_scr.as<int16_t>();
+    F.n_frames = n_frames;
+    F.utt_off = utt_off;
+    F.n_utts = plan->n_utts;
+    F.stream = stream;
+    F.reject = c.any ? &c.reject : NULL;
+    F.fpa = &mode;
+    ssw_alignment_set_t *a = forced_align_core(m, F);
     ssw_first_pass_plan_free(plan);
     return a;
 }

@@ -293,7 +293,7 @@ struct grammar_run_t {
     ssw_recognition_set_t *r;
     GrammarParams P;
     int max_seg;
-    size_t nseg_off, score_off, seg_off, only_off;
+    int *d_only; /* device [n_utts]: the utterances a round of the default configuration searches */
     std::vector<unsigned char> stage; /* must outlive its copy */
     std::vector<int> only_host;
     std::vector<int> group; /* first utterance of every history group, then n_utts */
@@ -303,8 +303,7 @@ struct grammar_run_t {
     const char *who; /* the default configuration's entry point, for the loop's messages */
 
     grammar_run_t() : m(NULL), d(NULL), plan(NULL), fsg_of_utt(NULL), n_utts(0), st(NULL), r(NULL),
-                      max_seg(1), nseg_off(0), score_off(0), seg_off(0), only_off(0), big_ws(NULL),
-                      big_ws_off(NULL), uploaded(false),
+                      max_seg(1), d_only(NULL), big_ws(NULL), big_ws_off(NULL), uploaded(false),
                       who("ssw_recognize_batch_active") {}
     ~grammar_run_t()
     {
@@ -313,8 +312,7 @@ struct grammar_run_t {
         delete r;
     }
     int begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_plan_t *plan_,
-              const int32_t *fsg_of_utt_, int32_t n_frames, const int32_t *utt_off, int32_t n_utts_,
-              void *stream);
+              const int32_t *fsg_of_utt_, const int32_t *utt_off, int32_t n_utts_, void *stream);
     hipError_t launch(const int16_t *d_senscr, const std::vector<int> *only, unsigned long long *mask,
                       const long long *d_act_off, const int *d_node_cnt);
     ssw_recognition_set_t *finish();
@@ -322,15 +320,14 @@ struct grammar_run_t {
 
 int
 grammar_run_t::begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_plan_t *plan_,
-                     const int32_t *fsg_of_utt_, int32_t n_frames, const int32_t *utt_off,
-                     int32_t n_utts_, void *stream)
+                     const int32_t *fsg_of_utt_, const int32_t *utt_off, int32_t n_utts_,
+                     void *stream)
 {
     m = m_;
     d = d_;
     plan = plan_;
     fsg_of_utt = fsg_of_utt_;
     n_utts = n_utts_;
-    (void)n_frames;
     const ssw_fp_graphs_t *g = plan->g;
     st = (hipStream_t)stream;
     std::vector<long long> hist_off, ws_off((size_t)n_utts + 1, 0);
@@ -369,46 +366,46 @@ grammar_run_t::begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_pl
     const size_t nG = (size_t)g->n_utts, nU = (size_t)n_utts, nN = (size_t)g->n_nodes;
     const size_t nL = (size_t)g->n_leaves, nS = (size_t)g->n_slots;
     WsLayout L;
-    const size_t o_node_off = L.in(g->node_off, sizeof(int) * (nG + 1));
-    const size_t o_leaf_off = L.in(g->leaf_off, sizeof(int) * (nG + 1));
-    const size_t o_state_off = L.in(g->state_off, sizeof(int) * (nG + 1));
-    const size_t o_senid = L.in(g->senid, sizeof(uint16_t) * 4 * nN);
-    const size_t o_pen = L.in(g->pen, sizeof(int) * nN);
-    const size_t o_parent = L.in(g->parent, sizeof(int) * nN);
-    const size_t o_info = L.in(g->info, sizeof(uint32_t) * nN);
-    const size_t o_ctxt = L.in(g->ctxt, sizeof(uint64_t) * nN);
-    const size_t o_leaf_ord = L.in(g->leaf_ord, sizeof(int) * nN);
-    const size_t o_leaf_wid = L.in(g->leaf_wid, sizeof(int) * nL);
-    const size_t o_leaf_node = L.in(g->leaf_node, sizeof(int) * nL);
-    const size_t o_leaf_lscr = L.in(g->leaf_lscr, sizeof(int) * nL);
-    const size_t o_slot_off = L.in(g->slot_off, sizeof(int) * ((size_t)g->n_states + 1));
-    const size_t o_slot_leaf = L.in(g->slot_leaf, sizeof(int) * nS);
-    const size_t o_slot_pen = L.in(g->slot_pen, sizeof(int) * nS);
-    const size_t o_slot_null = L.in(g->slot_null, sizeof(int) * nS);
-    const size_t o_slot_state = L.in(g->slot_state, sizeof(int) * nS);
-    const size_t o_ls_off = L.in(g->ls_off, sizeof(int) * (nL + 1));
-    const size_t o_ls_slot = L.in(g->ls_slot, sizeof(int) * (size_t)g->n_ls);
-    const size_t o_g_start = L.in(g->g_start, sizeof(int) * nG);
-    const size_t o_g_final = L.in(g->g_final, sizeof(int) * nG);
-    const size_t o_sn_off = L.in(g->sn_off, sizeof(int) * (nG + 1));
-    const size_t o_sn_to = L.in(g->sn_to, sizeof(int) * (size_t)g->n_sn);
-    const size_t o_sn_pen = L.in(g->sn_pen, sizeof(int) * (size_t)g->n_sn);
-    const size_t o_tw = L.in(g->tw, sizeof(int) * (size_t)g->n_tw);
-    const size_t o_tw_off = L.in(g->tw_off, sizeof(int) * (nG + 1));
-    const size_t o_twin_ref = L.in(g->twin_ref, sizeof(int) * nN);
-    const size_t o_tw_rk = L.in(g->tw_rk, sizeof(int) * nG);
+    L.in(&P.node_off, g->node_off, sizeof(int) * (nG + 1));
+    L.in(&P.leaf_off, g->leaf_off, sizeof(int) * (nG + 1));
+    L.in(&P.state_off, g->state_off, sizeof(int) * (nG + 1));
+    L.in(&P.senid, g->senid, sizeof(uint16_t) * 4 * nN);
+    L.in(&P.pen, g->pen, sizeof(int) * nN);
+    L.in(&P.parent, g->parent, sizeof(int) * nN);
+    L.in(&P.info, g->info, sizeof(uint32_t) * nN);
+    L.in(&P.ctxt, g->ctxt, sizeof(uint64_t) * nN);
+    L.in(&P.leaf_ord, g->leaf_ord, sizeof(int) * nN);
+    L.in(&P.leaf_wid, g->leaf_wid, sizeof(int) * nL);
+    L.in(&P.leaf_node, g->leaf_node, sizeof(int) * nL);
+    L.in(&P.leaf_lscr, g->leaf_lscr, sizeof(int) * nL);
+    L.in(&P.slot_off, g->slot_off, sizeof(int) * ((size_t)g->n_states + 1));
+    L.in(&P.slot_leaf, g->slot_leaf, sizeof(int) * nS);
+    L.in(&P.slot_pen, g->slot_pen, sizeof(int) * nS);
+    L.in(&P.slot_null, g->slot_null, sizeof(int) * nS);
+    L.in(&P.slot_state, g->slot_state, sizeof(int) * nS);
+    L.in(&P.ls_off, g->ls_off, sizeof(int) * (nL + 1));
+    L.in(&P.ls_slot, g->ls_slot, sizeof(int) * (size_t)g->n_ls);
+    L.in(&P.g_start, g->g_start, sizeof(int) * nG);
+    L.in(&P.g_final, g->g_final, sizeof(int) * nG);
+    L.in(&P.sn_off, g->sn_off, sizeof(int) * (nG + 1));
+    L.in(&P.sn_to, g->sn_to, sizeof(int) * (size_t)g->n_sn);
+    L.in(&P.sn_pen, g->sn_pen, sizeof(int) * (size_t)g->n_sn);
+    L.in(&P.tw, g->tw, sizeof(int) * (size_t)g->n_tw);
+    L.in(&P.tw_off, g->tw_off, sizeof(int) * (nG + 1));
+    L.in(&P.twin_ref, g->twin_ref, sizeof(int) * nN);
+    L.in(&P.tw_rk, g->tw_rk, sizeof(int) * nG);
     const size_t o_call = L.mark();
-    const size_t o_utt_off = L.in(utt_off, sizeof(int) * (nU + 1));
-    const size_t o_fsg_of_utt = L.in(fsg_of_utt, fsg_of_utt ? sizeof(int) * nU : 0);
-    const size_t o_hist_off = L.in(hist_off.data(), sizeof(long long) * nU);
-    const size_t o_ws_off = L.in(ws_off.data(), sizeof(long long) * nU);
+    L.in(&P.utt_off, utt_off, sizeof(int) * (nU + 1));
+    L.in(&P.fsg_of_utt, fsg_of_utt, fsg_of_utt ? sizeof(int) * nU : 0);
+    L.in(&P.hist_off, hist_off.data(), sizeof(long long) * nU);
+    L.in(&big_ws_off, ws_off.data(), sizeof(long long) * nU);
     const size_t in_bytes = L.in_bytes();
-    nseg_off = L.out(sizeof(int) * nU);
-    score_off = L.out(sizeof(int) * nU);
-    only_off = L.out(sizeof(int) * nU); /* (the utterances a round of the default configuration searches) */
-    seg_off = L.out(sizeof(ssw_fsg_seg_t) * nU * (size_t)max_seg);
-    const size_t hist_at = L.out(sizeof(int2) * (hist_total ? hist_total : 1));
-    const size_t big_at = L.out(sizeof(int) * ws_ints);
+    L.out(&P.n_seg, sizeof(int) * nU);
+    L.out(&P.score, sizeof(int) * nU);
+    L.out(&d_only, sizeof(int) * nU);
+    L.out(&P.seg, sizeof(ssw_fsg_seg_t) * nU * (size_t)max_seg);
+    L.out(&P.hist, sizeof(int2) * (hist_total ? hist_total : 1));
+    L.out(&big_ws, sizeof(int) * ws_ints);
 
     hipError_t e = hipSetDevice(m->device);
     if (e == hipSuccess) {
@@ -430,49 +427,14 @@ grammar_run_t::begin(ssw_model_t *m_, const ssw_dict_t *d_, const ssw_grammar_pl
         uploaded = true;
     }
     if (e == hipSuccess) {
-        unsigned char *ws = m->gr_ws.p;
+        L.resolve(m->gr_ws.p);
+        if (!fsg_of_utt)
+            P.fsg_of_utt = NULL;
         P.senscr = NULL;
         P.only = NULL;
         P.act_mask = NULL;
         P.act_off = NULL;
-        P.node_off = ws_at<const int>(ws, o_node_off);
-        P.leaf_off = ws_at<const int>(ws, o_leaf_off);
-        P.state_off = ws_at<const int>(ws, o_state_off);
-        P.senid = ws_at<const uint16_t>(ws, o_senid);
-        P.pen = ws_at<const int>(ws, o_pen);
-        P.parent = ws_at<const int>(ws, o_parent);
-        P.info = ws_at<const uint32_t>(ws, o_info);
-        P.ctxt = ws_at<const unsigned long long>(ws, o_ctxt);
-        P.leaf_ord = ws_at<const int>(ws, o_leaf_ord);
-        P.leaf_wid = ws_at<const int>(ws, o_leaf_wid);
-        P.leaf_node = ws_at<const int>(ws, o_leaf_node);
-        P.leaf_lscr = ws_at<const int>(ws, o_leaf_lscr);
-        P.slot_off = ws_at<const int>(ws, o_slot_off);
-        P.slot_leaf = ws_at<const int>(ws, o_slot_leaf);
-        P.slot_pen = ws_at<const int>(ws, o_slot_pen);
-        P.slot_null = ws_at<const int>(ws, o_slot_null);
-        P.slot_state = ws_at<const int>(ws, o_slot_state);
-        P.ls_off = ws_at<const int>(ws, o_ls_off);
-        P.ls_slot = ws_at<const int>(ws, o_ls_slot);
-        P.g_start = ws_at<const int>(ws, o_g_start);
-        P.g_final = ws_at<const int>(ws, o_g_final);
-        P.sn_off = ws_at<const int>(ws, o_sn_off);
-        P.sn_to = ws_at<const int>(ws, o_sn_to);
-        P.sn_pen = ws_at<const int>(ws, o_sn_pen);
-        P.tw = ws_at<const int>(ws, o_tw);
-        P.tw_off = ws_at<const int>(ws, o_tw_off);
-        P.twin_ref = ws_at<const int>(ws, o_twin_ref);
-        P.tw_rk = ws_at<const int>(ws, o_tw_rk);
-        P.utt_off = ws_at<const int>(ws, o_utt_off);
-        P.fsg_of_utt = fsg_of_utt ? ws_at<const int>(ws, o_fsg_of_utt) : NULL;
-        P.hist_off = ws_at<const long long>(ws, o_hist_off);
-        big_ws = ws_at<int>(ws, big_at);
-        big_ws_off = ws_at<const long long>(ws, o_ws_off);
         P.tp = (const uint32_t *)m->d_tp;
-        P.hist = ws_at<int2>(ws, hist_at);
-        P.n_seg = ws_at<int>(ws, nseg_off);
-        P.score = ws_at<int>(ws, score_off);
-        P.seg = ws_at<ssw_fsg_seg_t>(ws, seg_off);
         P.n_sen = m->h->n_sen;
         P.max_seg = max_seg;
         P.beam = g->beam;
@@ -496,7 +458,6 @@ grammar_run_t::launch(const int16_t *d_senscr, const std::vector<int> *only, uns
                       const long long *d_act_off, const int *d_node_cnt)
 {
     hipError_t e = hipSuccess;
-    unsigned char *ws = m->gr_ws.p;
     const bool exp = mask != NULL;
     const int n_run = only != NULL && !only->empty() ? (int)only->size() : n_utts;
     P.senscr = d_senscr;
@@ -515,9 +476,9 @@ grammar_run_t::launch(const int16_t *d_senscr, const std::vector<int> *only, uns
             only_host = *only; /* (kept here: every round ends in a synchronisation of the stream) */
             if (!std::is_sorted(only_host.begin(), only_host.end())) /* (fpa_run's are ascending) */
                 std::sort(only_host.begin(), only_host.end());
-            e = hipMemcpyAsync(ws + only_off, only_host.data(), sizeof(int) * (size_t)n_run,
+            e = hipMemcpyAsync(d_only, only_host.data(), sizeof(int) * (size_t)n_run,
                                hipMemcpyHostToDevice, st); /* once per round, every group's part */
-            P.only = (const int *)(ws + only_off);
+            P.only = d_only;
         }
         GrammarBigParams B;
         B.g = P;
@@ -543,9 +504,9 @@ grammar_run_t::launch(const int16_t *d_senscr, const std::vector<int> *only, uns
     }
     if (only != NULL && !only->empty()) {
         only_host = *only; /* (kept here: every round ends in a synchronisation of the stream) */
-        e = hipMemcpyAsync(ws + only_off, only_host.data(), sizeof(int) * (size_t)n_run,
+        e = hipMemcpyAsync(d_only, only_host.data(), sizeof(int) * (size_t)n_run,
                            hipMemcpyHostToDevice, st);
-        P.only = (const int *)(ws + only_off);
+        P.only = d_only;
     }
     if (e == hipSuccess && exp) {
         hipLaunchKernelGGL(fpa_clear_kernel, dim3((unsigned)n_run), dim3(256), 0, st, mask, d_act_off,
@@ -600,20 +561,13 @@ grammar_run_t::finish()
     }
     std::vector<int> n_seg((size_t)n_utts), score((size_t)n_utts);
     std::vector<ssw_fsg_seg_t> seg((size_t)n_utts * (size_t)max_seg);
-    hipError_t e = hipSuccess;
-    {
-        unsigned char *ws = m->gr_ws.p;
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(n_seg.data(), ws + nseg_off, sizeof(int) * (size_t)n_utts,
-                               hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(score.data(), ws + score_off, sizeof(int) * (size_t)n_utts,
-                               hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(seg.data(), ws + seg_off,
-                               sizeof(ssw_fsg_seg_t) * (size_t)n_utts * (size_t)max_seg,
-                               hipMemcpyDeviceToHost, st);
-    }
+    hipError_t e = hipMemcpyAsync(n_seg.data(), P.n_seg, sizeof(int) * (size_t)n_utts,
+                                  hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(score.data(), P.score, sizeof(int) * (size_t)n_utts, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(seg.data(), P.seg, sizeof(ssw_fsg_seg_t) * (size_t)n_utts * (size_t)max_seg,
+                           hipMemcpyDeviceToHost, st);
     if (e == hipSuccess)
         e = hipStreamSynchronize(st);
     else
@@ -673,23 +627,34 @@ grammar_run_t::finish()
     return out;
 }
 
+/* what every recognition entry point asks of its arguments; d_in: the rows or features it reads */
+static int
+recognize_check_args(const char *who, const ssw_model_t *m, const ssw_dict_t *d,
+                     const ssw_grammar_plan_t *plan, const void *d_in, int32_t n_frames,
+                     const int32_t *utt_off, int32_t n_utts)
+{
+    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
+        || !utt_off_spans(utt_off, n_utts, n_frames) || (n_frames > 0 && d_in == NULL)) {
+        ssw_set_error("bad arguments to %s", who);
+        return -1;
+    }
+    return 0;
+}
+
 extern "C" ssw_recognition_set_t *
 ssw_grammar_search_batch(ssw_model_t *m, const ssw_dict_t *d, const ssw_grammar_plan_t *plan,
                          const int32_t *fsg_of_utt, const int16_t *d_senscr, int32_t n_frames,
                          const int32_t *utt_off, int32_t n_utts, void *stream)
 {
-    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
-        || !utt_off_spans(utt_off, n_utts, n_frames) || (n_frames > 0 && d_senscr == NULL)) {
-        ssw_set_error("bad arguments to ssw_grammar_search_batch");
+    if (recognize_check_args("ssw_grammar_search_batch", m, d, plan, d_senscr, n_frames, utt_off, n_utts) < 0)
         return NULL;
-    }
     if (check_has_device(m) < 0)
         return NULL;
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
     grammar_run_t R;
-    if (R.begin(m, d, plan, fsg_of_utt, n_frames, utt_off, n_utts, stream) < 0)
+    if (R.begin(m, d, plan, fsg_of_utt, utt_off, n_utts, stream) < 0)
         return NULL;
     if (n_utts > 0) {
         const hipError_t e = R.launch(d_senscr, NULL, NULL, NULL, NULL);
@@ -743,6 +708,24 @@ grammar_active_search(void *arg, const int16_t *rows, const std::vector<int> &on
     return 0;
 }
 
+/* what the loop needs of a grammar run: every utterance's HMMs are those of its grammar */
+static void
+grammar_fpa_graph(fpa_graph_t &G, const char *who, grammar_run_t &R)
+{
+    const ssw_fp_graphs_t *g = R.plan->g;
+    G.who = who;
+    G.n_nodes = g->n_nodes;
+    G.senid = g->senid;
+    G.max_nodes = R.plan->max_nodes;
+    for (int u = 0; u < R.n_utts; ++u) {
+        const int gi = R.fsg_of_utt ? R.fsg_of_utt[u] : 0; /* (checked by begin) */
+        G.node_base.push_back(g->node_off[gi]);
+        G.node_cnt.push_back(g->node_off[gi + 1] - g->node_off[gi]);
+    }
+    G.search = grammar_active_search;
+    G.arg = &R;
+}
+
 /* decoder_set_fsg + decoder_process + decoder_hyp in the reference's DEFAULT configuration
  * (compallsen = no) for a batch, from features: every frame scored for the senones of the HMMs
  * fsg_search_sen_active lists (src/fsg_search.c:310-325), through acmod's flags2list with its
@@ -754,11 +737,8 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
                            int32_t n_frames, const int32_t *utt_off, int32_t n_utts,
                            int16_t *d_senscr, uint32_t *listed, int32_t *rounds, void *stream)
 {
-    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
-        || !utt_off_spans(utt_off, n_utts, n_frames) || (n_frames > 0 && d_feats == NULL)) {
-        ssw_set_error("bad arguments to ssw_recognize_batch_active");
+    if (recognize_check_args("ssw_recognize_batch_active", m, d, plan, d_feats, n_frames, utt_off, n_utts) < 0)
         return NULL;
-    }
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
@@ -807,23 +787,12 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
         rows = m->text_scr.as<int16_t>();
     }
     grammar_run_t R;
-    if (R.begin(m, d, plan, fsg_of_utt, n_frames, utt_off, n_utts, stream) < 0)
+    if (R.begin(m, d, plan, fsg_of_utt, utt_off, n_utts, stream) < 0)
         return NULL;
     if (n_utts == 0)
         return R.finish();
-    const ssw_fp_graphs_t *g = plan->g;
     fpa_graph_t G;
-    G.who = "ssw_recognize_batch_active";
-    G.n_nodes = g->n_nodes;
-    G.senid = g->senid;
-    G.max_nodes = plan->max_nodes;
-    for (int u = 0; u < n_utts; ++u) {
-        const int gi = fsg_of_utt ? fsg_of_utt[u] : 0; /* (checked by begin) */
-        G.node_base.push_back(g->node_off[gi]);
-        G.node_cnt.push_back(g->node_off[gi + 1] - g->node_off[gi]);
-    }
-    G.search = grammar_active_search;
-    G.arg = &R;
+    grammar_fpa_graph(G, "ssw_recognize_batch_active", R);
     if (fpa_run(m, G, scorer, d_feats, n_frames, utt_off, n_utts, rows, d_senscr != NULL, NULL,
                 rounds, listed, m->gra_stats, stream, NULL) < 0)
         return NULL;
@@ -911,10 +880,21 @@ recognition_align(ssw_model_t *m, const ssw_recognition_set_t *r, const int16_t 
 {
     rec_word_segs_t w;
     recognition_word_segs(r, w);
-    ssw_alignment_set_t *a = align_word_segments(m, r->d, d_senscr, utt_off, r->n_utts,
-                                                 w.n_seg.data(), w.seg.data(), w.max_seg,
-                                                 w.pre_status.data(), w.message, fpa, seed, d_carry,
-                                                 NULL, NULL, stream, 0.0);
+    AlignSegReq Q{};
+    Q.d = r->d;
+    Q.d_senscr = d_senscr;
+    Q.utt_off = utt_off;
+    Q.n_utts = r->n_utts;
+    Q.n_seg = w.n_seg.data();
+    Q.seg = w.seg.data();
+    Q.max_seg = w.max_seg;
+    Q.pre_status = w.pre_status.data();
+    Q.message = &w.message;
+    Q.fpa = fpa;
+    Q.seed = seed;
+    Q.d_carry = d_carry;
+    Q.stream = stream;
+    ssw_alignment_set_t *a = align_word_segments(m, Q);
     if (a != NULL)
         a->hyp = r->hyp; /* decoder_hyp's text, for the JSON line's "t" */
     return a;
@@ -949,11 +929,8 @@ recognize_align_rows(const char *who, ssw_model_t *m, const ssw_dict_t *d,
 {
     if (rec_out != NULL)
         *rec_out = NULL;
-    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
-        || !utt_off_spans(utt_off, n_utts, n_frames) || (n_frames > 0 && d_feats == NULL)) {
-        ssw_set_error("bad arguments to %s", who);
+    if (recognize_check_args(who, m, d, plan, d_feats, n_frames, utt_off, n_utts) < 0)
         return NULL;
-    }
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
@@ -968,32 +945,15 @@ recognize_align_rows(const char *who, ssw_model_t *m, const ssw_dict_t *d,
         return NULL;
     const bool two_pass = two_pass_history != 0
         && (scorer == SSW_SCORER_PTM || scorer == SSW_SCORER_S2_SEMI) && n_frames > 0 && n_utts > 0;
-    if (two_pass) { /* set aside while the first scoring's top-N block is still in the workspace */
-        if (carry_rows_reserve(m, n_utts, who) < 0)
-            return NULL;
-        hipLaunchKernelGGL(gather_last_orders_kernel, dim3((unsigned)n_utts), dim3(128), 0,
-                           (hipStream_t)stream, m->sw.cw(), m->sw.utt_off(), m->n_cbf,
-                           (const uint32_t *)NULL, m->carry_rows.as<uint32_t>());
-        if (hipGetLastError() != hipSuccess) {
-            ssw_set_error("%s: gather_last_orders_kernel failed to launch", who);
-            return NULL;
-        }
-    }
+    if (two_pass && carry_last_orders(m, who, n_utts, stream) < 0)
+        return NULL;
     ssw_recognition_set_t *r = ssw_grammar_search_batch(m, d, plan, fsg_of_utt, rows, n_frames,
                                                         utt_off, n_utts, stream);
     if (r == NULL)
         return NULL;
     ssw_alignment_set_t *a = NULL;
-    ScoreReq R{}; /* the second pass: every utterance from its first pass's history */
-    R.scorer = scorer;
-    R.d_feats = d_feats;
-    R.n_frames = n_frames;
-    R.utt_off = utt_off;
-    R.n_utts = n_utts;
-    R.d_out = rows;
-    R.stream = stream;
-    R.d_carry_rows = m->carry_rows.as<uint32_t>();
-    if (!two_pass || score_batch_impl(m, R) >= 0)
+    rescore_t rs = rescore_request(m, scorer, d_feats, n_frames, utt_off, n_utts, rows, stream);
+    if (!two_pass || rescore_run(&rs) >= 0)
         a = recognition_align(m, r, rows, utt_off, NULL, NULL, NULL, stream);
     if (a != NULL && rec_out != NULL)
         *rec_out = r;
@@ -1026,11 +986,8 @@ ssw_recognize_align_batch_active(ssw_model_t *m, const ssw_dict_t *d,
     const char *who = "ssw_recognize_align_batch_active";
     if (rec_out != NULL)
         *rec_out = NULL;
-    if (m == NULL || d == NULL || plan == NULL || n_utts < 0 || n_frames < 0 || utt_off == NULL
-        || !utt_off_spans(utt_off, n_utts, n_frames) || (n_frames > 0 && d_feats == NULL)) {
-        ssw_set_error("bad arguments to %s", who);
+    if (recognize_check_args(who, m, d, plan, d_feats, n_frames, utt_off, n_utts) < 0)
         return NULL;
-    }
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
@@ -1070,22 +1027,11 @@ ssw_recognize_align_batch_active(ssw_model_t *m, const ssw_dict_t *d,
     {
         grammar_run_t R;
         R.who = who;
-        if (R.begin(m, d, plan, fsg_of_utt, n_frames, utt_off, n_utts, stream) < 0)
+        if (R.begin(m, d, plan, fsg_of_utt, utt_off, n_utts, stream) < 0)
             return NULL;
         if (n_utts > 0) {
-            const ssw_fp_graphs_t *g = plan->g;
             fpa_graph_t G;
-            G.who = who;
-            G.n_nodes = g->n_nodes;
-            G.senid = g->senid;
-            G.max_nodes = plan->max_nodes;
-            for (int u = 0; u < n_utts; ++u) {
-                const int gi = fsg_of_utt ? fsg_of_utt[u] : 0; /* (checked by begin) */
-                G.node_base.push_back(g->node_off[gi]);
-                G.node_cnt.push_back(g->node_off[gi + 1] - g->node_off[gi]);
-            }
-            G.search = grammar_active_search;
-            G.arg = &R;
+            grammar_fpa_graph(G, who, R);
             if (fpa_run(m, G, scorer, d_feats, n_frames, utt_off, n_utts, rows, false, seed.data(),
                         rounds, NULL, m->gra_stats, stream,
                         carry2 ? m->carry_rows.as<uint32_t>() : NULL) < 0)

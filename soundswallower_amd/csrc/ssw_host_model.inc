@@ -260,13 +260,8 @@ struct ssw_model_s {
     hipEvent_t ev_up;
     uint64_t fp_ws_uid;     /* the graphs whose tables fp_ws holds (ssw_fp_graphs_t::uid), 0 = none */
     size_t fp_ws_uid_bytes; /* and how much of the workspace they take */
-    /* the default configuration's first pass as a batch (ssw_host_fpactive.inc): its workspace,
-     * and -- while one of its searches runs -- where first_pass_kernel<.., EXPORT> writes the
-     * sets of active HMMs (NULL otherwise) */
+    /* the default configuration's first pass as a batch (ssw_host_fpactive.inc): its workspace */
     DevBuf fpa_ws;
-    unsigned long long *fpa_mask;
-    const long long *fpa_act_off;
-    const int *fpa_node_cnt; /* device [n_utts]: phone-tree HMMs of every utterance's graph */
     int64_t gra_stats[4]; /* as fpa_stats, of ssw_recognize_batch_active */
     int64_t fpa_stats[4]; /* utterances, verify rounds summed over them, rounds of the last call, utterances that needed more than one */
     DevBuf text_scr; /* ssw_align_text_batch's score rows, int16 [n_frames][n_sen] (text_rows_reserve) */

@@ -75,11 +75,18 @@
  *   ssw_slot_layout.inc  host, no HIP: slot_layout (the senone kernels' slot order: by codebook,
  *                        every run of consecutive ids padded to whole quads), senone_shape (their
  *                        workgroups' shape) and the rule that chooses between the two layouts
+ *   ssw_fp_shape.inc     host, no HIP: fp_shape, what one launch of the first pass takes (the
+ *                        per-utterance LDS, HBM-workspace and history sizes, each formula once;
+ *                        register / window / HBM / HBM-banded kernel, threads, LDS bytes)
  *   ssw_host_model.inc   also the host side's three shared helpers, each holding one policy:
  *                        devbuf_reserve (the grow-only device buffer: no HIP call unless it
  *                        grows, hipFree's implicit synchronisation, sticky error cleared),
  *                        WsLayout (above), stage_upload / stage_release (the pinned upload: the
  *                        slot's event is always recorded behind its copies)
+ *   ssw_host_firstpass.inc  one first-pass run is an FpReq through fp_shape, fp_layout,
+ *                        FpUpload (the cached-graphs policy), fp_launch, fp_fetch;
+ *                        decoder_alignment's second half is an AlignSegReq through
+ *                        align_word_segments' steps, its threaded ones over for_utt_ranges
  *   ssw_host_*.inc       device model and loaders' upload, batched scoring, alignment, the
  *                        mgau_t / search-module shaped objects, features, the front end
  *                        (ssw_host_fe.inc; its tables are built in ssw_model.c), device-memory
@@ -145,6 +152,7 @@ namespace {
 #include "ssw_ws_layout.inc"
 #include "ssw_xcd_cut.inc"
 #include "ssw_slot_layout.inc"
+#include "ssw_fp_shape.inc"
 #include "ssw_feat_tiles.inc"
 #include "ssw_host_model.inc"
 #include "ssw_host_semi.inc"

@@ -15,17 +15,27 @@ align256(size_t x)
  * remembers which pieces have a host source, so that "one staging buffer, one copy" is written
  * once: the caller keeps the offset each call returns (no piece has a number), fill() stages
  * the uploaded pieces, and a mark() names a boundary between them (what is cached on the device
- * and what a call uploads again). */
+ * and what a call uploads again).  A piece registered with the pointer that is to address it (the
+ * typed overloads) is named once: resolve() sets every such pointer when the workspace is there. */
 struct WsLayout {
     struct Piece {
         const void *src;
         size_t bytes, off;
     };
+    struct Slot {
+        void *ptr; /* a T * of the caller's: where resolve() writes the piece's address */
+        size_t off;
+    };
     std::vector<Piece> ins;
+    std::vector<Slot> slots;
     size_t end = 0;    /* of the last piece, rounded up: where the next one goes */
     size_t in_end = 0; /* the same behind the last uploaded piece */
 
-    WsLayout() { ins.reserve(32); }
+    WsLayout()
+    {
+        ins.reserve(32);
+        slots.reserve(40);
+    }
     /* an uploaded table; zero bytes take no space (the next piece then has the same offset).
      * `room` > bytes: the space it takes nevertheless */
     size_t in(const void *src, size_t bytes, size_t room = 0)
@@ -41,6 +51,31 @@ struct WsLayout {
         const size_t at = end;
         end = align256(end + bytes);
         return at;
+    }
+    /* the same, and *slot = the piece's address once resolve() knows the workspace's (a piece of
+     * zero bytes gets the address of whatever follows it) */
+    template <typename T>
+    size_t in(T **slot, const void *src, size_t bytes, size_t room = 0)
+    {
+        const size_t at = in(src, bytes, room);
+        slots.push_back(Slot{ slot, at });
+        return at;
+    }
+    template <typename T>
+    size_t out(T **slot, size_t bytes)
+    {
+        const size_t at = out(bytes);
+        slots.push_back(Slot{ slot, at });
+        return at;
+    }
+    /* after devbuf_reserve: every registered pointer = base + its piece's offset (the pointer's
+     * value is copied: a T ** is not a void **) */
+    void resolve(unsigned char *base) const
+    {
+        for (const Slot &s : slots) {
+            unsigned char *at = base + s.off;
+            memcpy(s.ptr, &at, sizeof(at));
+        }
     }
     size_t mark() const { return end; }
     size_t size() const { return end; }

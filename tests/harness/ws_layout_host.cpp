@@ -1,5 +1,7 @@
 /* WsLayout (csrc/ssw_ws_layout.inc) on the CPU: offsets against a restatement of the rule the
- * hand-written piece tables used, and fill() against an image built piece by piece.  Built with
+ * hand-written piece tables used, and fill() against an image built piece by piece.  The typed
+ * overloads (a piece registered with the pointer that is to address it): the same offsets as the
+ * plain calls give, and resolve() sets every pointer to base + offset.  Built with
  * -fsanitize=address,undefined (tests/test_ws_layout_host.py); every stage buffer has exactly the
  * size fill() may write, so an overrun is an ASan report. */
 #include <cstdint>
@@ -33,7 +35,7 @@ main()
 {
     static const size_t sizes[] = { 0, 1, 255, 256, 257, 4096 };
     const unsigned char SENTINEL = 0xA5;
-    long n_layouts = 0, n_pieces = 0, n_fills = 0;
+    long n_layouts = 0, n_pieces = 0, n_fills = 0, n_slots = 0;
     for (int n = 1; n <= 40; ++n)
         for (int rep = 0; rep < 5; ++rep) {
             std::vector<size_t> bytes((size_t)n), want((size_t)n), got((size_t)n);
@@ -74,6 +76,34 @@ main()
             CHECK(L.size() == want_total, "total %zu, rule %zu", L.size(), want_total);
             CHECK(L.in_bytes() == want_in_end, "in_bytes %zu, rule %zu", L.in_bytes(), want_in_end);
             ++n_layouts;
+            /* the same pieces registered with typed pointers (three types in turn, as a kernel's
+             * parameter block mixes them): the offsets of the plain calls, and resolve() */
+            {
+                const int *pi[40];
+                uint16_t *ps[40];
+                const long long *pl[40];
+                WsLayout B;
+                for (int i = 0; i < n; ++i) {
+                    size_t at;
+                    if (i % 3 == 0)
+                        at = is_in[i] ? B.in(&pi[i], src[i].data(), bytes[i]) : B.out(&pi[i], bytes[i]);
+                    else if (i % 3 == 1)
+                        at = is_in[i] ? B.in(&ps[i], src[i].data(), bytes[i]) : B.out(&ps[i], bytes[i]);
+                    else
+                        at = is_in[i] ? B.in(&pl[i], src[i].data(), bytes[i]) : B.out(&pl[i], bytes[i]);
+                    CHECK(at == got[i], "piece %d of %d with a pointer: offset %zu, plain %zu", i, n, at, got[i]);
+                }
+                CHECK(B.size() == L.size() && B.in_bytes() == L.in_bytes() && B.ins.size() == L.ins.size(),
+                      "with pointers: total %zu (%zu), in_bytes %zu (%zu)", B.size(), L.size(),
+                      B.in_bytes(), L.in_bytes());
+                std::vector<unsigned char> ws(B.size() + 1);
+                B.resolve(ws.data());
+                for (int i = 0; i < n; ++i) {
+                    const void *p = i % 3 == 0 ? (const void *)pi[i] : i % 3 == 1 ? (const void *)ps[i] : (const void *)pl[i];
+                    CHECK(p == (const void *)(ws.data() + got[i]), "piece %d of %d: resolve() missed base + %zu", i, n, got[i]);
+                    ++n_slots;
+                }
+            }
             /* fill from every piece boundary (and from the end of the uploaded part) */
             std::vector<size_t> froms(got);
             froms.push_back(L.in_bytes());
@@ -109,6 +139,28 @@ main()
         CHECK(align256(0) == 0 && align256(1) == 256 && align256(256) == 256 && align256(257) == 512,
               "align256");
     }
+    /* a zero-byte optional table (the grammar search's fsg_of_utt: NULL = grammar 0) keeps its
+     * slot: it takes no space, and its pointer is resolved like any other -- to where the next
+     * piece lies; `room` and plain pieces mix with bound ones */
+    {
+        WsLayout L;
+        unsigned char four[4] = { 1, 2, 3, 4 }, base[1024 + 1];
+        const int *utt_off = NULL, *fsg_of_utt = NULL;
+        const long long *hist_off = NULL;
+        int *n_seg = NULL;
+        CHECK(L.in(&utt_off, four, 4) == 0, "first");
+        CHECK(L.in(&fsg_of_utt, NULL, 0) == 256 && L.mark() == 256, "an empty table with a pointer takes no space");
+        CHECK(L.in(&hist_off, four, 4, 4 + 16) == 256, "the next piece lies where the empty one does");
+        CHECK(L.in(four, 4) == 512, "a plain piece among bound ones");
+        CHECK(L.out(&n_seg, 4) == 768 && L.size() == 1024, "device-only space with a pointer");
+        CHECK(L.slots.size() == 4, "%zu slots, 4 registered", L.slots.size());
+        L.resolve(base);
+        CHECK((const void *)utt_off == base && (const void *)fsg_of_utt == base + 256
+                  && (const void *)hist_off == base + 256 && (void *)n_seg == base + 768,
+              "resolve() with an empty table");
+        n_slots += 4;
+    }
+    printf("slots: %ld pointers resolved\n", n_slots);
     printf("ok: %ld layouts, %ld pieces, %ld fills\n", n_layouts, n_pieces, n_fills);
     return 0;
 }

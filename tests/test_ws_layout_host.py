@@ -4,7 +4,9 @@ tests/harness/ws_layout_host.cpp includes the builder (plain C++17, no HIP heade
 layouts of 1 to 40 pieces with sizes drawn from {0, 1, 255, 256, 257, 4096} (fixed seed):
 offsets against the rule of the hand-written piece tables it replaced, alignment, no overlap,
 the total, and fill() from every piece boundary into a sentinel-filled buffer of exactly the
-size it may write.  Built with -fsanitize=address,undefined and run as a process of its own.
+size it may write; then the same pieces registered with typed pointers: the offsets of the
+plain calls, resolve() = base + offset for every pointer, a zero-byte optional table keeps its
+slot.  Built with -fsanitize=address,undefined and run as a process of its own.
 The rule is restated here too, over the offsets the program prints."""
 import os
 import re
@@ -28,6 +30,9 @@ def test_layout_offsets_and_fill(tmp_path):
     assert lines[-1].startswith("ok: "), r.stdout[-2000:] + r.stderr[-2000:]
     n_layouts, n_pieces, n_fills = [int(x) for x in re.findall(r"\d+", lines[-1])]
     assert n_layouts == 40 * 5 and n_pieces == 5 * sum(range(1, 41)) and n_fills > n_pieces
+    # every piece once more with a typed pointer, and the four of the optional-table case
+    assert lines[-2].startswith("slots: "), r.stdout[-2000:]
+    assert int(re.findall(r"\d+", lines[-2])[0]) == n_pieces + 4
     # the parent's rule: off = (off + bytes + 255) & ~255, a zero-byte piece takes no space
     seen = set()
     layouts = [ln for ln in lines if ln.startswith("L ")]
