@@ -77,7 +77,7 @@ mgau_alloc_pinned(ssw_mgau_impl *g)
 static int
 mgau_reset_device_hist(ssw_mgau_impl *g)
 {
-    std::vector<uint32_t> init((size_t)g->m->n_cbf, 0x03020100u); /* cw = m */
+    std::vector<uint32_t> init((size_t)g->m->n_cbf, SSW_ORDER_RESET); /* cw = m */
     for (int i = 0; i < 2; ++i) {
         HIP_OK(hipMemcpy(g->d_hist_cw[i], init.data(), init.size() * 4, hipMemcpyHostToDevice));
         memset(g->cb_mask[i], 0xff, sizeof(g->cb_mask[i])); /* all codebooks active */
@@ -162,7 +162,7 @@ static void
 semi_mgau_reset(ssw_mgau_impl *g)
 {
     for (int i = 0; i < 2; ++i) {
-        g->sc_hist[i].assign((size_t)g->m->n_cbf, 0x03020100u); /* codeword k (:993-1002) */
+        g->sc_hist[i].assign((size_t)g->m->n_cbf, SSW_ORDER_RESET); /* codeword k (:993-1002) */
         g->sc_row[i].assign((size_t)g->m->h->n_sen, 0);
     }
 }

@@ -486,7 +486,7 @@ launch_scan_mfma(const ScoreCall &C, FramesParams &F, int lo, int hi)
      * and count the pairs where a PROVEN scan result differs (ssw_scan_audit_stats) */
     F.audit_k = kn.scan_audit;
     /* masked batches (compallsen = no): the instances whose exact pass steps over the frames
-     * a codebook is not scanned in (ssw_k1a_frames.inc, carried_order_masked) */
+     * a codebook is not scanned in (ssw_scan_common.inc, carried_order_masked) */
     const bool masked = C.R.act != NULL && !ms && kn.scan_audit <= 0;
 #define SSW_MFMA_LAUNCH(MSV, NS)                                                             \
     if (masked)                                                                              \
@@ -624,7 +624,7 @@ score_upload_meta(const ScoreCall &C, bool want_carry)
          * reset history (the chain kernel reads a row per utterance, the scans only row 0) */
         uint32_t *car = reinterpret_cast<uint32_t *>(hs);
         for (size_t i = 0; i < ncar; ++i)
-            car[i] = 0x03020100u;
+            car[i] = SSW_ORDER_RESET;
         memcpy(car, C.R.carry_in, sizeof(uint32_t) * (size_t)m->n_cbf);
         HIP_OK(hipMemcpyAsync(m->carry0.as<uint32_t>(), car, b_car, hipMemcpyHostToDevice, C.st));
     }
@@ -741,7 +741,7 @@ score_batch_finish(const ScoreCall &C, int64_t exact_pairs, bool history, bool t
         return 0;
     if (!history) {
         for (int i = 0; i < m->n_cbf; ++i)
-            carry_out[i] = 0x03020100u; /* the ms scorer keeps no history */
+            carry_out[i] = SSW_ORDER_RESET; /* the ms scorer keeps no history */
         return 0;
     }
     /* what the next call starts from.  Default: the last frame's final order (the next call
@@ -761,14 +761,14 @@ score_batch_finish(const ScoreCall &C, int64_t exact_pairs, bool history, bool t
             else if (!C.chain) { /* utterances are independent: only the last one counts */
                 from_start = true;
                 for (int i = 0; i < m->n_cbf; ++i)
-                    carry_out[i] = (u == 0 && carry_in != NULL) ? carry_in[i] : 0x03020100u;
+                    carry_out[i] = (u == 0 && carry_in != NULL) ? carry_in[i] : SSW_ORDER_RESET;
                 break;
             }
         }
         if (row < 0 && !from_start) {
             from_start = true;
             for (int i = 0; i < m->n_cbf; ++i)
-                carry_out[i] = carry_in != NULL ? carry_in[i] : 0x03020100u;
+                carry_out[i] = carry_in != NULL ? carry_in[i] : SSW_ORDER_RESET;
         }
     }
     if (from_start)
@@ -844,7 +844,7 @@ score_batch_impl(ssw_model_t *m, const ScoreReq &R)
     refresh_knobs(m); /* tests: knobs flipped between calls on one model */
     if (R.carry_out != NULL && (R.n_frames == 0 || R.n_utts == 0)) { /* nothing scored: state unchanged */
         for (int i = 0; i < m->n_cbf; ++i)
-            R.carry_out[i] = R.carry_in ? R.carry_in[i] : 0x03020100u;
+            R.carry_out[i] = R.carry_in ? R.carry_in[i] : SSW_ORDER_RESET;
     }
     if (R.n_frames == 0 || R.n_utts == 0)
         return 0;

@@ -38,6 +38,14 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 #define SSW_MFMA_WIDEN 1.8537045e-05f /* (3 K + 17 + 6) 2^-24 with K = 96 (ssw_model.c) */
 #define SSW_MFMA_XMAX 255.0f          /* |x_j| beyond this: x_j^2 does not fit binary16 */
 
+/* this scan's form of key for scan_upper_bound (ssw_scan_common.inc): scaled by a power of two
+ * per codebook x stream, widened by the part of the error bound that grows with the key */
+struct ScanKeysMfma {
+    static constexpr float widen = SSW_MFMA_WIDEN;
+    float scale;
+    __device__ __forceinline__ float unscaled(float ub) const { return ub * scale; }
+};
+
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 struct SplitX {
@@ -232,11 +240,31 @@ mfma_swap_merge(float (&LA)[5], float (&LB)[5], float (&L)[5])
 }
 
 /* density index of a label: 32 rb + 8 (r / 4) + 4 half + r % 4 */
-__device__ __forceinline__ uint32_t
+__host__ __device__ __forceinline__ constexpr uint32_t
 mfma_label_density(uint32_t lab)
 {
     return ((lab >> 4) & 3u) * 32u + ((lab >> 2) & 3u) * 8u + (lab >> 6) * 4u + (lab & 3u);
 }
+
+/* ... and the label of a density: bits 0-1 = r % 4, 2 = half, 3-4 = r / 4, 5-6 = rb of the index
+ * go to bits 0-1, 6, 2-3, 4-5 of the label */
+__host__ __device__ __forceinline__ constexpr uint32_t
+mfma_density_label(int cw)
+{
+    return (uint32_t)((cw & 3) | ((cw >> 3) & 3) << 2 | (cw >> 5) << 4 | ((cw >> 2) & 1) << 6);
+}
+
+/* the two are inverses, on all 128 densities */
+constexpr bool
+mfma_labels_invert()
+{
+    for (int cw = 0; cw < 128; ++cw)
+        if (mfma_label_density(mfma_density_label(cw)) != (uint32_t)cw
+            || mfma_density_label((int)mfma_label_density((uint32_t)cw)) != (uint32_t)cw)
+            return false;
+    return true;
+}
+static_assert(mfma_labels_invert(), "mfma_density_label is the inverse of mfma_label_density");
 
 /* NSTEP = 64-frame steps per wave: 2 (a wave owns 128 frames) or 1 (64 frames, twice the
  * workgroups: the chip's 1,024 workgroup slots are then refilled as groups finish instead of
@@ -492,9 +520,7 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
                                    : __builtin_amdgcn_readlane((int)my_ex1, i - 64);
             float dd = exact_row((uint32_t)cwx);
             dd = (dd - d0) * inv_scale; /* into the scan's scaled domain (a power of two: exact) */
-            /* label of density cwx = 32 rb + 8 (r / 4) + 4 half + r % 4 */
-            const uint32_t lab = (uint32_t)((cwx & 3) | ((cwx >> 3) & 3) << 2 | (cwx >> 5) << 4
-                                            | ((cwx >> 2) & 1) << 6);
+            const uint32_t lab = mfma_density_label(cwx);
             const float key = __uint_as_float((__float_as_uint(dd) & keymask) | lab);
             SSW_TOP5_INSERT(L, key)
         }
@@ -508,35 +534,11 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
             dv[k] = exact_row((uint32_t)c[k]);
             sk[k] = MS ? ms_fden(dv[k]) : dens2int(dv[k]);
         }
-#define CSWAP(a, b)                                                                          \
-    {                                                                                        \
-        bool sw_ = MS ? (dv[b] > dv[a]) : (sk[b] > sk[a]);                                   \
-        int ts = sw_ ? sk[b] : sk[a], tc = sw_ ? c[b] : c[a];                                \
-        float td = sw_ ? dv[b] : dv[a];                                                      \
-        sk[b] = sw_ ? sk[a] : sk[b];                                                         \
-        c[b] = sw_ ? c[a] : c[b];                                                            \
-        dv[b] = sw_ ? dv[a] : dv[b];                                                         \
-        sk[a] = ts;                                                                          \
-        c[a] = tc;                                                                           \
-        dv[a] = td;                                                                          \
-    }
-        CSWAP(0, 1) CSWAP(2, 3) CSWAP(0, 2) CSWAP(1, 3) CSWAP(1, 2)
-#undef CSWAP
-        /* upper bound on every density outside the four: the 5th key, its 7 borrowed bits
-         * pushed up, widened by the part of the error bound that grows with the key
-         * (ssw_model.c), moved back to absolute */
-        uint32_t kb5 = __float_as_uint(L[4]);
-        float ub = __uint_as_float((kb5 & 0x80000000u) ? (kb5 & ~127u) : (kb5 | 127u));
-        ub = ub * scale; /* back from the scaled domain (a power of two) */
-        ub = ub + __builtin_fabsf(ub) * SSW_MFMA_WIDEN + 1.0e-3f;
-        ub = ub + d0;
-        ub = ub + __builtin_fabsf(ub) * 2.384185791015625e-07f;
-        bool proven;
-        if (MS)
-            proven = dv[0] > dv[1] && dv[1] > dv[2] && dv[2] > dv[3] && dv[3] > ub;
-        else
-            proven = sk[0] > sk[1] && sk[1] > sk[2] && sk[2] > sk[3] && ub == ub
-                && sk[3] > dens2int(ub);
+        /* sorted best first, then the proof: four distinct values above the bound the 5th key
+         * puts on every other density (ssw_scan_common.inc) */
+        sort4_best_first<MS>(sk, c, dv);
+        const ScanBound ub = scan_upper_bound(L[4], ScanKeysMfma{ scale }, d0);
+        bool proven = scan_proven<MS>(sk, dv, ub);
         /* a feature whose square does not fit binary16 made every key of this frame -inf or
          * NaN: nothing the scan says about it can be trusted (a NaN feature hides from v_max,
          * but then the four exact values are NaN and the tests above have already failed) */
@@ -560,8 +562,7 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
          * one codeword four times.)  Ties among the four no longer cost the floor: tying frames
          * are most of what is redone. */
         const int floor_s = (L[3] > -4.0e9f && am5 <= SSW_MFMA_XMAX) ? sk[3] : INT_MIN;
-        const uint32_t cpk_s = (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16)
-            | ((uint32_t)c[3] << 24);
+        const uint32_t cpk_s = order_pack(c);
         unsigned long long need_s = __ballot(!proven && t < P.n_frames);
         if (AUDIT && audit_wave) {
             const unsigned long long proven_s = __ballot(proven && t < P.n_frames);
@@ -587,16 +588,18 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
     }
     SSW_TL(2)
 
-    /* Exact in-wave pass (as in ptm_topn_frames_kernel, whose frame layout this now is: lane l
-     * of step h owns frame t_base + 64 h + l): unproven pairs redone by the whole wave in frame
-     * order; the frame before is the neighbouring lane, lane 63 of the step before, or -- for
-     * the tile's first frame, or behind a frame that did not scan this codebook -- re-derived. */
-    if (P.seg_of_frame != nullptr) { /* pairs of unscanned codebooks are nobody's input */
+    /* Exact in-wave pass: unproven pairs redone by the whole wave in frame order; the frame
+     * before is the neighbouring lane, lane 63 of the step before, or -- for the tile's first
+     * frame, or behind a frame that did not scan this codebook -- re-derived.  What it must do is
+     * stated once, in ssw_scan_common.inc ("the exact in-wave pass"); its text stays here and in
+     * ptm_topn_frames_kernel because any function around it, or around its choice of the carried
+     * order alone, changes this kernel's default instances.  Here: the utterance-start bits are
+     * the words prefetched above, the floor is the one kept per step (s3), and a redone pair is
+     * stored at once (the scan has already stored what it found). */
+    if (P.seg_of_frame != nullptr) {
 #pragma unroll
         for (int q = 0; q < NSTEP; ++q) {
-            const int tq = t_base + 64 * q + lane;
-            need[q] &= __ballot(tq < P.n_frames
-                                && cb_scanned(P, cbf / P.n_feat, tq < P.n_frames ? tq : 0));
+            need[q] &= scan_mask_unscanned(P, cbf, t_base + 64 * q + lane);
             audited[q] &= need[q];
         }
     }
@@ -644,9 +647,7 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
                         const uint32_t pk = l == 0
                             ? (uint32_t)__builtin_amdgcn_readlane((int)cpk[0], 63)
                             : (uint32_t)__builtin_amdgcn_readlane((int)cpk[h], l - 1);
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            Lc[k] = (int)((pk >> (8 * k)) & 0xffu);
+                        order_unpack(pk, Lc);
                     }
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
@@ -664,8 +665,7 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     if (lane == l) {
                         const size_t idx = (size_t)t * P.n_cbf + cbf;
-                        const uint32_t newpk = (uint32_t)Lc[0] | ((uint32_t)Lc[1] << 8)
-                            | ((uint32_t)Lc[2] << 16) | ((uint32_t)Lc[3] << 24);
+                        const uint32_t newpk = order_pack(Lc);
                         const int *old = reinterpret_cast<const int *>(P.topn_sc + idx);
                         bool same = __hip_atomic_load(P.topn_cw + idx, __ATOMIC_RELAXED,
                                                       __HIP_MEMORY_SCOPE_AGENT) == newpk;
@@ -678,8 +678,7 @@ ptm_topn_mfma_kernel(const float *__restrict__ rec, const uint4 *__restrict__ wf
                     }
                 }
                 if (lane == l) {
-                    cpk[h] = (uint32_t)Lc[0] | ((uint32_t)Lc[1] << 8) | ((uint32_t)Lc[2] << 16)
-                        | ((uint32_t)Lc[3] << 24);
+                    cpk[h] = order_pack(Lc);
                     const size_t idx = (size_t)t * P.n_cbf + cbf;
                     P.topn_cw[idx] = cpk[h];
                     P.topn_sc[idx] = make_int4(Ls[0], Ls[1], Ls[2], Ls[3]);

@@ -202,7 +202,7 @@ fpa_carry_rows_kernel(FramesParams P, const float *__restrict__ rec28, const flo
 {
     const int u = (int)blockIdx.x / P.n_cbf, cbf = (int)blockIdx.x % P.n_cbf, lane = threadIdx.x;
     const int t0 = utt_off[u], n = utt_off[u + 1] - t0;
-    uint32_t pk = 0x03020100u; /* an utterance of one frame never wrote slot 1: the reset order */
+    uint32_t pk = SSW_ORDER_RESET; /* an utterance of one frame never wrote slot 1: the reset order */
     if (n >= 2) {
         const int last_odd = t0 + ((n >> 1) << 1) - 1; /* T even: its last frame; T odd: T - 2 */
         const float *srow0 = rec28 + ((size_t)cbf * 128 + lane) * SSW_REC28_FLOATS;
@@ -210,7 +210,7 @@ fpa_carry_rows_kernel(FramesParams P, const float *__restrict__ rec28, const flo
         int Lc[4];
         carried_order_masked<13, true>(P, cbf, feats, P.featoff[cbf % P.n_feat], last_odd, lane, srow0,
                                        srow1, 0, Lc);
-        pk = (uint32_t)Lc[0] | ((uint32_t)Lc[1] << 8) | ((uint32_t)Lc[2] << 16) | ((uint32_t)Lc[3] << 24);
+        pk = order_pack(Lc);
     }
     if (lane == 0)
         rows[(size_t)u * P.n_cbf + cbf] = pk;

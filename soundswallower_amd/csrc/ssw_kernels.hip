@@ -13,11 +13,17 @@
  *   ssw_k1a_chain.inc    ptm_topn_chain_kernel (exact frame-sequential top-N: eval_topn + eval_cb,
  *                        src/ptm_mgau.c:86-225) and topn_exact_step, the exact step the scans'
  *                        in-wave pass shares
+ *   ssw_scan_common.inc  what the two speculative top-N scans share, each piece once: FramesParams,
+ *                        the packed codeword order, the sort of the four candidates, the 5th-key
+ *                        bound and the proof test, the mask of unscanned codebooks, the helpers of
+ *                        the exact in-wave pass (wave_frame_densities, topn_self_determined,
+ *                        start_order, carried_order_of, the masked walk, ms_exact_step) and the
+ *                        statement of what that pass, written in each scan, must do
  *   ssw_k1a_frames.inc   ptm_topn_frames_kernel (speculative history-free top-N on the vector
- *                        unit with a proof test per pair; the exact in-wave pass and its helpers)
+ *                        unit with a proof test per pair), gather_last_orders_kernel
  *   ssw_k1a_mfma.inc     ptm_topn_mfma_kernel: the same scan with its multiply-adds on the matrix
- *                        cores (keys from two-part binary16 operands, exact re-evaluation and
- *                        in-wave pass as above): what every batch takes
+ *                        cores (keys from two-part binary16 operands, exact re-evaluation, proof
+ *                        and in-wave pass as above): what every batch takes
  *   ssw_k1b_senone.inc   ptm_senone_kernel (codebook_norm + senone_eval, src/ptm_mgau.c:264-403),
  *                        ptm_senone_frame_kernel (one frame, active sets), ms_senone_kernel
  *   ssw_k4_feat.inc      feat_1s_c_d_dd_kernel (batch CMN + 1s_c_d_dd, src/feat.c:271-326)
@@ -129,6 +135,7 @@
 namespace {
 #include "ssw_dev_common.inc"
 #include "ssw_k1a_chain.inc"
+#include "ssw_scan_common.inc"
 #include "ssw_k1a_frames.inc"
 #include "ssw_top5_select.inc"
 #include "ssw_k1a_mfma.inc"

@@ -20,8 +20,9 @@ import soundswallower_amd as ssw
 from tests.conftest import MODEL_ROOT
 
 def widen(key, d0):
-    """The three statements after the scan (ssw_k1a_frames.inc, 'upper bound on the true
-    value of every density outside the four'), in float32 like the kernel."""
+    """The three statements after the scan (scan_upper_bound with ScanKeysFma,
+    ssw_scan_common.inc: 'upper bound on the true value of every density outside the four'),
+    in float32 like the kernel."""
     key = key.astype(np.float32)
     ub = key + np.abs(key) * np.float32(104.0 * 2.0 ** -24) + np.float32(1.0e-3)
     ub = ub + np.float32(d0)
