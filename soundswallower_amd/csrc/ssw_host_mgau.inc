@@ -354,12 +354,8 @@ mgau_frame_eval(ssw_mgau_t *mg, int16_t *senscr, uint8_t *senone_active,
             if (sen_act[s] && raw[s] < best)
                 best = raw[s];
         for (int s = 0; s < h->n_sen; ++s)
-            if (sen_act[s]) {
-                int bs = raw[s] - best;
-                bs = bs > 32767 ? 32767 : bs;
-                bs = bs < -32768 ? -32768 : bs;
-                senscr[s] = (int16_t)bs;
-            }
+            if (sen_act[s])
+                senscr[s] = (int16_t)clamp_i16(raw[s] - best);
         return 0;
     }
 

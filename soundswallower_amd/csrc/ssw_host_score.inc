@@ -239,7 +239,7 @@ launch_senone(const ScoreCall &C, int lo, int hi, bool move_stats)
         return -1;
     }
     if (scorer == SSW_SCORER_MS && !ms_packed) {
-        lds = 256 + 20 * (size_t)m->n_cbf + 16 * sizeof(int);
+        lds = MsSenoneCarve(m->n_cbf).bytes();
 #define SSW_MS_LAUNCH(RR)                                                                    \
     if (h->n_feat == 3 && !kn.sen_generic)                                                   \
         hipLaunchKernelGGL((ms_senone_kernel<RR, 3>), dim3(n_frames), dim3(threads), lds, st, S); \
@@ -266,12 +266,7 @@ launch_senone(const ScoreCall &C, int lo, int hi, bool move_stats)
                       m->n_quads, m->n_cbf);
         return -1;
     }
-    /* LDS: mirrored table | norm[3][fpb][8] | red[16] | item[2][n_cbf][fpb] of 32 bytes */
-    lds = (ms_packed ? 2 * SSW_LOGADD_MIRROR : SSW_LOGADD_MIRROR)
-        + 3 * 4 * (size_t)(ms_packed ? ((h->n_cb + 7) & ~7) : SSW_MAX_FEAT) * fpb + 16 * sizeof(int)
-        + 2 * 32 * (size_t)m->n_cbf * fpb
-        + 20 * (size_t)((fpb * m->n_cbf + 63) & ~63) /* DMA staging: scores + codewords */
-        + 16;
+    lds = SenoneCarve(fpb, m->n_cbf, h->n_cb, ms_packed).bytes();
     /* persistent groups: as many as the chip holds at once (32 wave slots per CU), each taking
      * the units (fpb frames) g, g + grid, ...; SSW_SEN_GROUPS overrides (tuning: 0 = one group
      * per unit, the round-2 form) */
@@ -374,9 +369,7 @@ launch_active(const ScoreCall &C, int lo, int hi)
         L.nw32 = (h->n_sen + 31) / 32;
         if (L.cap <= 0 || L.cap > h->n_sen)
             L.cap = h->n_sen; /* (the caller's bound on a frame's listed entries) */
-        const size_t per_wave = ((ms ? 0 : 8 * (size_t)m->n_cbf) + 4 * (size_t)((L.cap + 1) & ~1)
-                                 + 16 + 15) & ~(size_t)15;
-        const size_t lds = 4 * per_wave;
+        const size_t lds = ListedCarve(ms, m->n_cbf, L.cap).bytes();
         if (lds > 48 * 1024) {
             const hipError_t ea = hipFuncSetAttribute(
                 ms ? (const void *)senone_listed_kernel<true> : (const void *)senone_listed_kernel<false>,
@@ -392,9 +385,7 @@ launch_active(const ScoreCall &C, int lo, int hi)
     }
     SenoneActive2Params A = *act->a2;
     fill_active_common(C, A, lo, hi);
-    const size_t per_wave = (ms ? 0 : 8 * (size_t)m->n_cbf) + 2 * (size_t)((A.cap + 1) & ~1)
-        + (A.out_full != NULL ? 2 * (size_t)((h->n_sen + 1) & ~1) : 0);
-    const size_t lds = 4 * ((per_wave + 15) & ~(size_t)15);
+    const size_t lds = Active2Carve(ms, m->n_cbf, A.cap, h->n_sen, A.out_full != NULL).bytes();
     if (ms)
         hipLaunchKernelGGL(senone_active2_kernel<true>, grid, dim3(256), lds, st, A);
     else

@@ -159,8 +159,7 @@ cont_score_kernel(const float *__restrict__ tab, const uint8_t *__restrict__ pdf
             int v = scr[r];
             if (P.aw != 1)
                 v = v / P.aw; /* C division truncates toward zero */
-            v = v > 32767 ? 32767 : v;
-            v = v < -32768 ? -32768 : v;
+            v = clamp_i16(v);
             scr[r] = v;
             if (t0 + r < P.n_frames)
                 P.raw[(size_t)(t0 + r) * P.n_sen + sen] = (int16_t)v;
@@ -183,9 +182,6 @@ cont_norm_kernel(ContParams P)
     const size_t row = (size_t)blockIdx.x * P.n_sen;
     const int best = RAW ? 0 : P.fmin[blockIdx.x];
     for (int s = threadIdx.x; s < P.n_sen; s += 256) {
-        int bs = (int)P.raw[row + s] - best; /* src/ms_mgau.c:314-320 */
-        bs = bs > 32767 ? 32767 : bs;
-        bs = bs < -32768 ? -32768 : bs;
-        P.out[row + s] = (int16_t)bs;
+        P.out[row + s] = final_score<true>((int)P.raw[row + s], best);
     }
 }

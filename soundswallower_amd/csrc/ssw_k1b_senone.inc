@@ -48,25 +48,6 @@ struct SenoneParams {
 
 constexpr int SEN_MAX_THREADS = 1024;
 
-#define SSW_LOGADD_LDS 512 /* 8-bit log-add table in LDS: 256 entries + zero padding */
-/* the batch kernel's copy: T - tab[|s|] for s = -512 .. 511 at LDS address 512 + s, so that a
- * SIGNED difference indexes it (ds_read_u8 v, s offset:512: the address adder wraps, measured by
- * tools/microbench/addr_probe.hip) and the chain needs min(x, y) only, not max(x, y) as well */
-#define SSW_LOGADD_MIRROR 1024
-
-/* fast_logmath_add (tied_mgau_common.h:100-117): min(x, y) - table[|x - y|] */
-__device__ __forceinline__ int
-fast_logadd(int x, int y, const uint8_t *tab)
-{
-    /* x is the running value: it can dip up to 3 T below zero (two equal entries whose value is
-     * below tab[0]), so |x - y| is taken on the full ints (a 16-bit SAD would see the sign
-     * extension as a difference of 2^16).  d <= 351 + 3 T < SSW_LOGADD_LDS: the callers' tables
-     * are padded with zeros to 512 entries, the value every entry from 29 up holds. */
-    const int hi = x > y ? x : y;
-    const int r = x < y ? x : y;
-    return r - (int)tab[hi - r];
-}
-
 typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
 typedef uint32_t uint2u __attribute__((ext_vector_type(2), aligned(2))); /* 2-byte aligned 8 bytes */
 typedef uint32_t uint1u __attribute__((aligned(2)));                     /* 2-byte aligned 4 bytes */
@@ -183,18 +164,15 @@ quad_chains(const uint32_t (*mw)[TOPN], const uint2 *np, uint32_t (&acc)[2])
         acc[c & 1] += x2[c];
 }
 
-/* logmath_add on the shift-10 table (src/logmath.c:228-272): max(x, y) + table[|x - y|], with
- * the "zero" short-cuts; the table has exactly 256 entries for the bases the loader accepts. */
-__device__ __forceinline__ int
-ms_logadd(int x, int y, int zero, const uint8_t *tab)
+/* the four mixture-weight rows of one stream of a quad (its slots' weights for the four codewords),
+ * a dword each: ro = the rows' byte offsets as staged, soff = the round's offset */
+__device__ __forceinline__ void
+load_quad_rows(__amdgpu_buffer_rsrc_t mw_rsrc, uint4 ro, int soff, uint32_t (&mw)[4])
 {
-    int d = x > y ? x - y : y - x;
-    int r = x > y ? x : y;
-    int add = d < 256 ? (int)tab[d < 256 ? d : 255] : 0;
-    int v = r + add;
-    v = (y <= zero) ? x : v;
-    v = (x <= zero) ? y : v;
-    return v;
+    mw[0] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.x, soff, 0);
+    mw[1] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.y, soff, 0);
+    mw[2] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.z, soff, 0);
+    mw[3] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.w, soff, 0);
 }
 
 /* One frame of the ms scorer by the whole workgroup with the reference's own arithmetic
@@ -214,33 +192,13 @@ ms_exact_frame(const SenoneParams &P, int t, int tid, int nthr, int *scratch)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             v[j] = 0;
-        for (int f = 0; f < P.n_feat; ++f) {
-            const uint32_t cw4 = P.topn_cw[(size_t)t * n_cbf + cb * P.n_feat + f];
-            const int4 fd4 = P.topn_sc[(size_t)t * n_cbf + cb * P.n_feat + f];
-            const int fd[4] = { fd4.x, fd4.y, fd4.z, fd4.w };
-            uint32_t mw[4];
+        for (int f = 0; f < P.n_feat; ++f)
+            ms_quad_scores(mq, f, P.n_density, P.slot_stride,
+                           P.topn_cw[(size_t)t * n_cbf + cb * P.n_feat + f],
+                           P.topn_sc[(size_t)t * n_cbf + cb * P.n_feat + f], P.zero, P.logadd8, v);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t cw = (cw4 >> (8 * k)) & 0xffu;
-                mw[k] = *reinterpret_cast<const uint32_t *>(
-                    mq + ((size_t)f * P.n_density + cw) * P.slot_stride);
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int fscr = fd[0] - (int)((mw[0] >> (8 * j)) & 0xffu);
-#pragma unroll
-                for (int k = 1; k < 4; ++k) {
-                    int fw = fd[k] - (int)((mw[k] >> (8 * j)) & 0xffu);
-                    fscr = ms_logadd(fscr, fw, P.zero, P.logadd8);
-                }
-                v[j] -= fscr;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[j] = v[j] > 32767 ? 32767 : v[j];
-            v[j] = v[j] < -32768 ? -32768 : v[j];
-        }
+        for (int j = 0; j < 4; ++j)
+            v[j] = ms_finish(v[j], 1); /* (aw != 1 stays with ms_senone_kernel) */
     };
     int best = INT_MAX;
 #pragma unroll 1
@@ -280,6 +238,9 @@ ms_exact_frame(const SenoneParams &P, int t, int tid, int nthr, int *scratch)
             const int sj[4] = { s4.x, s4.y, s4.z, s4.w };
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
+                /* final_score<true> (ssw_senone_common.inc) as text: through the call -- or
+                 * through clamp_i16 -- the clamp is scheduled one instruction earlier in the 16
+                 * MS COMPACT instances of ptm_senone_kernel, which stay byte-equal */
                 int bs = v[j] - best; /* src/ms_mgau.c:314-320 */
                 bs = bs > 32767 ? 32767 : bs;
                 bs = bs < -32768 ? -32768 : bs;
@@ -348,9 +309,15 @@ ptm_senone_kernel(SenoneParams P)
      * <= 255 + 96 and the running value can dip 3 T below zero (the host refuses tables with
      * 351 + 3 T >= 512).  It holds T - tab[|s|] mirrored around LDS address 512 (this kernel has
      * no static LDS: its dynamic LDS starts at 0, which is what the look-ups' asm assumes).
-     * Carve: tab[1024] | norm[3][FPB][8] | red[3][FPB] (+ pad) | item[2][n_cbf][FPB] 32 B |
-     * stage_sc[pad64(FPB n_cbf)] int4 | stage_cw[..].  norm / red have three slots (unit i uses slot i % 3): a slot
-     * is re-armed two barriers after its last reader and two before its next writer. */
+     * The carve is SenoneCarve's (ssw_senone_lds.inc), from which launch_senone takes the byte
+     * count: tab[MIRROR] | norm[3][FPB][NORM_W] | red[16] | item[2][n_cbf][FPB] 32 B |
+     * stage_sc[pad64(FPB n_cbf)] int4 | stage_cw[..].  It stays written out here as typed-pointer
+     * steps: taken from the struct's byte offsets the same addresses are computed by other
+     * instructions and every instance's set-up is scheduled differently.
+     * tests/harness/senone_lds_host.cpp holds these lines verbatim and compares them with the
+     * struct region by region: change both together.  norm / red have three slots (unit i uses
+     * slot i % 3): a slot is re-armed two barriers after its last reader and two before its next
+     * writer. */
     uint8_t *s_tab = smem;
     /* norm: PTM [3][FPB][8] per-stream normalisers; MS [3][FPB][NORM_W] sums of fden_0 per codebook */
     const int NORM_W = MS ? ((P.n_cb + 7) & ~7) : SSW_MAX_FEAT;
@@ -530,10 +497,8 @@ ptm_senone_kernel(SenoneParams P)
             s_norm[i] = MS ? 0 : SSW_WORST_SCORE;
     if (tid < 16)
         s_red[tid] = tid < 12 ? INT_MAX : 0;
-    if (P.nfixed != nullptr && blockIdx.x == 0 && tid == 0) {
-        P.nfixed[1] = (P.nfixed_acc ? P.nfixed[1] : 0ull) + P.nfixed[0];
-        P.nfixed[0] = 0ull;
-    }
+    if (P.nfixed != nullptr && blockIdx.x == 0 && tid == 0)
+        move_exact_count(P.nfixed, P.nfixed_acc);
     lds_barrier();
     norm_item(u, 0);
 #pragma unroll
@@ -627,10 +592,7 @@ ptm_senone_kernel(SenoneParams P)
                                 np[f] = make_uint2(sc4.x, sc4.y);
                                 if (!MS)
                                     zsum += sc4.z;
-                                mw[f][0] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.x, soff, 0);
-                                mw[f][1] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.y, soff, 0);
-                                mw[f][2] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.z, soff, 0);
-                                mw[f][3] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.w, soff, 0);
+                                load_quad_rows(mw_rsrc, ro, soff, mw[f]);
                             }
                             if (!MS) {
                                 asc2[r][fr][0] += zsum;
@@ -647,10 +609,7 @@ ptm_senone_kernel(SenoneParams P)
                                 asc2[r][fr][1] += sc4.z;
                             }
                             uint32_t mw[1][TOPN];
-                            mw[0][0] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.x, soff, 0);
-                            mw[0][1] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.y, soff, 0);
-                            mw[0][2] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.z, soff, 0);
-                            mw[0][3] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(mw_rsrc, (int)ro.w, soff, 0);
+                            load_quad_rows(mw_rsrc, ro, soff, mw[0]);
                             quad_chains<1, TOPN, MID>(mw, &np, asc2[r][fr]);
                         }
                     }
@@ -945,8 +904,7 @@ ptm_frame_kernel(FrameFusedParams Q)
     const int c_out = blockIdx.x * nthr + tid; /* chunk of 8 senones this thread writes out */
     uint32_t act8 = 0;
     if (PHASE == 0 || PHASE == 2) {
-        for (int i = tid; i < SSW_LOGADD_LDS; i += nthr)
-            s_tab[i] = i < 256 ? P.logadd8[i] : (uint8_t)0;
+        logadd_table_to_lds(s_tab, P.logadd8, tid, nthr);
         if (tid < SSW_MAX_FEAT)
             s_norm[tid] = SSW_WORST_SCORE;
         if (sl < P.n_quads * 4) {
@@ -976,37 +934,14 @@ ptm_frame_kernel(FrameFusedParams Q)
                 atomicMax(&s_norm[i % P.n_feat], P.topn_sc[i].x >> SSW_SENSCR_SHIFT);
         __syncthreads();
         for (int i = tid; i < n_cbf; i += nthr) {
-            const int4 sc = P.topn_sc[i];
-            const int v[4] = { sc.x, sc.y, sc.z, sc.w };
-            const int norm = s_norm[i % P.n_feat];
-            const bool on = cb_on(i / P.n_feat) != 0ull;
-            uint32_t pk = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                int q = -((v[k] >> SSW_SENSCR_SHIFT) - norm);
-                q = q > SSW_MAX_NEG_ASCR ? SSW_MAX_NEG_ASCR : q;
-                q = on ? q : SSW_MAX_NEG_ASCR;
-                pk |= (uint32_t)(q & 0xff) << (8 * k);
-            }
-            s_ns4[i] = pk;
+            s_ns4[i] = ptm_norm_pack4(P.topn_sc[i], s_norm[i % P.n_feat], cb_on(i / P.n_feat) != 0ull);
             s_cw4[i] = P.topn_cw[i];
         }
         __syncthreads();
         /* senone_eval (src/ptm_mgau.c:326-403): one slot per thread */
         if (sen >= 0) {
-            int a = 0;
-            for (int f = 0; f < P.n_feat; ++f) {
-                const uint32_t cw4 = s_cw4[cb * P.n_feat + f], ns4 = s_ns4[cb * P.n_feat + f];
-                const uint8_t *mw = P.mixw + (size_t)f * P.n_density * P.slot_stride + sl;
-                int fden = (int)mw[(size_t)(cw4 & 0xffu) * P.slot_stride] + (int)(ns4 & 0xffu);
-#pragma unroll
-                for (int k = 1; k < 4; ++k) {
-                    int y = (int)mw[(size_t)((cw4 >> (8 * k)) & 0xffu) * P.slot_stride]
-                        + (int)((ns4 >> (8 * k)) & 0xffu);
-                    fden = fast_logadd(fden, y, s_tab);
-                }
-                a += fden;
-            }
+            const int a = ptm_slot_score(P.mixw + sl, P.n_feat, P.n_density, P.slot_stride,
+                                         s_cw4 + cb * P.n_feat, s_ns4 + cb * P.n_feat, s_tab);
             P.raw[sen] = (int16_t)a;
             best = a;
         }
@@ -1074,11 +1009,12 @@ ms_senone_kernel(SenoneParams P)
     extern __shared__ __align__(16) unsigned char smem[];
     const int n_cbf = P.n_cb * P.n_feat;
     /* LDS: static logadd[256] (constant address, folds into the lookups), then the dynamic
-     * carve (256 unused bytes) | fd[n_cbf] int4 | cw4[n_cbf] | red[16] */
+     * carve, MsSenoneCarve (ssw_senone_lds.inc) */
     __shared__ uint8_t s_tab[256];
-    int4 *s_fd = reinterpret_cast<int4 *>(smem + 256);
-    uint32_t *s_cw4 = reinterpret_cast<uint32_t *>(s_fd + n_cbf);
-    int *s_red = reinterpret_cast<int *>(s_cw4 + n_cbf);
+    const MsSenoneCarve carve(n_cbf);
+    int4 *s_fd = reinterpret_cast<int4 *>(smem + carve.fd());
+    uint32_t *s_cw4 = reinterpret_cast<uint32_t *>(smem + carve.cw4());
+    int *s_red = reinterpret_cast<int *>(smem + carve.red());
 
     const int t = blockIdx.x;
     const int tid = threadIdx.x;
@@ -1089,10 +1025,8 @@ ms_senone_kernel(SenoneParams P)
         s_fd[tid] = P.topn_sc[(size_t)t * n_cbf + tid];
         s_cw4[tid] = P.topn_cw[(size_t)t * n_cbf + tid];
     }
-    if (P.nfixed != nullptr && t == 0 && tid == 0) {
-        P.nfixed[1] = (P.nfixed_acc ? P.nfixed[1] : 0ull) + P.nfixed[0];
-        P.nfixed[0] = 0ull;
-    }
+    if (P.nfixed != nullptr && t == 0 && tid == 0)
+        move_exact_count(P.nfixed, P.nfixed_acc);
     lds_barrier();
 
     const int n_feat = NF ? NF : P.n_feat;
@@ -1111,36 +1045,13 @@ ms_senone_kernel(SenoneParams P)
             const uint8_t *mq = P.mixw + (size_t)q * 4;
             sen4[r] = P.slot_sen[q];
 #pragma unroll
-            for (int f = 0; f < n_feat; ++f) {
-                const uint32_t cw4 = s_cw4[cb * n_feat + f];
-                const int4 fd4 = s_fd[cb * n_feat + f];
-                const int fd[4] = { fd4.x, fd4.y, fd4.z, fd4.w };
-                uint32_t mw[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t cw = (cw4 >> (8 * k)) & 0xffu;
-                    mw[k] = *reinterpret_cast<const uint32_t *>(
-                        mq + ((size_t)f * P.n_density + cw) * P.slot_stride);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    int fscr = fd[0] - (int)((mw[0] >> (8 * j)) & 0xffu);
-#pragma unroll
-                    for (int k = 1; k < 4; ++k) {
-                        int fw = fd[k] - (int)((mw[k] >> (8 * j)) & 0xffu);
-                        fscr = ms_logadd(fscr, fw, P.zero, s_tab);
-                    }
-                    scr[r][j] -= fscr;
-                }
-            }
+            for (int f = 0; f < n_feat; ++f)
+                ms_quad_scores(mq, f, P.n_density, P.slot_stride, s_cw4[cb * n_feat + f],
+                               s_fd[cb * n_feat + f], P.zero, s_tab, scr[r]);
             const int sj[4] = { sen4[r].x, sen4[r].y, sen4[r].z, sen4[r].w };
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                int v = scr[r][j];
-                if (P.aw != 1) /* (wave-uniform; 1 is the default) */
-                    v = v / P.aw; /* C division truncates toward zero */
-                v = v > 32767 ? 32767 : v;
-                v = v < -32768 ? -32768 : v;
+                const int v = ms_finish(scr[r][j], P.aw); /* (wave-uniform; 1 is the default) */
                 scr[r][j] = v;
                 if (sj[j] >= 0)
                     best = v < best ? v : best;
@@ -1169,12 +1080,8 @@ ms_senone_kernel(SenoneParams P)
             const int sj[4] = { sen4[r].x, sen4[r].y, sen4[r].z, sen4[r].w };
             int16_t v[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int bs = scr[r][j] - best; /* src/ms_mgau.c:314-320 */
-                bs = bs > 32767 ? 32767 : bs;
-                bs = bs < -32768 ? -32768 : bs;
-                v[j] = (int16_t)bs;
-            }
+            for (int j = 0; j < 4; ++j)
+                v[j] = final_score<true>(scr[r][j], best);
             if (sj[0] >= 0 && sj[1] == sj[0] + 1 && sj[2] == sj[0] + 2 && sj[3] == sj[0] + 3) {
                 short4u pk = { v[0], v[1], v[2], v[3] }; /* consecutive ids: one 8-byte store */
                 *reinterpret_cast<short4u *>(orow + sj[0]) = pk;
@@ -1265,15 +1172,13 @@ senone_active2_kernel(SenoneActive2Params P)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     /* per wave: PTM normalised scores and codewords of every (codebook, stream), 4 x 8 bits
      * each | raw scores of the listed entries | the [n_sen] row (out_full only) */
-    const size_t per_wave = (MS ? 0 : 8 * (size_t)n_cbf) + 2 * (size_t)((P.cap + 1) & ~1)
-        + (P.out_full != nullptr ? 2 * (size_t)((P.n_sen + 1) & ~1) : 0);
-    unsigned char *mine = smem + (size_t)w * ((per_wave + 15) & ~(size_t)15);
-    uint32_t *s_ns4 = reinterpret_cast<uint32_t *>(mine);
-    uint32_t *s_cw4 = s_ns4 + (MS ? 0 : n_cbf);
-    int16_t *s_a = reinterpret_cast<int16_t *>(s_cw4 + (MS ? 0 : n_cbf));
-    int16_t *s_row = s_a + ((P.cap + 1) & ~1);
-    for (int i = tid; i < SSW_LOGADD_LDS; i += 256)
-        s_tab[i] = i < 256 ? P.logadd8[i] : (uint8_t)0;
+    const Active2Carve carve(MS, n_cbf, P.cap, P.n_sen, P.out_full != nullptr);
+    unsigned char *mine = smem + carve.wave(w);
+    uint32_t *s_ns4 = reinterpret_cast<uint32_t *>(mine + carve.ns4());
+    uint32_t *s_cw4 = reinterpret_cast<uint32_t *>(mine + carve.cw4());
+    int16_t *s_a = reinterpret_cast<int16_t *>(mine + carve.a());
+    int16_t *s_row = reinterpret_cast<int16_t *>(mine + carve.row());
+    logadd_table_to_lds(s_tab, P.logadd8, tid, 256);
     __syncthreads();
     const int t = P.frame_base + (int)blockIdx.x * 4 + w;
     if (t >= P.frame_base + P.n_frames)
@@ -1290,44 +1195,7 @@ senone_active2_kernel(SenoneActive2Params P)
     const uint32_t *cw = P.topn_cw + (size_t)(t - P.frame_base) * n_cbf;
     const int4 *sc = P.topn_sc + (size_t)(t - P.frame_base) * n_cbf;
     if (!MS) {
-        const unsigned long long cbmask = P.seg_cbmask[seg];
-        /* per-stream normaliser over the active codebooks (src/ptm_mgau.c:271-278) */
-        int nm[SSW_MAX_FEAT];
-#pragma unroll
-        for (int f = 0; f < SSW_MAX_FEAT; ++f)
-            nm[f] = SSW_WORST_SCORE;
-        for (int i = lane; i < n_cbf; i += 64)
-            if ((cbmask >> (i / P.n_feat)) & 1ull) {
-                const int v = sc[i].x >> SSW_SENSCR_SHIFT;
-                const int f = i % P.n_feat;
-#pragma unroll
-                for (int k = 0; k < SSW_MAX_FEAT; ++k)
-                    nm[k] = (k == f && v > nm[k]) ? v : nm[k];
-            }
-#pragma unroll
-        for (int f = 0; f < SSW_MAX_FEAT; ++f)
-            nm[f] = f < P.n_feat ? wave_max_dpp(nm[f]) : 0;
-        for (int i = lane; i < n_cbf; i += 64) {
-            const int4 v4 = sc[i];
-            const int v[4] = { v4.x, v4.y, v4.z, v4.w };
-            const int f = i % P.n_feat;
-            int norm = nm[0];
-#pragma unroll
-            for (int k = 1; k < SSW_MAX_FEAT; ++k)
-                norm = k == f ? nm[k] : norm;
-            const bool act = (cbmask >> (i / P.n_feat)) & 1ull;
-            uint32_t pk = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                int q = -((v[k] >> SSW_SENSCR_SHIFT) - norm);
-                q = q > SSW_MAX_NEG_ASCR ? SSW_MAX_NEG_ASCR : q;
-                if (!act)
-                    q = SSW_MAX_NEG_ASCR; /* src/ptm_mgau.c:353-364 */
-                pk |= (uint32_t)(q & 0xff) << (8 * k);
-            }
-            s_ns4[i] = pk;
-            s_cw4[i] = cw[i];
-        }
+        wave_codebook_norm(sc, cw, n_cbf, P.n_feat, P.seg_cbmask[seg], lane, s_ns4, s_cw4);
         wave_sync();
     }
     int best = INT_MAX;
@@ -1337,59 +1205,16 @@ senone_active2_kernel(SenoneActive2Params P)
             continue; /* not listed yet */
         const uint32_t ent = is_b ? P.bridge_ent[b0 + i - n_master] : real[i];
         const int sl = (int)(ent & 0xffffu), cb = (int)(ent >> 16);
-        int a = 0;
-        if (MS) {
-            /* senone_eval, src/ms_senone.c:314-362 */
-            for (int f = 0; f < P.n_feat; ++f) {
-                const uint32_t cw4 = cw[cb * P.n_feat + f];
-                const int4 fd4 = sc[cb * P.n_feat + f];
-                const int fd[4] = { fd4.x, fd4.y, fd4.z, fd4.w };
-                const uint8_t *mw = P.mixw + (size_t)f * P.n_density * P.slot_stride + sl;
-                int fscr = fd[0] - (int)mw[(size_t)(cw4 & 0xffu) * P.slot_stride];
-#pragma unroll
-                for (int k = 1; k < 4; ++k) {
-                    const int fw = fd[k] - (int)mw[(size_t)((cw4 >> (8 * k)) & 0xffu) * P.slot_stride];
-                    fscr = ms_logadd(fscr, fw, P.zero, s_tab);
-                }
-                a -= fscr;
-            }
-            if (P.aw != 1)
-                a = a / P.aw; /* C division truncates toward zero */
-            a = a > 32767 ? 32767 : a;
-            a = a < -32768 ? -32768 : a;
-        } else {
-            /* src/ptm_mgau.c:342-395 */
-            for (int f = 0; f < P.n_feat; ++f) {
-                const uint32_t cw4 = s_cw4[cb * P.n_feat + f], ns4 = s_ns4[cb * P.n_feat + f];
-                const uint8_t *mw = P.mixw + (size_t)f * P.n_density * P.slot_stride + sl;
-                int fden = (int)mw[(size_t)(cw4 & 0xffu) * P.slot_stride] + (int)(ns4 & 0xffu);
-#pragma unroll
-                for (int k = 1; k < 4; ++k) {
-                    const int y = (int)mw[(size_t)((cw4 >> (8 * k)) & 0xffu) * P.slot_stride]
-                        + (int)((ns4 >> (8 * k)) & 0xffu);
-                    fden = fast_logadd(fden, y, s_tab);
-                }
-                a += fden;
-            }
-        }
+        const int a = MS
+            ? ms_slot_score(P.mixw + sl, P.n_feat, P.n_density, P.slot_stride, cw + cb * P.n_feat,
+                            sc + cb * P.n_feat, P.zero, P.aw, s_tab)
+            : ptm_slot_score(P.mixw + sl, P.n_feat, P.n_density, P.slot_stride,
+                             s_cw4 + cb * P.n_feat, s_ns4 + cb * P.n_feat, s_tab);
         s_a[i] = (int16_t)a;
         best = a < best ? a : best;
     }
-    best = -wave_max_dpp(-(best == INT_MAX ? INT_MAX - 1 : best));
-    if (best == INT_MAX - 1)
-        best = 0; /* nothing listed (callers always list the alignment's first phone) */
+    best = wave_best_or_zero(best); /* 0: callers always list the alignment's first phone */
     wave_sync();
-    /* what acmod's buffer holds for a listed entry: PTM `senone_scores[i] -= bestscore` in int16
-     * (src/ptm_mgau.c:399); ms (score - best) with the clamp (src/ms_mgau.c:354-363) */
-    auto final_score = [&](int raw) -> int16_t {
-        if (MS) {
-            int bs = raw - best;
-            bs = bs > 32767 ? 32767 : bs;
-            bs = bs < -32768 ? -32768 : bs;
-            return (int16_t)bs;
-        }
-        return (int16_t)(raw - best);
-    };
     /* compact row: the real entries that are states of this utterance */
     int16_t *crow = P.out_c + P.crow_off[u] + (long long)(t - P.cutt_off[u]) * P.cstride[u];
     const uint32_t *cpos = P.cpos + (size_t)u * P.slot_stride;
@@ -1398,7 +1223,7 @@ senone_active2_kernel(SenoneActive2Params P)
             continue;
         const uint32_t cp = cpos[real[i] & 0xffffu];
         if (cp != 0xffffffffu)
-            crow[cp >> 1] = final_score((int)s_a[i]);
+            crow[cp >> 1] = final_score<MS>((int)s_a[i], best);
     }
     if (P.out_full != nullptr) {
         for (int sen = lane; sen < P.n_sen; sen += 64)
@@ -1409,7 +1234,7 @@ senone_active2_kernel(SenoneActive2Params P)
             if (!is_b && (int)rank[i] >= n_real)
                 continue;
             const uint32_t ent = is_b ? P.bridge_ent[b0 + i - n_master] : real[i];
-            s_row[P.slot_sen[ent & 0xffffu]] = final_score((int)s_a[i]);
+            s_row[P.slot_sen[ent & 0xffffu]] = final_score<MS>((int)s_a[i], best);
         }
         wave_sync();
         int16_t *orow = P.out_full + (size_t)t * P.n_sen;

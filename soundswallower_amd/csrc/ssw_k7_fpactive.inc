@@ -279,16 +279,14 @@ senone_listed_kernel(SenoneListedParams P)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     /* per wave: normalised scores and codewords of every (codebook, stream) | the list | its raw
      * scores | the entry counter */
-    const size_t per_wave = ((MS ? 0 : 8 * (size_t)n_cbf) + 4 * (size_t)((P.cap + 1) & ~1) + 16 + 15)
-        & ~(size_t)15;
-    unsigned char *mine = fpa_smem + (size_t)w * per_wave;
-    uint32_t *s_ns4 = reinterpret_cast<uint32_t *>(mine);
-    uint32_t *s_cw4 = s_ns4 + (MS ? 0 : n_cbf);
-    uint16_t *s_sen = reinterpret_cast<uint16_t *>(s_cw4 + (MS ? 0 : n_cbf));
-    int16_t *s_a = reinterpret_cast<int16_t *>(s_sen + ((P.cap + 1) & ~1));
-    int *s_n = reinterpret_cast<int *>(s_a + ((P.cap + 1) & ~1));
-    for (int i = tid; i < SSW_LOGADD_LDS; i += 256)
-        s_tab[i] = i < 256 ? P.logadd8[i] : (uint8_t)0;
+    const ListedCarve carve(MS, n_cbf, P.cap);
+    unsigned char *mine = fpa_smem + carve.wave(w);
+    uint32_t *s_ns4 = reinterpret_cast<uint32_t *>(mine + carve.ns4());
+    uint32_t *s_cw4 = reinterpret_cast<uint32_t *>(mine + carve.cw4());
+    uint16_t *s_sen = reinterpret_cast<uint16_t *>(mine + carve.sen());
+    int16_t *s_a = reinterpret_cast<int16_t *>(mine + carve.a());
+    int *s_n = reinterpret_cast<int *>(mine + carve.count());
+    logadd_table_to_lds(s_tab, P.logadd8, tid, 256);
     if (lane == 0)
         *s_n = 0;
     __syncthreads();
@@ -312,46 +310,8 @@ senone_listed_kernel(SenoneListedParams P)
             }
         }
     }
-    if (!MS) {
-        const unsigned long long cbmask = P.cbmask[t];
-        /* per-stream normaliser over the active codebooks (src/ptm_mgau.c:271-278) */
-        int nm[SSW_MAX_FEAT];
-#pragma unroll
-        for (int f = 0; f < SSW_MAX_FEAT; ++f)
-            nm[f] = SSW_WORST_SCORE;
-        for (int i = lane; i < n_cbf; i += 64)
-            if ((cbmask >> (i / P.n_feat)) & 1ull) {
-                const int v = sc[i].x >> SSW_SENSCR_SHIFT;
-                const int f = i % P.n_feat;
-#pragma unroll
-                for (int k = 0; k < SSW_MAX_FEAT; ++k)
-                    nm[k] = (k == f && v > nm[k]) ? v : nm[k];
-            }
-#pragma unroll
-        for (int f = 0; f < SSW_MAX_FEAT; ++f)
-            nm[f] = f < P.n_feat ? wave_max_dpp(nm[f]) : 0;
-        for (int i = lane; i < n_cbf; i += 64) {
-            const int4 v4 = sc[i];
-            const int v[4] = { v4.x, v4.y, v4.z, v4.w };
-            const int f = i % P.n_feat;
-            int norm = nm[0];
-#pragma unroll
-            for (int k = 1; k < SSW_MAX_FEAT; ++k)
-                norm = k == f ? nm[k] : norm;
-            const bool act = (cbmask >> (i / P.n_feat)) & 1ull;
-            uint32_t pk = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                int q = -((v[k] >> SSW_SENSCR_SHIFT) - norm);
-                q = q > SSW_MAX_NEG_ASCR ? SSW_MAX_NEG_ASCR : q;
-                if (!act)
-                    q = SSW_MAX_NEG_ASCR; /* src/ptm_mgau.c:353-364 */
-                pk |= (uint32_t)(q & 0xff) << (8 * k);
-            }
-            s_ns4[i] = pk;
-            s_cw4[i] = cw[i];
-        }
-    }
+    if (!MS)
+        wave_codebook_norm(sc, cw, n_cbf, P.n_feat, P.cbmask[t], lane, s_ns4, s_cw4);
     wave_sync();
     const int n_all = *s_n;
     const int n_ent = n_all < P.cap ? n_all : P.cap; /* (cap = n_sen: never short) */
@@ -359,45 +319,15 @@ senone_listed_kernel(SenoneListedParams P)
     for (int i = lane; i < n_ent; i += 64) {
         const int sen = s_sen[i];
         const int sl = P.sen_slot[sen], cb = P.sen2cb[sen];
-        int a = 0;
-        if (MS) { /* senone_eval, src/ms_senone.c:314-362 */
-            for (int f = 0; f < P.n_feat; ++f) {
-                const uint32_t cw4 = cw[cb * P.n_feat + f];
-                const int4 fd4 = sc[cb * P.n_feat + f];
-                const int fd[4] = { fd4.x, fd4.y, fd4.z, fd4.w };
-                const uint8_t *mw = P.mixw + (size_t)f * P.n_density * P.slot_stride + sl;
-                int fscr = fd[0] - (int)mw[(size_t)(cw4 & 0xffu) * P.slot_stride];
-#pragma unroll
-                for (int k = 1; k < 4; ++k) {
-                    const int fw = fd[k] - (int)mw[(size_t)((cw4 >> (8 * k)) & 0xffu) * P.slot_stride];
-                    fscr = ms_logadd(fscr, fw, P.zero, s_tab);
-                }
-                a -= fscr;
-            }
-            if (P.aw != 1)
-                a = a / P.aw; /* C division truncates toward zero */
-            a = a > 32767 ? 32767 : a;
-            a = a < -32768 ? -32768 : a;
-        } else { /* src/ptm_mgau.c:342-395 */
-            for (int f = 0; f < P.n_feat; ++f) {
-                const uint32_t cw4 = s_cw4[cb * P.n_feat + f], ns4 = s_ns4[cb * P.n_feat + f];
-                const uint8_t *mw = P.mixw + (size_t)f * P.n_density * P.slot_stride + sl;
-                int fden = (int)mw[(size_t)(cw4 & 0xffu) * P.slot_stride] + (int)(ns4 & 0xffu);
-#pragma unroll
-                for (int k = 1; k < 4; ++k) {
-                    const int y = (int)mw[(size_t)((cw4 >> (8 * k)) & 0xffu) * P.slot_stride]
-                        + (int)((ns4 >> (8 * k)) & 0xffu);
-                    fden = fast_logadd(fden, y, s_tab);
-                }
-                a += fden;
-            }
-        }
+        const int a = MS
+            ? ms_slot_score(P.mixw + sl, P.n_feat, P.n_density, P.slot_stride, cw + cb * P.n_feat,
+                            sc + cb * P.n_feat, P.zero, P.aw, s_tab)
+            : ptm_slot_score(P.mixw + sl, P.n_feat, P.n_density, P.slot_stride,
+                             s_cw4 + cb * P.n_feat, s_ns4 + cb * P.n_feat, s_tab);
         s_a[i] = (int16_t)a;
         best = a < best ? a : best;
     }
-    best = -wave_max_dpp(-(best == INT_MAX ? INT_MAX - 1 : best));
-    if (best == INT_MAX - 1)
-        best = 0; /* nothing listed: a frame the search has no HMM left in (it fails there) */
+    best = wave_best_or_zero(best); /* 0: a frame the search has no HMM left in (it fails there) */
     wave_sync();
     int16_t *orow = P.out + (size_t)t * P.n_sen;
     if (P.full == 2) {
@@ -413,10 +343,7 @@ senone_listed_kernel(SenoneListedParams P)
             delta = 0;
         for (int sen = lane; sen < P.n_sen; sen += 64)
             if (!((bits[sen >> 5] >> (sen & 31)) & 1u)) {
-                int v = (int)yrow[sen] - delta;
-                v = v > 32767 ? 32767 : v;
-                v = v < -32768 ? -32768 : v;
-                orow[sen] = (int16_t)v;
+                orow[sen] = (int16_t)clamp_i16((int)yrow[sen] - delta);
             }
     } else if (P.full) { /* the unlisted entries first: listed ones are skipped, no store is overwritten */
         const int16_t rest = MS ? (int16_t)0 : (int16_t)(0 - best);
@@ -424,18 +351,6 @@ senone_listed_kernel(SenoneListedParams P)
             if (!((bits[sen >> 5] >> (sen & 31)) & 1u))
                 orow[sen] = rest;
     }
-    /* PTM `senone_scores[i] -= bestscore` in int16 (src/ptm_mgau.c:399); ms (score - best) with
-     * the clamp (src/ms_mgau.c:354-363) */
-    for (int i = lane; i < n_ent; i += 64) {
-        const int raw = s_a[i];
-        int16_t v;
-        if (MS) {
-            int bs = raw - best;
-            bs = bs > 32767 ? 32767 : bs;
-            bs = bs < -32768 ? -32768 : bs;
-            v = (int16_t)bs;
-        } else
-            v = (int16_t)(raw - best);
-        orow[s_sen[i]] = v;
-    }
+    for (int i = lane; i < n_ent; i += 64)
+        orow[s_sen[i]] = final_score<MS>((int)s_a[i], best);
 }

@@ -24,6 +24,14 @@
  *   ssw_k1a_mfma.inc     ptm_topn_mfma_kernel: the same scan with its multiply-adds on the matrix
  *                        cores (keys from two-part binary16 operands, exact re-evaluation, proof
  *                        and in-wave pass as above): what every batch takes
+ *   ssw_senone_lds.inc   no HIP, ahead of the namespace: the dynamic LDS of the senone kernels,
+ *                        SenoneCarve / MsSenoneCarve / Active2Carve / ListedCarve -- the kernel
+ *                        takes its pointers and the launcher its byte count from the same struct
+ *   ssw_senone_common.inc the steps of the reference's senone scorers that several kernels
+ *                        share, once: clamp_i16, fast_logadd / ms_logadd, the padded table fill,
+ *                        ptm_norm_pack4, wave_codebook_norm, ptm_slot_score, ms_slot_score,
+ *                        ms_quad_scores, ms_finish, final_score, wave_best_or_zero,
+ *                        move_exact_count (src/ptm_mgau.c:271-400, src/ms_senone.c:314-362)
  *   ssw_k1b_senone.inc   ptm_senone_kernel (codebook_norm + senone_eval, src/ptm_mgau.c:264-403),
  *                        ptm_senone_frame_kernel (one frame, active sets), ms_senone_kernel
  *   ssw_k4_feat.inc      feat_1s_c_d_dd_kernel (batch CMN + 1s_c_d_dd, src/feat.c:271-326)
@@ -132,9 +140,12 @@
         }                                                                                    \
     } while (0)
 
+#include "ssw_senone_lds.inc"
+
 namespace {
 #include "ssw_dev_common.inc"
 #include "ssw_k1a_chain.inc"
+#include "ssw_senone_common.inc"
 #include "ssw_scan_common.inc"
 #include "ssw_k1a_frames.inc"
 #include "ssw_top5_select.inc"

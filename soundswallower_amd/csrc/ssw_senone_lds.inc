@@ -1,0 +1,102 @@
+/* ssw_senone_lds.inc -- the dynamic LDS of the senone kernels, each carve once: the kernel takes
+ * its pointers from it and the launcher its byte count.  Plain C++17, no HIP header:
+ * ssw_kernels.hip includes it ahead of the anonymous namespace, so that device and host code see
+ * the same formulas, and a host program can include it on its own
+ * (tests/harness/senone_lds_host.cpp).  Offsets are bytes from the start of the dynamic LDS. */
+#include <cstddef>
+
+#if defined(__HIPCC__)
+#define SSW_HD __host__ __device__
+#else
+#define SSW_HD
+#endif
+
+#define SSW_LOGADD_LDS 512 /* 8-bit log-add table in LDS: 256 entries + zero padding */
+/* the batch kernel's copy: T - tab[|s|] for s = -512 .. 511 at LDS address 512 + s, so that a
+ * SIGNED difference indexes it (ds_read_u8 v, s offset:512: the address adder wraps, measured by
+ * tools/microbench/addr_probe.hip) and the chain needs min(x, y) only, not max(x, y) as well */
+#define SSW_LOGADD_MIRROR 1024
+#define SSW_SENONE_NORM_W 8 /* PTM: normaliser words per frame (= SSW_MAX_FEAT) */
+
+/* ptm_senone_kernel: tab[mirror] | norm[3][fpb][norm_w] int | red[16] int | item[2][n_cbf][fpb]
+ * of 32 bytes | stage_sc[pad64(fpb n_cbf)] int4 | stage_cw[..] uint32 | 16 bytes that nothing
+ * reads or writes.  ms: the table is twice as long and a frame has a normaliser word per codebook
+ * (padded to 8) instead of one per stream.  launch_senone takes bytes() from here; the kernel
+ * keeps the same carve as typed-pointer steps (see there: its instances' code must not move) and
+ * tests/harness/senone_lds_host.cpp holds the two against each other. */
+struct SenoneCarve {
+    int fpb, n_cbf, norm_w, mirror;
+
+    SSW_HD SenoneCarve(int fpb_, int n_cbf_, int n_cb, bool ms)
+        : fpb(fpb_), n_cbf(n_cbf_), norm_w(ms ? ((n_cb + 7) & ~7) : SSW_SENONE_NORM_W),
+          mirror(ms ? 2 * SSW_LOGADD_MIRROR : SSW_LOGADD_MIRROR)
+    {
+    }
+    SSW_HD int item_pad() const { return (fpb * n_cbf + 63) & ~63; } /* whole waves of items */
+    SSW_HD int tab() const { return 0; }
+    SSW_HD int norm() const { return mirror; }
+    SSW_HD int red() const { return norm() + 4 * (3 * norm_w * fpb); }
+    SSW_HD int item() const { return red() + 4 * 16; }
+    SSW_HD int stage_sc() const { return item() + 16 * (2 * 2 * n_cbf * fpb); }
+    SSW_HD int stage_cw() const { return stage_sc() + 16 * item_pad(); }
+    SSW_HD size_t bytes() const { return (size_t)stage_cw() + 4 * (size_t)item_pad() + 16; }
+};
+
+/* ms_senone_kernel: 256 unused bytes (the table is static LDS) | fd[n_cbf] int4 | cw4[n_cbf]
+ * uint32 | red[16] int */
+struct MsSenoneCarve {
+    int n_cbf;
+
+    SSW_HD explicit MsSenoneCarve(int n_cbf_) : n_cbf(n_cbf_) {}
+    SSW_HD int fd() const { return 256; }
+    SSW_HD int cw4() const { return fd() + 16 * n_cbf; }
+    SSW_HD int red() const { return cw4() + 4 * n_cbf; }
+    SSW_HD size_t bytes() const { return (size_t)red() + 16 * sizeof(int); }
+};
+
+/* What the two wave-per-frame kernels keep first in a wave's block: PTM ns4[n_cbf] | cw4[n_cbf]
+ * uint32 (normalised scores and codewords of every (codebook, stream), 4 x 8 bits each); ms
+ * nothing.  pad2 = an even count of 16-bit entries. */
+struct WaveItems {
+    int n; /* entries of ns4 and of cw4 */
+
+    SSW_HD WaveItems(bool ms, int n_cbf) : n(ms ? 0 : n_cbf) {}
+    SSW_HD int ns4() const { return 0; }
+    SSW_HD int cw4() const { return 4 * n; }
+    SSW_HD int end() const { return 8 * n; }
+    SSW_HD static int pad2(int count) { return (count + 1) & ~1; }
+};
+
+/* senone_active2_kernel, per wave (four to a workgroup): ns4 | cw4 | a[pad2(cap)] int16, the raw
+ * scores of the listed entries | row[pad2(n_sen)] int16, only with `full` */
+struct Active2Carve : WaveItems {
+    int cap, n_sen;
+    bool full;
+
+    SSW_HD Active2Carve(bool ms, int n_cbf, int cap_, int n_sen_, bool full_)
+        : WaveItems(ms, n_cbf), cap(cap_), n_sen(n_sen_), full(full_)
+    {
+    }
+    SSW_HD int a() const { return end(); }
+    SSW_HD int row() const { return a() + 2 * pad2(cap); }
+    SSW_HD size_t per_wave() const
+    {
+        return ((size_t)row() + (full ? 2 * (size_t)pad2(n_sen) : 0) + 15) & ~(size_t)15;
+    }
+    SSW_HD size_t wave(int w) const { return (size_t)w * per_wave(); }
+    SSW_HD size_t bytes() const { return 4 * per_wave(); }
+};
+
+/* senone_listed_kernel, per wave: ns4 | cw4 | sen[pad2(cap)] uint16, the list | a[pad2(cap)]
+ * int16, its raw scores | n, the entry counter (an int, in 16 bytes of its own) */
+struct ListedCarve : WaveItems {
+    int cap;
+
+    SSW_HD ListedCarve(bool ms, int n_cbf, int cap_) : WaveItems(ms, n_cbf), cap(cap_) {}
+    SSW_HD int sen() const { return end(); }
+    SSW_HD int a() const { return sen() + 2 * pad2(cap); }
+    SSW_HD int count() const { return a() + 2 * pad2(cap); }
+    SSW_HD size_t per_wave() const { return ((size_t)count() + 16 + 15) & ~(size_t)15; }
+    SSW_HD size_t wave(int w) const { return (size_t)w * per_wave(); }
+    SSW_HD size_t bytes() const { return 4 * per_wave(); }
+};
