@@ -31,6 +31,16 @@ _Static_assert(offsetof(ssw_mgaufuncs_t, transform) == offsetof(mgaufuncs_t, tra
                "slot 2: transform");
 _Static_assert(offsetof(ssw_mgaufuncs_t, free) == offsetof(mgaufuncs_t, free), "slot 3: free");
 _Static_assert(sizeof(ssw_mgaufuncs_t) == sizeof(mgaufuncs_t), "no extra slots");
+/* the transform slot reads the mllr_t acmod_update_mllr passes as an ssw_mllr_t */
+_Static_assert(offsetof(ssw_mllr_t, refcnt) == offsetof(mllr_t, refcnt), "mllr: refcnt");
+_Static_assert(offsetof(ssw_mllr_t, n_class) == offsetof(mllr_t, n_class), "mllr: n_class");
+_Static_assert(offsetof(ssw_mllr_t, n_feat) == offsetof(mllr_t, n_feat), "mllr: n_feat");
+_Static_assert(offsetof(ssw_mllr_t, veclen) == offsetof(mllr_t, veclen), "mllr: veclen");
+_Static_assert(offsetof(ssw_mllr_t, A) == offsetof(mllr_t, A), "mllr: A");
+_Static_assert(offsetof(ssw_mllr_t, b) == offsetof(mllr_t, b), "mllr: b");
+_Static_assert(offsetof(ssw_mllr_t, h) == offsetof(mllr_t, h), "mllr: h");
+_Static_assert(offsetof(ssw_mllr_t, cb2mllr) == offsetof(mllr_t, cb2mllr), "mllr: cb2mllr");
+_Static_assert(sizeof(ssw_mllr_t) == sizeof(mllr_t), "mllr: no extra fields");
 
 static ssw_model_t *gpu_model;
 

@@ -135,6 +135,53 @@ enum ssw_table {
 const void *ssw_model_table(const ssw_model_t *m, int which, size_t *nbytes);
 
 /* ------------------------------------------------------------------------------------ */
+/* MLLR speaker adaptation: mllr_t (include/soundswallower/mllr.h:58-67), mllr_read      */
+/* (src/ps_mllr.c:47-127) and gauden_mllr_transform (src/ms_gauden.c:459-539), which      */
+/* every scorer's `transform` slot ends in.                                               */
+/* ------------------------------------------------------------------------------------ */
+/* Laid out exactly as mllr_t: the pointer acmod_update_mllr hands to the vtable's transform
+ * slot is read as one of these.  A[f][class][row][col], b[f][class][row], h[f][class][row]. */
+typedef struct ssw_mllr_s {
+    int refcnt;
+    int n_class;
+    int n_feat;
+    int *veclen;
+    float ****A;
+    float ***b;
+    float ***h;
+    int32_t *cb2mllr; /* unused, as in the reference */
+} ssw_mllr_t;
+
+/* mllr_read: the text file of whitespace-separated numbers -- n_class, n_feat, then per stream
+ * its veclen and per class A[veclen][veclen], b[veclen], h[veclen].  NULL on error
+ * (ssw_last_error: a file that cannot be opened, a short file, n_class < 1). */
+ssw_mllr_t *ssw_mllr_read(const char *path);
+/* From flat arrays: A[f] float32 [n_class][veclen[f]][veclen[f]], b[f] and h[f] float32
+ * [n_class][veclen[f]].  The numbers are copied. */
+ssw_mllr_t *ssw_mllr_create(int32_t n_class, int32_t n_feat, const int32_t *veclen,
+                            const float *const *A, const float *const *b, const float *const *h);
+ssw_mllr_t *ssw_mllr_retain(ssw_mllr_t *mllr);
+int ssw_mllr_free(ssw_mllr_t *mllr); /* the references left */
+
+/* gauden_mllr_transform on the model, in place: class 0 of the transform (the reference uses no
+ * other) on the means and variances AS THE FILES HOLD THEM -- a transform is never applied on top
+ * of an earlier one, applying twice equals applying once, and NULL puts the files' parameters
+ * back -- then every table derived from them is rebuilt and, on a device model, copied into the
+ * allocations the load made.  Works on a SSW_DEVICE_NONE model (host tables only).  Refused
+ * before anything is touched, model and device unchanged: n_feat or a veclen that is not the
+ * model's, n_class < 1, a non-finite number in class 0, a model in use by another thread.
+ * 0, or -1 (ssw_last_error).  Rows scored earlier (on the device, or held by ssw_mgau_prescore)
+ * are those of the parameters they were scored with: the caller scores again. */
+int ssw_model_apply_mllr(ssw_model_t *m, const ssw_mllr_t *mllr);
+/* 0 after load, +1 per successful ssw_model_apply_mllr (a NULL one included): callers that cache
+ * rows compare it */
+int ssw_model_mllr_generation(const ssw_model_t *m);
+/* measurement aid (tools/bench_mllr.py): what the last successful ssw_model_apply_mllr took, in
+ * ms -- [0] the host transform and table rebuild, [1] the synchronise and the copies to the
+ * device (0 on a SSW_DEVICE_NONE model) */
+int ssw_model_mllr_timing(const ssw_model_t *m, float ms[2]);
+
+/* ------------------------------------------------------------------------------------ */
 /* Batched senone scoring (NEW: the reference scores one frame per call).                */
 /* One call scores every frame of a batch of utterances with compallsen = yes:           */
 /*   acmod_score -> ptm_mgau_frame_eval   (src/acmod.c:822-860, src/ptm_mgau.c:408-454)   */
@@ -290,7 +337,11 @@ typedef struct ssw_mgaufuncs_s {
     int (*frame_eval)(ssw_mgau_t *mgau, int16_t *senscr, uint8_t *senone_active,
                       int32_t n_senone_active, float **feat, int32_t frame,
                       int32_t compallsen);
-    int (*transform)(ssw_mgau_t *mgau, void *mllr); /* MLLR is out of scope: returns -1 */
+    /* mllr: an ssw_mllr_t / the reference's mllr_t.  ssw_model_apply_mllr on the model behind
+     * the scorer; the rows ssw_mgau_prescore holds are dropped, the top-N history is left alone
+     * (as in the reference).  0, or -1: a refused transform, or NULL (the reference never
+     * passes one; the model stays as it is) */
+    int (*transform)(ssw_mgau_t *mgau, void *mllr);
     void (*free)(ssw_mgau_t *mgau);
 } ssw_mgaufuncs_t;
 struct ssw_mgau_s {

@@ -122,6 +122,18 @@ def lib() -> C.CDLL:
     L.ssw_model_is_continuous.argtypes = [vp]
     L.ssw_model_table.restype = vp
     L.ssw_model_table.argtypes = [vp, C.c_int, C.POINTER(sz)]
+    if hasattr(L, "ssw_mllr_read"):   # (an older build loaded through SSW_AMD_LIB for an A/B has
+        # no MLLR entry points: api.Mllr and Model.apply_mllr raise AttributeError)
+        L.ssw_mllr_read.restype = vp
+        L.ssw_mllr_read.argtypes = [C.c_char_p]
+        L.ssw_mllr_create.restype = vp
+        L.ssw_mllr_create.argtypes = [i32, i32, vp, vp, vp, vp]
+        L.ssw_mllr_retain.restype = vp
+        L.ssw_mllr_retain.argtypes = [vp]
+        L.ssw_mllr_free.argtypes = [vp]
+        L.ssw_model_apply_mllr.argtypes = [vp, vp]
+        L.ssw_model_mllr_generation.argtypes = [vp]
+        L.ssw_model_mllr_timing.argtypes = [vp, vp]
     L.ssw_score_batch.argtypes = [vp, C.c_int, vp, i32, vp, i32, vp, vp]
     L.ssw_debug_score_loop.argtypes = [vp, C.c_int, vp, i32, vp, i32, vp, i32, vp]
     L.ssw_score_batch_ex.argtypes = [vp, C.c_int, vp, i32, vp, i32, vp, vp, C.c_uint32, vp, vp]

@@ -144,11 +144,95 @@ def model_dir(name: str) -> str:
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "model", name)
 
 
+class Mllr:
+    """An MLLR speaker-adaptation transform (ssw_mllr_t, the reference's mllr_t): per stream a
+    rotation A [veclen][veclen], a bias b [veclen] and a variance scale h [veclen].
+
+        Mllr.read(path)                    the reference's text format (mllr_read)
+        Mllr(A=[...], b=[...], h=[...])    one array per stream, one class
+    """
+
+    def __init__(self, A=None, b=None, h=None, *, _handle=None):
+        self._L = _lib.lib()
+        if _handle is not None:
+            self._t = _handle
+            return
+        if A is None or b is None or h is None or not len(A) == len(b) == len(h):
+            raise SswError("Mllr: A, b and h are needed, one array per stream each")
+        As = [np.ascontiguousarray(a, np.float32) for a in A]
+        bs = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in b]
+        hs = [np.ascontiguousarray(x, np.float32).reshape(-1) for x in h]
+        for f, (a, bb, hh) in enumerate(zip(As, bs, hs)):
+            if a.ndim != 2 or a.shape != (len(bb), len(bb)) or len(hh) != len(bb):
+                raise SswError(f"Mllr: stream {f}: A {a.shape}, b {bb.shape} and h {hh.shape} "
+                               "are not [veclen][veclen], [veclen] and [veclen]")
+        made = self._create_raw(1, [len(x) for x in bs], As, bs, hs)
+        self._t, made._t = made._t, None
+
+    @classmethod
+    def _create_raw(cls, n_class, veclen, A, b, h) -> "Mllr":
+        """ssw_mllr_create as it is: per stream flat float32 arrays, class-major"""
+        L = _lib.lib()
+        veclen = np.array(veclen, np.int32)
+        ptrs = lambda arrs: (C.c_void_p * len(arrs))(*[x.ctypes.data for x in arrs])
+        t = L.ssw_mllr_create(int(n_class), len(veclen), _ptr(veclen), ptrs(A), ptrs(b), ptrs(h))
+        if not t:
+            raise SswError("ssw_mllr_create: " + _lib.last_error())
+        return cls(_handle=t)
+
+    @classmethod
+    def read(cls, path) -> "Mllr":
+        t = _lib.lib().ssw_mllr_read(os.fsencode(path))
+        if not t:
+            raise SswError("ssw_mllr_read: " + _lib.last_error())
+        return cls(_handle=t)
+
+    def _struct(self):
+        return C.cast(self._t, C.POINTER(_SswMllr)).contents
+
+    @property
+    def n_class(self) -> int:
+        return int(self._struct().n_class)
+
+    @property
+    def veclen(self):
+        s = self._struct()
+        return [int(s.veclen[f]) for f in range(s.n_feat)]
+
+    def arrays(self, klass=0):
+        """(A, b, h) of one class: lists of float32 arrays, one per stream"""
+        s = self._struct()
+        A, b, h = [], [], []
+        for f, vl in enumerate(self.veclen):
+            A.append(np.array([[s.A[f][klass][l][m] for m in range(vl)] for l in range(vl)],
+                              np.float32).reshape(vl, vl))
+            b.append(np.array([s.b[f][klass][l] for l in range(vl)], np.float32))
+            h.append(np.array([s.h[f][klass][l] for l in range(vl)], np.float32))
+        return A, b, h
+
+    def free(self):
+        if getattr(self, "_t", None):
+            self._L.ssw_mllr_free(self._t)
+            self._t = None
+
+    __del__ = free
+
+
+class _SswMllr(C.Structure):
+    """ssw_mllr_t"""
+    _fp = C.POINTER(C.c_float)
+    _fields_ = [("refcnt", C.c_int), ("n_class", C.c_int), ("n_feat", C.c_int),
+                ("veclen", C.POINTER(C.c_int)), ("A", C.POINTER(C.POINTER(C.POINTER(_fp)))),
+                ("b", C.POINTER(C.POINTER(_fp))), ("h", C.POINTER(C.POINTER(_fp))),
+                ("cb2mllr", C.POINTER(C.c_int32))]
+
+
 class Model:
-    """Acoustic model tables on the GPU (ssw_model_load)."""
+    """Acoustic model tables on the GPU (ssw_model_load).  mllr: the path of an MLLR transform
+    file, applied after the load (the reference's `mllr` configuration key)."""
 
     def __init__(self, path=None, *, mdef=None, means=None, variances=None, sendump=None,
-                 mixw=None, tmat=None, config=None):
+                 mixw=None, tmat=None, config=None, mllr=None):
         L = _lib.lib()
         if path is not None:
             j = lambda n: os.path.join(path, n)
@@ -171,16 +255,48 @@ class Model:
                                    enc(mixw), enc(tmat), C.byref(cfg))
         if not self._m:
             raise SswError("ssw_model_load: " + _lib.last_error())
+        self._read_info()
+        # outcome of the matrix-core self-test at load (ssw_amd.h, ssw_model_info_t)
+        self.selftest_message = (L.ssw_model_selftest_message(self._m) or b"").decode()
+        if mllr is not None:
+            t = Mllr.read(mllr)
+            try:
+                self.apply_mllr(t)
+            except SswError:
+                self.close()
+                raise
+            finally:
+                t.free()
+
+    def _read_info(self):
         info = SswModelInfo()
-        L.ssw_model_info(self._m, C.byref(info))
+        self._L.ssw_model_info(self._m, C.byref(info))
         self.info = info
         for name, ctype in SswModelInfo._fields_:
             if name != "veclen":
                 setattr(self, name, float(getattr(info, name)) if ctype is C.c_float
                         else int(getattr(info, name)))
         self.veclen = [int(info.veclen[i]) for i in range(self.n_feat)]
-        # outcome of the matrix-core self-test at load (ssw_amd.h, ssw_model_info_t)
-        self.selftest_message = (L.ssw_model_selftest_message(self._m) or b"").decode()
+
+    def apply_mllr(self, mllr):
+        """ssw_model_apply_mllr, in place: the transform's class 0 on the means and variances as
+        the files hold them (never on top of an earlier transform), every derived table rebuilt
+        and uploaded.  None puts the files' parameters back.  A transform that does not fit the
+        model is refused (SswError) and the model stays as it was."""
+        _check(self._L.ssw_model_apply_mllr(self._m, None if mllr is None else mllr._t),
+               "ssw_model_apply_mllr")
+        self._read_info()  # (n_floored follows the variances)
+
+    def mllr_timing(self):
+        """(host ms, upload ms) of the last apply_mllr (ssw_model_mllr_timing)"""
+        ms = np.zeros(2, np.float32)
+        _check(self._L.ssw_model_mllr_timing(self._m, _ptr(ms)), "ssw_model_mllr_timing")
+        return float(ms[0]), float(ms[1])
+
+    @property
+    def mllr_generation(self) -> int:
+        """0 after load, +1 per apply_mllr that succeeded"""
+        return int(self._L.ssw_model_mllr_generation(self._m))
 
     def close(self):
         if getattr(self, "_m", None):
@@ -884,7 +1000,11 @@ class PtmMgau:
         return out
 
     def transform(self, mllr=None):
-        return self._g.contents.vt.contents.transform(C.cast(self._g, C.c_void_p), None)
+        """the vtable's transform slot: an Mllr is applied to the model behind the scorer (0, or
+        -1 when it is refused: last_error says why); without one the slot gets NULL and
+        returns -1"""
+        return self._g.contents.vt.contents.transform(C.cast(self._g, C.c_void_p),
+                                                      None if mllr is None else mllr._t)
 
     def free(self):
         if getattr(self, "_g", None):

@@ -31,6 +31,7 @@ struct ssw_mgau_impl {
     /* whole-utterance cache filled by ssw_mgau_prescore */
     std::vector<int16_t> cache;
     int cache_frames;
+    int cache_gen; /* the model's MLLR generation the rows were scored at (mgau_cached) */
     /* the s2_semi scorer's ring of two slots (src/s2_semi_mgau.c:845-855), kept on the host: the
      * packed codeword order of every stream, and the whole row the slot's lists last gave */
     std::vector<uint32_t> sc_hist[2];
@@ -40,8 +41,17 @@ struct ssw_mgau_impl {
 static int mgau_frame_eval(ssw_mgau_t *mg, int16_t *senscr, uint8_t *senone_active,
                            int32_t n_senone_active, float **feat, int32_t frame,
                            int32_t compallsen);
+
 static int mgau_transform(ssw_mgau_t *mg, void *mllr);
 static void mgau_free(ssw_mgau_t *mg);
+
+/* does ssw_mgau_prescore's cache hold `frame`, scored with the model's present parameters?  (rows
+ * of before an ssw_model_apply_mllr -- through the vtable or not -- are not served) */
+static inline bool
+mgau_cached(const ssw_mgau_impl *g, int32_t frame)
+{
+    return frame < g->cache_frames && g->cache_gen == g->m->h->mllr_generation;
+}
 
 static ssw_mgaufuncs_t g_ptm_funcs = { "ptm", mgau_frame_eval, mgau_transform, mgau_free };
 
@@ -207,7 +217,7 @@ semi_mgau_frame_eval(ssw_mgau_impl *g, int16_t *senscr, const uint8_t *senone_ac
     const ssw_host_model_t *h = m->h;
     const int slot = frame % 2;
     const int16_t *row = g->sc_row[slot].data();
-    if (frame < g->cache_frames) /* ssw_mgau_prescore */
+    if (mgau_cached(g, frame)) /* ssw_mgau_prescore */
         row = g->cache.data() + (size_t)frame * h->n_sen;
     else if (frame >= g->base.frame_idx) {
         std::vector<float> x((size_t)h->veclen_total);
@@ -271,6 +281,7 @@ ssw_mgau_prescore(ssw_mgau_t *mg, const float *feats, int32_t n_frames)
     if (ssw_score_batch_host(g->m, g->scorer, feats, n_frames, off, 1, g->cache.data()) < 0)
         return -1;
     g->cache_frames = n_frames;
+    g->cache_gen = g->m->h->mllr_generation;
     return 0;
 }
 
@@ -317,7 +328,7 @@ mgau_frame_eval(ssw_mgau_t *mg, int16_t *senscr, uint8_t *senone_active,
         ssw_set_error("compallsen=no needs the active senone list");
         return -1;
     }
-    if (compallsen && frame < g->cache_frames) {
+    if (compallsen && mgau_cached(g, frame)) {
         memcpy(senscr, g->cache.data() + (size_t)frame * h->n_sen, sizeof(int16_t) * h->n_sen);
         return 0;
     }
@@ -468,10 +479,17 @@ mgau_frame_eval(ssw_mgau_t *mg, int16_t *senscr, uint8_t *senone_active,
 static int
 mgau_transform(ssw_mgau_t *mg, void *mllr)
 {
-    (void)mg;
-    (void)mllr;
-    ssw_set_error("MLLR transforms are outside the accelerated path");
-    return -1;
+    ssw_mgau_impl *g = reinterpret_cast<ssw_mgau_impl *>(mg);
+    if (mllr == NULL) { /* (acmod_update_mllr never passes one) */
+        ssw_set_error("transform: no MLLR transform given");
+        return -1;
+    }
+    /* ptm_mgau_mllr_transform, ms_mgau_mllr_transform, s2_semi_mgau_mllr_transform: all three
+     * are gauden_mllr_transform on the scorer's Gaussians; the top-N history stays as it is */
+    if (ssw_model_apply_mllr(g->m, static_cast<const ssw_mllr_t *>(mllr)) < 0)
+        return -1;
+    g->cache_frames = 0; /* ssw_mgau_prescore's rows are the old parameters' */
+    return 0;
 }
 
 static void

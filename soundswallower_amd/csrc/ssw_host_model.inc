@@ -290,6 +290,9 @@ struct ssw_model_s {
      * workspace: tile table, utterance offsets, means, scales, the CMN state */
     ssw_feat_t *own_feat;
     DevBuf featex_ws;
+    /* the last ssw_model_apply_mllr (ssw_host_mllr.inc): ms of the host transform and table
+     * rebuild, ms of the synchronise and the copies to the device */
+    float mllr_ms[2];
 };
 
 static inline void

@@ -142,6 +142,10 @@ typedef struct ssw_host_model_s {
     int32_t n_cb, n_feat, n_density, veclen_total, n_floored;
     int32_t veclen[SSW_MAX_FEAT], featoff[SSW_MAX_FEAT];
     float *mean, *var, *det; /* file order / [cb][feat][density] */
+    /* the means and variances as the files hold them (un-precomputed), file order: what an MLLR
+     * transform is applied to, and what its removal puts back (ssw_host_model_apply_mllr) */
+    float *mean0, *var0;
+    int32_t mllr_generation; /* 0 after load, +1 per transform applied or removed */
     /* device-layout Gaussian tables (ssw_host_build_records):
      *   rec     [cb*feat][density][32]  exact records (mean, det, scale)
      *   recq    [cb*feat][density][32]  quadratic-form scan records (a, c, b)
@@ -209,6 +213,16 @@ ssw_host_model_t *ssw_host_model_load(const char *mdef, const char *means,
                                       const ssw_config_t *cfg);
 void ssw_host_model_free(ssw_host_model_t *h);
 int ssw_host_build_records(ssw_host_model_t *h);
+/* Everything derived from (mean, raw variance): h->mean and h->var hold means and un-precomputed
+ * variances in file order; the variances are floored and scaled in place, det is made, and the
+ * tables of the model's scorer are rebuilt in the allocations they have (first call: made).  Both
+ * the loader and ssw_host_model_apply_mllr end here. */
+int ssw_host_derive_tables(ssw_host_model_t *h);
+/* gauden_mllr_transform (src/ms_gauden.c:459-539) over the parameters as read: class 0 of the
+ * transform on every codebook, then ssw_host_derive_tables.  NULL puts the files' parameters
+ * back.  A transform that does not fit the model, or holds a non-finite number, is refused before
+ * anything is touched: -1 and ssw_set_error. */
+int ssw_host_model_apply_mllr(ssw_host_model_t *h, const ssw_mllr_t *mllr);
 void ssw_set_error(const char *fmt, ...);
 
 /* Pronunciation dictionary (ssw_lexicon.c) */

@@ -185,6 +185,7 @@ static int cont_launch(ssw_model_s *m, const float *d_feats, int32_t n_frames, i
 #include "ssw_host_align.inc"
 #include "ssw_host_compact.inc"
 #include "ssw_host_active.inc"
+#include "ssw_host_mllr.inc"
 #include "ssw_host_mgau.inc"
 #include "ssw_host_search.inc"
 #include "ssw_host_feat.inc"

@@ -1368,16 +1368,17 @@ bad:
     return NULL;
 }
 
+/* The read step: means and variances as the files hold them (mean0, var0), the shape, and
+ * working copies (mean, var) for precompute_gaussians. */
 static int
-load_gaussians(ssw_host_model_t *h, const lbase_t *lb, const char *means, const char *vars)
+read_gaussians(ssw_host_model_t *h, const char *means, const char *vars)
 {
-    int32_t sm[3], sv[3], vlv[SSW_MAX_FEAT], c, f, d, j;
-    const float vfloor = (float)h->cfg.varfloor; /* float32 parameter, ms_gauden.c:218 */
-    float *mp, *vp, *dp;
+    int32_t sm[3], sv[3], vlv[SSW_MAX_FEAT], f;
+    size_t n;
 
-    if ((h->mean = read_gauss_file(means, sm, h->veclen)) == NULL)
+    if ((h->mean0 = read_gauss_file(means, sm, h->veclen)) == NULL)
         return -1;
-    if ((h->var = read_gauss_file(vars, sv, vlv)) == NULL)
+    if ((h->var0 = read_gauss_file(vars, sv, vlv)) == NULL)
         return -1;
     if (memcmp(sm, sv, sizeof(sm)) != 0 || memcmp(h->veclen, vlv, sizeof(int32_t) * sm[1])) {
         ssw_set_error("means and variances have different shapes");
@@ -1390,16 +1391,31 @@ load_gaussians(ssw_host_model_t *h, const lbase_t *lb, const char *means, const 
         h->featoff[f] = h->veclen_total;
         h->veclen_total += h->veclen[f];
     }
+    n = (size_t)h->n_cb * h->n_density * (size_t)h->veclen_total;
     h->det = (float *)malloc(sizeof(float) * (size_t)h->n_cb * h->n_feat * h->n_density);
-    if (h->det == NULL)
+    h->mean = (float *)malloc(sizeof(float) * n);
+    h->var = (float *)malloc(sizeof(float) * n);
+    if (h->det == NULL || h->mean == NULL || h->var == NULL) {
+        ssw_set_error("out of memory reading the Gaussians");
         return -1;
+    }
+    memcpy(h->mean, h->mean0, sizeof(float) * n);
+    memcpy(h->var, h->var0, sizeof(float) * n);
+    return 0;
+}
+
+/* The precompute step (gauden_dist_precompute, src/ms_gauden.c:211-247) over h->var, which holds
+ * un-precomputed variances: floor, det, scaled variance. */
+static void
+precompute_gaussians(ssw_host_model_t *h, const lbase_t *lb)
+{
+    const float vfloor = (float)h->cfg.varfloor; /* float32 parameter, ms_gauden.c:218 */
+    float *vp = h->var, *dp = h->det;
+    int32_t c, f, d, j;
 
     /* Walk the file order once: per density, det = sum_j (float)ilog(1/sqrt(2 pi var_j))
      * accumulated in float32; var_j <- (float)iln_to_log(1/(2 var_j)); floor first. */
-    mp = h->mean;
-    vp = h->var;
-    dp = h->det;
-    (void)mp;
+    h->n_floored = 0;
     for (c = 0; c < h->n_cb; ++c)
         for (f = 0; f < h->n_feat; ++f)
             for (d = 0; d < h->n_density; ++d) {
@@ -1414,7 +1430,6 @@ load_gaussians(ssw_host_model_t *h, const lbase_t *lb, const char *means, const 
                 }
                 *dp++ = acc;
             }
-    return 0;
 }
 
 /* ---------------------------------------------------------------------------------- */
@@ -1998,6 +2013,17 @@ mfma_density_terms(const double *q, int s, int ec, double *K_i, double *add)
     return 0;
 }
 
+/* A derived table of n elements, all zero: made on the first call, cleared in place on a later
+ * one (a rebuild after ssw_host_model_apply_mllr: every size is what it was). */
+static void *
+table_zeroed(void *have, size_t n, size_t size)
+{
+    if (have == NULL)
+        return calloc(n, size);
+    memset(have, 0, n * size);
+    return have;
+}
+
 static int
 ssw_host_build_mfma_records(ssw_host_model_t *h)
 {
@@ -2009,17 +2035,15 @@ ssw_host_build_mfma_records(ssw_host_model_t *h)
     double *geo;      /* [n_density][4]: delta, R, det, max |a|,|b| */
     unsigned char *inert;
 
-    h->recqm = NULL;
-    h->exlistm = NULL;
-    h->wfrag = NULL;
-    h->rec28 = NULL;
     h->n_exact_form_m = 0;
     if (h->n_density != 128)
         return 0; /* the MFMA scan is built for 128 densities; other shapes use the FMA scan */
-    h->recqm = (float *)calloc(nrec * SSW_REC_FLOATS, sizeof(float));
-    h->exlistm = (uint32_t *)calloc((size_t)ncbf * SSW_EXLIST_STRIDE, sizeof(uint32_t));
-    h->wfrag = (uint16_t *)calloc((size_t)ncbf * SSW_WFRAG_PER_CBF, sizeof(uint16_t));
-    h->rec28 = (float *)calloc(nrec * 28, sizeof(float));
+    h->recqm = (float *)table_zeroed(h->recqm, nrec * SSW_REC_FLOATS, sizeof(float));
+    h->exlistm = (uint32_t *)table_zeroed(h->exlistm, (size_t)ncbf * SSW_EXLIST_STRIDE,
+                                          sizeof(uint32_t));
+    h->wfrag = (uint16_t *)table_zeroed(h->wfrag, (size_t)ncbf * SSW_WFRAG_PER_CBF,
+                                        sizeof(uint16_t));
+    h->rec28 = (float *)table_zeroed(h->rec28, nrec * 28, sizeof(float));
     if (h->rec28 != NULL) {
         size_t i;
         for (i = 0; i < nrec; ++i) {
@@ -2281,10 +2305,11 @@ ssw_host_build_records(ssw_host_model_t *h)
                           h->veclen[f], SSW_MAX_VECLEN);
             return -1;
         }
-    h->rec = (float *)calloc(nrec * SSW_REC_FLOATS, sizeof(float));
-    h->recq = (float *)calloc(nrec * SSW_REC_FLOATS, sizeof(float));
-    h->recd0 = (float *)calloc((size_t)ncbf * SSW_REC_FLOATS, sizeof(float));
-    h->exlist = (uint32_t *)calloc((size_t)ncbf * SSW_EXLIST_STRIDE, sizeof(uint32_t));
+    h->rec = (float *)table_zeroed(h->rec, nrec * SSW_REC_FLOATS, sizeof(float));
+    h->recq = (float *)table_zeroed(h->recq, nrec * SSW_REC_FLOATS, sizeof(float));
+    h->recd0 = (float *)table_zeroed(h->recd0, (size_t)ncbf * SSW_REC_FLOATS, sizeof(float));
+    h->exlist = (uint32_t *)table_zeroed(h->exlist, (size_t)ncbf * SSW_EXLIST_STRIDE,
+                                         sizeof(uint32_t));
     dets = (float *)malloc(sizeof(float) * (size_t)h->n_density);
     if (!h->rec || !h->recq || !h->recd0 || !h->exlist || !dets) {
         free(dets);
@@ -2392,7 +2417,8 @@ build_semi_records(ssw_host_model_t *h)
                           f, h->veclen[f], SSW_SC_MAX_VECLEN);
             return -1;
         }
-    h->sc_rec = (float *)calloc((size_t)h->n_feat * SSW_SC_ROWS * SSW_SC_MAX_DENSITY, sizeof(float));
+    h->sc_rec = (float *)table_zeroed(h->sc_rec, (size_t)h->n_feat * SSW_SC_ROWS * SSW_SC_MAX_DENSITY,
+                                      sizeof(float));
     if (h->sc_rec == NULL) {
         ssw_set_error("out of memory building the s2_semi records");
         return -1;
@@ -2474,7 +2500,7 @@ build_cont_records(ssw_host_model_t *h)
     }
     h->cont_sp = (int32_t)sp;
     h->cont_floats = total;
-    h->cont_rec = (float *)calloc(total, sizeof(float));
+    h->cont_rec = (float *)table_zeroed(h->cont_rec, total, sizeof(float));
     if (h->cont_rec == NULL) {
         ssw_set_error("out of memory building the continuous model's table (%zu bytes)",
                       total * sizeof(float));
@@ -2492,6 +2518,327 @@ build_cont_records(ssw_host_model_t *h)
                 r[2 * vl * sp + (size_t)c] = *dp++;
             }
         }
+    return 0;
+}
+
+/* Everything derived from (mean, raw variance), for the loader and for ssw_host_model_apply_mllr:
+ * det and the scaled variances, then the tables of the model's scorer.  A single-codebook model
+ * is the s2_semi scorer's: its own table, none of the PTM scan's (records of 15 dimensions, at
+ * most 131 densities); a continuous model likewise has its own.  Mixture weights, sen2cb, the
+ * transition matrices and the log-add tables do not depend on the Gaussians. */
+int
+ssw_host_derive_tables(ssw_host_model_t *h)
+{
+    lbase_t lb;
+
+    lb.base = h->cfg.logbase;
+    lb.inv_ln_base = 1.0 / log(h->cfg.logbase);
+    precompute_gaussians(h, &lb);
+    if (h->continuous)
+        return build_cont_records(h);
+    if (ssw_host_scorer(h) == SSW_SCORER_S2_SEMI)
+        return build_semi_records(h);
+    return ssw_host_build_records(h);
+}
+
+/* ---------------------------------------------------------------------------------- */
+/* MLLR transforms (mllr_t, src/ps_mllr.c; gauden_mllr_transform, src/ms_gauden.c)      */
+/* ---------------------------------------------------------------------------------- */
+/* a transform of n_feat streams that have no arrays yet (mllr_alloc_stream) */
+static ssw_mllr_t *
+mllr_alloc(int n_class, int n_feat)
+{
+    ssw_mllr_t *t = (ssw_mllr_t *)calloc(1, sizeof(*t));
+
+    if (t != NULL) {
+        t->refcnt = 1;
+        t->n_class = n_class;
+        t->veclen = (int *)calloc((size_t)n_feat, sizeof(int));
+        t->A = (float ****)calloc((size_t)n_feat, sizeof(float ***));
+        t->b = (float ***)calloc((size_t)n_feat, sizeof(float **));
+        t->h = (float ***)calloc((size_t)n_feat, sizeof(float **));
+        if (t->veclen && t->A && t->b && t->h) {
+            t->n_feat = n_feat; /* (ssw_mllr_free walks n_feat streams) */
+            return t;
+        }
+    }
+    ssw_mllr_free(t);
+    ssw_set_error("out of memory for an MLLR transform");
+    return NULL;
+}
+
+/* stream f's arrays, laid out as ckd_calloc_3d / ckd_calloc_2d lay them out: the numbers in one
+ * block (A[f][0][0], b[f][0], h[f][0]), A's row pointers in one block (A[f][0]) */
+static int
+mllr_alloc_stream(ssw_mllr_t *t, int f, int veclen)
+{
+    const size_t vl = (size_t)veclen, nc = (size_t)t->n_class;
+    float *a = (float *)calloc(nc * vl * vl, sizeof(float));
+    float *b = (float *)calloc(nc * vl, sizeof(float)), *h = (float *)calloc(nc * vl, sizeof(float));
+    float **rows = (float **)calloc(nc * vl, sizeof(float *));
+    size_t c, l;
+
+    t->A[f] = (float ***)calloc(nc, sizeof(float **));
+    t->b[f] = (float **)calloc(nc, sizeof(float *));
+    t->h[f] = (float **)calloc(nc, sizeof(float *));
+    if (!a || !b || !h || !rows || !t->A[f] || !t->b[f] || !t->h[f]) {
+        free(a);
+        free(b);
+        free(h);
+        free(rows);
+        free(t->A[f]);
+        free(t->b[f]);
+        free(t->h[f]);
+        t->A[f] = NULL;
+        t->b[f] = t->h[f] = NULL;
+        ssw_set_error("out of memory for an MLLR transform");
+        return -1;
+    }
+    t->veclen[f] = veclen;
+    for (c = 0; c < nc; ++c) {
+        t->A[f][c] = rows + c * vl;
+        for (l = 0; l < vl; ++l)
+            t->A[f][c][l] = a + (c * vl + l) * vl;
+        t->b[f][c] = b + c * vl;
+        t->h[f][c] = h + c * vl;
+    }
+    return 0;
+}
+
+/* the limits a transform has whatever the model: -1 and ssw_set_error, naming `who` */
+static int
+mllr_check_counts(const char *who, int n_class, int n_feat)
+{
+    if (n_class < 1) {
+        ssw_set_error("%s: %d MLLR classes, at least one is needed", who, n_class);
+        return -1;
+    }
+    if (n_feat < 1 || n_feat > SSW_MAX_FEAT) {
+        ssw_set_error("%s: %d feature streams, 1 to %d are supported", who, n_feat, SSW_MAX_FEAT);
+        return -1;
+    }
+    return 0;
+}
+
+static int
+mllr_check_veclen(const char *who, int f, int veclen)
+{
+    if (veclen >= 1 && veclen <= SSW_CONT_MAX_VECLEN)
+        return 0;
+    ssw_set_error("%s: stream %d has %d dimensions, 1 to %d are supported", who, f, veclen,
+                  SSW_CONT_MAX_VECLEN);
+    return -1;
+}
+
+ssw_mllr_t *
+ssw_mllr_create(int32_t n_class, int32_t n_feat, const int32_t *veclen, const float *const *A,
+                const float *const *b, const float *const *h)
+{
+    ssw_mllr_t *t;
+    int f;
+
+    if (veclen == NULL || A == NULL || b == NULL || h == NULL) {
+        ssw_set_error("ssw_mllr_create: NULL argument");
+        return NULL;
+    }
+    if (mllr_check_counts("ssw_mllr_create", n_class, n_feat) < 0)
+        return NULL;
+    for (f = 0; f < n_feat; ++f)
+        if (mllr_check_veclen("ssw_mllr_create", f, veclen[f]) < 0)
+            return NULL;
+    if ((t = mllr_alloc(n_class, n_feat)) == NULL)
+        return NULL;
+    for (f = 0; f < n_feat; ++f) {
+        const size_t v = (size_t)veclen[f], nc = (size_t)n_class;
+        if (mllr_alloc_stream(t, f, veclen[f]) < 0) {
+            ssw_mllr_free(t);
+            return NULL;
+        }
+        memcpy(t->A[f][0][0], A[f], sizeof(float) * nc * v * v);
+        memcpy(t->b[f][0], b[f], sizeof(float) * nc * v);
+        memcpy(t->h[f][0], h[f], sizeof(float) * nc * v);
+    }
+    return t;
+}
+
+/* `count` numbers as mllr_read reads them ("%f "); -1 with the message set */
+static int
+mllr_read_floats(FILE *fp, const char *path, const char *what, int f, int c, float *dst,
+                 size_t count)
+{
+    size_t i;
+    for (i = 0; i < count; ++i)
+        if (fscanf(fp, "%f ", &dst[i]) != 1) {
+            ssw_set_error("%s: short file: cannot read the MLLR %s of stream %d, class %d "
+                          "(number %zu of %zu)", path, what, f, c, i, count);
+            return -1;
+        }
+    return 0;
+}
+
+/* mllr_read (src/ps_mllr.c:47-127): whitespace-separated numbers -- n_class, n_feat, then per
+ * stream its veclen and per class A[veclen][veclen], b[veclen], h[veclen] as %f */
+ssw_mllr_t *
+ssw_mllr_read(const char *path)
+{
+    FILE *fp;
+    ssw_mllr_t *t = NULL;
+    int n_class = 0, n_feat = 0, f, c, n;
+
+    if (path == NULL) {
+        ssw_set_error("ssw_mllr_read: NULL path");
+        return NULL;
+    }
+    if ((fp = fopen(path, "r")) == NULL) {
+        ssw_set_error("%s: cannot open the MLLR file for reading", path);
+        return NULL;
+    }
+    if (fscanf(fp, "%d", &n_class) != 1) {
+        ssw_set_error("%s: cannot read the number of MLLR classes", path);
+        goto bad;
+    }
+    if (n_class >= 1 && fscanf(fp, "%d", &n_feat) != 1) {
+        ssw_set_error("%s: short file: cannot read the number of feature streams", path);
+        goto bad;
+    }
+    if (mllr_check_counts(path, n_class, n_feat) < 0 || (t = mllr_alloc(n_class, n_feat)) == NULL)
+        goto bad;
+    for (f = 0; f < n_feat; ++f) {
+        if (fscanf(fp, "%d", &n) != 1) {
+            ssw_set_error("%s: short file: cannot read the length of stream %d", path, f);
+            goto bad;
+        }
+        if (mllr_check_veclen(path, f, n) < 0 || mllr_alloc_stream(t, f, n) < 0)
+            goto bad;
+        for (c = 0; c < n_class; ++c)
+            if (mllr_read_floats(fp, path, "rotation", f, c, t->A[f][c][0], (size_t)n * n) < 0
+                || mllr_read_floats(fp, path, "bias", f, c, t->b[f][c], (size_t)n) < 0
+                || mllr_read_floats(fp, path, "variance scale", f, c, t->h[f][c], (size_t)n) < 0)
+                goto bad;
+    }
+    fclose(fp);
+    return t;
+bad:
+    fclose(fp);
+    ssw_mllr_free(t);
+    return NULL;
+}
+
+ssw_mllr_t *
+ssw_mllr_retain(ssw_mllr_t *t)
+{
+    if (t != NULL)
+        ++t->refcnt;
+    return t;
+}
+
+int
+ssw_mllr_free(ssw_mllr_t *t)
+{
+    int f;
+
+    if (t == NULL)
+        return 0;
+    if (--t->refcnt > 0)
+        return t->refcnt;
+    for (f = 0; f < t->n_feat; ++f) {
+        if (t->A && t->A[f]) { /* (a stream mllr_alloc_stream made has all of its blocks) */
+            free(t->A[f][0][0]);
+            free(t->A[f][0]);
+            free(t->A[f]);
+            free(t->b[f][0]);
+            free(t->b[f]);
+            free(t->h[f][0]);
+            free(t->h[f]);
+        }
+    }
+    free(t->veclen);
+    free(t->A);
+    free(t->b);
+    free(t->h);
+    free(t->cb2mllr);
+    free(t);
+    return 0;
+}
+
+/* what gauden_mllr_transform does not ask (it reads out of bounds instead): does the transform
+ * fit the model, and is every number of class 0 -- the one class it uses -- finite */
+static int
+mllr_check(const ssw_host_model_t *h, const ssw_mllr_t *t)
+{
+    int f, l, m;
+
+    if (t->n_class < 1) {
+        ssw_set_error("MLLR transform: %d classes, at least one is needed", t->n_class);
+        return -1;
+    }
+    if (t->n_feat != h->n_feat) {
+        ssw_set_error("MLLR transform: %d feature streams, the model has %d", t->n_feat, h->n_feat);
+        return -1;
+    }
+    if (t->veclen == NULL || t->A == NULL || t->b == NULL || t->h == NULL) {
+        ssw_set_error("MLLR transform: an array is missing");
+        return -1;
+    }
+    for (f = 0; f < h->n_feat; ++f)
+        if (t->veclen[f] != h->veclen[f]) {
+            ssw_set_error("MLLR transform: stream %d has %d dimensions, the model's has %d", f,
+                          t->veclen[f], h->veclen[f]);
+            return -1;
+        }
+    for (f = 0; f < h->n_feat; ++f)
+        for (l = 0; l < h->veclen[f]; ++l) {
+            int finite = isfinite(t->b[f][0][l]) && isfinite(t->h[f][0][l]);
+            for (m = 0; m < h->veclen[f]; ++m)
+                finite = finite && isfinite(t->A[f][0][l][m]);
+            if (!finite) {
+                ssw_set_error("MLLR transform: a non-finite number in row %d of stream %d", l, f);
+                return -1;
+            }
+        }
+    return 0;
+}
+
+int
+ssw_host_model_apply_mllr(ssw_host_model_t *h, const ssw_mllr_t *t)
+{
+    const size_t n = (size_t)h->n_cb * h->n_density * (size_t)h->veclen_total;
+    double temp[SSW_CONT_MAX_VECLEN];
+    float *mp, *vp;
+    int c, f, d, l, m;
+
+    if (t != NULL && mllr_check(h, t) < 0)
+        return -1;
+    /* the parameters as read: a transform is never applied on top of an earlier one */
+    memcpy(h->mean, h->mean0, sizeof(float) * n);
+    memcpy(h->var, h->var0, sizeof(float) * n);
+    mp = h->mean;
+    vp = h->var;
+    for (c = 0; t != NULL && c < h->n_cb; ++c)
+        for (f = 0; f < h->n_feat; ++f) {
+            const int vl = h->veclen[f];
+            float **A = t->A[f][0];
+            const float *b = t->b[f][0], *hs = t->h[f][0];
+            for (d = 0; d < h->n_density; ++d, mp += vl, vp += vl) {
+                /* float32 products (no contraction), summed in float64 in index order from 0.0,
+                 * then + b; every temp before any mean is overwritten */
+                for (l = 0; l < vl; ++l) {
+                    temp[l] = 0.0;
+                    for (m = 0; m < vl; ++m) {
+                        const float prod = A[l][m] * mp[m];
+                        temp[l] += prod;
+                    }
+                    temp[l] += b[l];
+                }
+                for (l = 0; l < vl; ++l) {
+                    mp[l] = (float)temp[l];
+                    vp[l] *= hs[l];
+                }
+            }
+        }
+    if (ssw_host_derive_tables(h) < 0)
+        return -1;
+    ++h->mllr_generation;
     return 0;
 }
 
@@ -2531,7 +2878,7 @@ ssw_host_model_load(const char *mdef, const char *means, const char *variances,
     }
     if (mdef && load_mdef(h, mdef) < 0)
         goto bad;
-    if (load_gaussians(h, &lb, means, variances) < 0)
+    if (read_gaussians(h, means, variances) < 0)
         goto bad;
     /* the senones: the mdef's, or without one the mixture-weights file's */
     n_sen_known = h->n_sen;
@@ -2560,16 +2907,7 @@ ssw_host_model_load(const char *mdef, const char *means, const char *variances,
             goto bad;
         }
     }
-    /* a single-codebook model is the s2_semi scorer's: its own table, none of the PTM scan's
-     * (records of 15 dimensions, at most 131 densities), no senone-to-codebook map; a continuous
-     * model likewise has its own */
-    if (h->continuous) {
-        if (build_cont_records(h) < 0)
-            goto bad;
-    } else if (ssw_host_scorer(h) == SSW_SCORER_S2_SEMI) {
-        if (build_semi_records(h) < 0)
-            goto bad;
-    } else if (ssw_host_build_records(h) < 0)
+    if (ssw_host_derive_tables(h) < 0)
         goto bad;
     if (tmat && load_tmat(h, &lb, tmat) < 0)
         goto bad;
@@ -2654,6 +2992,8 @@ ssw_host_model_free(ssw_host_model_t *h)
         return;
     free(h->mean);
     free(h->var);
+    free(h->mean0);
+    free(h->var0);
     free(h->det);
     free(h->pid_memo);
     free(h->rec);
