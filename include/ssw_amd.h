@@ -210,10 +210,27 @@ int ssw_model_scorer(const ssw_model_t *m);
  * densities, topn <= 8 or >= the densities (then all of them, in index order, no selection), no
  * sendump, <= 32767 senones.  It is scored in whole rows (compallsen = yes): ssw_score_batch(_ex,
  * _host), the ms drop-in, ssw_forced_align_batch, ssw_align_text_batch, ssw_first_pass_batch and
- * ssw_recognize_batch take it (flags, carry_in, carry_out and ds are ignored, as for ms); the
- * *_active entry points, the compact-row calls, ssw_score_batch_topn, the ssw_debug_scan_* calls
- * and SSW_SCAN / SSW_SCAN_AUDIT settings are refused by name. */
+ * ssw_recognize_batch take it (flags, carry_in, carry_out and ds are ignored, as for ms).  The
+ * *_active entry points (the reference's default configuration, compallsen = no) refuse it by
+ * name until ssw_model_enable_active has been called on it, and take it from then on:
+ * ms_cont_mgau_frame_eval then evaluates the codebooks of the listed senones only and normalises
+ * over them (src/ms_mgau.c:322-365).  The compact-row calls, ssw_score_batch_topn, the
+ * ssw_debug_scan_* calls and SSW_SCAN / SSW_SCAN_AUDIT settings are refused by name for every
+ * continuous model. */
 int ssw_model_is_continuous(const ssw_model_t *m);
+/* continuous model: build and upload the senone-major table of the listed-senone kernel; from
+ * then on the *_active entry points take the model.  Idempotent.  0 for a model that is not
+ * continuous (its *_active calls need nothing).  -1: no device, out of memory (model unchanged).
+ * The table holds the Gaussians once more in a second layout, i.e. it doubles their device
+ * memory; ssw_model_apply_mllr keeps it up to date and ssw_model_free releases it. */
+int ssw_model_enable_active(ssw_model_t *m);
+int ssw_model_active_enabled(const ssw_model_t *m);   /* 1 / 0 */
+/* test surface, like the other ssw_debug_* calls: ms_cont_mgau_frame_eval(compallsen = no) for a
+ * batch.  listed: host uint32 [n_frames][(n_sen + 31) / 32], bridges being ordinary bits.
+ * full 0: only listed entries of d_out are written; 1: the others as senone_listed_kernel<true>
+ * writes them for ms.  Refused unless the model is continuous and enabled. */
+int ssw_debug_cont_score_listed(ssw_model_t *m, const float *d_feats, int32_t n_frames,
+                                const uint32_t *listed, int32_t full, int16_t *d_out, void *stream);
 
 /* device pointers, asynchronous on `stream` (a hipStream_t, NULL = default stream) */
 int ssw_score_batch(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
@@ -1040,7 +1057,9 @@ ssw_alignment_set_t *ssw_recognize_align_batch(ssw_model_t *m, const ssw_dict_t 
  * seeded with acmod's flags after the grammar search's last frame (no bridges) and only growing
  * from there (src/state_align_search.c:186-189); with two_pass_history (PTM) it starts from the
  * orders the search left in history slot 1.  The s2_semi scorer takes the whole-rows route, as
- * in every *_active call; a continuous model is refused by name.  Limits and refusals as
+ * in every *_active call; a continuous model is refused by name until
+ * ssw_model_enable_active was called on it, and is then served by its listed-senone kernel
+ * (two_pass_history is ignored for it, as for ms: that scorer keeps no history).  Limits and refusals as
  * ssw_recognize_batch_active (a plan with a grammar beyond one workgroup must come from
  * ssw_grammar_prepare_large_active) and ssw_align_batch_active_ex, reported under this name.
  * rounds as ssw_recognize_batch_active's. */

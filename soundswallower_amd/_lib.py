@@ -120,6 +120,13 @@ def lib() -> C.CDLL:
     L.ssw_model_scorer.argtypes = [vp]
     L.ssw_model_is_continuous.restype = C.c_int
     L.ssw_model_is_continuous.argtypes = [vp]
+    if hasattr(L, "ssw_model_enable_active"):   # (absent from an older build loaded for an A/B)
+        L.ssw_model_enable_active.restype = C.c_int
+        L.ssw_model_enable_active.argtypes = [vp]
+        L.ssw_model_active_enabled.restype = C.c_int
+        L.ssw_model_active_enabled.argtypes = [vp]
+        L.ssw_debug_cont_score_listed.restype = C.c_int
+        L.ssw_debug_cont_score_listed.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, vp]
     L.ssw_model_table.restype = vp
     L.ssw_model_table.argtypes = [vp, C.c_int, C.POINTER(sz)]
     if hasattr(L, "ssw_mllr_read"):   # (an older build loaded through SSW_AMD_LIB for an A/B has

@@ -229,10 +229,11 @@ class _SswMllr(C.Structure):
 
 class Model:
     """Acoustic model tables on the GPU (ssw_model_load).  mllr: the path of an MLLR transform
-    file, applied after the load (the reference's `mllr` configuration key)."""
+    file, applied after the load (the reference's `mllr` configuration key).  active=True:
+    enable_active() after the load (a continuous model then serves the active=True calls)."""
 
     def __init__(self, path=None, *, mdef=None, means=None, variances=None, sendump=None,
-                 mixw=None, tmat=None, config=None, mllr=None):
+                 mixw=None, tmat=None, config=None, mllr=None, active=False):
         L = _lib.lib()
         if path is not None:
             j = lambda n: os.path.join(path, n)
@@ -258,6 +259,12 @@ class Model:
         self._read_info()
         # outcome of the matrix-core self-test at load (ssw_amd.h, ssw_model_info_t)
         self.selftest_message = (L.ssw_model_selftest_message(self._m) or b"").decode()
+        if active:
+            try:
+                self.enable_active()
+            except SswError:
+                self.close()
+                raise
         if mllr is not None:
             t = Mllr.read(mllr)
             try:
@@ -329,6 +336,18 @@ class Model:
         """ssw_model_is_continuous: one codebook per senone (the reference's `.cont.` map); the
         model is scored with SCORER_MS, in whole rows."""
         return bool(self._L.ssw_model_is_continuous(self._m))
+
+    def enable_active(self):
+        """ssw_model_enable_active: a continuous model gets the second (senone-major) Gaussian
+        table of the listed-senone kernel, which doubles the Gaussians' device memory; from then
+        on the active=True calls and the *_active functions take it (the reference's default
+        compallsen = no).  Idempotent; nothing to do for any other model."""
+        _check(self._L.ssw_model_enable_active(self._m), "ssw_model_enable_active")
+
+    @property
+    def active_enabled(self) -> bool:
+        """ssw_model_active_enabled: a continuous model after enable_active()"""
+        return bool(self._L.ssw_model_active_enabled(self._m))
 
     @property
     def tmat_n_emit(self) -> int:

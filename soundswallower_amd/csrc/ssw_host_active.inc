@@ -3,107 +3,7 @@
  * (src/acmod.c:822-999, src/ptm_mgau.c:264-403, src/state_align_search.c:177-213).
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 
-/* Which phones of an utterance are active in which frames.  state_align_search has no beam:
- * phone 0 is entered at frame 0; a phone active in frame t stays active in t + 1 unless
- * t + 1 > ef[i] (prune_hmms); phone i + 1 is entered in frame t + 1 as soon as phone i is active
- * there and t + 1 >= sf[i + 1] (phone_transition; "if inactive" enters whatever the score).  With
- * windows that do not decrease along the phones (what alignment_populate produces: the phones of
- * a word share their word's window) none of this depends on a score:
- *     first[0] = 0,  first[i] = max(1, sf[i], first[i - 1]),  active = [first[i], ef[i]],
- * and a phone whose first frame lies beyond its predecessor's last is never entered (nor any
- * after it).  acmod's active bit vector is never cleared by this search
- * (src/state_align_search.c:186-189; acmod_clear_active is only called by fsg_search), so the
- * set of frame t is the seed plus the senones of every phone with first[i] <= t. */
-static int
-active_first_frames(const int32_t *sf, const int32_t *ef, int n_phones, int n_frames,
-                    std::vector<int32_t> &first)
-{
-    first.assign((size_t)n_phones, INT_MAX);
-    int32_t prev_first = 0, prev_last = 0;
-    for (int i = 0; i < n_phones; ++i) {
-        if (i > 0 && (sf[i] < sf[i - 1] || ef[i] < ef[i - 1])) {
-            ssw_set_error("ssw_align_batch_active: phone windows must not decrease along an "
-                          "utterance (phone %d); with such windows the reference's active set "
-                          "depends on the path scores", i);
-            return -1;
-        }
-        int32_t fi = i == 0 ? 0 : std::max(std::max((int32_t)1, sf[i]), prev_first);
-        if (i > 0 && fi > prev_last)
-            break; /* never entered: the alignment fails, nothing more becomes active */
-        if (fi >= n_frames)
-            break;
-        first[i] = fi;
-        prev_first = fi;
-        prev_last = ef[i] < fi ? fi : ef[i]; /* entered at fi it is active in fi at least */
-    }
-    return 0;
-}
-
-/* The listed senones of an utterance as the search's set grows (the header of
- * senone_active2_kernel, ssw_k1b_senone.inc): REAL senones in the order they are first listed,
- * and the bridge entries acmod_flags2list inserts where two listed neighbours are more than 255
- * apart (src/acmod.c:966-975; the scorer decodes them as listed senones, src/ptm_mgau.c:342-352),
- * kept up to date under insertions -- a new senone only changes the bridges of the one gap it
- * falls into.  The set is a bit per senone (neighbours by word scans), the bridges a short
- * sorted vector: no allocation per insertion (a node-based set made the host side of a
- * 256-utterance call 10 ms). */
-struct ActiveSetBuilder {
-    std::vector<uint64_t> bits;
-    std::vector<int> bridges; /* ascending */
-    std::vector<int> order;   /* real senones by first listing */
-    explicit ActiveSetBuilder(int n_sen) : bits(((size_t)n_sen + 63) / 64, 0ull) {}
-    int pred(int s) const /* largest listed senone below s, -1 if none */
-    {
-        int w = s >> 6;
-        uint64_t v = bits[(size_t)w] & ((1ull << (s & 63)) - 1ull);
-        for (;;) {
-            if (v != 0ull)
-                return w * 64 + 63 - __builtin_clzll(v);
-            if (--w < 0)
-                return -1;
-            v = bits[(size_t)w];
-        }
-    }
-    int succ(int s) const /* smallest listed senone above s, -1 if none */
-    {
-        int w = s >> 6;
-        uint64_t v = (s & 63) == 63 ? 0ull : bits[(size_t)w] & ~((2ull << (s & 63)) - 1ull);
-        for (;;) {
-            if (v != 0ull)
-                return w * 64 + __builtin_ctzll(v);
-            if (++w >= (int)bits.size())
-                return -1;
-            v = bits[(size_t)w];
-        }
-    }
-    /* bridges of the gap between listed neighbours lo < hi (lo = -1: the list's start, from
-     * which the delta list counts as from senone 0) */
-    void gap(int lo, int hi, bool add)
-    {
-        int last = lo < 0 ? 0 : lo;
-        while (hi - last > 255) {
-            last += 255;
-            auto it = std::lower_bound(bridges.begin(), bridges.end(), last);
-            if (add)
-                bridges.insert(it, last);
-            else if (it != bridges.end() && *it == last)
-                bridges.erase(it);
-        }
-    }
-    void insert(int s)
-    {
-        if ((bits[(size_t)s >> 6] >> (s & 63)) & 1ull)
-            return;
-        const int hi = succ(s), lo = pred(s);
-        if (hi >= 0) {
-            gap(lo, hi, false);
-            gap(s, hi, true);
-        }
-        gap(lo, s, true);
-        bits[(size_t)s >> 6] |= 1ull << (s & 63);
-        order.push_back(s);
-    }
-};
+/* (active_first_frames and ActiveSetBuilder: ssw_active_set.inc) */
 
 /* one utterance's segments, built by a host thread of its own */
 struct ActiveUtt {
@@ -265,13 +165,13 @@ align_batch_active_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_
     const ssw_host_model_t *h = m->h;
     hipStream_t st = (hipStream_t)stream;
     if (semi_refuse(scorer, "ssw_align_batch_active") < 0
-        || cont_refuse(m, "ssw_align_batch_active") < 0)
+        || cont_refuse_active(m, "ssw_align_batch_active") < 0)
         return -1;
     if (n_utts <= 0)
         return 0;
     if (check_scorer_shape(m, scorer) < 0)
         return -1;
-    if (h->n_cb > 64 || h->n_emit_state != 3) {
+    if ((h->n_cb > 64 && !h->continuous) || h->n_emit_state != 3) {
         ssw_set_error("ssw_align_batch_active: built for <= 64 codebooks and 3-state HMMs");
         return -1;
     }
@@ -286,6 +186,9 @@ align_batch_active_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_
         return -1;
     }
     HIP_OK(hipSetDevice(m->device));
+    if (h->continuous) /* bitmap rows and the listed-senone kernel, no compact plan */
+        return cont_align_active(m, d_feats, n_utts, frame_off, phone_off, senid, tmatid, sf, ef,
+                                 seed_active, state_io, status, d_senscr, stream);
     const int n_frames = frame_off[n_utts];
     /* slot of every senone: the device table's host twin (upload_model) */
     const uint16_t *sen_slot = m->h_sen_slot;
@@ -400,6 +303,7 @@ align_batch_active_impl(ssw_model_t *m, int scorer, const float *d_feats, int32_
         act.seg_cbmask = A.seg_cbmask;
         act.a2 = &A;
         act.ls = NULL;
+        act.row_of_frame = NULL;
         ScoreReq R{};
         R.scorer = scorer;
         R.d_feats = d_feats;

@@ -29,8 +29,8 @@ cont_check_shape(const ssw_model_s *m, int scorer)
     return 0;
 }
 
-/* the calls that are out of scope for a continuous model (the *_active entry points, compact
- * score rows, the views of the PTM scan); -1 with the message set when `m` is one */
+/* the calls that are out of scope for every continuous model (compact score rows, the views of
+ * the PTM scan); -1 with the message set when `m` is one */
 static int
 cont_refuse(const ssw_model_s *m, const char *who)
 {
@@ -41,7 +41,19 @@ cont_refuse(const ssw_model_s *m, const char *who)
     return -1;
 }
 
-/* every (frame, senone) of one batch on `st`.  The workspace takes 2 n_sen + 4 bytes per frame. */
+/* the *_active entry points: a continuous model is taken once ssw_model_enable_active has given
+ * it the listed-senone kernel's table (ssw_host_cont_listed.inc); until then refused as above */
+static int
+cont_refuse_active(const ssw_model_s *m, const char *who)
+{
+    if (m == NULL || m->h == NULL || !m->h->continuous || m->d_cont_rec_sm != NULL)
+        return 0;
+    ssw_set_error("%s: not available with a continuous model (one codebook per senone): it is "
+                  "scored in whole rows only (until ssw_model_enable_active is called on it)", who);
+    return -1;
+}
+
+/* every (frame, senone) of one batch on `st`. The workspace takes 2 n_sen + 4 bytes per frame. */
 static int
 cont_launch(ssw_model_s *m, const float *d_feats, int32_t n_frames, int16_t *d_out, hipStream_t st)
 {

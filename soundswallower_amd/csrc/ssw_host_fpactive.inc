@@ -64,7 +64,8 @@ fpa_check_limits(ssw_model_t *m, const char *who, int scorer)
     const ssw_host_model_t *h = m->h;
     if (check_scorer_shape(m, scorer) < 0)
         return -1;
-    if (h->n_cb > 64 || h->n_emit_state != 3) {
+    /* (the bound on the codebooks is the PTM codebook mask's: a continuous model has none) */
+    if ((h->n_cb > 64 && !h->continuous) || h->n_emit_state != 3) {
         ssw_set_error("%s: built for <= 64 codebooks and 3-state HMMs", who);
         return -1;
     }
@@ -118,8 +119,10 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
     {
         /* what the two per-frame kernels keep in LDS per wave (four waves a workgroup) */
         const size_t plan_lds = 4 * ((4 * (size_t)nw32 + 2 * (size_t)cap + 8 + 15) & ~(size_t)15);
-        const size_t sen_lds = 4 * (((scorer == SSW_SCORER_MS ? 0 : 8 * (size_t)m->n_cbf)
-                                     + 4 * (size_t)((cap + 1) & ~1) + 16 + 15) & ~(size_t)15);
+        const size_t sen_lds = h->continuous
+            ? cont_listed_lds(m, cap)
+            : 4 * (((scorer == SSW_SCORER_MS ? 0 : 8 * (size_t)m->n_cbf)
+                    + 4 * (size_t)((cap + 1) & ~1) + 16 + 15) & ~(size_t)15);
         if (std::max(plan_lds, sen_lds) > 156 * 1024) {
             ssw_set_error("%s: %d senones x texts of up to %d phone-tree "
                           "HMMs need %zu KB of LDS per workgroup (160 KB a CU)", G.who, h->n_sen, max_nodes,
@@ -224,6 +227,7 @@ fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, 
         act.seg_cbmask = d_cbm + lo;
         act.a2 = NULL;
         act.ls = &L;
+        act.row_of_frame = NULL;
         std::vector<int32_t> sub;
         const int32_t *uo = utt_off;
         if (lo != 0 || hi != n_frames) {
@@ -457,7 +461,7 @@ ssw_first_pass_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
         ssw_set_error("bad arguments to ssw_first_pass_batch_active");
         return -1;
     }
-    if (cont_refuse(m, "ssw_first_pass_batch_active") < 0)
+    if (cont_refuse_active(m, "ssw_first_pass_batch_active") < 0)
         return -1;
     ModelBusy busy_(m);
     if (!busy_.ok)
@@ -525,7 +529,7 @@ ssw_align_text_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
         ssw_set_error("bad arguments to ssw_align_text_batch_active");
         return NULL;
     }
-    if (cont_refuse(m, "ssw_align_text_batch_active") < 0)
+    if (cont_refuse_active(m, "ssw_align_text_batch_active") < 0)
         return NULL;
     if (scorer == SSW_SCORER_S2_SEMI) { /* the compallsen = yes route (semi_active_done) */
         ssw_alignment_set_t *a = ssw_align_text_batch(m, d, cfg, scorer, d_feats, n_frames, utt_off,

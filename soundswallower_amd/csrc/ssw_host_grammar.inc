@@ -744,7 +744,7 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
         return NULL;
     if (check_has_device(m) < 0)
         return NULL;
-    if (cont_refuse(m, "ssw_recognize_batch_active") < 0)
+    if (cont_refuse_active(m, "ssw_recognize_batch_active") < 0)
         return NULL;
     if (plan->big && !plan->active) {
         ssw_set_error("grammar %d (%s) has %d phone-tree HMMs and is searched from an HBM workspace: "
@@ -993,7 +993,7 @@ ssw_recognize_align_batch_active(ssw_model_t *m, const ssw_dict_t *d,
         return NULL;
     if (check_has_device(m) < 0)
         return NULL;
-    if (cont_refuse(m, who) < 0)
+    if (cont_refuse_active(m, who) < 0)
         return NULL;
     if (plan->big && !plan->active) {
         ssw_set_error("%s: grammar %d (%s) has %d phone-tree HMMs and is searched from an HBM "

@@ -21,6 +21,9 @@ reupload_gaussians(ssw_model_s *m)
     if (h->cont_rec != NULL)
         HIP_OK(hipMemcpy(m->d_cont_rec, h->cont_rec, h->cont_floats * sizeof(float),
                          hipMemcpyHostToDevice));
+    if (h->cont_rec_sm != NULL && m->d_cont_rec_sm != NULL) /* (ssw_model_enable_active) */
+        HIP_OK(hipMemcpy(m->d_cont_rec_sm, h->cont_rec_sm, h->cont_sm_floats * sizeof(float),
+                         hipMemcpyHostToDevice));
     if (h->rec != NULL) {
         const size_t nrec = ncbf * h->n_density * SSW_REC_FLOATS;
         const size_t nd0 = ncbf * SSW_REC_FLOATS, nex = ncbf * SSW_EXLIST_STRIDE;

@@ -285,6 +285,11 @@ struct ssw_model_s {
     float *d_cont_rec;
     uint8_t *d_cont_pdf;
     DevBuf cont_ws;
+    /* ssw_model_enable_active: the senone-major table of cont_listed_kernel
+     * (ssw_host_model_t::cont_rec_sm), NULL until then; its per-frame bitmap rows of the
+     * alignment path and of ssw_debug_cont_score_listed */
+    float *d_cont_rec_sm;
+    DevBuf cont_act_ws;
     /* dynamic features of every configuration (ssw_host_featex.inc): the model's own
      * configuration, built by the first ssw_feat_batch_ex call that passes none, and the
      * workspace: tile table, utterance offsets, means, scales, the CMN state */
@@ -886,6 +891,8 @@ ssw_model_free(ssw_model_t *m)
     (void)hipFree(m->d_cont_rec);
     (void)hipFree(m->d_cont_pdf);
     (void)hipFree(m->cont_ws.p);
+    (void)hipFree(m->d_cont_rec_sm);
+    (void)hipFree(m->cont_act_ws.p);
     if (m->sw.timing) {
         for (int i = 0; i < 3; ++i)
             (void)hipEventDestroy(m->sw.ev[i]);
@@ -946,6 +953,49 @@ extern "C" int
 ssw_model_is_continuous(const ssw_model_t *m)
 {
     return m->h->continuous ? 1 : 0;
+}
+
+extern "C" int
+ssw_model_active_enabled(const ssw_model_t *m)
+{
+    return m != NULL && m->h->continuous && m->d_cont_rec_sm != NULL ? 1 : 0;
+}
+
+extern "C" int
+ssw_model_enable_active(ssw_model_t *m)
+{
+    if (m == NULL) {
+        ssw_set_error("ssw_model_enable_active: NULL model");
+        return -1;
+    }
+    ssw_host_model_t *h = m->h;
+    if (!h->continuous || m->d_cont_rec_sm != NULL)
+        return 0; /* nothing to add / done before */
+    if (check_has_device(m) < 0)
+        return -1;
+    ModelBusy busy_(m);
+    if (!busy_.ok)
+        return -1;
+    if (ssw_host_build_cont_sm(h) < 0)
+        return -1;
+    float *d_tab = NULL;
+    hipError_t e = hipSetDevice(m->device);
+    if (e == hipSuccess)
+        e = hipMalloc(reinterpret_cast<void **>(&d_tab), h->cont_sm_floats * sizeof(float));
+    if (e == hipSuccess)
+        e = hipMemcpy(d_tab, h->cont_rec_sm, h->cont_sm_floats * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { /* the model as it was: no second table on either side */
+        (void)hipGetLastError();
+        (void)hipFree(d_tab);
+        free(h->cont_rec_sm);
+        h->cont_rec_sm = NULL;
+        h->cont_sm_floats = 0;
+        ssw_set_error("ssw_model_enable_active: the senone-major table (%zu bytes): %s",
+                      h->cont_sm_sen * (size_t)h->n_cb * sizeof(float), hipGetErrorString(e));
+        return -1;
+    }
+    m->d_cont_rec_sm = d_tab;
+    return 0;
 }
 
 extern "C" const char *

@@ -119,6 +119,9 @@ struct ActiveSets {
     /* or (a2 == NULL): a listed set per frame as a bitmap, ssw_k7_fpactive.inc -- listed, cbmask,
      * out, full, cap are the caller's, the rest is filled here */
     const SenoneListedParams *ls;
+    /* a continuous model (ls: listed, out, full, cap, yes are read): NULL, or the bitmap row of
+     * every frame of the call where frames share rows (cont_align_active) */
+    const int32_t *row_of_frame;
 };
 
 /* One scoring call.  `ScoreReq R{}` is all zeros; a caller names what it sets. */
@@ -852,13 +855,23 @@ score_batch_impl(ssw_model_t *m, const ScoreReq &R)
     if (m->h->continuous) {
         /* no history, no utterance boundaries, none of the PTM scan's workspaces: its own two
          * kernels (ssw_host_cont.inc); flags, carry_in and ds are ignored as for ms */
-        if (R.act != NULL || R.cp != NULL) {
-            ssw_set_error("internal error: active sets or compact rows with a continuous model");
+        if (R.cp != NULL || (R.act != NULL && (R.act->a2 != NULL || R.act->ls == NULL))) {
+            ssw_set_error("internal error: segment lists or compact rows with a continuous model");
             return -1;
         }
+        if (R.act != NULL && cont_refuse_active(m, "active-set scoring") < 0)
+            return -1;
         if (m->sw.timing) {
             HIP_OK(hipEventRecord(m->sw.ev[0], C.st));
             m->sw.timing_semi = 0;
+        }
+        if (R.act != NULL) { /* compallsen = no: the listed senones of every frame alone */
+            const SenoneListedParams &ls = *R.act->ls;
+            ContListedReq Q{ R.d_feats, R.n_frames, ls.listed, R.act->row_of_frame, ls.out, ls.yes,
+                             ls.cap,    ls.full };
+            if (cont_listed_launch(m, Q, C.st) < 0)
+                return -1;
+            return score_batch_finish(C, 0, false, false);
         }
         if (cont_launch(m, R.d_feats, R.n_frames, R.d_out, C.st) < 0)
             return -1;

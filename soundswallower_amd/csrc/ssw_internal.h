@@ -202,6 +202,14 @@ typedef struct ssw_host_model_s {
     float *cont_rec;
     int32_t continuous, cont_sp;
     size_t cont_off[SSW_MAX_FEAT], cont_floats;
+    /* the same floats senone-major, for cont_listed_kernel (ssw_host_build_cont_sm; NULL until
+     * then): senone s owns cont_sm_sen floats, its stream f's record starts cont_sm_off[f] floats
+     * in and holds, for n = n_density and v = veclen[f],
+     *   [v][n][2]  (mean, scale) of dimension j, density d, as a pair
+     *   [n]        det
+     * padded with one 0.0f to an even count of floats */
+    float *cont_rec_sm;
+    size_t cont_sm_off[SSW_MAX_FEAT], cont_sm_sen, cont_sm_floats;
 } ssw_host_model_t;
 
 /* the scorer acmod_load_am would choose for the model's shape (enum ssw_scorer) */
@@ -218,6 +226,10 @@ int ssw_host_build_records(ssw_host_model_t *h);
  * tables of the model's scorer are rebuilt in the allocations they have (first call: made).  Both
  * the loader and ssw_host_model_apply_mllr end here. */
 int ssw_host_derive_tables(ssw_host_model_t *h);
+/* a continuous model's second table (cont_rec_sm above) from mean / var / det as they stand;
+ * rebuilt in its allocation when it exists.  From then on ssw_host_derive_tables keeps it up to
+ * date.  -1 and ssw_set_error: not a continuous model, out of memory (the model is unchanged). */
+int ssw_host_build_cont_sm(ssw_host_model_t *h);
 /* gauden_mllr_transform (src/ms_gauden.c:459-539) over the parameters as read: class 0 of the
  * transform on every codebook, then ssw_host_derive_tables.  NULL puts the files' parameters
  * back.  A transform that does not fit the model, or holds a non-finite number, is refused before

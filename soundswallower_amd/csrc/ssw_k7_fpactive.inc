@@ -31,7 +31,7 @@ struct FpaPlanParams {
                                            rows -- a text's own graph, or the grammar it is searched
                                            against (many utterances may share one) */
     const uint16_t *senid;              /* [n_nodes][4] */
-    const uint8_t *sen2cb;
+    const uint8_t *sen2cb;              /* NULL (a continuous model): no codebook mask is made */
     uint32_t *listed;                   /* [n_frames][nw32] listed senones, bridges included */
     unsigned long long *cbmask;         /* [n_frames] */
     int32_t *iota;                      /* [n_frames] = t (the scan's segment table) */
@@ -134,17 +134,17 @@ fpa_plan_kernel(FpaPlanParams P, int cap)
     int n_bridge = 0;
     for (int i = lane; i < n; i += 64) {
         const int sen = lst[i], prev = i > 0 ? (int)lst[i - 1] : 0;
-        const int cb = P.sen2cb[sen];
+        const int cb = P.sen2cb != nullptr ? (int)P.sen2cb[sen] : 64;
         mycb0 |= cb < 32 ? 1u << cb : 0u;
-        mycb1 |= cb >= 32 ? 1u << (cb - 32) : 0u;
+        mycb1 |= cb >= 32 && cb < 64 ? 1u << (cb - 32) : 0u;
         const int r = sen - prev;
         const int K = r > 0 ? (r - 1) / 255 : 0;
         for (int k = 1; k <= K; ++k) {
             const int b = prev + 255 * k;
             atomicOr(&bm[b >> 5], 1u << (b & 31));
-            const int cbb = P.sen2cb[b];
+            const int cbb = P.sen2cb != nullptr ? (int)P.sen2cb[b] : 64;
             mycb0 |= cbb < 32 ? 1u << cbb : 0u;
-            mycb1 |= cbb >= 32 ? 1u << (cbb - 32) : 0u;
+            mycb1 |= cbb >= 32 && cbb < 64 ? 1u << (cbb - 32) : 0u;
             ++n_bridge;
         }
     }

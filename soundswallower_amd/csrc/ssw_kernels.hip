@@ -75,6 +75,11 @@
  *                        cont_score_kernel (compute_dist + senone_eval, a lane per senone),
  *                        cont_norm_kernel (the frame's minimum), src/ms_gauden.c:349-432,
  *                        src/ms_senone.c:314-362, src/ms_mgau.c:299-321
+ *                        cont_listed_kernel (compallsen = no: a group of lanes per LISTED senone
+ *                        over the senone-major table, src/ms_mgau.c:322-365)
+ *   ssw_cont_select.inc  compute_dist's selection, once: cont_insert (sequential) and
+ *                        cont_select_rank (a density's slot as a count; a host program can
+ *                        include it on its own)
  *   ssw_k12_feat.inc     dynamic features of every type feat_init_s3file accepts, with batch or
  *                        live CMN, varnorm, an LDA and a subvector gather: feat_stats_kernel /
  *                        feat_chain_kernel (the utterances' means and scales, live CMN's state)
@@ -92,6 +97,9 @@
  *   ssw_fp_shape.inc     host, no HIP: fp_shape, what one launch of the first pass takes (the
  *                        per-utterance LDS, HBM-workspace and history sizes, each formula once;
  *                        register / window / HBM / HBM-banded kernel, threads, LDS bytes)
+ *   ssw_active_set.inc   host, no HIP: the second pass's active set from the phone windows
+ *                        (active_first_frames, ActiveSetBuilder) and a continuous model's bitmap
+ *                        rows of it (cont_active_rows)
  *   ssw_host_model.inc   also the host side's three shared helpers, each holding one policy:
  *                        devbuf_reserve (the grow-only device buffer: no HIP call unless it
  *                        grows, hipFree's implicit synchronisation, sticky error cleared),
@@ -149,6 +157,8 @@ namespace {
 #include "ssw_scan_common.inc"
 #include "ssw_k1a_frames.inc"
 #include "ssw_top5_select.inc"
+#define SSW_CONT_SEL_FN __host__ __device__ __forceinline__
+#include "ssw_cont_select.inc"
 #include "ssw_k1a_mfma.inc"
 #include "ssw_k1b_senone.inc"
 #include "ssw_k4_feat.inc"
@@ -181,9 +191,30 @@ static int cont_check_shape(const ssw_model_s *m, int scorer);
 static int cont_refuse(const ssw_model_s *m, const char *who);
 static int cont_launch(ssw_model_s *m, const float *d_feats, int32_t n_frames, int16_t *d_out,
                        hipStream_t st);
+static int cont_refuse_active(const ssw_model_s *m, const char *who);
+/* one launch of cont_listed_kernel: device pointers; d_row_of_frame NULL = frame t reads bitmap
+ * row t; cap <= 0 = n_sen; d_yes only with full == 2 */
+struct ContListedReq {
+    const float *d_feats;
+    int32_t n_frames;
+    const uint32_t *d_listed;
+    const int32_t *d_row_of_frame;
+    int16_t *d_out;
+    const int16_t *d_yes;
+    int cap, full;
+};
+static size_t cont_listed_lds(const ssw_model_s *m, int cap);
+static int cont_listed_launch(ssw_model_s *m, const ContListedReq &Q, hipStream_t st);
+static int cont_align_active(ssw_model_t *m, const float *d_feats, int32_t n_utts,
+                             const int32_t *frame_off, const int32_t *phone_off,
+                             const uint16_t *senid, const int16_t *tmatid, const int32_t *sf,
+                             const int32_t *ef, const uint32_t *seed_active,
+                             ssw_align_entry_t *state_io, int32_t *status, int16_t *d_senscr,
+                             void *stream);
 #include "ssw_host_score.inc"
 #include "ssw_host_align.inc"
 #include "ssw_host_compact.inc"
+#include "ssw_active_set.inc"
 #include "ssw_host_active.inc"
 #include "ssw_host_mllr.inc"
 #include "ssw_host_mgau.inc"
@@ -198,3 +229,5 @@ static int cont_launch(ssw_model_s *m, const float *d_feats, int32_t n_frames, i
 #include "ssw_host_cont.inc"
 /* ... and the feature kernels of every configuration behind those, for the same reason */
 #include "ssw_host_featex.inc"
+/* ... and the listed-senone kernel of continuous models behind those */
+#include "ssw_host_cont_listed.inc"

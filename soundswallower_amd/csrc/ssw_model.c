@@ -2521,6 +2521,51 @@ build_cont_records(ssw_host_model_t *h)
     return 0;
 }
 
+/* The table of cont_listed_kernel (ssw_k11_cont.inc), senone-major so that the data of a listed
+ * senone is whole contiguous records: the layout is stated at ssw_host_model_t::cont_rec_sm.  The
+ * floats are those of build_cont_records (the same mean, var and det arrays, file order). */
+int
+ssw_host_build_cont_sm(ssw_host_model_t *h)
+{
+    const float *mp = h->mean, *vp = h->var, *dp = h->det;
+    const size_t nd = (size_t)h->n_density;
+    size_t per_sen = 0, total;
+    float *tab;
+    int c, f, d, j;
+
+    if (!h->continuous || h->cont_rec == NULL) {
+        ssw_set_error("the senone-major table is a continuous model's");
+        return -1;
+    }
+    for (f = 0; f < h->n_feat; ++f) {
+        h->cont_sm_off[f] = per_sen;
+        per_sen += (nd * (2 * (size_t)h->veclen[f] + 1) + 1) & ~(size_t)1;
+    }
+    total = per_sen * (size_t)h->n_cb;
+    tab = (float *)table_zeroed(h->cont_rec_sm, total, sizeof(float));
+    if (tab == NULL) {
+        ssw_set_error("out of memory building the continuous model's senone-major table (%zu bytes)",
+                      total * sizeof(float));
+        return -1;
+    }
+    h->cont_rec_sm = tab;
+    h->cont_sm_sen = per_sen;
+    h->cont_sm_floats = total;
+    for (c = 0; c < h->n_cb; ++c)
+        for (f = 0; f < h->n_feat; ++f) {
+            const size_t vl = (size_t)h->veclen[f];
+            float *r = tab + (size_t)c * per_sen + h->cont_sm_off[f];
+            for (d = 0; d < h->n_density; ++d) {
+                for (j = 0; j < h->veclen[f]; ++j) {
+                    r[2 * ((size_t)j * nd + (size_t)d)] = *mp++;
+                    r[2 * ((size_t)j * nd + (size_t)d) + 1] = *vp++;
+                }
+                r[2 * vl * nd + (size_t)d] = *dp++;
+            }
+        }
+    return 0;
+}
+
 /* Everything derived from (mean, raw variance), for the loader and for ssw_host_model_apply_mllr:
  * det and the scaled variances, then the tables of the model's scorer.  A single-codebook model
  * is the s2_semi scorer's: its own table, none of the PTM scan's (records of 15 dimensions, at
@@ -2534,8 +2579,12 @@ ssw_host_derive_tables(ssw_host_model_t *h)
     lb.base = h->cfg.logbase;
     lb.inv_ln_base = 1.0 / log(h->cfg.logbase);
     precompute_gaussians(h, &lb);
-    if (h->continuous)
-        return build_cont_records(h);
+    if (h->continuous) {
+        if (build_cont_records(h) < 0)
+            return -1;
+        /* (the second table only once it was asked for: ssw_model_enable_active) */
+        return h->cont_rec_sm != NULL ? ssw_host_build_cont_sm(h) : 0;
+    }
     if (ssw_host_scorer(h) == SSW_SCORER_S2_SEMI)
         return build_semi_records(h);
     return ssw_host_build_records(h);
@@ -3006,6 +3055,7 @@ ssw_host_model_free(ssw_host_model_t *h)
     free(h->rec28);
     free(h->sc_rec);
     free(h->cont_rec);
+    free(h->cont_rec_sm);
     free(h->sseq);
     free(h->sen2cb);
     free(h->phone_ssid);

@@ -100,3 +100,22 @@ struct ListedCarve : WaveItems {
     SSW_HD size_t wave(int w) const { return (size_t)w * per_wave(); }
     SSW_HD size_t bytes() const { return 4 * per_wave(); }
 };
+
+/* cont_listed_kernel (ssw_k11_cont.inc), per wave: x[pad4(featdim)] float, the frame's features |
+ * fw[64] int, a slot per lane: the terms a group's leader combines | sen[pad2(cap)] uint16, the
+ * list | a[pad2(cap)] int16, its raw scores | n, the entry counter (an int, in 16 bytes of its
+ * own) */
+struct ContListedCarve {
+    int featdim, cap;
+
+    SSW_HD ContListedCarve(int featdim_, int cap_) : featdim(featdim_), cap(cap_) {}
+    SSW_HD static int pad2(int count) { return (count + 1) & ~1; }
+    SSW_HD int x() const { return 0; }
+    SSW_HD int fw() const { return 4 * ((featdim + 3) & ~3); }
+    SSW_HD int sen() const { return fw() + 4 * 64; }
+    SSW_HD int a() const { return sen() + 2 * pad2(cap); }
+    SSW_HD int count() const { return a() + 2 * pad2(cap); }
+    SSW_HD size_t per_wave() const { return ((size_t)count() + 16 + 15) & ~(size_t)15; }
+    SSW_HD size_t wave(int w) const { return (size_t)w * per_wave(); }
+    SSW_HD size_t bytes() const { return 4 * per_wave(); }
+};
