@@ -5,7 +5,8 @@
  * Part of the single translation unit ssw_kernels.hip, included LAST: the kernel is emitted behind
  * every other one, whose placement in the code object stays as it was. */
 
-/* the kernel's dynamic LDS for lists of up to `cap` senones (fpa_run checks it against a CU's) */
+/* the kernel's dynamic LDS for lists of up to `cap` senones (fpa_shape checks the same carve
+ * against a CU's) */
 static size_t
 cont_listed_lds(const ssw_model_s *m, int cap)
 {

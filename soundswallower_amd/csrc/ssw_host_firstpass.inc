@@ -439,11 +439,32 @@ struct fpa_mode_t {
     const float *d_feats;
     bool two_pass; /* cfg->two_pass_history: the second pass starts from what the first left */
 };
-static int first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const float *d_feats,
-                                 int32_t n_frames, const int32_t *utt_off, int32_t n_utts,
-                                 int32_t max_seg, int32_t *n_seg, ssw_word_seg_t *seg,
-                                 int16_t *d_rows, bool full_rows, uint32_t *seed_out,
-                                 int32_t *rounds_out, void *stream, uint32_t *d_carry_out = NULL);
+/* One call of the loop of speculation and proof (fpa_run, ssw_host_fpactive.inc), filled by name;
+ * what is not set is NULL / 0. */
+struct FpaReq {
+    int scorer;
+    const float *d_feats;
+    int32_t n_frames;
+    const int32_t *utt_off;
+    int32_t n_utts;
+    int16_t *d_rows;       /* device int16 [n_frames][n_sen]: the rows the call scores into
+                              (workspace and, with full_rows, output) */
+    bool full_rows;        /* the rows as acmod's buffer would hold them, unlisted entries written */
+    uint32_t *seed_out;    /* NULL or host [n_utts][(n_sen + 31) / 32]: acmod's flags after every
+                              utterance's last frame */
+    int32_t *rounds_out;   /* NULL or host [n_utts]: searches of the utterance over default-
+                              configuration scores until its sets were proven (1 = the assumed
+                              trajectory was already the right one) */
+    uint32_t *listed_out;  /* NULL or host [n_frames][(n_sen + 31) / 32]: the proven listed senones
+                              of every frame, bridges included */
+    uint32_t *d_carry_out; /* NULL or device [n_utts][n_cbf]: history slot 1 as every utterance's
+                              first pass leaves it (two_pass_history) */
+    int64_t *stats;        /* the four counters the call feeds (fpa_stats / gra_stats) */
+    void *stream;
+};
+/* the first pass's: the request, and what is the first pass's own */
+static int first_pass_active_run(ssw_model_t *m, const FpaReq &R, ssw_fp_graphs_t *g, int32_t max_seg,
+                                 int32_t *n_seg, ssw_word_seg_t *seg);
 
 /* decoder_alignment for a batch of texts: the first pass, then align_word_segments.  The texts
  * come as a plan, or as cfg + word_off + words. */
@@ -577,6 +598,25 @@ ssw_forced_align_planned(ssw_model_t *m, const ssw_dict_t *d, const ssw_first_pa
     return forced_align_core(m, F);
 }
 
+/* the first pass of F in the default configuration (F.fpa): the rows are its workspace, the seed
+ * of the second pass and, with two_pass_history, the carried orders come out */
+static FpaReq
+forced_align_fpa_req(ssw_model_t *m, const ForcedAlignReq &F, uint32_t *seed, bool carry2)
+{
+    FpaReq A{};
+    A.scorer = F.fpa->scorer;
+    A.d_feats = F.fpa->d_feats;
+    A.n_frames = F.n_frames;
+    A.utt_off = F.utt_off;
+    A.n_utts = F.n_utts;
+    A.d_rows = const_cast<int16_t *>(F.d_senscr);
+    A.seed_out = seed;
+    A.d_carry_out = carry2 ? m->carry_rows.as<uint32_t>() : NULL;
+    A.stats = m->fpa_stats;
+    A.stream = F.stream;
+    return A;
+}
+
 static ssw_alignment_set_t *
 forced_align_core(ssw_model_t *m, const ForcedAlignReq &F)
 {
@@ -617,10 +657,8 @@ forced_align_core(ssw_model_t *m, const ForcedAlignReq &F)
         }
         const ssw_first_pass_plan_t *use = plan ? plan : own_plan;
         const int rc = fpa != NULL
-            ? first_pass_active_run(m, use->g, fpa->scorer, fpa->d_feats, F.n_frames, F.utt_off,
-                                    n_utts, max_seg, n_seg.data(), seg.data(),
-                                    const_cast<int16_t *>(F.d_senscr), false, seed.data(), NULL,
-                                    F.stream, carry2 ? m->carry_rows.as<uint32_t>() : NULL)
+            ? first_pass_active_run(m, forced_align_fpa_req(m, F, seed.data(), carry2), use->g,
+                                    max_seg, n_seg.data(), seg.data())
             : use ? ssw_first_pass_run(m, use, F.d_senscr, F.n_frames, F.utt_off, max_seg,
                                        n_seg.data(), seg.data(), F.stream)
                   : ssw_first_pass_batch(m, F.d, F.cfg, F.d_senscr, F.n_frames, F.utt_off, n_utts,

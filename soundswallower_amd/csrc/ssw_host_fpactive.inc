@@ -1,6 +1,8 @@
 /* ssw_host_fpactive.inc -- host: the first pass (and decoder_alignment) in the reference's DEFAULT
  * configuration, compallsen = no, for a batch: ssw_first_pass_batch_active,
  * ssw_align_text_batch_active.  Kernels and the argument why this is exact: ssw_k7_fpactive.inc.
+ * One call of the loop is an FpaReq (ssw_host_firstpass.inc) through fpa_run's steps; its sizes
+ * and the policy of its rounds are ssw_fpa_shape.inc's.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 
 /* What the loop of speculation and proof (fpa_run) needs of the search it drives.  Two kinds:
@@ -57,7 +59,9 @@ fpa_fp_search(void *arg, const int16_t *rows, const std::vector<int> &only,
     return first_pass_run(a.m, R);
 }
 
-/* what the loop serves: refused with a message before anything is uploaded or launched */
+/* what the loop serves: refused with a message before anything is uploaded or launched.  Every
+ * path to fpa_run asks once: the grammar entries ahead of their run's begin, the first pass's in
+ * first_pass_active_run. */
 static int
 fpa_check_limits(ssw_model_t *m, const char *who, int scorer)
 {
@@ -77,353 +81,386 @@ fpa_check_limits(ssw_model_t *m, const char *who, int scorer)
     return 0;
 }
 
-/* d_rows: int16 [n_frames][n_sen] device rows the call scores into (workspace and, with
- * full_rows, output).  seed_out: NULL or host [n_utts][(n_sen + 31) / 32].  rounds_out: NULL or
- * host [n_utts]: searches of the utterance over default-configuration scores until its sets
- * were proven (1 = the assumed trajectory was already the right one).
- * listed_out: NULL or host [n_frames][(n_sen + 31) / 32]: the proven listed senones of every
- * frame, bridges included.  stats: the caller's four counters. */
-static int
-fpa_run(ssw_model_t *m, const fpa_graph_t &G, int scorer, const float *d_feats, int32_t n_frames,
-        const int32_t *utt_off, int32_t n_utts, int16_t *d_rows, bool full_rows, uint32_t *seed_out,
-        int32_t *rounds_out, uint32_t *listed_out, int64_t *stats, void *stream,
-        uint32_t *d_carry_out)
+/* one call's state: its shape, the workspace's tables (named once, in fpa_layout_upload) and
+ * the rounds' bookkeeping */
+struct FpaState {
+    FpaShape S;
+    unsigned long long *mask_x, *mask_y; /* the sets assumed, the sets the search then took */
+    const long long *d_act_off;
+    const int *d_utt_off, *d_node_base, *d_node_cnt;
+    const uint16_t *d_senid;
+    uint32_t *d_listed;
+    unsigned long long *d_cbm;
+    int32_t *d_iota;
+    uint32_t *d_seed;
+    int32_t *d_diff, *d_only;
+    int16_t *d_yes;    /* one utterance's compallsen = yes rows (the rounds over few utterances) */
+    uint32_t *d_start; /* two-pass history: the whole batch's utterance-start bits */
+    std::vector<int> only; /* empty = every utterance */
+    std::vector<int32_t> rounds, diff;
+    int n_round;
+};
+
+static FpaModelSizes
+fpa_model_sizes(const ssw_model_t *m, int scorer)
 {
-    ModelBusy busy_(m);
-    if (!busy_.ok)
-        return -1;
     const ssw_host_model_t *h = m->h;
-    hipStream_t st = (hipStream_t)stream;
-    if (n_utts <= 0)
-        return 0;
-    if (fpa_check_limits(m, G.who, scorer) < 0)
+    FpaModelSizes M;
+    M.kind = h->continuous ? FPA_CONT : scorer == SSW_SCORER_MS ? FPA_MS : FPA_PTM;
+    M.n_sen = h->n_sen;
+    M.n_cbf = m->n_cbf;
+    M.featdim = h->veclen_total;
+    return M;
+}
+
+/* step 2: the workspace laid out, reserved, its tables uploaded in one copy (act_off | utt_off |
+ * node base, count | senid) and every pointer of T resolved */
+static int
+fpa_layout_upload(ssw_model_t *m, const fpa_graph_t &G, const FpaReq &R, FpaState &T)
+{
+    const FpaShape &S = T.S;
+    const size_t nf = (size_t)std::max(R.n_frames, 1), nU = (size_t)R.n_utts, nw32 = (size_t)S.nw32;
+    const size_t mask_bytes = sizeof(unsigned long long) * (size_t)std::max(S.mask_words, 1ll);
+    WsLayout L;
+    L.out(&T.mask_x, mask_bytes);
+    L.out(&T.mask_y, mask_bytes);
+    const size_t o_up = L.mark();
+    L.in(&T.d_act_off, S.act_off.data(), sizeof(long long) * nU);
+    L.in(&T.d_utt_off, R.utt_off, sizeof(int) * (nU + 1));
+    L.in(&T.d_node_base, G.node_base.data(), sizeof(int) * nU);
+    L.in(&T.d_node_cnt, G.node_cnt.data(), sizeof(int) * nU);
+    L.in(&T.d_senid, G.senid, sizeof(uint16_t) * 4 * (size_t)G.n_nodes, 1);
+    L.out(&T.d_listed, sizeof(uint32_t) * nf * nw32);
+    L.out(&T.d_cbm, sizeof(unsigned long long) * nf);
+    L.out(&T.d_iota, sizeof(int32_t) * nf);
+    L.out(&T.d_seed, sizeof(uint32_t) * nU * nw32);
+    L.out(&T.d_diff, sizeof(int32_t) * nU);
+    L.out(&T.d_only, sizeof(int32_t) * nU);
+    L.out(&T.d_yes, sizeof(int16_t) * (size_t)std::max(S.max_len, 1) * (size_t)m->h->n_sen);
+    L.out(&T.d_start, S.start_bytes);
+    if (devbuf_reserve(m->fpa_ws, L.size(), G.who) < 0)
         return -1;
+    L.resolve(m->fpa_ws.p);
+    return stage_upload(m, m->fpa_ws.p + o_up, L.in_bytes() - o_up, (hipStream_t)R.stream,
+                        [&](unsigned char *hs) { L.fill(hs, o_up); });
+}
+
+/* step 3, the assumption: the trajectory of the search over the compallsen = yes scores, its
+ * sets into mask_x */
+static int
+fpa_assume(ssw_model_t *m, const fpa_graph_t &G, const FpaReq &R, FpaState &T)
+{
+    HIP_OK(hipMemsetAsync(T.d_seed, 0, sizeof(uint32_t) * (size_t)R.n_utts * (size_t)T.S.nw32,
+                          (hipStream_t)R.stream));
+    if (R.n_frames > 0
+        && ssw_score_batch(m, R.scorer, R.d_feats, R.n_frames, R.utt_off, R.n_utts, R.d_rows, R.stream) < 0)
+        return -1;
+    return G.search(G.arg, R.d_rows, T.only, T.mask_x, T.d_act_off, T.d_node_cnt);
+}
+
+/* frames [lo, hi) = utterances [u_lo, u_hi), planned from mask_x (the sets assumed -> listed
+ * senones and active codebooks per frame) and scored into d_rows (the scores the reference would
+ * compute for them).  full: senone_listed_kernel's. */
+static int
+fpa_plan_and_score(ssw_model_t *m, const FpaReq &R, FpaState &T, int lo, int hi, int u_lo, int u_hi,
+                   int full)
+{
+    const ssw_host_model_t *h = m->h;
+    hipStream_t st = (hipStream_t)R.stream;
+    if (hi <= lo)
+        return 0;
+    FpaPlanParams Q;
+    Q.act_mask = T.mask_x;
+    Q.act_off = T.d_act_off;
+    Q.utt_off = T.d_utt_off;
+    Q.node_base = T.d_node_base;
+    Q.node_cnt = T.d_node_cnt;
+    Q.senid = T.d_senid;
+    Q.sen2cb = m->d_sen2cb;
+    Q.listed = T.d_listed;
+    Q.cbmask = T.d_cbm;
+    Q.iota = T.d_iota;
+    Q.seed = T.d_seed;
+    Q.n_listed = NULL;
+    Q.n_utts = R.n_utts;
+    Q.n_frames = R.n_frames;
+    Q.n_sen = h->n_sen;
+    Q.nw32 = T.S.nw32;
+    Q.frame_lo = lo;
+    Q.frame_hi = hi;
+    if (T.S.plan_lds > 48 * 1024)
+        HIP_OK(hipFuncSetAttribute((const void *)fpa_plan_kernel,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)T.S.plan_lds));
+    hipLaunchKernelGGL(fpa_plan_kernel, dim3((unsigned)((hi - lo + 3) / 4)), dim3(256), T.S.plan_lds,
+                       st, Q, T.S.cap);
+    HIP_OK(hipGetLastError());
+    SenoneListedParams L;
+    memset(&L, 0, sizeof(L));
+    L.listed = T.d_listed + (size_t)lo * T.S.nw32;
+    L.cbmask = T.d_cbm + lo;
+    L.out = R.d_rows + (size_t)lo * h->n_sen;
+    L.full = full;
+    L.yes = T.d_yes; /* (full == 2: one utterance, its yes rows from frame 0) */
+    L.cap = T.S.cap;
+    ActiveSets act;
+    /* (0 .. : the identity, whatever the sub-batch.  iota must hold 0 .. n for any sub-batch: the
+     * whole batch's plan writes iota[t] = t once; a sub-batch's plan writes the same values at
+     * the same places) */
+    act.seg_of_frame = T.d_iota;
+    act.seg_cbmask = T.d_cbm + lo;
+    act.a2 = NULL;
+    act.ls = &L;
+    act.row_of_frame = NULL;
+    std::vector<int32_t> sub;
+    const int32_t *uo = R.utt_off;
+    if (lo != 0 || hi != R.n_frames) {
+        for (int u = u_lo; u <= u_hi; ++u)
+            sub.push_back(R.utt_off[u] - lo);
+        uo = sub.data();
+    }
+    ScoreReq Sc{};
+    Sc.scorer = R.scorer;
+    Sc.d_feats = R.d_feats + (size_t)lo * h->veclen_total;
+    Sc.n_frames = hi - lo;
+    Sc.utt_off = uo;
+    Sc.n_utts = u_hi - u_lo;
+    Sc.d_out = R.d_rows;
+    Sc.stream = R.stream;
+    Sc.act = &act;
+    return score_batch_impl(m, Sc);
+}
+
+/* a round's plan and scoring (steps 2 + 3 of ssw_k7_fpactive.inc).  Few unproven utterances left
+ * (fpa_one_by_one): they are scored one by one; else the whole batch again (the proven ones' rows
+ * come out as they are: their sets have not changed) */
+static int
+fpa_score_round(ssw_model_t *m, const FpaReq &R, FpaState &T)
+{
+    if (!fpa_one_by_one(T.only.size(), R.n_utts, m->kn.fpa_sub))
+        return fpa_plan_and_score(m, R, T, 0, R.n_frames, 0, R.n_utts, 0);
+    /* each of them with its unlisted entries refreshed from its compallsen = yes scores
+     * (senone_listed_kernel, full == 2): what such an utterance still gets wrong is the
+     * fate of HMMs that enter outside the assumed sets, judged on whatever the row held */
+    for (int u : T.only) {
+        const int a = R.utt_off[u], b = R.utt_off[u + 1];
+        if (b <= a)
+            continue;
+        const int32_t uo[2] = { 0, b - a };
+        if (ssw_score_batch(m, R.scorer, R.d_feats + (size_t)a * m->h->veclen_total, b - a, uo, 1,
+                            T.d_yes, R.stream) < 0)
+            return -1;
+        if (fpa_plan_and_score(m, R, T, a, b, u, u + 1, 2) < 0)
+            return -1;
+    }
+    return 0;
+}
+
+/* step 5 of a round: an utterance is proven where the sets the search took (mask_y) are the
+ * assumed ones (mask_x).  The round's utterances get its number; `again`: the ones not yet
+ * proven, ascending.  Ends in the round's synchronisation of the stream. */
+static int
+fpa_compare(ssw_model_t *m, const FpaReq &R, FpaState &T, std::vector<int> &again)
+{
+    hipStream_t st = (hipStream_t)R.stream;
+    const std::vector<int> &only = T.only;
+    const int n_cmp = only.empty() ? R.n_utts : (int)only.size();
+    if (!only.empty()
+        && stage_upload(m, T.d_only, sizeof(int32_t) * only.size(), st, [&](unsigned char *hs) {
+               memcpy(hs, only.data(), sizeof(int32_t) * only.size());
+           }) < 0)
+        return -1;
+    HIP_OK(hipMemsetAsync(T.d_diff, 0x7f, sizeof(int32_t) * (size_t)R.n_utts, st));
+    hipLaunchKernelGGL(fpa_compare_kernel, dim3((unsigned)n_cmp, fpa_compare_slices(T.S.mask_words, n_cmp)),
+                       dim3(256), 0, st, T.mask_x, T.mask_y, T.d_act_off, T.d_utt_off, T.d_node_cnt,
+                       only.empty() ? (const int *)NULL : T.d_only, T.d_diff);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(T.diff.data(), T.d_diff, sizeof(int32_t) * (size_t)R.n_utts,
+                          hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int i = 0; i < n_cmp; ++i) {
+        const int u = only.empty() ? i : only[(size_t)i];
+        T.rounds[(size_t)u] = T.n_round;
+        if (T.diff[(size_t)u] != FPA_NO_DIFF)
+            again.push_back(u);
+    }
+    return 0;
+}
+
+/* step 6, two_pass_history: history slot 1 as every utterance's first pass leaves it
+ * (fpa_carry_rows_kernel), from the features and the proven codebook masks -- d_cbm holds, for
+ * every utterance, those of the last plan of its frames */
+static int
+fpa_carry_rows(ssw_model_t *m, const FpaReq &R, FpaState &T)
+{
+    const ssw_host_model_t *h = m->h;
+    hipStream_t st = (hipStream_t)R.stream;
+    if (R.d_carry_out == NULL || R.scorer != SSW_SCORER_PTM)
+        return 0;
+    if (m->d_rec28 == NULL) {
+        ssw_set_error("two_pass_history in the default configuration needs codebooks of 128 densities");
+        return -1;
+    }
+    if (R.n_frames <= 0)
+        return 0;
+    const size_t n_words = T.S.n_start_words;
+    if (stage_upload(m, T.d_start, sizeof(uint32_t) * n_words, st, [&](unsigned char *hs) {
+            uint32_t *bits = reinterpret_cast<uint32_t *>(hs);
+            memset(bits, 0, sizeof(uint32_t) * n_words);
+            for (int u = 0; u < R.n_utts; ++u)
+                if (R.utt_off[u] < R.n_frames)
+                    bits[(size_t)R.utt_off[u] >> 5] |= 1u << (R.utt_off[u] & 31);
+        }) < 0)
+        return -1;
+    FramesParams F;
+    memset(&F, 0, sizeof(F));
+    F.utt_start = T.d_start;
+    F.utt_off = T.d_utt_off;
+    F.n_utts = R.n_utts;
+    F.seg_of_frame = T.d_iota;
+    F.seg_cbmask = T.d_cbm;
+    F.n_frames = R.n_frames;
+    F.n_cbf = m->n_cbf;
+    F.n_feat = h->n_feat;
+    F.featdim = h->veclen_total;
+    for (int f = 0; f < h->n_feat; ++f)
+        F.featoff[f] = h->featoff[f];
+    hipLaunchKernelGGL(fpa_carry_rows_kernel, dim3((unsigned)((size_t)R.n_utts * m->n_cbf)), dim3(64), 0,
+                       st, F, m->d_rec28, R.d_feats, T.d_utt_off, R.d_carry_out);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+/* step 7: what the caller asked for, on the host when this returns */
+static int
+fpa_copy_out(const FpaReq &R, const FpaState &T)
+{
+    hipStream_t st = (hipStream_t)R.stream;
+    const size_t nw32 = (size_t)T.S.nw32;
+    if (R.listed_out != NULL && R.n_frames > 0)
+        HIP_OK(hipMemcpyAsync(R.listed_out, T.d_listed, sizeof(uint32_t) * (size_t)R.n_frames * nw32,
+                              hipMemcpyDeviceToHost, st));
+    if (R.seed_out != NULL)
+        HIP_OK(hipMemcpyAsync(R.seed_out, T.d_seed, sizeof(uint32_t) * (size_t)R.n_utts * nw32,
+                              hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (R.rounds_out != NULL)
+        memcpy(R.rounds_out, T.rounds.data(), sizeof(int32_t) * (size_t)R.n_utts);
+    return 0;
+}
+
+/* step 8: the counters of ssw_first_pass_active_stats / ssw_grammar_active_stats */
+static void
+fpa_add_stats(const FpaReq &R, const FpaState &T)
+{
+    int more = 0;
+    long long sum = 0;
+    for (int u = 0; u < R.n_utts; ++u) {
+        sum += T.rounds[(size_t)u];
+        more += T.rounds[(size_t)u] > 1 ? 1 : 0;
+    }
+    R.stats[0] += R.n_utts;
+    R.stats[1] += sum;
+    R.stats[2] = T.n_round;
+    R.stats[3] += more;
+}
+
+/* The loop of speculation and proof for one request.  The caller holds the model (ModelBusy) and
+ * has asked fpa_check_limits. */
+static int
+fpa_run(ssw_model_t *m, const fpa_graph_t &G, const FpaReq &R)
+{
+    hipStream_t st = (hipStream_t)R.stream;
+    if (R.n_utts <= 0)
+        return 0;
     HIP_OK(hipSetDevice(m->device));
     refresh_knobs(m);
     const bool timing = m->kn.align_timing;
     const double t_in = now_ms();
-    const int nw32 = (h->n_sen + 31) / 32;
-    /* the exported sets: [n_frames_u][ceil(N_u / 64)] 64-bit words per utterance */
-    std::vector<long long> act_off((size_t)n_utts);
-    long long mask_words = 0;
-    int max_nodes = G.max_nodes;
-    for (int u = 0; u < n_utts; ++u) {
-        const int nn = G.node_cnt[(size_t)u];
-        act_off[(size_t)u] = mask_words;
-        mask_words += (long long)(utt_off[u + 1] - utt_off[u]) * ((nn + 63) / 64);
-        max_nodes = std::max(max_nodes, nn);
+    FpaState T;
+    /* 1: the shape */
+    if (fpa_shape(G.who, fpa_model_sizes(m, R.scorer), G.node_cnt.data(), G.max_nodes, R.utt_off,
+                  R.n_utts, R.n_frames, R.d_carry_out != NULL, T.S) < 0) {
+        ssw_set_error("%s", T.S.err);
+        return -1;
     }
-    /* a frame lists at most three senones per HMM plus the bridges between them */
-    /* (even: the plan kernel's LDS words behind the list stay 4-byte aligned) */
-    const int cap = ((int)std::min<long long>(h->n_sen, 3ll * max_nodes + h->n_sen / 255 + 2) + 1) & ~1;
-    {
-        /* what the two per-frame kernels keep in LDS per wave (four waves a workgroup) */
-        const size_t plan_lds = 4 * ((4 * (size_t)nw32 + 2 * (size_t)cap + 8 + 15) & ~(size_t)15);
-        const size_t sen_lds = h->continuous
-            ? cont_listed_lds(m, cap)
-            : 4 * (((scorer == SSW_SCORER_MS ? 0 : 8 * (size_t)m->n_cbf)
-                    + 4 * (size_t)((cap + 1) & ~1) + 16 + 15) & ~(size_t)15);
-        if (std::max(plan_lds, sen_lds) > 156 * 1024) {
-            ssw_set_error("%s: %d senones x texts of up to %d phone-tree "
-                          "HMMs need %zu KB of LDS per workgroup (160 KB a CU)", G.who, h->n_sen, max_nodes,
-                          std::max(plan_lds, sen_lds) / 1024);
-            return -1;
-        }
-    }
-    const size_t nf = (size_t)std::max(n_frames, 1), nU = (size_t)n_utts;
-    WsLayout L;
-    const size_t o_ma = L.out(sizeof(unsigned long long) * (size_t)std::max(mask_words, 1ll));
-    const size_t o_mb = L.out(sizeof(unsigned long long) * (size_t)std::max(mask_words, 1ll));
-    const size_t o_up = L.mark(); /* uploaded in one copy: act_off | utt_off | node base, count | senid */
-    const size_t o_ao = L.in(act_off.data(), sizeof(long long) * nU);
-    const size_t o_uo = L.in(utt_off, sizeof(int) * (nU + 1));
-    const size_t o_nb = L.in(G.node_base.data(), sizeof(int) * nU);
-    const size_t o_nc = L.in(G.node_cnt.data(), sizeof(int) * nU);
-    const size_t o_sid = L.in(G.senid, sizeof(uint16_t) * 4 * (size_t)G.n_nodes, 1);
-    const size_t o_listed = L.out(sizeof(uint32_t) * nf * (size_t)nw32);
-    const size_t o_cbm = L.out(sizeof(unsigned long long) * nf);
-    const size_t o_iota = L.out(sizeof(int32_t) * nf);
-    const size_t o_seed = L.out(sizeof(uint32_t) * nU * (size_t)nw32);
-    const size_t o_diff = L.out(sizeof(int32_t) * nU);
-    const size_t o_only = L.out(sizeof(int32_t) * nU);
-    int max_len = 0;
-    for (int u = 0; u < n_utts; ++u)
-        max_len = std::max(max_len, utt_off[u + 1] - utt_off[u]);
-    /* one utterance's compallsen = yes rows (the rounds over few utterances, below) */
-    const size_t o_yes = L.out(sizeof(int16_t) * (size_t)std::max(max_len, 1) * (size_t)h->n_sen);
-    /* (two-pass history: the whole batch's utterance-start bits, for fpa_carry_rows_kernel) */
-    const size_t n_start_words = nf / 32 + 2;
-    const size_t o_start = L.out(d_carry_out != NULL ? sizeof(uint32_t) * n_start_words : 0);
-    if (devbuf_reserve(m->fpa_ws, L.size(), G.who) < 0)
-        return -1;
-    unsigned char *ws = m->fpa_ws.p;
-    if (stage_upload(m, ws + o_up, L.in_bytes() - o_up, st,
-                     [&](unsigned char *hs) { L.fill(hs, o_up); }) < 0)
-        return -1;
-    unsigned long long *mask_x = reinterpret_cast<unsigned long long *>(ws + o_ma);
-    unsigned long long *mask_y = reinterpret_cast<unsigned long long *>(ws + o_mb);
-    const long long *d_act_off = reinterpret_cast<const long long *>(ws + o_ao);
-    const int *d_utt_off = reinterpret_cast<const int *>(ws + o_uo);
-    const int *d_node_base = reinterpret_cast<const int *>(ws + o_nb);
-    const int *d_node_cnt = reinterpret_cast<const int *>(ws + o_nc);
-    uint32_t *d_listed = reinterpret_cast<uint32_t *>(ws + o_listed);
-    unsigned long long *d_cbm = reinterpret_cast<unsigned long long *>(ws + o_cbm);
-    int32_t *d_iota = reinterpret_cast<int32_t *>(ws + o_iota);
-    uint32_t *d_seed = reinterpret_cast<uint32_t *>(ws + o_seed);
-    int32_t *d_diff = reinterpret_cast<int32_t *>(ws + o_diff);
-    int32_t *d_only = reinterpret_cast<int32_t *>(ws + o_only);
-    int16_t *d_yes = reinterpret_cast<int16_t *>(ws + o_yes);
-
-    HIP_OK(hipMemsetAsync(d_seed, 0, sizeof(uint32_t) * (size_t)n_utts * (size_t)nw32, st));
-    /* 0: the assumption -- the trajectory of the search over the compallsen = yes scores */
-    std::vector<int> only; /* empty = every utterance */
-    if (n_frames > 0
-        && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, d_rows, stream) < 0)
-        return -1;
-    if (G.search(G.arg, d_rows, only, mask_x, d_act_off, d_node_cnt) < 0)
+    T.rounds.assign((size_t)R.n_utts, 0);
+    T.diff.assign((size_t)R.n_utts, 0);
+    T.n_round = 0;
+    /* 2: layout and upload; 3: the assumption */
+    if (fpa_layout_upload(m, G, R, T) < 0 || fpa_assume(m, G, R, T) < 0)
         return -1;
     const double t_spec = now_ms();
-    std::vector<int32_t> rounds((size_t)n_utts, 0), diff((size_t)n_utts);
-    auto plan_and_score = [&](int lo, int hi, int u_lo, int u_hi, int full) -> int {
-        /* frames [lo, hi) = utterances [u_lo, u_hi), planned from mask_x and scored into d_rows */
-        if (hi <= lo)
-            return 0;
-        FpaPlanParams Q;
-        Q.act_mask = mask_x;
-        Q.act_off = d_act_off;
-        Q.utt_off = d_utt_off;
-        Q.node_base = d_node_base;
-        Q.node_cnt = d_node_cnt;
-        Q.senid = reinterpret_cast<const uint16_t *>(ws + o_sid);
-        Q.sen2cb = m->d_sen2cb;
-        Q.listed = d_listed;
-        Q.cbmask = d_cbm;
-        Q.iota = d_iota;
-        Q.seed = d_seed;
-        Q.n_listed = NULL;
-        Q.n_utts = n_utts;
-        Q.n_frames = n_frames;
-        Q.n_sen = h->n_sen;
-        Q.nw32 = nw32;
-        Q.frame_lo = lo;
-        Q.frame_hi = hi;
-        const size_t per_wave = (4 * (size_t)nw32 + 2 * (size_t)cap + 8 + 15) & ~(size_t)15;
-        if (4 * per_wave > 48 * 1024)
-            HIP_OK(hipFuncSetAttribute((const void *)fpa_plan_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(4 * per_wave)));
-        hipLaunchKernelGGL(fpa_plan_kernel, dim3((unsigned)((hi - lo + 3) / 4)), dim3(256),
-                           4 * per_wave, st, Q, cap);
-        HIP_OK(hipGetLastError());
-        SenoneListedParams L;
-        memset(&L, 0, sizeof(L));
-        L.listed = d_listed + (size_t)lo * nw32;
-        L.cbmask = d_cbm + lo;
-        L.out = d_rows + (size_t)lo * h->n_sen;
-        L.full = full;
-        L.yes = d_yes; /* (full == 2: one utterance, its yes rows from frame 0) */
-        L.cap = cap;
-        ActiveSets act;
-        act.seg_of_frame = d_iota; /* (0 .. : the identity, whatever the sub-batch) */
-        act.seg_cbmask = d_cbm + lo;
-        act.a2 = NULL;
-        act.ls = &L;
-        act.row_of_frame = NULL;
-        std::vector<int32_t> sub;
-        const int32_t *uo = utt_off;
-        if (lo != 0 || hi != n_frames) {
-            for (int u = u_lo; u <= u_hi; ++u)
-                sub.push_back(utt_off[u] - lo);
-            uo = sub.data();
-        }
-        ScoreReq R{};
-        R.scorer = scorer;
-        R.d_feats = d_feats + (size_t)lo * h->veclen_total;
-        R.n_frames = hi - lo;
-        R.utt_off = uo;
-        R.n_utts = u_hi - u_lo;
-        R.d_out = d_rows;
-        R.stream = stream;
-        R.act = &act;
-        return score_batch_impl(m, R);
-    };
-    /* (iota must hold 0 .. n for any sub-batch: the whole batch's plan writes iota[t] = t once;
-     * a sub-batch's plan writes the same values at the same places) */
-    int n_round = 0;
+    /* 4: rounds until every utterance's sets are proven */
     for (;;) {
-        ++n_round;
+        ++T.n_round;
         const double r0 = now_ms();
-        /* 2 + 3: the sets assumed (mask_x) -> listed senones and active codebooks per frame ->
-         * the scores the reference would compute for them.  Few unproven utterances left: they
-         * are scored one by one; else the whole batch again (the proven ones' rows come out as
-         * they are: their sets have not changed) */
-        /* (at most four, or a quarter of the batch: a batch of one long utterance is "few") */
-        const bool one_by_one = !only.empty()
-            && (m->kn.fpa_sub == 1
-                || (m->kn.fpa_sub != 0 && (int)only.size() <= std::max(4, n_utts / 4)));
-        if (!one_by_one) {
-            if (plan_and_score(0, n_frames, 0, n_utts, 0) < 0)
-                return -1;
-        } else {
-            /* each of them with its unlisted entries refreshed from its compallsen = yes scores
-             * (senone_listed_kernel, full == 2): what such an utterance still gets wrong is the
-             * fate of HMMs that enter outside the assumed sets, judged on whatever the row held */
-            for (int u : only) {
-                const int a = utt_off[u], b = utt_off[u + 1];
-                if (b <= a)
-                    continue;
-                const int32_t uo[2] = { 0, b - a };
-                if (ssw_score_batch(m, scorer, d_feats + (size_t)a * h->veclen_total, b - a, uo, 1,
-                                    d_yes, stream) < 0)
-                    return -1;
-                if (plan_and_score(a, b, u, u + 1, 2) < 0)
-                    return -1;
-            }
-        }
+        if (fpa_score_round(m, R, T) < 0)
+            return -1;
         if (timing)
             HIP_OK(hipStreamSynchronize(st));
         const double r1 = now_ms();
-        /* 4: the search over those scores, its sets into mask_y */
-        if (G.search(G.arg, d_rows, only, mask_y, d_act_off, d_node_cnt) < 0)
+        /* the search over those scores, its sets into mask_y */
+        if (G.search(G.arg, R.d_rows, T.only, T.mask_y, T.d_act_off, T.d_node_cnt) < 0)
             return -1;
         const double r2 = now_ms();
-        /* 5: proven where the sets are the assumed ones */
-        const int n_cmp = only.empty() ? n_utts : (int)only.size();
-        if (!only.empty()
-            && stage_upload(m, d_only, sizeof(int32_t) * only.size(), st, [&](unsigned char *hs) {
-                   memcpy(hs, only.data(), sizeof(int32_t) * only.size());
-               }) < 0)
-            return -1;
-        HIP_OK(hipMemsetAsync(d_diff, 0x7f, sizeof(int32_t) * (size_t)n_utts, st));
-        /* (slices: enough workgroups for a single long utterance, few for a batch of short ones) */
-        const unsigned slices = (unsigned)std::min<long long>(
-            64, std::max<long long>(1, mask_words / std::max(1, n_cmp) / (256 * 16)));
-        hipLaunchKernelGGL(fpa_compare_kernel, dim3((unsigned)n_cmp, slices), dim3(256), 0, st, mask_x, mask_y,
-                           d_act_off, d_utt_off, d_node_cnt, only.empty() ? (const int *)NULL : d_only,
-                           d_diff);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpyAsync(diff.data(), d_diff, sizeof(int32_t) * (size_t)n_utts,
-                              hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
+        const int n_cmp = T.only.empty() ? R.n_utts : (int)T.only.size();
         std::vector<int> again;
-        if (only.empty()) {
-            for (int u = 0; u < n_utts; ++u) {
-                rounds[(size_t)u] = n_round;
-                if (diff[(size_t)u] != FPA_NO_DIFF)
-                    again.push_back(u);
-            }
-        } else {
-            for (int u : only) {
-                rounds[(size_t)u] = n_round;
-                if (diff[(size_t)u] != FPA_NO_DIFF)
-                    again.push_back(u);
-            }
-        }
+        if (fpa_compare(m, R, T, again) < 0)
+            return -1;
         if (timing)
             fprintf(stderr, "%s: round %d, %d searched, %zu not yet proven "
                             "(plan + scoring %.2f ms, search %.2f, comparison %.2f)\n",
-                    G.who, n_round, n_cmp, again.size(), r1 - r0, r2 - r1, now_ms() - r2);
+                    G.who, T.n_round, n_cmp, again.size(), r1 - r0, r2 - r1, now_ms() - r2);
         if (again.empty())
             break;
         /* every round proves at least one more frame of each of them (the first differing
          * frame's set in mask_y is the reference's), so this ends; the cap is a guard against
          * a defect, not a budget */
-        if (n_round > 4 * 16384) {
-            ssw_set_error("%s: utterance %d not proven after %d rounds", G.who, again[0],
-                          n_round);
+        if (T.n_round > 4 * 16384) {
+            ssw_set_error("%s: utterance %d not proven after %d rounds", G.who, again[0], T.n_round);
             return -1;
         }
-        std::swap(mask_x, mask_y); /* (the proven utterances' sets are the same in both) */
-        only.swap(again);
-        if ((int)only.size() == n_utts && n_utts > 4 && m->kn.fpa_sub != 1)
-            only.clear(); /* every one of them: the whole batch as a whole */
+        std::swap(T.mask_x, T.mask_y); /* (the proven utterances' sets are the same in both) */
+        fpa_next_only(T.only, again, R.n_utts, m->kn.fpa_sub);
     }
     /* mask_x now holds every utterance's proven sets (for the ones of the last round mask_y is
-     * equal to it).  The seed of the second pass and, on request, the rows as acmod's buffer
-     * would hold them come from one more plan (+ scoring with the unlisted entries written) */
-    /* (every utterance's seed row was written by the last plan of its frames, the one whose sets
-     * were then proven) */
-    if (full_rows && plan_and_score(0, n_frames, 0, n_utts, 1) < 0)
+     * equal to it), and every utterance's seed row was written by the last plan of its frames,
+     * the one whose sets were then proven.
+     * 5: on request the rows as acmod's buffer would hold them, from one more plan (+ scoring
+     * with the unlisted entries written); 6: the carried orders; 7: the copies out; 8: stats */
+    if (R.full_rows && fpa_plan_and_score(m, R, T, 0, R.n_frames, 0, R.n_utts, 1) < 0)
         return -1;
-    if (d_carry_out != NULL && scorer == SSW_SCORER_PTM && m->d_rec28 == NULL) {
-        ssw_set_error("two_pass_history in the default configuration needs codebooks of 128 densities");
+    if (fpa_carry_rows(m, R, T) < 0 || fpa_copy_out(R, T) < 0)
         return -1;
-    }
-    if (d_carry_out != NULL && scorer == SSW_SCORER_PTM && n_frames > 0) {
-        /* history slot 1 as every utterance's first pass leaves it (fpa_carry_rows_kernel): from
-         * the features and the proven codebook masks -- d_cbm holds, for every utterance, those of
-         * the last plan of its frames */
-        uint32_t *d_start = ws_at<uint32_t>(ws, o_start);
-        if (stage_upload(m, d_start, sizeof(uint32_t) * n_start_words, st, [&](unsigned char *hs) {
-                uint32_t *bits = reinterpret_cast<uint32_t *>(hs);
-                memset(bits, 0, sizeof(uint32_t) * n_start_words);
-                for (int u = 0; u < n_utts; ++u)
-                    if (utt_off[u] < n_frames)
-                        bits[(size_t)utt_off[u] >> 5] |= 1u << (utt_off[u] & 31);
-            }) < 0)
-            return -1;
-        FramesParams F;
-        memset(&F, 0, sizeof(F));
-        F.utt_start = d_start;
-        F.utt_off = d_utt_off;
-        F.n_utts = n_utts;
-        F.seg_of_frame = d_iota;
-        F.seg_cbmask = d_cbm;
-        F.n_frames = n_frames;
-        F.n_cbf = m->n_cbf;
-        F.n_feat = h->n_feat;
-        F.featdim = h->veclen_total;
-        for (int f = 0; f < h->n_feat; ++f)
-            F.featoff[f] = h->featoff[f];
-        hipLaunchKernelGGL(fpa_carry_rows_kernel, dim3((unsigned)((size_t)n_utts * m->n_cbf)), dim3(64), 0,
-                           st, F, m->d_rec28, d_feats, d_utt_off, d_carry_out);
-        HIP_OK(hipGetLastError());
-    }
-    if (listed_out != NULL && n_frames > 0)
-        HIP_OK(hipMemcpyAsync(listed_out, d_listed, sizeof(uint32_t) * (size_t)n_frames * (size_t)nw32,
-                              hipMemcpyDeviceToHost, st));
-    if (seed_out != NULL)
-        HIP_OK(hipMemcpyAsync(seed_out, d_seed, sizeof(uint32_t) * (size_t)n_utts * (size_t)nw32,
-                              hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    int more = 0;
-    long long sum = 0;
-    for (int u = 0; u < n_utts; ++u) {
-        sum += rounds[(size_t)u];
-        more += rounds[(size_t)u] > 1 ? 1 : 0;
-    }
-    stats[0] += n_utts;
-    stats[1] += sum;
-    stats[2] = n_round;
-    stats[3] += more;
-    if (rounds_out != NULL)
-        memcpy(rounds_out, rounds.data(), sizeof(int32_t) * (size_t)n_utts);
+    fpa_add_stats(R, T);
     if (timing)
         fprintf(stderr, "%s: assumption (compallsen = yes scoring + search) "
-                        "%.2f ms, %d round(s) %.2f ms\n", G.who, t_spec - t_in, n_round, now_ms() - t_spec);
+                        "%.2f ms, %d round(s) %.2f ms\n", G.who, t_spec - t_in, T.n_round, now_ms() - t_spec);
     return 0;
 }
 
 /* the first pass's graphs: every utterance its own */
 static int
-first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const float *d_feats,
-                      int32_t n_frames, const int32_t *utt_off, int32_t n_utts, int32_t max_seg,
-                      int32_t *n_seg, ssw_word_seg_t *seg, int16_t *d_rows, bool full_rows,
-                      uint32_t *seed_out, int32_t *rounds_out, void *stream, uint32_t *d_carry_out)
+first_pass_active_run(ssw_model_t *m, const FpaReq &R, ssw_fp_graphs_t *g, int32_t max_seg,
+                      int32_t *n_seg, ssw_word_seg_t *seg)
 {
-    fpa_fp_search_t a = { m, g, utt_off, n_utts, max_seg, n_seg, seg, stream };
+    fpa_fp_search_t a = { m, g, R.utt_off, R.n_utts, max_seg, n_seg, seg, R.stream };
     fpa_graph_t G;
     G.who = "ssw_first_pass_batch_active";
+    if (R.n_utts <= 0)
+        return 0;
+    if (fpa_check_limits(m, G.who, R.scorer) < 0)
+        return -1;
     G.n_nodes = g->n_nodes;
     G.senid = g->senid;
     G.max_nodes = 0;
-    for (int u = 0; u < n_utts; ++u) {
+    for (int u = 0; u < R.n_utts; ++u) {
         G.node_base.push_back(g->node_off[u]);
         G.node_cnt.push_back(g->node_off[u + 1] - g->node_off[u]);
     }
     G.search = fpa_fp_search;
     G.arg = &a;
-    return fpa_run(m, G, scorer, d_feats, n_frames, utt_off, n_utts, d_rows, full_rows, seed_out,
-                   rounds_out, NULL, m->fpa_stats, stream, d_carry_out);
+    return fpa_run(m, G, R);
 }
 
 /* The s2_semi scorer in the *_active calls.  s2_semi_mgau_frame_eval evaluates every Gaussian and
@@ -432,15 +469,37 @@ first_pass_active_run(ssw_model_t *m, ssw_fp_graphs_t *g, int scorer, const floa
  * listed ones alone.  The default configuration's search therefore reads the very scores of the
  * compallsen = yes rows, and these calls take that route: one search, nothing to prove.  The
  * stats report one round per utterance and every first assumption accepted; the sets of listed
- * senones are not made (seed_active / listed are refused), d_senscr receives whole rows. */
-static void
-semi_active_done(int64_t stats[4], int32_t n_utts, int32_t *rounds)
+ * senones are not made (`sets`, the entry's seed_active or listed named sets_name, is refused),
+ * d_senscr receives whole rows.  yes(): the entry's compallsen = yes call, 0 or -1. */
+template <typename Yes>
+static int
+semi_active_route(const char *who, const void *sets, const char *sets_name, int64_t stats[4],
+                  int32_t n_utts, int32_t *rounds, Yes yes)
 {
+    if (sets != NULL) {
+        ssw_set_error("%s: the s2_semi scorer makes no sets of listed senones (%s)", who, sets_name);
+        return -1;
+    }
+    if (yes() < 0)
+        return -1;
     stats[0] += n_utts;
     stats[1] += n_utts;
     stats[2] = 1;
     for (int u = 0; rounds != NULL && u < n_utts; ++u)
         rounds[u] = 1;
+    return 0;
+}
+
+/* the rows a call scores into: the caller's, or the model's own (ssw_align_text_batch's
+ * workspace) after text_rows_reserve; NULL with the error set.  The device is current. */
+static int16_t *
+active_rows(ssw_model_t *m, int16_t *d_senscr, int32_t n_frames, const char *who)
+{
+    if (d_senscr != NULL)
+        return d_senscr;
+    if (text_rows_reserve(m, n_frames, who) < 0)
+        return NULL;
+    return m->text_scr.as<int16_t>();
 }
 
 extern "C" int
@@ -451,6 +510,7 @@ ssw_first_pass_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
                             ssw_word_seg_t *seg, uint32_t *seed_active, int16_t *d_senscr,
                             int32_t *rounds, void *stream)
 {
+    const char *who = "ssw_first_pass_batch_active";
     if (n_utts == 0)
         return 0;
     if (check_has_device(m) < 0)
@@ -461,39 +521,39 @@ ssw_first_pass_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
         ssw_set_error("bad arguments to ssw_first_pass_batch_active");
         return -1;
     }
-    if (cont_refuse_active(m, "ssw_first_pass_batch_active") < 0)
+    if (cont_refuse_active(m, who) < 0)
         return -1;
     ModelBusy busy_(m);
     if (!busy_.ok)
         return -1;
-    int16_t *rows = d_senscr;
-    if (rows == NULL) { /* the model's own rows (ssw_align_text_batch's workspace) */
-        HIP_OK(hipSetDevice(m->device));
-        if (text_rows_reserve(m, n_frames, "ssw_first_pass_batch_active") < 0)
-            return -1;
-        rows = m->text_scr.as<int16_t>();
-    }
-    if (scorer == SSW_SCORER_S2_SEMI) { /* the compallsen = yes route (semi_active_done) */
-        if (seed_active != NULL) {
-            ssw_set_error("ssw_first_pass_batch_active: the s2_semi scorer makes no sets of listed "
-                          "senones (seed_active)");
-            return -1;
-        }
-        if (n_frames > 0
-            && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, rows, stream) < 0)
-            return -1;
-        if (ssw_first_pass_batch(m, d, cfg, rows, n_frames, utt_off, n_utts, word_off, words, max_seg,
-                                 n_seg, seg, stream) < 0)
-            return -1;
-        semi_active_done(m->fpa_stats, n_utts, rounds);
-        return 0;
-    }
+    HIP_OK(hipSetDevice(m->device));
+    int16_t *rows = active_rows(m, d_senscr, n_frames, who);
+    if (rows == NULL)
+        return -1;
+    if (scorer == SSW_SCORER_S2_SEMI)
+        return semi_active_route(who, seed_active, "seed_active", m->fpa_stats, n_utts, rounds, [&] {
+            if (n_frames > 0
+                && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, rows, stream) < 0)
+                return -1;
+            return ssw_first_pass_batch(m, d, cfg, rows, n_frames, utt_off, n_utts, word_off, words,
+                                        max_seg, n_seg, seg, stream);
+        });
     ssw_fp_graphs_t *g = ssw_fp_graphs_build(m, d, cfg, n_utts, word_off, words);
     if (g == NULL)
         return -1;
-    const int rc = first_pass_active_run(m, g, scorer, d_feats, n_frames, utt_off, n_utts, max_seg,
-                                         n_seg, seg, rows, d_senscr != NULL, seed_active, rounds,
-                                         stream);
+    FpaReq R{};
+    R.scorer = scorer;
+    R.d_feats = d_feats;
+    R.n_frames = n_frames;
+    R.utt_off = utt_off;
+    R.n_utts = n_utts;
+    R.d_rows = rows;
+    R.full_rows = d_senscr != NULL;
+    R.seed_out = seed_active;
+    R.rounds_out = rounds;
+    R.stats = m->fpa_stats;
+    R.stream = stream;
+    const int rc = first_pass_active_run(m, R, g, max_seg, n_seg, seg);
     ssw_fp_graphs_free(g);
     return rc;
 }
@@ -519,6 +579,7 @@ ssw_align_text_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
                             const int32_t *utt_off, int32_t n_utts, const int32_t *word_off,
                             const char *const *words, void *stream)
 {
+    const char *who = "ssw_align_text_batch_active";
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
@@ -529,18 +590,21 @@ ssw_align_text_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
         ssw_set_error("bad arguments to ssw_align_text_batch_active");
         return NULL;
     }
-    if (cont_refuse_active(m, "ssw_align_text_batch_active") < 0)
+    if (cont_refuse_active(m, who) < 0)
         return NULL;
-    if (scorer == SSW_SCORER_S2_SEMI) { /* the compallsen = yes route (semi_active_done) */
-        ssw_alignment_set_t *a = ssw_align_text_batch(m, d, cfg, scorer, d_feats, n_frames, utt_off,
-                                                      n_utts, word_off, words, stream);
-        if (a != NULL)
-            semi_active_done(m->fpa_stats, n_utts, NULL);
+    ssw_alignment_set_t *a = NULL;
+    if (scorer == SSW_SCORER_S2_SEMI) {
+        semi_active_route(who, NULL, NULL, m->fpa_stats, n_utts, NULL, [&] {
+            a = ssw_align_text_batch(m, d, cfg, scorer, d_feats, n_frames, utt_off, n_utts, word_off,
+                                     words, stream);
+            return a != NULL ? 0 : -1;
+        });
         return a;
     }
     if (hipSetDevice(m->device) != hipSuccess)
         return NULL;
-    if (text_rows_reserve(m, n_frames, "ssw_align_text_batch_active") < 0)
+    int16_t *rows = active_rows(m, NULL, n_frames, who);
+    if (rows == NULL)
         return NULL;
     checked_texts_t c;
     check_texts(d, n_utts, word_off, words, c);
@@ -553,14 +617,14 @@ ssw_align_text_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_first
     ForcedAlignReq F{};
     F.d = d;
     F.plan = plan;
-    F.d_senscr = m->text_scr.as<int16_t>();
+    F.d_senscr = rows;
     F.n_frames = n_frames;
     F.utt_off = utt_off;
     F.n_utts = plan->n_utts;
     F.stream = stream;
     F.reject = c.any ? &c.reject : NULL;
     F.fpa = &mode;
-    ssw_alignment_set_t *a = forced_align_core(m, F);
+    a = forced_align_core(m, F);
     ssw_first_pass_plan_free(plan);
     return a;
 }

@@ -726,6 +726,24 @@ grammar_fpa_graph(fpa_graph_t &G, const char *who, grammar_run_t &R)
     G.arg = &R;
 }
 
+/* the loop's request as both grammar entries start it: the inputs, the rows, the grammar
+ * entries' counters; each then names the outputs it wants */
+static FpaReq
+grammar_fpa_req(ssw_model_t *m, int scorer, const float *d_feats, int32_t n_frames,
+                const int32_t *utt_off, int32_t n_utts, int16_t *rows, void *stream)
+{
+    FpaReq A{};
+    A.scorer = scorer;
+    A.d_feats = d_feats;
+    A.n_frames = n_frames;
+    A.utt_off = utt_off;
+    A.n_utts = n_utts;
+    A.d_rows = rows;
+    A.stats = m->gra_stats;
+    A.stream = stream;
+    return A;
+}
+
 /* decoder_set_fsg + decoder_process + decoder_hyp in the reference's DEFAULT configuration
  * (compallsen = no) for a batch, from features: every frame scored for the senones of the HMMs
  * fsg_search_sen_active lists (src/fsg_search.c:310-325), through acmod's flags2list with its
@@ -737,14 +755,15 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
                            int32_t n_frames, const int32_t *utt_off, int32_t n_utts,
                            int16_t *d_senscr, uint32_t *listed, int32_t *rounds, void *stream)
 {
-    if (recognize_check_args("ssw_recognize_batch_active", m, d, plan, d_feats, n_frames, utt_off, n_utts) < 0)
+    const char *who = "ssw_recognize_batch_active";
+    if (recognize_check_args(who, m, d, plan, d_feats, n_frames, utt_off, n_utts) < 0)
         return NULL;
     ModelBusy busy_(m);
     if (!busy_.ok)
         return NULL;
     if (check_has_device(m) < 0)
         return NULL;
-    if (cont_refuse_active(m, "ssw_recognize_batch_active") < 0)
+    if (cont_refuse_active(m, who) < 0)
         return NULL;
     if (plan->big && !plan->active) {
         ssw_set_error("grammar %d (%s) has %d phone-tree HMMs and is searched from an HBM workspace: "
@@ -753,48 +772,41 @@ ssw_recognize_batch_active(ssw_model_t *m, const ssw_dict_t *d, const ssw_gramma
                       plan->big_name.c_str(), plan->big_nodes);
         return NULL;
     }
-    if (scorer == SSW_SCORER_S2_SEMI) { /* the compallsen = yes route (semi_active_done) */
-        if (listed != NULL) {
-            ssw_set_error("ssw_recognize_batch_active: the s2_semi scorer makes no sets of listed "
-                          "senones (listed)");
-            return NULL;
-        }
-        if (hipSetDevice(m->device) != hipSuccess)
-            return NULL;
-        int16_t *all = d_senscr;
-        if (all == NULL) {
-            if (text_rows_reserve(m, n_frames, "ssw_recognize_batch_active") < 0)
-                return NULL;
-            all = m->text_scr.as<int16_t>();
-        }
-        if (n_frames > 0
-            && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, all, stream) < 0)
-            return NULL;
-        ssw_recognition_set_t *r = ssw_grammar_search_batch(m, d, plan, fsg_of_utt, all, n_frames,
-                                                            utt_off, n_utts, stream);
-        if (r != NULL)
-            semi_active_done(m->gra_stats, n_utts, rounds);
+    if (scorer == SSW_SCORER_S2_SEMI) {
+        ssw_recognition_set_t *r = NULL;
+        semi_active_route(who, listed, "listed", m->gra_stats, n_utts, rounds, [&] {
+            if (hipSetDevice(m->device) != hipSuccess)
+                return -1;
+            int16_t *all = active_rows(m, d_senscr, n_frames, who);
+            if (all == NULL)
+                return -1;
+            if (n_frames > 0
+                && ssw_score_batch(m, scorer, d_feats, n_frames, utt_off, n_utts, all, stream) < 0)
+                return -1;
+            r = ssw_grammar_search_batch(m, d, plan, fsg_of_utt, all, n_frames, utt_off, n_utts, stream);
+            return r != NULL ? 0 : -1;
+        });
         return r;
     }
-    if (fpa_check_limits(m, "ssw_recognize_batch_active", scorer) < 0)
+    if (fpa_check_limits(m, who, scorer) < 0)
         return NULL;
     if (hipSetDevice(m->device) != hipSuccess)
         return NULL;
-    int16_t *rows = d_senscr;
-    if (rows == NULL) { /* the model's own rows */
-        if (text_rows_reserve(m, n_frames, "ssw_recognize_batch_active") < 0)
-            return NULL;
-        rows = m->text_scr.as<int16_t>();
-    }
+    int16_t *rows = active_rows(m, d_senscr, n_frames, who);
+    if (rows == NULL)
+        return NULL;
     grammar_run_t R;
     if (R.begin(m, d, plan, fsg_of_utt, utt_off, n_utts, stream) < 0)
         return NULL;
     if (n_utts == 0)
         return R.finish();
     fpa_graph_t G;
-    grammar_fpa_graph(G, "ssw_recognize_batch_active", R);
-    if (fpa_run(m, G, scorer, d_feats, n_frames, utt_off, n_utts, rows, d_senscr != NULL, NULL,
-                rounds, listed, m->gra_stats, stream, NULL) < 0)
+    grammar_fpa_graph(G, who, R);
+    FpaReq A = grammar_fpa_req(m, scorer, d_feats, n_frames, utt_off, n_utts, rows, stream);
+    A.full_rows = d_senscr != NULL;
+    A.rounds_out = rounds;
+    A.listed_out = listed;
+    if (fpa_run(m, G, A) < 0)
         return NULL;
     return R.finish();
 }
@@ -1002,21 +1014,22 @@ ssw_recognize_align_batch_active(ssw_model_t *m, const ssw_dict_t *d,
                       who, plan->big_fsg, plan->big_name.c_str(), plan->big_nodes);
         return NULL;
     }
-    if (scorer == SSW_SCORER_S2_SEMI) { /* the compallsen = yes route (semi_active_done) */
-        ssw_alignment_set_t *a = recognize_align_rows(who, m, d, plan, fsg_of_utt, scorer, d_feats,
-                                                      n_frames, utt_off, n_utts, two_pass_history,
-                                                      rec_out, stream);
-        if (a != NULL)
-            semi_active_done(m->gra_stats, n_utts, rounds);
+    if (scorer == SSW_SCORER_S2_SEMI) {
+        ssw_alignment_set_t *a = NULL;
+        semi_active_route(who, NULL, NULL, m->gra_stats, n_utts, rounds, [&] {
+            a = recognize_align_rows(who, m, d, plan, fsg_of_utt, scorer, d_feats, n_frames, utt_off,
+                                     n_utts, two_pass_history, rec_out, stream);
+            return a != NULL ? 0 : -1;
+        });
         return a;
     }
     if (fpa_check_limits(m, who, scorer) < 0)
         return NULL;
     if (hipSetDevice(m->device) != hipSuccess)
         return NULL;
-    if (text_rows_reserve(m, n_frames, who) < 0)
+    int16_t *rows = active_rows(m, NULL, n_frames, who);
+    if (rows == NULL)
         return NULL;
-    int16_t *rows = m->text_scr.as<int16_t>();
     const bool carry2 = two_pass_history != 0 && scorer == SSW_SCORER_PTM && n_utts > 0;
     if (carry2 && carry_rows_reserve(m, n_utts, who) < 0)
         return NULL;
@@ -1032,9 +1045,11 @@ ssw_recognize_align_batch_active(ssw_model_t *m, const ssw_dict_t *d,
         if (n_utts > 0) {
             fpa_graph_t G;
             grammar_fpa_graph(G, who, R);
-            if (fpa_run(m, G, scorer, d_feats, n_frames, utt_off, n_utts, rows, false, seed.data(),
-                        rounds, NULL, m->gra_stats, stream,
-                        carry2 ? m->carry_rows.as<uint32_t>() : NULL) < 0)
+            FpaReq A = grammar_fpa_req(m, scorer, d_feats, n_frames, utt_off, n_utts, rows, stream);
+            A.seed_out = seed.data();
+            A.rounds_out = rounds;
+            A.d_carry_out = carry2 ? m->carry_rows.as<uint32_t>() : NULL;
+            if (fpa_run(m, G, A) < 0)
                 return NULL;
         }
         r = R.finish();

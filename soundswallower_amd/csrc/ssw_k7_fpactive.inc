@@ -43,14 +43,20 @@ struct FpaPlanParams {
     int frame_lo, frame_hi;             /* the frames this launch plans */
 };
 
-/* One wave per frame, four frames per workgroup.  Per wave in LDS: the senone bitmap
- * [nw32 words] and the ascending list of the flagged senones [cap uint16]. */
+/* One wave per frame, four frames per workgroup.  Per wave in LDS (FpaPlanCarve): the senone
+ * bitmap [nw32 words], the ascending list of the flagged senones [cap uint16] and the two words
+ * of the codebook mask. */
 __global__ void __launch_bounds__(256)
 fpa_plan_kernel(FpaPlanParams P, int cap)
 {
     extern __shared__ __align__(16) unsigned char fpa_smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const size_t per_wave = (4 * (size_t)P.nw32 + 2 * (size_t)cap + 8 + 15) & ~(size_t)15;
+    /* The wave's block is FpaPlanCarve's (ssw_senone_lds.inc), from which fpa_shape takes the byte
+     * count.  Within it the carve stays written out as typed-pointer steps: taken from the
+     * struct's byte offsets the same addresses are computed by other instructions.
+     * tests/harness/senone_lds_host.cpp holds these lines verbatim and compares them with the
+     * struct region by region: change both together. */
+    const size_t per_wave = FpaPlanCarve(P.nw32, cap).per_wave();
     uint32_t *bm = reinterpret_cast<uint32_t *>(fpa_smem + (size_t)w * per_wave);
     uint16_t *lst = reinterpret_cast<uint16_t *>(bm + P.nw32);
     uint32_t *cbm = reinterpret_cast<uint32_t *>(lst + cap); /* two words */

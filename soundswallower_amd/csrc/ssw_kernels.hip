@@ -25,7 +25,8 @@
  *                        cores (keys from two-part binary16 operands, exact re-evaluation, proof
  *                        and in-wave pass as above): what every batch takes
  *   ssw_senone_lds.inc   no HIP, ahead of the namespace: the dynamic LDS of the senone kernels,
- *                        SenoneCarve / MsSenoneCarve / Active2Carve / ListedCarve -- the kernel
+ *                        SenoneCarve / MsSenoneCarve / Active2Carve / ListedCarve / ContListedCarve,
+ *                        and FpaPlanCarve of the default configuration's plan kernel -- the kernel
  *                        takes its pointers and the launcher its byte count from the same struct
  *   ssw_senone_common.inc the steps of the reference's senone scorers that several kernels
  *                        share, once: clamp_i16, fast_logadd / ms_logadd, the padded table fill,
@@ -97,6 +98,10 @@
  *   ssw_fp_shape.inc     host, no HIP: fp_shape, what one launch of the first pass takes (the
  *                        per-utterance LDS, HBM-workspace and history sizes, each formula once;
  *                        register / window / HBM / HBM-banded kernel, threads, LDS bytes)
+ *   ssw_fpa_shape.inc    host, no HIP: fpa_shape, what one call of the default configuration's loop
+ *                        takes (the exported sets' layout, the list capacity, the LDS of its two
+ *                        per-frame kernels from their carves, the 156 KB refusal), the comparison's
+ *                        slices and the policy of its rounds (one by one / the whole batch)
  *   ssw_active_set.inc   host, no HIP: the second pass's active set from the phone windows
  *                        (active_first_frames, ActiveSetBuilder) and a continuous model's bitmap
  *                        rows of it (cont_active_rows)
@@ -181,6 +186,7 @@ namespace {
 #include "ssw_xcd_cut.inc"
 #include "ssw_slot_layout.inc"
 #include "ssw_fp_shape.inc"
+#include "ssw_fpa_shape.inc"
 #include "ssw_feat_tiles.inc"
 #include "ssw_host_model.inc"
 #include "ssw_host_semi.inc"

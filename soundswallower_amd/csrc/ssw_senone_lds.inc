@@ -119,3 +119,21 @@ struct ContListedCarve {
     SSW_HD size_t wave(int w) const { return (size_t)w * per_wave(); }
     SSW_HD size_t bytes() const { return 4 * per_wave(); }
 };
+
+/* fpa_plan_kernel (ssw_k7_fpactive.inc), per wave: bm[nw32] uint32, the frame's senone bitmap |
+ * lst[cap] uint16, the flagged senones in ascending order | cbm[2] uint32, the codebook mask's two
+ * words.  cap is even (fpa_cap, ssw_fpa_shape.inc): the words behind the list stay 4-byte aligned */
+struct FpaPlanCarve {
+    int nw32, cap;
+
+    SSW_HD FpaPlanCarve(int nw32_, int cap_) : nw32(nw32_), cap(cap_) {}
+    SSW_HD int bitmap() const { return 0; }
+    SSW_HD int list() const { return 4 * nw32; }
+    SSW_HD int cbm() const { return list() + 2 * cap; }
+    SSW_HD size_t per_wave() const
+    {
+        return (4 * (size_t)nw32 + 2 * (size_t)cap + 8 + 15) & ~(size_t)15;
+    }
+    SSW_HD size_t wave(int w) const { return (size_t)w * per_wave(); }
+    SSW_HD size_t bytes() const { return 4 * per_wave(); }
+};

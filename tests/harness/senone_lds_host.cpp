@@ -1,4 +1,4 @@
-/* SenoneCarve, MsSenoneCarve, Active2Carve and ListedCarve (csrc/ssw_senone_lds.inc) on the CPU,
+/* SenoneCarve, MsSenoneCarve, Active2Carve, ListedCarve and FpaPlanCarve (csrc/ssw_senone_lds.inc) on the CPU,
  * against a verbatim copy of the formulas they replaced: the kernels' typed-pointer carves (run
  * here over a host buffer standing in for the dynamic LDS) and the launchers' byte counts.  Every
  * region offset and bytes() must be equal; the regions of a carve must not overlap, must end
@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 
 #include "../../soundswallower_amd/csrc/ssw_senone_lds.inc"
 
@@ -226,9 +227,51 @@ listed(bool MS, int n_cb, int n_feat, int cap)
     }
 }
 
+/* fpa_plan_kernel's pointer steps, kept there as typed-pointer steps, and the byte count the
+ * three places that sized its launch had (kernel, LDS limit check, launch) */
+static void
+fpa_plan(int nw32, int cap)
+{
+    char what[96];
+    snprintf(what, sizeof(what), "FpaPlanCarve nw32 %d cap %d", nw32, cap);
+    struct { int nw32; } P = { nw32 };
+    const FpaPlanCarve c(nw32, cap);
+    {   /* the host, twice */
+        const size_t plan_lds = 4 * ((4 * (size_t)nw32 + 2 * (size_t)cap + 8 + 15) & ~(size_t)15);
+        if (c.bytes() != plan_lds)
+            FAIL("bytes() %zu, the host had %zu", c.bytes(), plan_lds);
+    }
+    for (int w = 0; w < 4; ++w) {
+        unsigned char *fpa_smem = smem;
+        /* the kernel */
+        const size_t per_wave = (4 * (size_t)P.nw32 + 2 * (size_t)cap + 8 + 15) & ~(size_t)15;
+        uint32_t *bm = reinterpret_cast<uint32_t *>(fpa_smem + (size_t)w * per_wave);
+        uint16_t *lst = reinterpret_cast<uint16_t *>(bm + P.nw32);
+        uint32_t *cbm = reinterpret_cast<uint32_t *>(lst + cap); /* two words */
+
+        if (c.per_wave() != per_wave)
+            FAIL("per_wave() %zu, the kernel had %zu", c.per_wave(), per_wave);
+        const size_t b = c.wave(w);
+        if (b % 16)
+            FAIL("wave %d's block at %zu is not 16-aligned", w, b);
+        /* (an odd cap leaves the mask's words 2-aligned: fpa_cap hands out even ones only, and
+         * the carve says so by the alignment this asks of it) */
+        const Region r[] = {
+            { "bitmap", b + (size_t)c.bitmap(), 4 * (size_t)nw32, 4 },
+            { "list", b + (size_t)c.list(), 2 * (size_t)cap, 2 },
+            { "cbm", b + (size_t)c.cbm(), 8, cap % 2 ? (size_t)2 : (size_t)4 },
+        };
+        const size_t old_off[] = { off_of(bm), off_of(lst), off_of(cbm) };
+        check(what, r, old_off, 3, b, w < 3 ? c.wave(w + 1) : c.bytes());
+    }
+}
+
 int
 main()
 {
+    for (int nw32 : { 1, 2, 63, 64, 65, 66, 161, 2048 })
+        for (int cap : { 2, 3, 64, 65, 66, 448, 449, 450, 5126, 65534 })
+            fpa_plan(nw32, cap);
     const int fpbs[] = { 1, 2 }, n_cbs[] = { 1, 7, 8, 9, 36, 42, 64 }, n_feats[] = { 1, 3, 4 };
     const int caps[] = { 1, 2, 63, 64, 65, 449, 5126 }, n_sens[] = { 1, 2107, 2108, 5126 };
     for (int n_cb : n_cbs)
