@@ -564,6 +564,32 @@ int32_t ssw_dict_word_id(const ssw_dict_t *d, const char *word);
 int32_t ssw_dict_base_id(const ssw_dict_t *d, int32_t wid);
 int32_t ssw_dict_is_filler(const ssw_dict_t *d, int32_t wid);
 
+/* Words added at run time.  The filler range is fixed when the dictionary is loaded, as
+ * dict_init fixes filler_start and filler_end (src/dict.c:318, 337: the words of the filler
+ * file, then <s>, </s> and <sil> where the file lacks them, so all three lie inside the range;
+ * dict_filler_word excepts <s> and </s> by id, :378-383).  A word added later lies past
+ * filler_end: it is no filler, and the silence loops of the graph builders
+ * (fsg_search_add_silences, src/fsg_search.c:84-119) pass it over.
+ *
+ * decoder_add_word (src/decoder.c:801-865) on a loaded dictionary: phones = CI phone names
+ * separated by white space.  Returns the new word id (appended: ids never move), or -1 with
+ * the dictionary unchanged: an unknown phone (named), a word that exists, "w(2)" whose base
+ * word is missing (src/dict.c:92-102), no phones, more phones than ssw_dict_load takes (256),
+ * white space in the word.  An alternate "w(2)" is linked at the head of its base word's list
+ * (src/dict.c:104-107), so graphs built with use_altpron after the add offer it.  Objects built
+ * before the add (compiled grammars, graphs, plans) are snapshots and stay as they are, as the
+ * reference's search_module_reinit does not add alternates again either.  Pointers that
+ * ssw_dict_word returned stay valid when the dictionary grows.  Cross-word triphones are looked
+ * up per phone pair when a graph or an alignment is built, so dict2pid_add_word has no
+ * counterpart.  Adding while another thread runs any call on the same dictionary is the
+ * caller's error. */
+int32_t ssw_dict_add_word(ssw_dict_t *d, const ssw_model_t *m, const char *word, const char *phones);
+/* decoder_lookup_word (src/decoder.c:867-888): the phone names separated by one space into
+ * out (cut to max - 1 characters and terminated when max > 0); returns the length it needs
+ * without the terminator, -1 for an unknown word. */
+int32_t ssw_dict_lookup_word(const ssw_dict_t *d, const ssw_model_t *m, const char *word,
+                             char *out, int32_t max);
+
 /* ------------------------------------------------------------------------------------ */
 /* First pass of forced alignment: which fillers and alternate          */
 /* pronunciations the text is spoken with, and every word's frames -- the word windows the  */
@@ -1238,6 +1264,23 @@ int ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pc
 int ssw_fe_batch_ex(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
                     const int64_t *samp_off, const double *samprate, int32_t n_utts,
                     float *d_cep, int32_t *frame_off_out, void *stream);
+/* ssw_fe_batch_ex for float32 samples: what fe_process_float32 over all samples + fe_end
+ * compute (src/fe_interface.c:578-712, src/fe_sigproc.c:350-376, 413-444).  Every argument,
+ * refusal, frame count, per-utterance rate and table as ssw_fe_batch_ex; the sample type is the
+ * one difference.  The reference keeps its sample buffer in float32, spch[i] = sample *
+ * 32768.0F (FLOAT32_SCALE, include/soundswallower/fe.h:370), and fe_end's overflow frame is
+ * the raw floats scaled the same way (create_overflow_frame, src/fe_interface.c:503-510), so
+ * every sample, and the prior sample of a frame, enters pre-emphasis as
+ * (double)(float)(x * 32768.0f).  The product is by a power of two and therefore exact, for
+ * subnormal products too, except where it overflows to infinity.  Everything after that point
+ * is the int16 path's code.  The cepstra equal the reference's for finite samples of any
+ * magnitude: values outside [-1, 1) are not clipped, +-0 gives 0, x / 32768 of int16 audio gives
+ * ssw_fe_batch_ex's bytes.  For a non-finite sample the call is deterministic and does not
+ * fault, no address is computed from a sample, and the frames whose window and prior sample
+ * hold none are as without it (with remove_noise the tracker carries it forward). */
+int ssw_fe_batch_f32(ssw_model_t *m, const ssw_fe_config_t *cfg, const float *d_pcm,
+                     const int64_t *samp_off, const double *samprate, int32_t n_utts,
+                     float *d_cep, int32_t *frame_off_out, void *stream);
 /* Frames ssw_fe_batch_ex makes of n_samples samples at samprate Hz (one entry of its
  * samprate[]; cfg NULL = feat_params.json): 0 for 0 samples, 1 below one window, else the full
  * frames 1 + (n - size) / shift and fe_end's frame of the samples left over (src/fe_interface.c:

@@ -364,6 +364,13 @@ def lib() -> C.CDLL:
     L.ssw_fe_frame_count_ex.argtypes = [vp, C.POINTER(SswFeConfig), C.c_double, C.c_int64]
     L.ssw_fe_frame_count_ex.restype = C.c_int64
     L.ssw_fe_batch_ex.argtypes = [vp, C.POINTER(SswFeConfig), vp, vp, vp, i32, vp, vp, vp]
+    if hasattr(L, "ssw_fe_batch_f32"):   # (an older build loaded through SSW_AMD_LIB has neither
+        # float32 audio nor run-time words: Model.fe_batch_f32_device, Lexicon.add_word raise)
+        L.ssw_fe_batch_f32.argtypes = [vp, C.POINTER(SswFeConfig), vp, vp, vp, i32, vp, vp, vp]
+        L.ssw_dict_add_word.restype = i32
+        L.ssw_dict_add_word.argtypes = [vp, vp, C.c_char_p, C.c_char_p]
+        L.ssw_dict_lookup_word.restype = i32
+        L.ssw_dict_lookup_word.argtypes = [vp, vp, C.c_char_p, C.c_char_p, i32]
     L.ssw_fe_kernel_timing.argtypes = [vp, vp]
     L.ssw_comm_unique_id.argtypes = [C.c_char_p]
     L.ssw_comm_init.restype = vp

@@ -139,6 +139,59 @@ def _check(rv, what):
     return rv
 
 
+def _is_device_tensor(a) -> bool:
+    return hasattr(a, "data_ptr") and bool(getattr(a, "is_cuda", False))
+
+
+def _pcm_kind(pcm, pcm_format=None, who="pcm") -> str:
+    """The sample type of audio handed to the front end: "i16" (ssw_fe_batch, ssw_fe_batch_ex)
+    or "f32" (ssw_fe_batch_f32).  np.float32 arrays and torch.float32 device tensors are "f32";
+    integer arrays and torch.int16 device tensors "i16"; a raw device pointer is "i16" unless
+    pcm_format="f32".  Any other dtype raises: a float64 array would be cut to integers, a
+    device tensor of another type read as something it is not.  A list must be all one kind."""
+    if pcm_format not in (None, "i16", "f32"):
+        raise SswError(f"{who}: unknown pcm_format {pcm_format!r} (\"i16\" or \"f32\")")
+    if isinstance(pcm, (list, tuple)) and pcm and not np.isscalar(pcm[0]):
+        kinds = {_pcm_kind(p, pcm_format, who) for p in pcm}
+        if len(kinds) > 1:
+            raise SswError(f"{who}: a list of arrays must be all int16 or all float32")
+        return kinds.pop()
+    if hasattr(pcm, "data_ptr"):                      # torch tensor
+        name = str(pcm.dtype)
+        kind = {"torch.int16": "i16", "torch.float32": "f32"}.get(name)
+        if kind is None or not _is_device_tensor(pcm):
+            if kind is None:
+                raise SswError(f"{who}: audio of dtype {name} (torch.int16 or torch.float32)")
+            return _pcm_kind(pcm.numpy(), pcm_format, who)
+    elif pcm is None or isinstance(pcm, (int, C.c_void_p)):
+        return pcm_format or "i16"                    # a raw device pointer
+    else:
+        dt = np.asarray(pcm).dtype
+        if dt == np.float32:
+            kind = "f32"
+        elif dt.kind in "iub":
+            kind = "i16"
+        else:
+            raise SswError(f"{who}: audio of dtype {dt} (an integer type or float32)")
+    if pcm_format is not None and pcm_format != kind:
+        raise SswError(f"{who}: pcm_format {pcm_format!r} given for {kind} audio")
+    return kind
+
+
+_PCM_DTYPE = {"i16": np.int16, "f32": np.float32}
+
+
+def _pcm_concat(pcm, kind):
+    """One contiguous host array of the kind's dtype, and samp_off when pcm was a list."""
+    dt = _PCM_DTYPE[kind]
+    samp_off = None
+    if isinstance(pcm, (list, tuple)):
+        samp_off = np.concatenate([[0], np.cumsum([len(p) for p in pcm])]).astype(np.int64)
+        pcm = np.concatenate([np.asarray(p, dt).reshape(-1) for p in pcm]) if pcm \
+            else np.zeros(0, dt)
+    return np.ascontiguousarray(pcm, dt).reshape(-1), samp_off
+
+
 def model_dir(name: str) -> str:
     """Path of a bundled acoustic model ("en-us", "fr-fr")."""
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "model", name)
@@ -774,6 +827,8 @@ class Model:
         frame_off int32 [n_utts + 1] on the host, as feat_batch takes them).  d_cep None: a torch
         tensor is allocated.  cfg: None (feat_params.json), a dict of overrides or an
         SswFeConfig."""
+        if _pcm_kind(d_pcm, None, "fe_batch_device") == "f32":
+            return self.fe_batch_f32_device(d_pcm, samp_off, None, d_cep, cfg, stream)
         off = np.ascontiguousarray(samp_off, np.int64)
         n_frames = int(fe_frame_counts(np.diff(off)).sum())
         if d_cep is None:
@@ -788,12 +843,15 @@ class Model:
 
     def fe_batch(self, pcm, samp_off=None, cfg=None):
         """The MFCC front end on the GPU, host in and host out: int16 PCM (one array, with
-        samp_off for a batch, or a list of arrays) -> (cep float32 [n_frames][13], frame_off)."""
-        if isinstance(pcm, (list, tuple)):
-            samp_off = np.concatenate([[0], np.cumsum([len(p) for p in pcm])])
-            pcm = np.concatenate([np.asarray(p, np.int16).reshape(-1) for p in pcm]) if pcm \
-                else np.zeros(0, np.int16)
-        pcm = np.ascontiguousarray(pcm, np.int16).reshape(-1)
+        samp_off for a batch, or a list of arrays) -> (cep float32 [n_frames][13], frame_off).
+        float32 samples (np.float32, the reference's fe_process_float32 scale: 1.0 is 32768)
+        go through ssw_fe_batch_f32 at the configuration's rate, as fe_batch_rates takes them;
+        any other float type raises."""
+        kind = _pcm_kind(pcm, None, "fe_batch")
+        if kind == "f32":
+            return self.fe_batch_rates(pcm, None, samp_off, cfg)
+        pcm, off_ = _pcm_concat(pcm, kind)
+        samp_off = samp_off if off_ is None else off_
         off = (np.array([0, len(pcm)], np.int64) if samp_off is None
                else np.ascontiguousarray(samp_off, np.int64))
         if len(off) < 1 or off[-1] != len(pcm):
@@ -830,9 +888,16 @@ class Model:
             raise SswError("ssw_fe_frame_count_ex: " + _lib.last_error())
         return out
 
-    def fe_batch_rates_device(self, d_pcm, samp_off, samprate, d_cep=None, cfg=None, stream=None):
+    def _fe_entry(self, kind):
+        return ((self._L.ssw_fe_batch_f32, "ssw_fe_batch_f32") if kind == "f32" else
+                (self._L.ssw_fe_batch_ex, "ssw_fe_batch_ex"))
+
+    def fe_batch_rates_device(self, d_pcm, samp_off, samprate, d_cep=None, cfg=None, stream=None,
+                              pcm_format=None):
         """ssw_fe_batch_ex: fe_batch_device with utterance u at samprate[u] Hz (a number for all,
-        one per utterance, or None for the configuration's samprate)."""
+        one per utterance, or None for the configuration's samprate).  A torch.float32 tensor,
+        or a device pointer with pcm_format="f32", goes through ssw_fe_batch_f32."""
+        fn, who = self._fe_entry(_pcm_kind(d_pcm, pcm_format, "fe_batch_rates_device"))
         off = np.ascontiguousarray(samp_off, np.int64)
         n_utts = len(off) - 1
         rates = (None if samprate is None else
@@ -843,20 +908,25 @@ class Model:
             dev = d_pcm.device if hasattr(d_pcm, "device") else "cuda"
             d_cep = torch.empty((n_frames, FE_NCEP), dtype=torch.float32, device=dev)
         fo = np.zeros(len(off), np.int32)
-        _check(self._L.ssw_fe_batch_ex(self._m, self._fe_cfg(cfg), _ptr(d_pcm), _ptr(off),
-                                       _ptr(rates), n_utts, _ptr(d_cep), _ptr(fo), _ptr(stream)),
-               "ssw_fe_batch_ex")
+        _check(fn(self._m, self._fe_cfg(cfg), _ptr(d_pcm), _ptr(off), _ptr(rates), n_utts,
+                  _ptr(d_cep), _ptr(fo), _ptr(stream)), who)
         return d_cep, fo
 
+    def fe_batch_f32_device(self, d_pcm, samp_off, samprate=None, d_cep=None, cfg=None,
+                            stream=None):
+        """ssw_fe_batch_f32: fe_batch_rates_device for float32 samples in HBM (torch.float32
+        tensor or device pointer), scaled as fe_process_float32 takes them (1.0 is 32768)."""
+        return self.fe_batch_rates_device(d_pcm, samp_off, samprate, d_cep, cfg, stream,
+                                          pcm_format="f32")
+
     def fe_batch_rates(self, pcm, samprate, samp_off=None, cfg=None):
-        """The front end at each utterance's own rate, host in and host out (ssw_fe_batch_ex):
-        int16 PCM as fe_batch takes it, samprate a number or one per utterance (None: the
-        configuration's) -> (cep float32 [n_frames][13], frame_off)."""
-        if isinstance(pcm, (list, tuple)):
-            samp_off = np.concatenate([[0], np.cumsum([len(p) for p in pcm])])
-            pcm = np.concatenate([np.asarray(p, np.int16).reshape(-1) for p in pcm]) if pcm \
-                else np.zeros(0, np.int16)
-        pcm = np.ascontiguousarray(pcm, np.int16).reshape(-1)
+        """The front end at each utterance's own rate, host in and host out (ssw_fe_batch_ex;
+        ssw_fe_batch_f32 for np.float32 samples): PCM as fe_batch takes it, samprate a number or
+        one per utterance (None: the configuration's) -> (cep float32 [n_frames][13],
+        frame_off)."""
+        kind = _pcm_kind(pcm, None, "fe_batch_rates")
+        pcm, off_ = _pcm_concat(pcm, kind)
+        samp_off = samp_off if off_ is None else off_
         off = (np.array([0, len(pcm)], np.int64) if samp_off is None
                else np.ascontiguousarray(samp_off, np.int64))
         if len(off) < 1 or off[-1] != len(pcm):
@@ -864,11 +934,12 @@ class Model:
         n_utts = len(off) - 1
         rates = (None if samprate is None else
                  np.ascontiguousarray(np.broadcast_to(np.asarray(samprate, np.float64), (n_utts,))))
-        # (ssw_fe_batch_ex without a device or frames checks everything, then writes frame_off)
+        fn, who = self._fe_entry(kind)
+        # (the entry without a device or frames checks everything, then writes frame_off)
         fo = np.zeros(len(off), np.int32)
         if self.device == SSW_DEVICE_NONE or off[-1] == 0:
-            _check(self._L.ssw_fe_batch_ex(self._m, self._fe_cfg(cfg), None, _ptr(off), _ptr(rates),
-                                           n_utts, None, _ptr(fo), None), "ssw_fe_batch_ex")
+            _check(fn(self._m, self._fe_cfg(cfg), None, _ptr(off), _ptr(rates), n_utts, None,
+                      _ptr(fo), None), who)
         n_frames = int(fo[-1]) if fo[-1] or off[-1] == 0 else \
             int(self.fe_frame_counts_rates(np.diff(off), rates, cfg).sum())
         cep = np.zeros((n_frames, FE_NCEP), np.float32)
@@ -877,7 +948,7 @@ class Model:
         d_pcm = self.to_device(pcm)
         d_cep = self.device_malloc(cep.nbytes)
         try:
-            _, fo = self.fe_batch_rates_device(d_pcm, off, rates, d_cep, cfg)
+            _, fo = self.fe_batch_rates_device(d_pcm, off, rates, d_cep, cfg, pcm_format=kind)
             _check(self._L.ssw_memcpy_d2h(_ptr(cep), d_cep, cep.nbytes), "ssw_memcpy_d2h")
         finally:
             self.device_free(d_pcm)
@@ -1172,6 +1243,32 @@ class Lexicon:
 
     def word_id(self, word: str) -> int:
         return int(self._L.ssw_dict_word_id(self._d, word.encode()))
+
+    def is_filler(self, wid: int) -> bool:
+        """dict_filler_word: from the filler dictionary, <s> and </s> excepted."""
+        return bool(self._L.ssw_dict_is_filler(self._d, int(wid)))
+
+    def add_word(self, word: str, phones: str) -> int:
+        """decoder_add_word (ssw_dict_add_word): a word and its CI phone names, separated by
+        white space, appended to the loaded dictionary; "w(2)" adds an alternate of w.  Returns
+        the new word id.  KeyError for a word that exists, as the reference's binding raises;
+        SswError for any other refusal, the dictionary unchanged.  Graphs, plans and grammars
+        built before the add are snapshots and do not know the word."""
+        if self.word_id(word) >= 0:
+            raise KeyError(word)
+        return int(_check(self._L.ssw_dict_add_word(self._d, self.model._m, word.encode(),
+                                                    phones.encode()), "ssw_dict_add_word"))
+
+    def lookup_word(self, word: str):
+        """decoder_lookup_word: the word's phone names separated by one space, None when the
+        dictionary does not have it."""
+        w = word.encode()
+        need = self._L.ssw_dict_lookup_word(self._d, self.model._m, w, None, 0)
+        if need < 0:
+            return None
+        buf = C.create_string_buffer(need + 1)
+        self._L.ssw_dict_lookup_word(self._d, self.model._m, w, buf, need + 1)
+        return buf.value.decode()
 
     def first_pass_config(self, **kw) -> FirstPassConfig:
         cfg = FirstPassConfig()
@@ -1471,8 +1568,45 @@ def align_text_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, texts,
     return AlignmentSet(L, h, lex)
 
 
+class _AudioIn:
+    """The audio helpers' way in: the batch's samples in HBM and its cepstra.  int16 audio goes
+    as ever (ssw_fe_batch when samprate is None, else ssw_fe_batch_ex); float32 audio (np.float32
+    array, torch.float32 device tensor, or a device pointer with pcm_format="f32") through
+    ssw_fe_batch_f32, at the configuration's rate when samprate is None."""
+
+    def __init__(self, model: Model, pcm, samp_off, samprate, fe_cfg, pcm_format, who):
+        self.model = model
+        self.kind = _pcm_kind(pcm, pcm_format, who)
+        self.off = np.ascontiguousarray(samp_off, np.int64)
+        self.samprate = samprate
+        self.fe_cfg = fe_cfg
+        n = np.diff(self.off)
+        self.n_frames = int(fe_frame_counts(n).sum() if samprate is None and self.kind == "i16"
+                            else model.fe_frame_counts_rates(n, samprate, fe_cfg).sum())
+        self.on_device = _is_device_tensor(pcm) or isinstance(pcm, (int, C.c_void_p))
+        self.d_pcm = pcm if self.on_device else (
+            model.to_device(np.ascontiguousarray(pcm, _PCM_DTYPE[self.kind]))
+            if self.off[-1] > 0 else None)
+
+    def cepstra(self, d_cep, stream):
+        m = self.model
+        if self.kind == "f32":
+            return m.fe_batch_f32_device(self.d_pcm, self.off, self.samprate, d_cep, self.fe_cfg,
+                                         stream)[1]
+        if self.samprate is None:
+            return m.fe_batch_device(self.d_pcm, self.off, d_cep, self.fe_cfg, stream)[1]
+        return m.fe_batch_rates_device(self.d_pcm, self.off, self.samprate, d_cep, self.fe_cfg,
+                                       stream)[1]
+
+    def free(self):
+        if self.d_pcm is not None and not self.on_device:
+            self.model.device_free(self.d_pcm)
+        self.d_pcm = None
+
+
 def align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, texts, cfg=None, active=False,
-                      fe_cfg=None, scorer=None, stream=None, samprate=None) -> AlignmentSet:
+                      fe_cfg=None, scorer=None, stream=None, samprate=None,
+                      pcm_format=None) -> AlignmentSet:
     """Audio and text in, alignments out: what decoder_process_int16 over each utterance and
     decoder_alignment give (src/decoder.c:737-798), for a batch.  int16 PCM (host array or
     device tensor; utterance u = samples samp_off[u] .. samp_off[u + 1]) -> ssw_fe_batch ->
@@ -1481,30 +1615,24 @@ def align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, texts, cfg=None
     reference's default compallsen = no).  cfg: FirstPassConfig; fe_cfg: front-end settings
     (None = the model's feat_params.json).  samprate None: 16 kHz audio through ssw_fe_batch;
     a number, or one per utterance: the cepstra at that rate through ssw_fe_batch_ex, as the
-    reference computes them at the rate the audio has."""
+    reference computes them at the rate the audio has.  float32 audio (np.float32 array,
+    torch.float32 device tensor, or a device pointer with pcm_format="f32"; 1.0 is 32768) is
+    what decoder_process_float32 takes (src/decoder.c:960-1000) and goes through
+    ssw_fe_batch_f32; arrays and tensors of any other float type raise."""
     width = model._audio_feat_width()
-    off = np.ascontiguousarray(samp_off, np.int64)
-    n_frames = int(fe_frame_counts(np.diff(off)).sum() if samprate is None else
-                   model.fe_frame_counts_rates(np.diff(off), samprate, fe_cfg).sum())
-    on_device = hasattr(pcm, "data_ptr") and getattr(pcm, "is_cuda", False)
-    d_pcm = pcm if on_device else (model.to_device(np.ascontiguousarray(pcm, np.int16))
-                                   if off[-1] > 0 else None)
+    audio = _AudioIn(model, pcm, samp_off, samprate, fe_cfg, pcm_format, "align_audio_batch")
+    n_frames = audio.n_frames
     d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
     d_feat = model.device_malloc(n_frames * width * 4) if n_frames else None
     try:
-        if samprate is None:
-            _, fo = model.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, fe_cfg, stream)
-        else:
-            _, fo = model.fe_batch_rates_device(d_pcm, off, samprate, d_cep if d_cep else 0,
-                                                fe_cfg, stream)
+        fo = audio.cepstra(d_cep if d_cep else 0, stream)
         if n_frames:
             model._audio_feats(d_cep, n_frames, fo, d_feat, stream)
         fn = align_text_batch_active if active else align_text_batch
         return fn(model, lex, d_feat if d_feat else 0, fo, texts, cfg=cfg, scorer=scorer,
                   stream=stream)
     finally:
-        if d_pcm is not None and not on_device:
-            model.device_free(d_pcm)
+        audio.free()
         for p in (d_cep, d_feat):
             if p:
                 model.device_free(p)
@@ -1846,28 +1974,21 @@ def recognize_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, plan: G
 
 def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: GrammarPlan,
                           fsg_of_utt=None, samprate=None, fe_cfg=None, scorer=None,
-                          stream=None, active=False) -> RecognitionSet:
+                          stream=None, active=False, pcm_format=None) -> RecognitionSet:
     """Audio in, hypotheses out: decoder_process_int16(full_utt) + decoder_hyp / decoder_seg_iter
     under decoder_set_fsg with compallsen = yes, for a batch.  int16 PCM (host array or device
     tensor; utterance u = samples samp_off[u] .. samp_off[u + 1]) -> ssw_fe_batch (samprate None:
     16 kHz) or ssw_fe_batch_ex -> ssw_feat_batch (ssw_feat_batch_ex when the model's
     feat_params.json asks for anything but the plain features) -> ssw_recognize_batch, or
-    ssw_recognize_batch_active when active=True (the reference's default compallsen = no)."""
+    ssw_recognize_batch_active when active=True (the reference's default compallsen = no).
+    float32 audio as align_audio_batch takes it (decoder_process_float32)."""
     width = model._audio_feat_width()
-    off = np.ascontiguousarray(samp_off, np.int64)
-    n_frames = int(fe_frame_counts(np.diff(off)).sum() if samprate is None else
-                   model.fe_frame_counts_rates(np.diff(off), samprate, fe_cfg).sum())
-    on_device = hasattr(pcm, "data_ptr") and getattr(pcm, "is_cuda", False)
-    d_pcm = pcm if on_device else (model.to_device(np.ascontiguousarray(pcm, np.int16))
-                                   if off[-1] > 0 else None)
+    audio = _AudioIn(model, pcm, samp_off, samprate, fe_cfg, pcm_format, "recognize_audio_batch")
+    n_frames = audio.n_frames
     d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
     d_feat = model.device_malloc(n_frames * width * 4) if n_frames else None
     try:
-        if samprate is None:
-            _, fo = model.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, fe_cfg, stream)
-        else:
-            _, fo = model.fe_batch_rates_device(d_pcm, off, samprate, d_cep if d_cep else 0,
-                                                fe_cfg, stream)
+        fo = audio.cepstra(d_cep if d_cep else 0, stream)
         if n_frames:
             model._audio_feats(d_cep, n_frames, fo, d_feat, stream)
         if active:
@@ -1876,8 +1997,7 @@ def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: Gramm
         return recognize_batch(model, lex, d_feat if d_feat else 0, fo, plan, fsg_of_utt,
                                scorer=scorer, stream=stream)
     finally:
-        if d_pcm is not None and not on_device:
-            model.device_free(d_pcm)
+        audio.free()
         for p in (d_cep, d_feat):
             if p:
                 model.device_free(p)
@@ -1927,35 +2047,28 @@ def recognize_align_batch_active(model: Model, lex: Lexicon, d_feats, utt_off, p
 
 def recognize_align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: GrammarPlan,
                                 fsg_of_utt=None, samprate=None, fe_cfg=None, scorer=None,
-                                stream=None, active=False, two_pass_history=False):
+                                stream=None, active=False, two_pass_history=False,
+                                pcm_format=None):
     """Audio in, hypotheses with phone and state times out: recognize_audio_batch followed by
     decoder_alignment, i.e. decoder_result_json(d, start, 1 or 2) after decoder_set_fsg /
     decoder_set_jsgf_*, for a batch.  The front end is recognize_audio_batch's; then
     ssw_recognize_align_batch, or ssw_recognize_align_batch_active when active=True (the
     reference's default compallsen = no).  Returns (RecognitionSet, AlignmentSet)."""
     width = model._audio_feat_width()
-    off = np.ascontiguousarray(samp_off, np.int64)
-    n_frames = int(fe_frame_counts(np.diff(off)).sum() if samprate is None else
-                   model.fe_frame_counts_rates(np.diff(off), samprate, fe_cfg).sum())
-    on_device = hasattr(pcm, "data_ptr") and getattr(pcm, "is_cuda", False)
-    d_pcm = pcm if on_device else (model.to_device(np.ascontiguousarray(pcm, np.int16))
-                                   if off[-1] > 0 else None)
+    audio = _AudioIn(model, pcm, samp_off, samprate, fe_cfg, pcm_format,
+                     "recognize_align_audio_batch")
+    n_frames = audio.n_frames
     d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
     d_feat = model.device_malloc(n_frames * width * 4) if n_frames else None
     try:
-        if samprate is None:
-            _, fo = model.fe_batch_device(d_pcm, off, d_cep if d_cep else 0, fe_cfg, stream)
-        else:
-            _, fo = model.fe_batch_rates_device(d_pcm, off, samprate, d_cep if d_cep else 0,
-                                                fe_cfg, stream)
+        fo = audio.cepstra(d_cep if d_cep else 0, stream)
         if n_frames:
             model._audio_feats(d_cep, n_frames, fo, d_feat, stream)
         fn = recognize_align_batch_active if active else recognize_align_batch
         return fn(model, lex, d_feat if d_feat else 0, fo, plan, fsg_of_utt, scorer=scorer,
                   two_pass_history=two_pass_history, stream=stream)[:2]
     finally:
-        if d_pcm is not None and not on_device:
-            model.device_free(d_pcm)
+        audio.free()
         for p in (d_cep, d_feat):
             if p:
                 model.device_free(p)

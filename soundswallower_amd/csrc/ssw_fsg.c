@@ -524,7 +524,7 @@ build_one(builder_t *b, const ssw_model_t *m, const ssw_host_model_t *h, const s
             const int sw = ssw_dict_find(d, "<sil>"), start = ssw_dict_find(d, "<s>"),
                       fin = ssw_dict_find(d, "</s>");
             int f;
-            for (f = -1; f < d->n_words - 1; f = (f < 0 ? d->filler_start : f + 1)) {
+            for (f = -1; f < d->filler_end; f = (f < 0 ? d->filler_start : f + 1)) {
                 const int w = f < 0 ? sw : f;
                 if (w < 0 || (f >= 0 && (w == sw || w == start || w == fin)))
                     continue;

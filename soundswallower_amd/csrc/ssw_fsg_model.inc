@@ -385,7 +385,7 @@ ssw_fsg_compile(const ssw_fsg_t *f, const ssw_dict_t *d, const ssw_first_pass_co
         const int logsil = (int32_t)((float)ilog0(f->logbase, (double)cfg.silprob) * cfg.lw);
         const int logfil = (int32_t)((float)ilog0(f->logbase, (double)cfg.fillprob) * cfg.lw);
         int fw;
-        for (fw = -1; fw < d->n_words - 1; fw = (fw < 0 ? d->filler_start : fw + 1)) {
+        for (fw = -1; fw < d->filler_end; fw = (fw < 0 ? d->filler_start : fw + 1)) {
             const int w = fw < 0 ? sw : fw;
             int vid;
             if (w < 0 || (fw >= 0 && (w == start || w == fin)))

@@ -1,4 +1,4 @@
-/* ssw_host_fe.inc -- host: ssw_fe_batch(_ex), ssw_fe_frame_count(_ex), ssw_model_fe_config.
+/* ssw_host_fe.inc -- host: ssw_fe_batch(_ex, _f32), ssw_fe_frame_count(_ex), ssw_model_fe_config.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 /* ---------------------------------------------------------------------------------- */
 /* MFCC front end (SURVEY 2 row 19, 8(f)): PCM -> cepstra for a batch                    */
@@ -127,12 +127,13 @@ fe_rates_upload(ssw_model_s *m, std::vector<FeRate> &rates)
     return 0;
 }
 
-/* ssw_fe_batch and ssw_fe_batch_ex: every utterance at samprate[u] (NULL: c->samprate; ex = 0:
- * ssw_fe_batch's checks, which allow 16 kHz only) */
+/* ssw_fe_batch, ssw_fe_batch_ex and ssw_fe_batch_f32: every utterance at samprate[u] (NULL:
+ * c->samprate; ex = 0: ssw_fe_batch's checks, which allow 16 kHz only); d_pcm holds float32
+ * samples when f32, int16 otherwise */
 static int
-fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm, const int64_t *samp_off,
+fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const int64_t *samp_off,
          const double *samprate, int32_t n_utts, float *d_cep, int32_t *frame_off_out,
-         void *stream, bool ex, const char *who)
+         void *stream, bool ex, bool f32, const char *who)
 {
     if (m == NULL) {
         ssw_set_error("bad arguments to %s", who);
@@ -300,10 +301,10 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm, const
         G.grp_off = d_grp_off + off_at[o];
         G.n_grp = grp_n[o];
         G.n_grp_frames = grp_frames[o];
-        switch (o) {
-#define FE_SPEC_LAUNCH(L)                                                                       \
+        if (!f32) switch (o) {
+#define FE_SPEC_LAUNCH(L)                                                                      \
         case L:                                                                                 \
-            hipLaunchKernelGGL(fe_spectrum_kernel<L>,                                           \
+            hipLaunchKernelGGL((fe_spectrum_kernel<L, int16_t>),                                \
                                dim3((G.n_grp_frames + fe_spec_waves(L) - 1) / fe_spec_waves(L)), \
                                dim3(64 * fe_spec_waves(L)), 0, st, G);                          \
             break;
@@ -316,6 +317,25 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm, const
         FE_SPEC_LAUNCH(12)
         FE_SPEC_LAUNCH(13)
 #undef FE_SPEC_LAUNCH
+        }
+        /* (after the table above: the order of first launch places the template kernels in the
+         * code object, DESIGN 6a) */
+        else switch (o) {
+#define FE_SPEC_F32_LAUNCH(L)                                                                   \
+        case L:                                                                                 \
+            hipLaunchKernelGGL((fe_spectrum_kernel<L, float>),                                  \
+                               dim3((G.n_grp_frames + fe_spec_waves(L) - 1) / fe_spec_waves(L)), \
+                               dim3(64 * fe_spec_waves(L)), 0, st, G);                          \
+            break;
+        FE_SPEC_F32_LAUNCH(6)
+        FE_SPEC_F32_LAUNCH(7)
+        FE_SPEC_F32_LAUNCH(8)
+        FE_SPEC_F32_LAUNCH(9)
+        FE_SPEC_F32_LAUNCH(10)
+        FE_SPEC_F32_LAUNCH(11)
+        FE_SPEC_F32_LAUNCH(12)
+        FE_SPEC_F32_LAUNCH(13)
+#undef FE_SPEC_F32_LAUNCH
         }
         e = hipGetLastError();
     }
@@ -350,7 +370,7 @@ ssw_fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm,
              void *stream)
 {
     return fe_batch(m, cfg, d_pcm, samp_off, NULL, n_utts, d_cep, frame_off_out, stream, false,
-                    "ssw_fe_batch");
+                    false, "ssw_fe_batch");
 }
 
 extern "C" int
@@ -359,7 +379,16 @@ ssw_fe_batch_ex(ssw_model_t *m, const ssw_fe_config_t *cfg, const int16_t *d_pcm
                 int32_t *frame_off_out, void *stream)
 {
     return fe_batch(m, cfg, d_pcm, samp_off, samprate, n_utts, d_cep, frame_off_out, stream, true,
-                    "ssw_fe_batch_ex");
+                    false, "ssw_fe_batch_ex");
+}
+
+extern "C" int
+ssw_fe_batch_f32(ssw_model_t *m, const ssw_fe_config_t *cfg, const float *d_pcm,
+                 const int64_t *samp_off, const double *samprate, int32_t n_utts, float *d_cep,
+                 int32_t *frame_off_out, void *stream)
+{
+    return fe_batch(m, cfg, d_pcm, samp_off, samprate, n_utts, d_cep, frame_off_out, stream, true,
+                    true, "ssw_fe_batch_f32");
 }
 
 extern "C" int

@@ -238,6 +238,7 @@ int ssw_host_model_apply_mllr(ssw_host_model_t *h, const ssw_mllr_t *mllr);
 void ssw_set_error(const char *fmt, ...);
 
 /* Pronunciation dictionary (ssw_lexicon.c) */
+#define SSW_DICT_MAX_PRON 256 /* phones of one word: a dictionary line's are cut there */
 struct ssw_dict_s {
     int n_words, cap_words;
     char **word;
@@ -246,7 +247,9 @@ struct ssw_dict_s {
     int *slot;      /* open-addressing hash: word index + 1, 0 = empty */
     int n_slots;
     int filler_start; /* first word that came from the filler dictionary (dict_filler_start) */
-    int *alt;         /* dict_nextalt: next alternate pronunciation of the same base word, -1 */
+    int filler_end;   /* last word of the load, <s>, </s> and <sil> included (dict_filler_end,
+                       * src/dict.c:337); fixed by ssw_dict_load, so words added later are past it */
+    int *alt;        /* dict_nextalt: next alternate pronunciation of the same base word, -1 */
     int *base;        /* dict_basewid */
 };
 int ssw_dict_find(const struct ssw_dict_s *d, const char *w);

@@ -1,13 +1,13 @@
 /* ssw_k8_fe.inc -- K8: the MFCC front end, whole utterances.
  * Part of the single translation unit ssw_kernels.hip (included there, in this order). */
 /* ---------------------------------------------------------------------------------- */
-/* K8: PCM -> cepstra (fe_process_int16 + fe_end over whole utterances)                 */
+/* K8: PCM -> cepstra (fe_process_int16 / fe_process_float32 + fe_end, whole utterances)  */
 /* ---------------------------------------------------------------------------------- */
 /* The reference's front end, frame by frame (src/fe_sigproc.c:219-738, src/fe_noise.c:111-327),
  * in its own types: pre-emphasis, window, FFT, power and mel spectra in double, the noise
  * tracker in double, log in double, the DCT with float accumulators rounded after every add.
- * The only operations that are not +, -, *, / or a compare are the log (ocml's, which may sit
- * one double ulp away from glibc's; the float rounding of the DCT absorbs that, DESIGN K8) and
+ * The only operations that are not +, -, *, / or a compare are the log (fe_log, ssw_fe_log.inc:
+ * correctly rounded, as a good libm's is for all but a few arguments in 100,000; DESIGN K8) and
  * the conversions.  The tables come from the host (csrc/ssw_model.c), built as fe_init builds them.
  *
  * Framing (src/fe_interface.c:560-712) at any rate: frame f of an utterance of n samples covers
@@ -26,6 +26,9 @@
  *                       disjoint points: N/4 per stage, lanes past N/4 idle at N = 64 and 128),
  *                       the power spectrum in place, mel sums in the reference's j order
  *                       -> double mfspec [frame][nfilt]
+ *                       fe_spectrum_kernel<LOG2N, S>: S = int16_t, or float for ssw_fe_batch_f32,
+ *                       where a sample is (double)(float)(x * 32768.0f), as fe_process_float32
+ *                       stores it (fe_sample)
  *   fe_noise_kernel     remove_noise: one wave per utterance, lane = filter, frames in order
  *                       (the tracker is a recurrence); the +-4 gain smoothing by lane shuffles
  *   fe_cep_kernel       log(mfspec + 1e-4), then DCT-II (transform = dct) or fe_spec2cep
@@ -37,7 +40,7 @@ struct FeUtt {
 };
 
 struct FeParams {
-    const int16_t *pcm;
+    const void *pcm;           /* fe_spectrum_kernel's S: int16_t or float */
     const FeUtt *utt;          /* [n_utts] */
     const int *frame_off;      /* [n_utts + 1] */
     const int *grp_utt;        /* fe_spectrum_kernel: the utterances of the launch's FFT size */
@@ -82,7 +85,28 @@ fe_rate_part(const ssw_fe_rate_t *R, int off)
     return (const T *)((const char *)R + off);
 }
 
-template <int LOG2N>
+/* One sample as fe_spch_to_frame reads it from spch: an int16 as it is (fe_process_int16 copies
+ * the samples, src/fe_sigproc.c:319-348, 378-411), a float32 as the float it was stored as,
+ * spch[i] = sample * FLOAT32_SCALE (32768.0F; src/fe_sigproc.c:350-376, 413-444, and
+ * create_overflow_frame for fe_end's frame, src/fe_interface.c:503-510).  The product is by a
+ * power of two: exact, subnormal results included (the kernels run with float denormals on),
+ * unless it overflows to infinity.  No address is computed from a sample. */
+__device__ __forceinline__ double
+fe_sample(const int16_t *pcm, long long i)
+{
+    return (double)pcm[i];
+}
+
+__device__ __forceinline__ double
+fe_sample(const float *pcm, long long i)
+{
+    return (double)(float)(pcm[i] * 32768.0f);
+}
+
+/* S: the sample type, int16_t (ssw_fe_batch, ssw_fe_batch_ex) or float (ssw_fe_batch_f32).  The
+ * type is a parameter of the kernel itself: with the body in a function of its own the int16
+ * instantiations at N = 4096 and 8192 came out with other registers than before */
+template <int LOG2N, typename S>
 __global__ void __launch_bounds__(64 * fe_spec_waves(LOG2N))
 fe_spectrum_kernel(FeParams P)
 {
@@ -109,14 +133,15 @@ fe_spectrum_kernel(FeParams P)
         const int len = left < size ? (int)left : size;
         const double *ham = fe_rate_part<double>(R, R->hamming_off);
         const double alpha = (double)P.tab->alpha;
-        const double prior = fl == 0 ? 0.0 : (double)P.pcm[start - 1];
+        const S *pcm = (const S *)P.pcm;
+        const double prior = fl == 0 ? 0.0 : fe_sample(pcm, start - 1);
 #pragma unroll 8
         for (int t = 0; t < N / 64; ++t) {
             const int i = lane + 64 * t;
             double v = 0.0;
             if (i < len) {
-                const double prev = i == 0 ? prior : (double)P.pcm[start + i - 1];
-                v = (double)P.pcm[start + i] - prev * alpha;
+                const double prev = i == 0 ? prior : fe_sample(pcm, start + i - 1);
+                v = fe_sample(pcm, start + i) - prev * alpha;
             }
             /* fe_hamming_window: the first and last size / 2 samples (an odd size's middle
              * sample is not windowed) */
@@ -284,7 +309,7 @@ fe_cep_kernel(FeParams P)
     for (int idx = threadIdx.x; idx < FE_CEP_FRAMES * n; idx += FE_CEP_THREADS) {
         const int r = idx / n, j = idx - r * n;
         if (f0 + r < P.n_frames)
-            s_lm[r][j] = log(P.mfspec[(size_t)(f0 + r) * n + j] + 1e-4);
+            s_lm[r][j] = fe_log(P.mfspec[(size_t)(f0 + r) * n + j] + 1e-4);
     }
     __syncthreads();
     const int r = threadIdx.x / SSW_FE_NCEP, i = threadIdx.x - r * SSW_FE_NCEP, f = f0 + r;

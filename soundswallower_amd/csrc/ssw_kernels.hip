@@ -174,6 +174,7 @@ namespace {
 #include "ssw_k5_firstpass.inc"
 #include "ssw_k6_compact.inc"
 #include "ssw_k7_fpactive.inc"
+#include "ssw_fe_log.inc"
 #include "ssw_k8_fe.inc"
 #include "ssw_k9_grammar.inc"
 #include "ssw_k10_semi.inc"

@@ -143,7 +143,7 @@ dict_read(ssw_dict_t *d, const ssw_host_model_t *h, const char *path)
         return -1;
     }
     while (fgets(line, sizeof(line), fp)) {
-        int16_t pron[256];
+        int16_t pron[SSW_DICT_MAX_PRON];
         int n = 0;
         char *save = NULL, *w, *tok;
         ++lineno;
@@ -154,7 +154,7 @@ dict_read(ssw_dict_t *d, const ssw_host_model_t *h, const char *path)
         w = strtok_r(line, " \t\r\n", &save);
         if (w == NULL)
             continue;
-        while ((tok = strtok_r(NULL, " \t\r\n", &save)) != NULL && n < 256) {
+        while ((tok = strtok_r(NULL, " \t\r\n", &save)) != NULL && n < SSW_DICT_MAX_PRON) {
             int id = ci_id(h, tok);
             if (id < 0) {
                 n = -1;
@@ -206,6 +206,8 @@ ssw_dict_load(const ssw_model_t *m, const char *dict_path, const char *filler_pa
         dict_add(d, "</s>", &sil, 1);
         dict_add(d, "<sil>", &sil, 1);
     }
+    /* dict_filler_end (src/dict.c:337): fixed here; words added later lie past it */
+    d->filler_end = d->n_words - 1;
     return d;
 }
 
@@ -261,7 +263,122 @@ ssw_dict_is_filler(const ssw_dict_t *d, int32_t wid)
     b = d->base[wid];
     if (strcmp(d->word[b], "<s>") == 0 || strcmp(d->word[b], "</s>") == 0)
         return 0;
-    return b >= d->filler_start;
+    return b >= d->filler_start && b <= d->filler_end;
+}
+
+/* decoder_add_word (src/decoder.c:801-865): the phone string is cut at white space exactly as
+ * there (isspace_c), every name looked up with bin_mdef_ciphone_id, then dict_add_word
+ * (src/dict.c:72-134).  dict2pid_add_word has no counterpart: triphones are derived per phone
+ * pair when a graph or an alignment is built (ssw_phone_id_nearest), never tabulated per word. */
+int32_t
+ssw_dict_add_word(ssw_dict_t *d, const ssw_model_t *m, const char *word, const char *phones)
+{
+    const ssw_host_model_t *h;
+    int16_t pron[SSW_DICT_MAX_PRON];
+    char name[64];
+    const char *p;
+    int n = 0, bl;
+    if (d == NULL || m == NULL || word == NULL || phones == NULL || word[0] == '\0') {
+        ssw_set_error("bad arguments to ssw_dict_add_word");
+        return -1;
+    }
+    h = ssw_model_host(m);
+    if (h->ciname == NULL) {
+        ssw_set_error("the dictionary needs a model loaded with its mdef");
+        return -1;
+    }
+    for (p = word; *p; ++p)
+        if (isspace((unsigned char)*p)) { /* (a dictionary line could not hold it) */
+            ssw_set_error("white space in the word '%s'", word);
+            return -1;
+        }
+    for (p = phones;;) {
+        size_t len;
+        int id;
+        while (*p && isspace((unsigned char)*p))
+            ++p;
+        if (*p == '\0')
+            break;
+        for (len = 0; p[len] && !isspace((unsigned char)p[len]); ++len)
+            ;
+        if (len < sizeof(name)) {
+            memcpy(name, p, len);
+            name[len] = '\0';
+            id = ci_id(h, name);
+        } else
+            id = -1;
+        if (id < 0) {
+            ssw_set_error("Unknown phone %.*s in phone string %s", (int)len, p, phones);
+            return -1;
+        }
+        if (n == SSW_DICT_MAX_PRON) {
+            ssw_set_error("more than %d phones for '%s'", SSW_DICT_MAX_PRON, word);
+            return -1;
+        }
+        pron[n++] = (int16_t)id;
+        p += len;
+    }
+    if (n == 0) {
+        ssw_set_error("no phones for '%s'", word);
+        return -1;
+    }
+    if (dict_find(d, word) >= 0) {
+        ssw_set_error("the word '%s' exists", word);
+        return -1;
+    }
+    if ((bl = base_len(word)) > 0) {
+        char *b = strdup(word);
+        int base;
+        if (b == NULL) {
+            ssw_set_error("out of memory");
+            return -1;
+        }
+        b[bl] = '\0';
+        base = dict_find(d, b);
+        free(b);
+        if (base < 0) {
+            ssw_set_error("Missing base word for: %s", word); /* src/dict.c:96-102 */
+            return -1;
+        }
+    }
+    if (dict_add(d, word, pron, n) != 1) {
+        ssw_set_error("out of memory");
+        return -1;
+    }
+    return d->n_words - 1;
+}
+
+int32_t
+ssw_dict_lookup_word(const ssw_dict_t *d, const ssw_model_t *m, const char *word, char *out,
+                     int32_t max)
+{
+    const ssw_host_model_t *h;
+    const size_t room = max > 0 ? (size_t)max : 0;
+    size_t len = 0;
+    int w, j;
+    if (d == NULL || m == NULL || word == NULL || (out == NULL && max > 0)) {
+        ssw_set_error("bad arguments to ssw_dict_lookup_word");
+        return -1;
+    }
+    h = ssw_model_host(m);
+    if ((w = dict_find(d, word)) < 0) {
+        ssw_set_error("word '%s' is not in the dictionary", word);
+        return -1;
+    }
+    for (j = 0; j < d->pronlen[w]; ++j) {
+        const char *nm = h->ciname[d->pron[w][j]];
+        if (j > 0) {
+            if (len + 1 < room)
+                out[len] = ' ';
+            ++len;
+        }
+        for (; *nm; ++nm, ++len) /* (cut where the buffer ends, as snprintf cuts) */
+            if (len + 1 < room)
+                out[len] = *nm;
+    }
+    if (max > 0)
+        out[len < (size_t)max ? len : (size_t)max - 1] = '\0';
+    return (int32_t)len;
 }
 
 int32_t
