@@ -217,6 +217,7 @@ struct ssw_model_s {
     DevBuf act_ws; /* ssw_align_batch_active: segments, lists, scores */
     int n_quads, slot_stride;
     int logadd_max; /* the largest log-add entry (upload_model) */
+    int fold_hb[2]; /* Hb of the folded log-add table (ssw_senone_lds.inc): PTM weights, ms pdf */
     ScoreWs sw;     /* scoring workspace */
     DevBuf carry0;              /* ssw_score_batch_ex: carried codeword orders, uint32 [n_utts][n_cbf] */
     DevBuf carry_rows;          /* ssw_align_text_batch, two_pass_history: uint32 [n_utts][n_cbf] */
@@ -554,21 +555,27 @@ upload_model(ssw_model_s *m)
     HIP_OK(hipMalloc((void **)&m->d_logadd8, 256));
     HIP_OK(hipMemcpy(m->d_logadd8, h->logadd8, 256, hipMemcpyHostToDevice));
     {
-        /* the batch senone kernels' LDS table as it stands in LDS (ssw_k1b_senone.inc): entry e =
-         * T - tab[|e - mid|], tab = 0 beyond its 256 entries, T = the largest entry; 1,024 bytes
-         * around 512 for the PTM kernel, then 2,048 around 1,024 for the ms kernel */
+        /* the batch senone kernels' LDS table as it stands in LDS (ssw_k1b_senone.inc): the folded
+         * table of senone_fold_table (ssw_senone_lds.inc), entry mid + d = Hb - tab[|d|] -
+         * max(d, 0); 1,024 bytes around 512 for the PTM kernel, then 2,048 around 1,024 for the
+         * ms kernel, each with the Hb of the largest byte its chains can start from: the
+         * mixture weights' and the ms pdf's (the device tables below hold these bytes, in slot
+         * order, and zeros; MLLR and added words leave both alone) */
         int T = 0;
         for (int i = 0; i < 256; ++i)
             T = h->logadd8[i] > T ? h->logadd8[i] : T;
         m->logadd_max = T; /* (launch_senone and ms_takes_packed_kernel read it) */
         std::vector<uint8_t> mir((size_t)3 * SSW_LOGADD_MIRROR);
+        const size_t n_w = (size_t)h->n_feat * h->n_density * h->n_sen;
         for (int part = 0; part < 2; ++part) {
-            const int size = (part + 1) * SSW_LOGADD_MIRROR, mid = size / 2;
-            uint8_t *out = mir.data() + (part ? SSW_LOGADD_MIRROR : 0);
-            for (int e = 0; e < size; ++e) {
-                const int d = e < mid ? mid - e : e - mid;
-                out[e] = (uint8_t)(T - (d < 256 ? (int)h->logadd8[d] : 0));
-            }
+            const int size = (part + 1) * SSW_LOGADD_MIRROR;
+            const uint8_t *w = part ? h->ms_pdf : h->ptm_mixw;
+            int wmax = w != NULL ? 0 : 255;
+            for (size_t i = 0; w != NULL && i < n_w; ++i)
+                wmax = w[i] > wmax ? w[i] : wmax;
+            m->fold_hb[part] = senone_fold_hb(h->logadd8, wmax);
+            senone_fold_table(h->logadd8, wmax, m->fold_hb[part], size,
+                              mir.data() + (part ? SSW_LOGADD_MIRROR : 0));
         }
         HIP_OK(hipMalloc((void **)&m->d_logadd_mirror, mir.size()));
         HIP_OK(hipMemcpy(m->d_logadd_mirror, mir.data(), mir.size(), hipMemcpyHostToDevice));

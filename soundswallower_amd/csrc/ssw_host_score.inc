@@ -108,7 +108,8 @@ ms_takes_packed_kernel(const ssw_model_s *m, int n_frames)
 {
     const ssw_host_model_t *h = m->h;
     return h->cfg.aw == 1 && !m->ms_raw && n_frames >= 4 * 512 && h->n_cb <= 64
-        && 255 + 640 + 6 * m->logadd_max < SSW_LOGADD_MIRROR && !m->kn.ms_senone_old;
+        && 255 + 640 + 6 * m->logadd_max < SSW_LOGADD_MIRROR && m->fold_hb[1] <= 255
+        && !m->kn.ms_senone_old;
 }
 
 /* per-frame active sets of a compallsen = no batch (device pointers; ssw_host_active.inc) */
@@ -208,9 +209,13 @@ launch_senone(const ScoreCall &C, int lo, int hi, bool move_stats)
     S.slot_stride = m->slot_stride;
     S.n_quads = m->n_quads;
     S.tab_max = m->logadd_max;
-    /* the PTM kernel indexes a 512-entry table with |x - y|, x >= -3 tab_max, y <= 255 + 96 */
-    if (scorer != SSW_SCORER_MS && 255 + SSW_MAX_NEG_ASCR + 3 * S.tab_max >= SSW_LOGADD_LDS) {
-        ssw_set_error("unsupported log-add table (largest entry %d)", S.tab_max);
+    S.hb = m->fold_hb[scorer == SSW_SCORER_MS ? 1 : 0];
+    /* the PTM kernel indexes its folded table with 512 + x - y, x >= -3 tab_max, y <= 255 + 96,
+     * and the table's entries are bytes only up to Hb = 255 (ssw_senone_lds.inc) */
+    if (scorer != SSW_SCORER_MS
+        && (255 + SSW_MAX_NEG_ASCR + 3 * S.tab_max >= SSW_LOGADD_LDS || S.hb > 255)) {
+        ssw_set_error("unsupported log-add table (largest entry %d, folded height %d)", S.tab_max,
+                      S.hb);
         return -1;
     }
     /* Shape of the PTM workgroups (measured on MI355X, en-us, 4096 frames, round 2 kernel):

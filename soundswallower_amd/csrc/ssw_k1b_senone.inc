@@ -24,7 +24,8 @@ struct SenoneParams {
     int aw, zero; /* ms scorer: acoustic weight divisor, logmath zero at shift 10 */
     int raw;      /* ms scorer: 1 = skip the frame normalisation (the caller applies it over an
                    * active set, src/ms_mgau.c:342-364) */
-    int tab_max;  /* PTM: largest entry of logadd8 (its entry 0) */
+    int tab_max;  /* largest entry of logadd8 (its entry 0) */
+    int hb;       /* what every look-up of the folded table adds (senone_fold_hb, ssw_senone_lds.inc) */
     /* COMPACT instances (round 5, ssw_score_batch_compact): `out` holds, per utterance, rows of
      * its OWN states only -- what its forced alignment will read (src/state_align_search.c:
      * 186-189 activates just those senones) -- instead of [n_sen] rows: every senone is still
@@ -74,26 +75,29 @@ pk_max_u16(uint32_t a, uint32_t b)
  * barriers and the launch of 704-thread groups, which is what bounded the one-frame version.
  *
  * The chain of fast_logmath_add steps (tied_mgau_common.h:100-117: x <- min(x, y) -
- * tab[|x - y|]) runs on TWO slots per register, 16 bits each, arranged so that a step is 5
+ * tab[|x - y|]) runs on TWO slots per register, 16 bits each, arranged so that a step is 4
  * vector instructions for the pair:
- *   - step k works on x' = x + T k (T = the largest table entry) and y' = y + T (k - 1), so
- *     that x' <- min(x', y') + (T - tab[d]): nothing is ever subtracted, the halves stay
- *     non-negative and cannot borrow from each other; d = |x' - y'| = |x - y| is unchanged;
+ *   - the step is x + G[d], d = x - y, G[d] = -tab[|d|] - max(d, 0): the minimum is folded
+ *     into the table.  d <= wmax, the largest weight byte (x starts from a weight and only
+ *     falls, y >= 0 relative to the stream's best codeword), so H[d] = Hb + G[d] is a byte
+ *     (senone_fold_table, ssw_senone_lds.inc; the host refuses Hb > 255);
+ *   - step k works on x' = x + Hb (k - 1) and leaves x' + H[d]: nothing is ever subtracted,
+ *     the halves stay non-negative, below 2^16 (255 + 3 x 255), and cannot carry into each other;
  *   - the offsets are the same for every senone of the frame and cancel in `score - best`
  *     (src/ptm_mgau.c:394-400);
- *   - T - tab[d] comes from ONE byte table (4 neighbouring d share a bank word, so look-ups
- *     rarely conflict; a dword table per half was measured at 40 x the bank conflicts): the low
+ *   - H comes from ONE byte table (4 neighbouring d share a bank word, so look-ups rarely
+ *     conflict; a dword table per half was measured at 40 x the bank conflicts): the low
  *     half's entry with ds_read_u8, the high half's with ds_read_u8_d16_hi, which on gfx950
  *     delivers `byte << 16` with a zero low half (tools/microbench/d16_probe.hip).  The
  *     compiler does not select d16 loads on sramecc targets, so the look-ups of a batch of
  *     chains are inline asm, followed by one s_waitcnt through which their results pass;
- *   - round 3: the table is MIRRORED around LDS address 512 and indexed by the signed
- *     difference x' - y' of each half (one v_sub_u32_sdwa per half, the look-up's immediate
- *     offset adds the 512 and the address adder wraps: tools/microbench/addr_probe.hip), so
- *     max(x', y') is never formed.
- * Per step and pair: v_pk_min_u16, two v_sub_u32_sdwa (one per half), the two look-ups,
- * v_add3_u32; y' itself is a byte shuffle of the mixture-weight dword and one add of the
- * (splat) normalised score.
+ *   - the table stands around LDS address CZ (512; ms 1,024) and the look-up's address is
+ *     CZ + d itself, never negative: z = x' + npz_k with npz_k = CZ - rel_k - Hb (k - 1) staged
+ *     per item (16-bit wrap, as the packed add's), then z - the weight BYTE as it lies in the
+ *     gathered mixture-weight dword (v_sub_u32_sdwa WORD_n - BYTE_m, one per half): y itself
+ *     is never formed.
+ * Per step and pair: v_pk_add_u16, two v_sub_u32_sdwa (one per half), the two look-ups,
+ * v_add3_u32.
  * Round 3 as well: the 12 mixture-weight dwords of a quad and frame are fetched with buffer
  * loads whose resource has ADD_TID_ENABLE set (stride 4): address = wave base + row offset (the
  * VGPR read from LDS as it stands) + 4 x lane, no per-lane address add (addr_probe.hip). */
@@ -114,16 +118,16 @@ pk_add_bcast_u16(uint32_t a, uint32_t b)
     return r;
 }
 
-template <int NS, int TOPN, int MID>
+template <int NS, int TOPN>
 __device__ __forceinline__ void
 quad_chains(const uint32_t (*mw)[TOPN], const uint2 *np, uint32_t (&acc)[2])
 {
-    /* np[f] = the stream's normalised scores RELATIVE TO ITS BEST CODEWORD'S (+ step offsets),
-     * 16 bits each: x = codewords 0 | 1 << 16, y = 2 | 3 << 16; the packed add broadcasts the
-     * half it needs.  Round 4: log-add commutes with a common shift (min(x + c, y + c) -
-     * tab[|x - y|]), so the best codeword's score is taken out of the chain -- its term is the
-     * weight as it stands, one packed add less per chain -- and the three streams' best scores
-     * go into the accumulator once per quad (the caller: asc2 starts from their sum). */
+    /* np[f] = per codeword k = 1..3 of the stream, 16 bits each (x = . | 1 << 16, y = 2 | 3 <<
+     * 16; the packed add broadcasts the half it needs): npz_k = CZ - rel_k - Hb (k - 1), rel_k =
+     * its normalised score RELATIVE TO THE BEST CODEWORD'S.  Round 4: log-add commutes with a
+     * common shift (min(x + c, y + c) - tab[|x - y|]), so the best codeword's score is taken
+     * out of the chain -- its term is the weight as it stands -- and the three streams' best
+     * scores go into the accumulator once per quad (the caller: asc2 starts from their sum). */
     constexpr int NC = 2 * NS;
     uint32_t x2[NC];
 #pragma unroll
@@ -132,20 +136,19 @@ quad_chains(const uint32_t (*mw)[TOPN], const uint2 *np, uint32_t (&acc)[2])
                                       (c & 1) ? 0x0c030c02u : 0x0c010c00u);
 #pragma unroll
     for (int k = 1; k < TOPN; ++k) {
-        uint32_t mn[NC], tl[NC], th[NC];
+        uint32_t tl[NC], th[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            const uint32_t sp = __builtin_amdgcn_perm(mw[c >> 1][k], mw[c >> 1][k],
-                                                      (c & 1) ? 0x0c030c02u : 0x0c010c00u);
-            const uint32_t y2 = k == 1 ? pk_add_bcast_u16<1>(sp, np[c >> 1].x)
-                : k == 2               ? pk_add_bcast_u16<0>(sp, np[c >> 1].y)
-                                       : pk_add_bcast_u16<1>(sp, np[c >> 1].y);
-            mn[c] = pk_min_u16(x2[c], y2);
-            /* signed differences of the halves; the table is mirrored around 512 */
-            const uint32_t dlo = (x2[c] & 0xffffu) - (y2 & 0xffffu);
-            const uint32_t dhi = (x2[c] >> 16) - (y2 >> 16);
-            asm volatile("ds_read_u8 %0, %2 offset:%c4\n\tds_read_u8_d16_hi %1, %3 offset:%c4"
-                         : "=&v"(tl[c]), "=&v"(th[c]) : "v"(dlo), "v"(dhi), "i"(MID));
+            const uint32_t w = mw[c >> 1][k];
+            const uint32_t z = k == 1 ? pk_add_bcast_u16<1>(x2[c], np[c >> 1].x)
+                : k == 2              ? pk_add_bcast_u16<0>(x2[c], np[c >> 1].y)
+                                      : pk_add_bcast_u16<1>(x2[c], np[c >> 1].y);
+            /* CZ + x - y of each half = the look-up's address: the half of z minus the slot's
+             * weight byte where it lies (slots 2 (c & 1) and 2 (c & 1) + 1 of the quad) */
+            const uint32_t dlo = (z & 0xffffu) - ((w >> ((c & 1) ? 16 : 0)) & 0xffu);
+            const uint32_t dhi = (z >> 16) - ((w >> ((c & 1) ? 24 : 8)) & 0xffu);
+            asm volatile("ds_read_u8 %0, %2\n\tds_read_u8_d16_hi %1, %3"
+                         : "=&v"(tl[c]), "=&v"(th[c]) : "v"(dlo), "v"(dhi));
         }
         if constexpr (NC == 6)
             asm volatile("s_waitcnt lgkmcnt(0)"
@@ -157,7 +160,7 @@ quad_chains(const uint32_t (*mw)[TOPN], const uint2 *np, uint32_t (&acc)[2])
                          : "+v"(tl[0]), "+v"(tl[1]), "+v"(th[0]), "+v"(th[1]));
 #pragma unroll
         for (int c = 0; c < NC; ++c)
-            x2[c] = mn[c] + tl[c] + th[c];
+            x2[c] = x2[c] + tl[c] + th[c];
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c)
@@ -271,7 +274,7 @@ ms_exact_frame(const SenoneParams &P, int t, int tid, int nthr, int *scratch)
  * tab[|x - y|] (tab = 0 from 256 up) with the `zero` short-cuts.  Relative to the stream's best
  * codeword and negated, X = fden_0 - x, that is the PTM chain min(X, Y) - tab[|X - Y|] with
  * X_0 = pdf_0, Y_k = pdf_k + (fden_0 - fden_k); a difference beyond 640 is as good as 640 (the
- * table is 0 from 256 and X <= 255 + 3 T), so everything fits 16 bits with the table mirrored
+ * table is 0 from 256 and X <= 255), so everything fits 16 bits with the folded table
  * around 1024.  The slot's score -sum_f fscr_f = sum_f X_f - sum_f fden_0f: the second sum is
  * one number per (frame, codebook), added up with LDS atomics where the PTM kernel takes its
  * normaliser, and the accumulator starts from it.  What this form cannot express -- a density
@@ -307,7 +310,8 @@ ptm_senone_kernel(SenoneParams P)
     const int n_cbf = P.n_cb * P.n_feat;
     /* The log-add table is indexed by the difference without a bound, as in the reference; x, y
      * <= 255 + 96 and the running value can dip 3 T below zero (the host refuses tables with
-     * 351 + 3 T >= 512).  It holds T - tab[|s|] mirrored around LDS address 512 (this kernel has
+     * 351 + 3 T >= 512, so that MID + x - y >= 0; it is <= MID + 255).  It holds the folded
+     * entries Hb - tab[|d|] - max(d, 0) at LDS address MID + d (this kernel has
      * no static LDS: its dynamic LDS starts at 0, which is what the look-ups' asm assumes).
      * The carve is SenoneCarve's (ssw_senone_lds.inc), from which launch_senone takes the byte
      * count: tab[MIRROR] | norm[3][FPB][NORM_W] | red[16] | item[2][n_cbf][FPB] 32 B |
@@ -340,6 +344,7 @@ ptm_senone_kernel(SenoneParams P)
     const int tid = threadIdx.x;
     const int nthr = blockDim.x;
     const uint32_t T = (uint32_t)P.tab_max;
+    const uint32_t Hb = (uint32_t)P.hb;
     const int n_units = (P.n_frames + FPB - 1) / FPB;
     const int stride_u = (int)gridDim.x;
     int u = (int)blockIdx.x;
@@ -437,19 +442,31 @@ ptm_senone_kernel(SenoneParams P)
                     q = -((v[k] >> SSW_SENSCR_SHIFT) - norm);
                     q = q > SSW_MAX_NEG_ASCR ? SSW_MAX_NEG_ASCR : q;
                 }
-                const uint32_t e = (uint32_t)(q & 0x3ff) + (k > 1 ? T * (uint32_t)(k - 1) : 0u);
-                sp[k] = e;
+                sp[k] = (uint32_t)(q & 0x3ff);
             }
             /* the chain works relative to the best codeword's score (the block is sorted: it is
              * the smallest); that score itself travels in the item's third dword, in both
-             * halves, and starts the accumulator (MS: already relative, sp[0] = 0) */
+             * halves, and starts the accumulator (MS: already relative, sp[0] = 0).  What is
+             * staged per codeword k >= 1 is npz_k = MID - rel_k - Hb (k - 1), which the chain
+             * adds to its running value to get the look-up's address less the weight byte
+             * (quad_chains); it may be negative and wraps within its 16 bits, as the packed add
+             * does */
             const uint32_t e0 = MS ? 0u : sp[0];
 #pragma unroll
             for (int k = 0; k < TOPN; ++k)
-                sp[k] -= e0;
+                sp[k] = k == 0 ? 0u
+                               : ((uint32_t)MID - (sp[k] - e0) - Hb * (uint32_t)(k - 1)) & 0xffffu;
+            /* MS: the accumulator ends at sum_f (X_f + 3 Hb) + a0n = sum_f X_f - (sum of fden_0),
+             * a0n = -(sum of fden_0) - 3 Hb per stream.  X_f >= -3 T and <= 255, so with
+             * a0 = -(sum of fden_0) - 3 T per stream in 0 .. 30,000 every slot's end value lies
+             * in 0 .. 30,000 + n_feat (255 + 3 T) < 2^15 (T <= 21: ms_takes_packed_kernel):
+             * otherwise the frame is marked, as it always was.  a0n itself may be negative
+             * (Hb > T): then the low half starts from a0n + 2^16 and, since it ends in
+             * 0 .. 2^16 - 1 and 32-bit sums do not depend on their order, carries into the high
+             * half exactly once -- which therefore starts one lower.  Nothing else can carry: a
+             * slot's sum of streams is at most n_feat (255 + 3 x 255) = 8,160. */
+            const int a0n = -norm - (int)(3u * Hb) * n_feat;
             if (MS) {
-                /* the accumulator starts from -(sum of fden_0) - 3 T per stream and must stay
-                 * within 16 bits with the slot sums on top: otherwise the frame is marked */
                 const int a0 = -norm - (int)(3u * T) * n_feat;
                 if (a0 < 0 || a0 > 30000)
                     atomicOr(&s_red[12 + ns], 1 << (int)(my_a & 0xfu));
@@ -464,8 +481,9 @@ ptm_senone_kernel(SenoneParams P)
                 = make_uint2(sp[0] | (sp[1] << 16), sp[2] | (sp[3] << 16));
             /* what the quads of this codebook start their sums from, in both halves: MS the
              * frame's offset (stream 0's item is the one read), PTM this stream's best score */
+            /* (PTM: a slot ends at most at n_feat (255 + 3 x 255 + 96) = 8,928 < 2^15) */
             reinterpret_cast<uint32_t *>(dst + 1)[2] = MS
-                ? (uint32_t)((-norm - (int)(3u * T) * n_feat) & 0xffff) * 0x10001u
+                ? (uint32_t)(a0n & 0xffff) | (uint32_t)((a0n - (a0n < 0 ? 1 : 0)) & 0xffff) << 16
                 : e0 * 0x10001u;
         }
     };
@@ -480,7 +498,7 @@ ptm_senone_kernel(SenoneParams P)
         const int q = r * nthr + tid;
         qi_ld[r] = q < P.n_quads ? P.quad_info[q] : 0u;
     }
-    /* the mirrored table comes ready-made (entry e = T - tab[|e - MID|]): nthr >= 256, one or
+    /* the folded table comes ready-made (ssw_host_model.inc): nthr >= 256, one or
      * two dwords per thread */
     constexpr int TAB_DW = MIRROR / 4;
     uint32_t tv[(TAB_DW + 255) / 256] = {};
@@ -598,7 +616,7 @@ ptm_senone_kernel(SenoneParams P)
                                 asc2[r][fr][0] += zsum;
                                 asc2[r][fr][1] += zsum;
                             }
-                            quad_chains<NF ? NF : 1, TOPN, MID>(mw, np, asc2[r][fr]);
+                            quad_chains<NF ? NF : 1, TOPN>(mw, np, asc2[r][fr]);
                         } else
                         for (int f = 0; f < n_feat; ++f) {
                             const uint4 ro = item_cb[2 * (f * FPB + fr)];
@@ -610,7 +628,7 @@ ptm_senone_kernel(SenoneParams P)
                             }
                             uint32_t mw[1][TOPN];
                             load_quad_rows(mw_rsrc, ro, soff, mw[0]);
-                            quad_chains<1, TOPN, MID>(mw, &np, asc2[r][fr]);
+                            quad_chains<1, TOPN>(mw, &np, asc2[r][fr]);
                         }
                     }
                 }

@@ -12,11 +12,45 @@
 #endif
 
 #define SSW_LOGADD_LDS 512 /* 8-bit log-add table in LDS: 256 entries + zero padding */
-/* the batch kernel's copy: T - tab[|s|] for s = -512 .. 511 at LDS address 512 + s, so that a
- * SIGNED difference indexes it (ds_read_u8 v, s offset:512: the address adder wraps, measured by
- * tools/microbench/addr_probe.hip) and the chain needs min(x, y) only, not max(x, y) as well */
+/* the batch kernel's copy, 1,024 bytes around LDS address CZ = 512 (ms: 2,048 around 1,024): the
+ * FOLDED table of senone_fold_table below, indexed by CZ + the signed difference x - y */
 #define SSW_LOGADD_MIRROR 1024
 #define SSW_SENONE_NORM_W 8 /* PTM: normaliser words per frame (= SSW_MAX_FEAT) */
+
+/* The log-add step x <- min(x, y) - tab[|x - y|] (tied_mgau_common.h:100-117) is x + G[d] with
+ * d = x - y and G[d] = -tab[|d|] - max(d, 0).  In ptm_senone_kernel's chains x starts from a
+ * mixture-weight byte and only falls, and y = weight + a score relative to the stream's best
+ * codeword >= 0: d <= wmax, the largest weight byte.  Over d <= wmax, G lies in [-Hb, 0] with
+ *   Hb = max(T, max over 0 <= d <= wmax of d + tab[d]),     T = the largest entry of tab
+ * (T = tab[0] in every table logmath writes, so that the first term changes nothing), and
+ * H[d] = Hb + G[d] is ONE BYTE per entry whenever Hb <= 255: the minimum is folded into the
+ * look-up and the chain only ever adds.  tab = 0 beyond its 256 entries, so H = Hb there; the
+ * entries above wmax, which no chain reaches, hold Hb as well. */
+inline int
+senone_fold_hb(const unsigned char *tab /* [256] */, int wmax)
+{
+    int hb = 0;
+    for (int d = 0; d < 256; ++d) {
+        hb = tab[d] > hb ? tab[d] : hb;
+        if (d <= wmax)
+            hb = d + tab[d] > hb ? d + tab[d] : hb;
+    }
+    return hb;
+}
+
+/* out[size]: entry cz + d = H[d], cz = size / 2; only for hb <= 255 (the callers refuse the
+ * model, or leave the kernel, otherwise) */
+inline void
+senone_fold_table(const unsigned char *tab /* [256] */, int wmax, int hb, int size,
+                  unsigned char *out)
+{
+    const int cz = size / 2;
+    for (int e = 0; e < size; ++e) {
+        const int d = e - cz, ad = d < 0 ? -d : d;
+        const int h = d > wmax ? hb : hb - (ad < 256 ? (int)tab[ad] : 0) - (d > 0 ? d : 0);
+        out[e] = (unsigned char)h;
+    }
+}
 
 /* ptm_senone_kernel: tab[mirror] | norm[3][fpb][norm_w] int | red[16] int | item[2][n_cbf][fpb]
  * of 32 bytes | stage_sc[pad64(fpb n_cbf)] int4 | stage_cw[..] uint32 | 16 bytes that nothing

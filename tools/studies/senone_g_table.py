@@ -22,6 +22,16 @@ chain in doubled units -- which needs the spread weights doubled, the packed ins
 was to remove) costs per look-up what the byte-domain add saves per pair (DESIGN.md, round 5,
 item 9).
 
+Later: the byte form, which is what the kernel runs now.  Relative to the stream's best codeword
+x <= w_0 <= wmax (the largest weight byte) and y >= 0, so d = x - y <= wmax, and over that reach
+G[d] - T lies in [-Hb, 0] with Hb = max over 0 <= d <= wmax of d + tab[d]: H[d] = Hb - tab[|d|] -
+max(d, 0) is ONE BYTE, indexed by d itself -- no doubling.  The packed add forms the look-up's
+address instead of y (z = x' + CZ - rel_k - Hb (k - 1), then z - the weight byte), so the spread
+of the weight bytes, the add that formed y' and the packed minimum all go: 4 vector instructions
+per pair and step where there were 6.  h_chain below restates it with its range claims as
+assertions (csrc/ssw_senone_lds.inc, csrc/ssw_k1b_senone.inc; tests/harness/senone_fold_host.cpp
+is the same in C++ with the kernel's packed 32-bit operations).
+
     python tools/studies/senone_g_table.py
 """
 import numpy as np
@@ -56,6 +66,27 @@ def g_chain(w, rel):
     return x - 3 * T                                                              # offsets cancel in score - best
 
 
+def h_chain(w, rel, wmax, cz=512):
+    """the byte form: H[d] = Hb - tab[|d|] - max(d, 0) at table address cz + d, the running value
+    x' = x + Hb k in 16 bits, nothing ever subtracted; rel is relative to the best codeword"""
+    assert (rel[:, 0] == 0).all() and w.max() <= wmax
+    hb = int((np.arange(wmax + 1) + TAB[:wmax + 1]).max())
+    assert T <= hb <= 255, "the folded table needs 2-byte entries"
+    dd = np.arange(-cz, cz)
+    H = hb - TAB[np.minimum(np.abs(dd), 1023)] - np.maximum(dd, 0)
+    H[dd > wmax] = hb                                 # beyond the reach of any chain
+    assert H.min() >= 0 and H.max() == hb             # one byte per entry
+    x = w[:, 0].copy()                                # x'_0: the best codeword's weight as it stands
+    for k in range(1, 4):
+        npz = (cz - rel[:, k] - hb * (k - 1)) & 0xffff
+        z = (x + npz) & 0xffff                        # v_pk_add_u16, per half
+        a = z - w[:, k]                               # v_sub_u32_sdwa WORD - BYTE: the address
+        assert a.min() >= 0 and a.max() <= cz + wmax < 2 * cz and z.max() < 0x8000
+        x = x + H[a]                                  # v_add3_u32: no carry out of the half
+        assert x.max() < 0x10000
+    return x - 3 * hb                                 # the offsets cancel in score - best
+
+
 def main():
     rng = np.random.default_rng(1)
     n = 4_000_000
@@ -69,6 +100,20 @@ def main():
         rel[:len(ext)] = 0
         a, b = ref_chain(w, rel), g_chain(w, rel)
         print(name, "chains:", n, "differences:", int((a != b).sum()), "min value", int(a.min()))
+        assert (a == b).all()
+    # the byte form: wmax as shipped and at its limit; relative scores up to the clamp; ties,
+    # maxima, alternating weights, relative scores 0 and 96
+    n = 3_000_000
+    for wmax in (158, 255):
+        w = rng.integers(0, wmax + 1, size=(n, 4))
+        rel = np.sort(rng.integers(0, 97, size=(n, 4)), axis=1)
+        rel[:, 0] = 0
+        ext = np.array([[0, 0, 0, 0], [wmax] * 4, [0, wmax, 0, wmax], [wmax, 0, wmax, 0]])
+        for i, r in enumerate((0, 96)):
+            w[i * len(ext):(i + 1) * len(ext)] = ext
+            rel[i * len(ext):(i + 1) * len(ext), 1:] = r
+        a, b = ref_chain(w, rel), h_chain(w, rel, wmax)
+        print("byte table, weights <= %d" % wmax, "chains:", n, "differences:", int((a != b).sum()))
         assert (a == b).all()
 
 
