@@ -1288,11 +1288,77 @@ int ssw_fe_batch_f32(ssw_model_t *m, const ssw_fe_config_t *cfg, const float *d_
  * refuses the settings. */
 int64_t ssw_fe_frame_count_ex(const ssw_model_t *m, const ssw_fe_config_t *cfg,
                               double samprate, int64_t n_samples);
-/* measurement aid: with ssw_set_kernel_timing on, the last ssw_fe_batch(_ex) call's
+/* measurement aid: with ssw_set_kernel_timing on, the last ssw_fe_batch(_ex, _f32, _any) call's
  * milliseconds per kernel -- ms[0] spectrum (framing, FFT, mel; every FFT size's launch),
  * ms[1] noise removal (0 when off), ms[2] log, DCT and lifter.  0, or -1 when no timed call
  * has been made. */
 int ssw_fe_kernel_timing(ssw_model_t *m, float ms[3]);
+
+/* ------------------------------------------------------------------------------------ */
+/* The front end in every configuration fe_init accepts (src/fe_interface.c:84-330,        */
+/* src/fe_sigproc.c:70-738, src/fe_warp.c, src/fe_warp_inverse_linear.c,                   */
+/* src/fe_warp_affine.c, src/fe_warp_piecewise_linear.c).  ssw_fe_batch, _ex and _f32 above */
+/* keep their family of settings and their refusals; these take the rest.  Bit-exact       */
+/* float32 against fe_process_int16 / fe_process_float32 over all samples + fe_end.        */
+/* ------------------------------------------------------------------------------------ */
+/* A resolved configuration: ssw_fe_config_t with the two settings that are strings,
+ * "warp_type" (inverse_linear, affine or piecewise_linear; NULL = inverse_linear, the default)
+ * and "warp_params" (NULL or "" = no warping).  cfg NULL = the model's feat_params.json with the
+ * warp strings it read there (a non-NULL string still overrides).  Host work only: the settings
+ * are checked and the warp parameters parsed as each type's set_parameters parses them (atof of
+ * blank-separated tokens, one for inverse_linear, two for the others, the rest ignored; slope 0 =
+ * no warping; piecewise_linear's F = 0 means 0.85 samprate) and kept in the ssw_fe_t -- the
+ * reference keeps them in process-wide statics.  Accepted besides what ssw_fe_batch_ex takes:
+ *   alpha          any finite float32; 0 copies the samples (fe_copy_to_frame,
+ *                  src/fe_sigproc.c:297-309), which differs from a product by 0 for a
+ *                  non-finite float32 sample
+ *   remove_dc      after pre-emphasis and zero padding the mean of the frame_size doubles, summed
+ *                  in index order with the zeros of a short last frame, is subtracted, then the
+ *                  window applied (fe_hamming_window, :277-285)
+ *   transform htk  fe_dct2 with C0 scaled by sqrt_inv_2n (:677-699); the lifter follows
+ *   ncep           1 .. 64; it may exceed nfilt
+ *   logspec        rows of nfilt floats, (float)log(mfspec + 1e-4); no lifter
+ *   smoothspec     rows of nfilt floats, fe_dct2 then fe_dct3 (:714-726); wins over logspec
+ *   doublebw, unit_area = no, round_filters = no   fe_build_melfilters (:85-199)
+ *   warping        fe_mel and fe_melinv through the warping function; a warped frequency above
+ *                  Nyquist only makes the reference warn, and is used here as there
+ * Refused, naming the reason: dither (its random stream belongs to a process's lifetime); with
+ * cfg NULL, a feat_params.json whose input_endian is not the host's; a warp_type that is none of
+ * the three ("Unimplemented warping function ..."); cfg->warp set without warp_params; ncep or
+ * nfilt outside 1 .. 64; a negative lifter; lowerf < 0 or >= upperf.  At the first rate where it
+ * shows, ssw_fe_batch_any and ssw_fe_frames refuse what ssw_fe_batch_ex refuses of framing and
+ * filters (a filter with no DFT point, or narrower than one), and a doublebw bank whose outer
+ * edges fall below 0 or above Nyquist -- a deliberate difference: the reference warns there and
+ * goes on without a filter bank.  NULL on error (ssw_last_error). */
+typedef struct ssw_fe_s ssw_fe_t;
+ssw_fe_t *ssw_fe_create(ssw_model_t *m, const ssw_fe_config_t *cfg, const char *warp_type,
+                        const char *warp_params);
+void ssw_fe_free(ssw_fe_t *fe);
+/* fe_get_output_size: floats per row, ncep, or nfilt with logspec / smoothspec.  -1 on NULL. */
+int32_t ssw_fe_out_dim(const ssw_fe_t *fe);
+/* ssw_fe_frame_count_ex for a resolved configuration */
+int64_t ssw_fe_frames(const ssw_fe_t *fe, double samprate, int64_t n_samples);
+/* ssw_fe_batch_ex (sample_type 0: d_pcm int16) or ssw_fe_batch_f32 (1: float32) under fe's
+ * settings: every other argument as there, d_cep float32 [total frames][ssw_fe_out_dim(fe)].
+ * Tables that depend on the rate -- warping depends on the Nyquist frequency -- are built per
+ * distinct (fe's settings, samprate, nfft) at the first call that needs them.  A configuration
+ * that ssw_fe_batch_ex takes runs its kernels and gives its bytes.  With remove_dc the frame's
+ * sum is the reference's: a parallel reduction where the host proves from alpha's bit pattern,
+ * the frame size and the sample type that no order of summing rounds (int16 samples and, e.g.,
+ * alpha 0.97 at any supported frame size), else a sum in index order (float32 samples; int16
+ * with an alpha on a fine grid, such as 0.001).  0, or -1 (ssw_last_error). */
+int ssw_fe_batch_any(ssw_model_t *m, ssw_fe_t *fe, const void *d_pcm, int32_t sample_type,
+                     const int64_t *samp_off, const double *samprate, int32_t n_utts,
+                     float *d_cep, int32_t *frame_off_out, void *stream);
+/* 1 when ssw_fe_batch_ex takes the settings of the model's feat_params.json (no warping, the
+ * host's input_endian) or reports why that file cannot be used, 0 when only ssw_fe_batch_any
+ * takes them; -1 on NULL */
+int ssw_model_fe_plain(const ssw_model_t *m);
+/* "warp_type" and "warp_params" as ssw_model_load read them from feat_params.json
+ * ("inverse_linear" and "" when absent; "warp_params": "" or null reads as ""), truncated to the
+ * buffers.  0, or -1 on bad arguments. */
+int ssw_model_fe_warp(const ssw_model_t *m, char *type, int32_t type_len, char *params,
+                      int32_t params_len);
 
 /* ------------------------------------------------------------------------------------ */
 /* Multi-GPU (NEW: the reference is single-process).  The path shards by utterance -- one   */

@@ -372,6 +372,18 @@ def lib() -> C.CDLL:
         L.ssw_dict_lookup_word.restype = i32
         L.ssw_dict_lookup_word.argtypes = [vp, vp, C.c_char_p, C.c_char_p, i32]
     L.ssw_fe_kernel_timing.argtypes = [vp, vp]
+    if hasattr(L, "ssw_fe_create"):      # (an older build has only the three entry points above)
+        L.ssw_fe_create.restype = vp
+        L.ssw_fe_create.argtypes = [vp, C.POINTER(SswFeConfig), C.c_char_p, C.c_char_p]
+        L.ssw_fe_free.argtypes = [vp]
+        L.ssw_fe_free.restype = None
+        L.ssw_fe_out_dim.argtypes = [vp]
+        L.ssw_fe_out_dim.restype = i32
+        L.ssw_fe_frames.argtypes = [vp, C.c_double, C.c_int64]
+        L.ssw_fe_frames.restype = C.c_int64
+        L.ssw_fe_batch_any.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, vp, vp]
+        L.ssw_model_fe_plain.argtypes = [vp]
+        L.ssw_model_fe_warp.argtypes = [vp, C.c_char_p, i32, C.c_char_p, i32]
     L.ssw_comm_unique_id.argtypes = [C.c_char_p]
     L.ssw_comm_init.restype = vp
     L.ssw_comm_init.argtypes = [C.c_char_p, i32, i32, i32]

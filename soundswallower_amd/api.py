@@ -363,6 +363,9 @@ class Model:
             if getattr(self, "_feat0", None) is not None:
                 self._feat0.free()
                 self._feat0 = None
+            if getattr(self, "_fe0", None) is not None:
+                self._fe0.free()
+                self._fe0 = None
             self._L.ssw_model_free(self._m)
             self._m = None
 
@@ -791,14 +794,15 @@ class Model:
                            f"but its Gaussians' streams are {self.veclen_total} wide together")
         return feat.out_dim
 
-    def _audio_feats(self, d_cep, n_frames, fo, d_feat, stream):
-        """The feature rows of the audio helpers: the plain configuration through ssw_feat_batch,
-        as ever; any other through ssw_feat_batch_ex."""
-        if self.feat_plain():
+    def _audio_feats(self, d_cep, n_frames, fo, d_feat, stream, ncep=FE_NCEP):
+        """The feature rows of the audio helpers: the plain configuration over rows of 13 cepstra
+        through ssw_feat_batch, as ever; any other, and rows of another width (ssw_fe_batch_any:
+        ncep, or nfilt with logspec / smoothspec), through ssw_feat_batch_ex."""
+        if self.feat_plain() and ncep == FE_NCEP:
             _check(self._L.ssw_feat_batch(self._m, d_cep, n_frames, _ptr(fo), len(fo) - 1,
                                           FE_NCEP, d_feat, _ptr(stream)), "ssw_feat_batch")
         else:
-            self.feat_batch_ex_device(d_cep, n_frames, fo, d_feat, None, None, stream, ncep=FE_NCEP)
+            self.feat_batch_ex_device(d_cep, n_frames, fo, d_feat, None, None, stream, ncep=ncep)
 
     # ---- MFCC front end ----------------------------------------------------------------
     def fe_config(self, **overrides) -> SswFeConfig:
@@ -961,6 +965,88 @@ class Model:
         _check(self._L.ssw_fe_kernel_timing(self._m, ms), "ssw_fe_kernel_timing")
         return tuple(ms)
 
+    # ---- the front end under any settings fe_init accepts ----------------------------
+    def fe(self, cfg=None, warp_type=None, warp_params=None) -> "Fe":
+        """ssw_fe_create: a front-end configuration resolved and checked on the host.  cfg None:
+        the model's feat_params.json with the warp strings it read there; else a dict of
+        overrides or an SswFeConfig, with warp_type ("inverse_linear", "affine",
+        "piecewise_linear") and warp_params (e.g. "0.9 3000") beside it."""
+        return Fe(self, cfg, warp_type, warp_params)
+
+    def fe_plain(self) -> bool:
+        """ssw_model_fe_plain: whether ssw_fe_batch_ex takes the model's own front-end settings.
+        When not, the helpers that go from audio use ssw_fe_batch_any."""
+        return bool(_check(self._L.ssw_model_fe_plain(self._m), "ssw_model_fe_plain"))
+
+    def fe_warp(self):
+        """ssw_model_fe_warp: ("warp_type", "warp_params") of the model's feat_params.json,
+        ("inverse_linear", "") when it names none."""
+        t, p = C.create_string_buffer(32), C.create_string_buffer(256)
+        _check(self._L.ssw_model_fe_warp(self._m, t, len(t), p, len(p)), "ssw_model_fe_warp")
+        return t.value.decode(), p.value.decode()
+
+    def _own_fe(self) -> "Fe":
+        if getattr(self, "_fe0", None) is None:
+            self._fe0 = Fe(self)
+        return self._fe0
+
+    def fe_batch_any_device(self, d_pcm, samp_off, samprate=None, d_cep=None, fe=None,
+                            stream=None, pcm_format=None):
+        """ssw_fe_batch_any on device buffers: int16 or float32 samples in HBM (torch tensor, or
+        a device pointer with pcm_format) -> (d_cep float32 [n_frames][fe.out_dim], frame_off).
+        fe None: the model's own settings; samprate as fe_batch_rates_device takes it."""
+        fe = fe if fe is not None else self._own_fe()
+        kind = _pcm_kind(d_pcm, pcm_format, "fe_batch_any_device")
+        off = np.ascontiguousarray(samp_off, np.int64)
+        n_utts = len(off) - 1
+        rates = (None if samprate is None else
+                 np.ascontiguousarray(np.broadcast_to(np.asarray(samprate, np.float64), (n_utts,))))
+        if d_cep is None:
+            import torch
+            n_frames = int(fe.frames(np.diff(off), rates).sum())
+            dev = d_pcm.device if hasattr(d_pcm, "device") else "cuda"
+            d_cep = torch.empty((n_frames, fe.out_dim), dtype=torch.float32, device=dev)
+        fo = np.zeros(len(off), np.int32)
+        _check(self._L.ssw_fe_batch_any(self._m, fe._h, _ptr(d_pcm), int(kind == "f32"), _ptr(off),
+                                        _ptr(rates), n_utts, _ptr(d_cep), _ptr(fo), _ptr(stream)),
+               "ssw_fe_batch_any")
+        return d_cep, fo
+
+    def fe_batch_any(self, pcm, samprate=None, fe=None, samp_off=None):
+        """The front end under any settings, host in and host out: PCM as fe_batch_rates takes it
+        (int16, or np.float32 where 1.0 is 32768) -> (rows float32 [n_frames][fe.out_dim],
+        frame_off).  fe None: the model's own settings (Model.fe())."""
+        fe = fe if fe is not None else self._own_fe()
+        kind = _pcm_kind(pcm, None, "fe_batch_any")
+        pcm, off_ = _pcm_concat(pcm, kind)
+        samp_off = samp_off if off_ is None else off_
+        off = (np.array([0, len(pcm)], np.int64) if samp_off is None
+               else np.ascontiguousarray(samp_off, np.int64))
+        if len(off) < 1 or off[-1] != len(pcm):
+            raise SswError("fe_batch_any: samp_off must end at len(pcm)")
+        n_utts = len(off) - 1
+        rates = (None if samprate is None else
+                 np.ascontiguousarray(np.broadcast_to(np.asarray(samprate, np.float64), (n_utts,))))
+        # (the entry without a device or frames checks everything, then writes frame_off)
+        fo = np.zeros(len(off), np.int32)
+        if self.device == SSW_DEVICE_NONE or off[-1] == 0:
+            _check(self._L.ssw_fe_batch_any(self._m, fe._h, None, int(kind == "f32"), _ptr(off),
+                                            _ptr(rates), n_utts, None, _ptr(fo), None),
+                   "ssw_fe_batch_any")
+        n_frames = int(fo[-1]) if fo[-1] or off[-1] == 0 else int(fe.frames(np.diff(off), rates).sum())
+        cep = np.zeros((n_frames, fe.out_dim), np.float32)
+        if n_frames == 0:
+            return cep, fo
+        d_pcm = self.to_device(pcm)
+        d_cep = self.device_malloc(cep.nbytes)
+        try:
+            _, fo = self.fe_batch_any_device(d_pcm, off, rates, d_cep, fe, pcm_format=kind)
+            _check(self._L.ssw_memcpy_d2h(_ptr(cep), d_cep, cep.nbytes), "ssw_memcpy_d2h")
+        finally:
+            self.device_free(d_pcm)
+            self.device_free(d_cep)
+        return cep, fo
+
     # ---- device memory (no torch needed) --------------------------------------------
     def to_device(self, arr: np.ndarray) -> int:
         arr = np.ascontiguousarray(arr)
@@ -973,6 +1059,43 @@ class Model:
 
     def device_free(self, p):
         self._L.ssw_device_free(p)
+
+
+class Fe:
+    """An ssw_fe_t: front-end settings resolved as fe_init resolves them, warp parameters
+    included (Model.fe).  Host state only."""
+
+    def __init__(self, model: Model, cfg=None, warp_type=None, warp_params=None):
+        self._L = model._L
+        self._model = model
+        c = None if cfg is None else (cfg if isinstance(cfg, SswFeConfig) else model.fe_config(**cfg))
+        self._h = self._L.ssw_fe_create(
+            model._m, None if c is None else C.byref(c),
+            None if warp_type is None else warp_type.encode(),
+            None if warp_params is None else warp_params.encode())
+        if not self._h:
+            raise SswError("ssw_fe_create: " + _lib.last_error())
+        self.out_dim = int(self._L.ssw_fe_out_dim(self._h))
+        self.samprate = float((c if c is not None else model.fe_config()).samprate)
+
+    def frames(self, n, rate=None) -> np.ndarray:
+        """ssw_fe_frames per utterance: n samples each at rate Hz (a number, one per utterance,
+        or None for the configuration's samprate)"""
+        n = np.asarray(n, np.int64)
+        sr = np.broadcast_to(np.asarray(self.samprate if rate is None else rate, np.float64),
+                             n.shape)
+        out = np.array([self._L.ssw_fe_frames(self._h, float(r), int(k))
+                        for k, r in zip(n.reshape(-1), sr.reshape(-1))], np.int64).reshape(n.shape)
+        if (out < 0).any():
+            raise SswError("ssw_fe_frames: " + _lib.last_error())
+        return out
+
+    def free(self):
+        if getattr(self, "_h", None):
+            self._L.ssw_fe_free(self._h)
+            self._h = None
+
+    __del__ = free
 
 
 class Feat:
@@ -1581,8 +1704,16 @@ class _AudioIn:
         self.samprate = samprate
         self.fe_cfg = fe_cfg
         n = np.diff(self.off)
-        self.n_frames = int(fe_frame_counts(n).sum() if samprate is None and self.kind == "i16"
-                            else model.fe_frame_counts_rates(n, samprate, fe_cfg).sum())
+        # ssw_fe_batch_any in exactly two cases: the caller's Fe, or no fe_cfg and settings of
+        # the model's own that the older entry points refuse
+        self.fe = fe_cfg if isinstance(fe_cfg, Fe) else (
+            model._own_fe() if fe_cfg is None and not model.fe_plain() else None)
+        self.ncep = FE_NCEP if self.fe is None else self.fe.out_dim
+        if self.fe is not None:
+            self.n_frames = int(self.fe.frames(n, samprate).sum())
+        else:
+            self.n_frames = int(fe_frame_counts(n).sum() if samprate is None and self.kind == "i16"
+                                else model.fe_frame_counts_rates(n, samprate, fe_cfg).sum())
         self.on_device = _is_device_tensor(pcm) or isinstance(pcm, (int, C.c_void_p))
         self.d_pcm = pcm if self.on_device else (
             model.to_device(np.ascontiguousarray(pcm, _PCM_DTYPE[self.kind]))
@@ -1590,6 +1721,9 @@ class _AudioIn:
 
     def cepstra(self, d_cep, stream):
         m = self.model
+        if self.fe is not None:
+            return m.fe_batch_any_device(self.d_pcm, self.off, self.samprate, d_cep, self.fe,
+                                         stream, pcm_format=self.kind)[1]
         if self.kind == "f32":
             return m.fe_batch_f32_device(self.d_pcm, self.off, self.samprate, d_cep, self.fe_cfg,
                                          stream)[1]
@@ -1618,16 +1752,19 @@ def align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, texts, cfg=None
     reference computes them at the rate the audio has.  float32 audio (np.float32 array,
     torch.float32 device tensor, or a device pointer with pcm_format="f32"; 1.0 is 32768) is
     what decoder_process_float32 takes (src/decoder.c:960-1000) and goes through
-    ssw_fe_batch_f32; arrays and tensors of any other float type raise."""
+    ssw_fe_batch_f32; arrays and tensors of any other float type raise.  The cepstra come
+    from ssw_fe_batch_any instead in two cases: fe_cfg is an Fe (Model.fe), or fe_cfg is None and
+    the model's own settings are ones only that entry takes (Model.fe_plain is False: remove_dc,
+    round_filters = no, warping, ...); their rows, fe.out_dim wide, go on to the feature stage."""
     width = model._audio_feat_width()
     audio = _AudioIn(model, pcm, samp_off, samprate, fe_cfg, pcm_format, "align_audio_batch")
     n_frames = audio.n_frames
-    d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
+    d_cep = model.device_malloc(n_frames * audio.ncep * 4) if n_frames else None
     d_feat = model.device_malloc(n_frames * width * 4) if n_frames else None
     try:
         fo = audio.cepstra(d_cep if d_cep else 0, stream)
         if n_frames:
-            model._audio_feats(d_cep, n_frames, fo, d_feat, stream)
+            model._audio_feats(d_cep, n_frames, fo, d_feat, stream, audio.ncep)
         fn = align_text_batch_active if active else align_text_batch
         return fn(model, lex, d_feat if d_feat else 0, fo, texts, cfg=cfg, scorer=scorer,
                   stream=stream)
@@ -1985,12 +2122,12 @@ def recognize_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan: Gramm
     width = model._audio_feat_width()
     audio = _AudioIn(model, pcm, samp_off, samprate, fe_cfg, pcm_format, "recognize_audio_batch")
     n_frames = audio.n_frames
-    d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
+    d_cep = model.device_malloc(n_frames * audio.ncep * 4) if n_frames else None
     d_feat = model.device_malloc(n_frames * width * 4) if n_frames else None
     try:
         fo = audio.cepstra(d_cep if d_cep else 0, stream)
         if n_frames:
-            model._audio_feats(d_cep, n_frames, fo, d_feat, stream)
+            model._audio_feats(d_cep, n_frames, fo, d_feat, stream, audio.ncep)
         if active:
             return recognize_batch_active(model, lex, d_feat if d_feat else 0, fo, plan,
                                           fsg_of_utt, scorer=scorer, stream=stream)[0]
@@ -2058,12 +2195,12 @@ def recognize_align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan:
     audio = _AudioIn(model, pcm, samp_off, samprate, fe_cfg, pcm_format,
                      "recognize_align_audio_batch")
     n_frames = audio.n_frames
-    d_cep = model.device_malloc(n_frames * FE_NCEP * 4) if n_frames else None
+    d_cep = model.device_malloc(n_frames * audio.ncep * 4) if n_frames else None
     d_feat = model.device_malloc(n_frames * width * 4) if n_frames else None
     try:
         fo = audio.cepstra(d_cep if d_cep else 0, stream)
         if n_frames:
-            model._audio_feats(d_cep, n_frames, fo, d_feat, stream)
+            model._audio_feats(d_cep, n_frames, fo, d_feat, stream, audio.ncep)
         fn = recognize_align_batch_active if active else recognize_align_batch
         return fn(model, lex, d_feat if d_feat else 0, fo, plan, fsg_of_utt, scorer=scorer,
                   two_pass_history=two_pass_history, stream=stream)[:2]

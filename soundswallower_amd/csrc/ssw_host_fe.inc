@@ -83,10 +83,12 @@ struct FeRate {
     ssw_fe_rate_t *dev = nullptr;
 };
 
+/* key: the bytes of the configuration (ssw_fe_config_t, or ssw_fe_s for ssw_fe_batch_any's own
+ * tables, which differ in length) */
 static std::string
-fe_rate_key(const ssw_fe_config_t *key, const ssw_fe_framing_t *fr)
+fe_rate_key(const std::string &key, const ssw_fe_framing_t *fr)
 {
-    return std::string((const char *)key, sizeof(*key)) + std::string((const char *)fr, sizeof(*fr));
+    return key + std::string((const char *)fr, sizeof(*fr));
 }
 
 /* the rate blocks the model does not hold yet, on the device; a model that has gathered more
@@ -127,13 +129,15 @@ fe_rates_upload(ssw_model_s *m, std::vector<FeRate> &rates)
     return 0;
 }
 
-/* ssw_fe_batch, ssw_fe_batch_ex and ssw_fe_batch_f32: every utterance at samprate[u] (NULL:
- * c->samprate; ex = 0: ssw_fe_batch's checks, which allow 16 kHz only); d_pcm holds float32
- * samples when f32, int16 otherwise */
+/* ssw_fe_batch, ssw_fe_batch_ex, ssw_fe_batch_f32 and ssw_fe_batch_any: every utterance at
+ * samprate[u] (NULL: c->samprate; ex = 0: ssw_fe_batch's checks, which allow 16 kHz only); d_pcm
+ * holds float32 samples when f32, int16 otherwise.  any: NULL, or the resolved configuration
+ * whose settings the kernels of ssw_k8_fe_any.inc compute (cfg is then its cfg, checked when it
+ * was resolved) */
 static int
 fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const int64_t *samp_off,
          const double *samprate, int32_t n_utts, float *d_cep, int32_t *frame_off_out,
-         void *stream, bool ex, bool f32, const char *who)
+         void *stream, bool ex, bool f32, const char *who, const ssw_fe_s *any = nullptr)
 {
     if (m == NULL) {
         ssw_set_error("bad arguments to %s", who);
@@ -152,13 +156,22 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const in
         return -1;
     }
     const ssw_fe_config_t *c = cfg != NULL ? cfg : &m->h->fe;
-    if ((ex ? ssw_fe_config_check_ex(c) : ssw_fe_config_check(c)) < 0)
+    if (any == nullptr && (ex ? ssw_fe_config_check_ex(c) : ssw_fe_config_check(c)) < 0)
         return -1;
     ssw_fe_config_t key;
-    bool ok;
-    std::unique_ptr<ssw_fe_tables_t> fresh = fe_tables_if_new(m, c, &key, &ok);
+    bool ok = true;
+    std::unique_ptr<ssw_fe_tables_t> fresh;
+    std::unique_ptr<ssw_fe_any_tables_t> fresh_any;
+    if (any == nullptr) {
+        fresh = fe_tables_if_new(m, c, &key, &ok);
+    } else if (m->d_fe_any_tab == NULL || memcmp(any, &m->fe_any_key, sizeof(*any)) != 0) {
+        fresh_any.reset(new ssw_fe_any_tables_t());
+        ssw_fe_any_tables_build(any, fresh_any.get());
+    }
     if (!ok)
         return -1;
+    const std::string key_bytes = any != nullptr ? std::string((const char *)any, sizeof(*any))
+                                                 : std::string((const char *)&key, sizeof(key));
     /* every utterance's framing, and the distinct (samprate, nfft) of the batch, before anything
      * is written */
     if (m->fe_rate_tab == nullptr)
@@ -187,12 +200,13 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const in
         if (r == rates.size()) {
             rates.emplace_back();
             rates[r].fr = fr;
-            rates[r].key = fe_rate_key(&key, &fr);
+            rates[r].key = fe_rate_key(key_bytes, &fr);
             auto hit = m->fe_rate_tab->find(rates[r].key);
             if (hit != m->fe_rate_tab->end()) {
                 rates[r].dev = hit->second;
             } else {
-                rates[r].host.reset(ssw_fe_rate_build(c, &fr, ex));
+                rates[r].host.reset(any != nullptr ? ssw_fe_any_rate_build(any, &fr)
+                                                   : ssw_fe_rate_build(c, &fr, ex));
                 if (rates[r].host == nullptr)
                     return -1;
             }
@@ -217,12 +231,24 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const in
     HIP_OK(hipSetDevice(m->device));
     if (fresh && fe_tables_upload(m, fresh.get(), &key) < 0)
         return -1;
+    if (fresh_any) {
+        if (m->d_fe_any_tab == NULL)
+            HIP_OK(hipMalloc((void **)&m->d_fe_any_tab, sizeof(ssw_fe_any_tables_t)));
+        HIP_OK(hipMemcpy(m->d_fe_any_tab, fresh_any.get(), sizeof(ssw_fe_any_tables_t),
+                         hipMemcpyHostToDevice));
+        m->fe_any_key = *any;
+    }
     if (fe_rates_upload(m, rates) < 0)
         return -1;
     /* the utterance records, the frame offsets, and per FFT size present the group's
      * utterances and frame prefix (one spectrum launch each) */
     std::vector<FeUtt> utt((size_t)n_utts);
     int grp_frames[SSW_FE_MAX_LOG2N + 1] = {0}, grp_n[SSW_FE_MAX_LOG2N + 1] = {0};
+    /* remove_dc: a launch sums its frames in any order only where that is exact at every rate
+     * it holds (ssw_fe_dc_sum_exact) */
+    int grp_dc[SSW_FE_MAX_LOG2N + 1];
+    for (int o = 0; o <= SSW_FE_MAX_LOG2N; ++o)
+        grp_dc[o] = any != nullptr && any->cfg.remove_dc ? SSW_FE_DC_ANY_ORDER : SSW_FE_DC_NONE;
     for (int32_t u = 0; u < n_utts; ++u) {
         const FeRate &r = rates[(size_t)rate_of[u]];
         utt[u].start = samp_off[u];
@@ -233,6 +259,9 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const in
         utt[u].size = r.fr.frame_size;
         utt[u].pad = 0;
         ++grp_n[r.fr.fft_order];
+        if (grp_dc[r.fr.fft_order] == SSW_FE_DC_ANY_ORDER
+            && !ssw_fe_dc_sum_exact((float)any->cfg.alpha, r.fr.frame_size, f32))
+            grp_dc[r.fr.fft_order] = SSW_FE_DC_IN_ORDER;
     }
     std::vector<int> grp_utt((size_t)n_utts), grp_off((size_t)n_utts + SSW_FE_MAX_LOG2N + 1);
     int grp_at[SSW_FE_MAX_LOG2N + 1], off_at[SSW_FE_MAX_LOG2N + 1];
@@ -252,7 +281,8 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const in
         for (int o = 0; o <= SSW_FE_MAX_LOG2N; ++o)
             grp_frames[o] = grp_n[o] ? grp_off[(size_t)off_at[o] + grp_n[o]] : 0;
     }
-    const int n_frames = (int)total, nfilt = m->fe_nfilt;
+    const int n_frames = (int)total, nfilt = any != nullptr ? any->cfg.nfilt : m->fe_nfilt;
+    const bool noise = any != nullptr ? any->cfg.remove_noise != 0 : m->fe_noise != 0;
     /* grow-only workspace: records, offsets, groups, then the mel spectra */
     const size_t utt_bytes = sizeof(FeUtt) * (size_t)n_utts;
     const size_t int_bytes = sizeof(int) * (grp_utt.size() + grp_off.size() + (size_t)n_utts + 1);
@@ -277,7 +307,8 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const in
     F.frame_off = (const int *)(m->fe_ws.p + utt_bytes);
     const int *d_grp_utt = F.frame_off + n_utts + 1;
     const int *d_grp_off = d_grp_utt + n_utts;
-    F.tab = m->d_fe_tab;
+    /* (fe_noise_kernel reads nfilt alone, which both table blocks begin with) */
+    F.tab = any != nullptr ? (const ssw_fe_tables_t *)m->d_fe_any_tab : m->d_fe_tab;
     F.mfspec = (double *)(m->fe_ws.p + off_bytes);
     F.cep = d_cep;
     F.grp_utt = F.grp_off = nullptr; /* (set per spectrum launch) */
@@ -301,7 +332,7 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const in
         G.grp_off = d_grp_off + off_at[o];
         G.n_grp = grp_n[o];
         G.n_grp_frames = grp_frames[o];
-        if (!f32) switch (o) {
+        if (any == nullptr && !f32) switch (o) {
 #define FE_SPEC_LAUNCH(L)                                                                      \
         case L:                                                                                 \
             hipLaunchKernelGGL((fe_spectrum_kernel<L, int16_t>),                                \
@@ -320,7 +351,7 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const in
         }
         /* (after the table above: the order of first launch places the template kernels in the
          * code object, DESIGN 6a) */
-        else switch (o) {
+        else if (any == nullptr) switch (o) {
 #define FE_SPEC_F32_LAUNCH(L)                                                                   \
         case L:                                                                                 \
             hipLaunchKernelGGL((fe_spectrum_kernel<L, float>),                                  \
@@ -337,19 +368,57 @@ fe_batch(ssw_model_t *m, const ssw_fe_config_t *cfg, const void *d_pcm, const in
         FE_SPEC_F32_LAUNCH(13)
 #undef FE_SPEC_F32_LAUNCH
         }
+        else {
+            FeAnyParams A;
+            A.P = G;
+            A.any = m->d_fe_any_tab;
+            A.dc = grp_dc[o];
+#define FE_SPEC_ANY_LAUNCH(L, S)                                                                \
+            case L:                                                                             \
+                hipLaunchKernelGGL((fe_spectrum_any_kernel<L, S>),                              \
+                                   dim3((G.n_grp_frames + fe_spec_waves(L) - 1) / fe_spec_waves(L)), \
+                                   dim3(64 * fe_spec_waves(L)), 0, st, A);                      \
+                break;
+#define FE_SPEC_ANY_SWITCH(S)                                                                   \
+            switch (o) {                                                                        \
+                FE_SPEC_ANY_LAUNCH(6, S)                                                        \
+                FE_SPEC_ANY_LAUNCH(7, S)                                                        \
+                FE_SPEC_ANY_LAUNCH(8, S)                                                        \
+                FE_SPEC_ANY_LAUNCH(9, S)                                                        \
+                FE_SPEC_ANY_LAUNCH(10, S)                                                       \
+                FE_SPEC_ANY_LAUNCH(11, S)                                                       \
+                FE_SPEC_ANY_LAUNCH(12, S)                                                       \
+                FE_SPEC_ANY_LAUNCH(13, S)                                                       \
+            }
+            if (!f32)
+                FE_SPEC_ANY_SWITCH(int16_t)
+            else
+                FE_SPEC_ANY_SWITCH(float)
+#undef FE_SPEC_ANY_SWITCH
+#undef FE_SPEC_ANY_LAUNCH
+        }
         e = hipGetLastError();
     }
     if (e == hipSuccess && timed)
         e = hipEventRecord(m->fe_ev[1], st);
-    if (e == hipSuccess && m->fe_noise) {
+    if (e == hipSuccess && noise) {
         hipLaunchKernelGGL(fe_noise_kernel, dim3(n_utts), dim3(64), 0, st, F);
         e = hipGetLastError();
     }
     if (e == hipSuccess && timed)
         e = hipEventRecord(m->fe_ev[2], st);
-    if (e == hipSuccess) {
+    if (e == hipSuccess && any == nullptr) {
         hipLaunchKernelGGL(fe_cep_kernel, dim3((n_frames + FE_CEP_FRAMES - 1) / FE_CEP_FRAMES),
                            dim3(FE_CEP_THREADS), 0, st, F);
+        e = hipGetLastError();
+    } else if (e == hipSuccess) {
+        FeAnyParams A;
+        A.P = F;
+        A.any = m->d_fe_any_tab;
+        A.dc = SSW_FE_DC_NONE;
+        hipLaunchKernelGGL(fe_cep_any_kernel,
+                           dim3((n_frames + FE_CEP_FRAMES - 1) / FE_CEP_FRAMES),
+                           dim3(FE_CEP_THREADS), 0, st, A);
         e = hipGetLastError();
     }
     if (e == hipSuccess && timed)

@@ -251,6 +251,9 @@ struct ssw_model_s {
     ssw_fe_config_t fe_tab_cfg;
     std::map<std::string, ssw_fe_rate_t *> *fe_rate_tab; /* (a pointer: the struct is memset) */
     int fe_nfilt, fe_noise;
+    /* the same for ssw_fe_batch_any's own kernels: the resolved configuration is the key */
+    ssw_fe_any_tables_t *d_fe_any_tab;
+    struct ssw_fe_s fe_any_key;
     DevBuf fe_ws;
     hipEvent_t fe_ev[4];
     int fe_ev_ready, fe_timed;
@@ -839,6 +842,7 @@ ssw_model_free(ssw_model_t *m)
     (void)hipFree(m->text_scr.p);
     (void)hipFree(m->feat_off.p);
     (void)hipFree(m->d_fe_tab);
+    (void)hipFree(m->d_fe_any_tab);
     if (m->fe_rate_tab)
         for (auto &kv : *m->fe_rate_tab)
             (void)hipFree(kv.second);

@@ -78,6 +78,15 @@ typedef struct ssw_fe_rate_s {
 /* feat_params.json over *c (which holds the defaults): 0 read, 1 no such file, -1 unusable
  * (message in err) */
 int ssw_fe_config_read(const char *path, ssw_fe_config_t *c, char *err, size_t err_len);
+/* the front end's string settings, which have no place in ssw_fe_config_t: "warp_type",
+ * "warp_params" ("" when null or empty: no warping) and "input_endian" */
+typedef struct ssw_fe_strings_s {
+    char warp_type[32], warp_params[256], input_endian[16];
+} ssw_fe_strings_t;
+void ssw_fe_strings_defaults(ssw_fe_strings_t *s);
+/* ssw_fe_config_read that keeps the strings too, over *s (which holds the defaults) */
+int ssw_fe_config_read_strings(const char *path, ssw_fe_config_t *c, ssw_fe_strings_t *s,
+                               char *err, size_t err_len);
 /* 0 when ssw_fe_batch supports the configuration, else -1 and ssw_set_error */
 int ssw_fe_config_check(const ssw_fe_config_t *c);
 /* the same for ssw_fe_batch_ex: every setting but the rate and the framing, which
@@ -92,6 +101,52 @@ int ssw_fe_tables_build(const ssw_fe_config_t *c, ssw_fe_tables_t *t);
 ssw_fe_rate_t *ssw_fe_rate_build(const ssw_fe_config_t *c, const ssw_fe_framing_t *f, int finite);
 int64_t ssw_fe_frames_of(int64_t n_samples);
 int64_t ssw_fe_frames_at(const ssw_fe_framing_t *f, int64_t n_samples);
+
+/* The front end in every configuration fe_init accepts (ssw_fe_create, ssw_fe_batch_any;
+ * ssw_model.c, ssw_k8_fe_any.inc, ssw_host_fe_any.inc). */
+#define SSW_FE_MAX_CEP 64
+enum ssw_fe_warp { SSW_FE_WARP_INVERSE_LINEAR = 0, SSW_FE_WARP_AFFINE = 1,
+                   SSW_FE_WARP_PIECEWISE_LINEAR = 2 }; /* FE_WARP_ID_*, fe_warp.c:68-73 */
+enum ssw_fe_logspec { SSW_FE_CEPSTRA = 0, SSW_FE_RAW_LOG_SPEC = 1, SSW_FE_SMOOTH_LOG_SPEC = 2 };
+/* how a frame's DC sum is formed: not at all, by a parallel reduction (the host proved that no
+ * partial sum in any order rounds, ssw_fe_dc_sum_exact), or in index order */
+enum ssw_fe_dc { SSW_FE_DC_NONE = 0, SSW_FE_DC_ANY_ORDER = 1, SSW_FE_DC_IN_ORDER = 2 };
+
+/* a resolved configuration (ssw_fe_t): the settings, the warping function with its parameters as
+ * the type's set_parameters parses them (the reference keeps them in statics), and what follows
+ * from the settings alone */
+struct ssw_fe_s {
+    ssw_fe_config_t cfg;
+    int32_t warp_id;     /* enum ssw_fe_warp */
+    int32_t warp_on;     /* 0: is_neutral (no parameters, or slope 0) */
+    float warp_p[2];     /* params[] */
+    int32_t plain;       /* ssw_fe_batch_ex takes the settings: the existing kernels run */
+    int32_t log_spec;    /* enum ssw_fe_logspec */
+    int32_t out_dim;     /* fe_get_output_size */
+    char warp_type[32], warp_params[256];
+};
+
+/* ssw_fe_tables_t for any ncep and every transform.  The first eight fields are ssw_fe_tables_t's:
+ * fe_noise_kernel reads nfilt through that type */
+typedef struct ssw_fe_any_tables_s {
+    int32_t nfilt, ncep, transform, remove_noise, lifter_val;
+    float alpha, sqrt_inv_n, sqrt_inv_2n;
+    int32_t log_spec, remove_dc, out_dim, pad;
+    float mel_cosine[SSW_FE_MAX_CEP * SSW_FE_MAX_FILT]; /* [ncep][nfilt] */
+    float lifter[SSW_FE_MAX_CEP];
+} ssw_fe_any_tables_t;
+
+/* cfg with the warp strings (NULL type: inverse_linear; NULL or "" params: none) -> *fe, or -1
+ * and ssw_set_error: everything ssw_fe_create refuses */
+int ssw_fe_resolve(const ssw_fe_config_t *cfg, const char *warp_type, const char *warp_params,
+                   struct ssw_fe_s *fe);
+void ssw_fe_any_tables_build(const struct ssw_fe_s *fe, ssw_fe_any_tables_t *t);
+/* ssw_fe_rate_build with fe's filter builder: doublebw, unit_area, round_filters and warping at
+ * this rate's Nyquist frequency */
+ssw_fe_rate_t *ssw_fe_any_rate_build(const struct ssw_fe_s *fe, const ssw_fe_framing_t *f);
+/* 1 when every order of summing a frame of frame_size pre-emphasised int16 samples gives the
+ * same double (f32 samples: never) */
+int ssw_fe_dc_sum_exact(float alpha, int32_t frame_size, int f32);
 
 /* Dynamic features (ssw_model.c, ssw_k12_feat.inc, ssw_host_featex.inc): a configuration as
  * feat_init_s3file resolves it (src/feat.c:732-927). */
@@ -137,6 +192,7 @@ typedef struct ssw_host_model_s {
     /* front end: feat_params.json beside the means file (ssw_model.c); fe_err holds why that file
      * could not be used ("" when it could, or when there is none) */
     ssw_fe_config_t fe;
+    ssw_fe_strings_t fe_str;
     char fe_err[256];
     /* Gaussians (gauden_t) */
     int32_t n_cb, n_feat, n_density, veclen_total, n_floored;

@@ -63,6 +63,9 @@
  *                        fe_noise_kernel (fe_remove_noise, one wave per utterance),
  *                        fe_cep_kernel (log, DCT-II or legacy transform, lifter),
  *                        src/fe_sigproc.c:219-738, src/fe_noise.c:111-327
+ *   ssw_k8_fe_any.inc    the same for every configuration fe_init accepts: fe_spectrum_any_kernel
+ *                        (alpha of any value, remove_dc with the reference's ordered sum),
+ *                        fe_cep_any_kernel (any ncep, htk, logspec, smoothspec)
  *   ssw_k9_grammar.inc   grammar_search_kernel: K5's search over the phone trees of any word FSG,
  *                        null transitions folded into the states' entering lists
  *                        (fsg_search_start / _null_prop / _find_exit, src/fsg_search.c:543-924)
@@ -176,6 +179,7 @@ namespace {
 #include "ssw_k7_fpactive.inc"
 #include "ssw_fe_log.inc"
 #include "ssw_k8_fe.inc"
+#include "ssw_k8_fe_any.inc"
 #include "ssw_k9_grammar.inc"
 #include "ssw_k10_semi.inc"
 #include "ssw_k11_cont.inc"
@@ -228,6 +232,7 @@ static int cont_align_active(ssw_model_t *m, const float *d_feats, int32_t n_utt
 #include "ssw_host_search.inc"
 #include "ssw_host_feat.inc"
 #include "ssw_host_fe.inc"
+#include "ssw_host_fe_any.inc"
 #include "ssw_host_firstpass.inc"
 #include "ssw_host_fpactive.inc"
 #include "ssw_host_grammar.inc"

@@ -163,10 +163,18 @@ parse_int(const char *v, int32_t *out)
     return 0;
 }
 
+/* what feat_params.json says about the front end: the settings, and the strings that have no
+ * place in ssw_fe_config_t (NULL: not wanted) */
+typedef struct {
+    ssw_fe_config_t *c;
+    ssw_fe_strings_t *s;
+} fe_keys_t;
+
 /* one key of the front end's; unknown keys are ignored (they belong to other modules) */
 static int
-fe_set_key(ssw_fe_config_t *c, const char *key, const char *v, int is_string)
+fe_set_key(fe_keys_t *k, const char *key, const char *v, int is_string)
 {
+    ssw_fe_config_t *c = k->c;
     double d;
     if (key[0] == '-') /* command-line spelling */
         ++key;
@@ -213,6 +221,16 @@ fe_set_key(ssw_fe_config_t *c, const char *key, const char *v, int is_string)
     }
     if (!strcmp(key, "warp_params")) { /* null or "" = no warping (the default) */
         c->warp = is_string ? v[0] != '\0' : strcmp(v, "null") != 0;
+        if (k->s != NULL)
+            snprintf(k->s->warp_params, sizeof(k->s->warp_params), "%s", c->warp ? v : "");
+        return 0;
+    }
+    if (k->s != NULL && !strcmp(key, "warp_type")) {
+        snprintf(k->s->warp_type, sizeof(k->s->warp_type), "%s", v);
+        return 0;
+    }
+    if (k->s != NULL && !strcmp(key, "input_endian")) {
+        snprintf(k->s->input_endian, sizeof(k->s->input_endian), "%s", v);
         return 0;
     }
     return 0;
@@ -286,16 +304,35 @@ done:
 static int
 fe_set_key_cb(void *ctx, const char *key, const char *v, int is_string)
 {
-    return fe_set_key((ssw_fe_config_t *)ctx, key, v, is_string);
+    return fe_set_key((fe_keys_t *)ctx, key, v, is_string);
+}
+
+void
+ssw_fe_strings_defaults(ssw_fe_strings_t *s)
+{
+    memset(s, 0, sizeof(*s));
+    strcpy(s->warp_type, "inverse_linear"); /* config_defs.h:294, :385-393 */
+    strcpy(s->input_endian, "little");      /* config_defs.h: "input_endian" */
+}
+
+int
+ssw_fe_config_read_strings(const char *path, ssw_fe_config_t *c, ssw_fe_strings_t *s, char *err,
+                           size_t err_len)
+{
+    fe_keys_t k;
+    int rv;
+    k.c = c;
+    k.s = s;
+    rv = json_object_read(path, fe_set_key_cb, &k, err, err_len);
+    if (rv == 0)
+        c->from_file = 1;
+    return rv;
 }
 
 int
 ssw_fe_config_read(const char *path, ssw_fe_config_t *c, char *err, size_t err_len)
 {
-    const int rv = json_object_read(path, fe_set_key_cb, c, err, err_len);
-    if (rv == 0)
-        c->from_file = 1;
-    return rv;
+    return ssw_fe_config_read_strings(path, c, NULL, err, err_len);
 }
 
 /* ---------------------------------------------------------------------------------- */
@@ -457,35 +494,132 @@ ssw_fe_framing(const ssw_fe_config_t *c, double samprate, ssw_fe_framing_t *f)
     return 0;
 }
 
-static float
-fe_mel(float x) /* fe_mel, src/fe_sigproc.c:70-76 (no warping) */
+/* One warping function at one rate: what fe_warp_set and the type's set_parameters leave in the
+ * reference's statics (src/fe_warp.c:99-144, src/fe_warp_inverse_linear.c:95-133,
+ * src/fe_warp_affine.c:96-134, src/fe_warp_piecewise_linear.c:105-159).  NULL = neutral. */
+typedef struct {
+    int id;
+    float p[2], final_piece[2], nyquist;
+} fe_warp_t;
+
+/* NULL when fe is neutral, else w filled in for samprate */
+static const fe_warp_t *
+fe_warp_at(const struct ssw_fe_s *fe, float samprate, fe_warp_t *w)
 {
-    return (float)(2595.0 * log10(1.0 + x / 700.0));
+    if (fe == NULL || !fe->warp_on)
+        return NULL;
+    memset(w, 0, sizeof(*w));
+    w->id = fe->warp_id;
+    w->p[0] = fe->warp_p[0];
+    w->p[1] = fe->warp_p[1];
+    w->nyquist = samprate / 2;
+    if (w->id == SSW_FE_WARP_PIECEWISE_LINEAR && w->p[1] < samprate) {
+        /* the line through (F, aF) and (N, N); F = 0 means 0.85 samprate */
+        if (w->p[1] == 0)
+            w->p[1] = samprate * 0.85f;
+        w->final_piece[0] = (w->nyquist - w->p[0] * w->p[1]) / (w->nyquist - w->p[1]);
+        w->final_piece[1] = w->nyquist * w->p[1] * (w->p[0] - 1.0f) / (w->nyquist - w->p[1]);
+    }
+    return w;
+}
+
+/* fe_warp_unwarped_to_warped */
+static float
+fe_warp_fwd(const fe_warp_t *w, float linear)
+{
+    float temp;
+    if (w == NULL)
+        return linear;
+    switch (w->id) {
+    case SSW_FE_WARP_INVERSE_LINEAR:
+        return linear / w->p[0];
+    case SSW_FE_WARP_AFFINE:
+        temp = linear * w->p[0];
+        temp += w->p[1];
+        return temp;
+    default:
+        if (linear < w->p[1])
+            return linear * w->p[0];
+        return w->final_piece[0] * linear + w->final_piece[1];
+    }
+}
+
+/* fe_warp_warped_to_unwarped (a result above Nyquist only makes the reference warn) */
+static float
+fe_warp_inv(const fe_warp_t *w, float nonlinear)
+{
+    float temp;
+    if (w == NULL)
+        return nonlinear;
+    switch (w->id) {
+    case SSW_FE_WARP_INVERSE_LINEAR:
+        return nonlinear * w->p[0];
+    case SSW_FE_WARP_AFFINE:
+        temp = nonlinear - w->p[1];
+        temp /= w->p[0];
+        return temp;
+    default:
+        if (nonlinear < w->p[0] * w->p[1]) {
+            temp = nonlinear / w->p[0];
+        } else {
+            temp = nonlinear - w->final_piece[1];
+            temp /= w->final_piece[0];
+        }
+        return temp;
+    }
 }
 
 static float
-fe_melinv(float x) /* fe_melinv, src/fe_sigproc.c:78-83 */
+fe_mel(const fe_warp_t *w, float x) /* fe_mel, src/fe_sigproc.c:70-76 */
 {
-    return (float)(700.0 * (pow(10.0, x / 2595.0) - 1.0));
+    float warped = fe_warp_fwd(w, x);
+    return (float)(2595.0 * log10(1.0 + warped / 700.0));
 }
 
-/* the three edge frequencies of filter i, src/fe_sigproc.c:111-121 */
+static float
+fe_melinv(const fe_warp_t *w, float x) /* fe_melinv, src/fe_sigproc.c:78-83 */
+{
+    float warped = (float)(700.0 * (pow(10.0, x / 2595.0) - 1.0));
+    return fe_warp_inv(w, warped);
+}
+
+/* the three edge frequencies of filter i, src/fe_sigproc.c:120-132 */
 static void
-filter_edges(int i, float melbw, float melmin, float fftfreq, int round_filters, float fr[3])
+filter_edges(const fe_warp_t *w, int i, float melbw, float melmin, float fftfreq, int doublewide,
+             int round_filters, float fr[3])
 {
     int j;
     for (j = 0; j < 3; ++j) {
-        fr[j] = fe_melinv((i + j) * melbw + melmin);
+        if (doublewide)
+            fr[j] = fe_melinv(w, (i + j * 2) * melbw + melmin);
+        else
+            fr[j] = fe_melinv(w, (i + j) * melbw + melmin);
         if (round_filters)
             fr[j] = ((int)(fr[j] / fftfreq + 0.5)) * fftfreq;
     }
+}
+
+/* fe_compute_melcosine, src/fe_sigproc.c:201-236: cosines [ncep][nfilt], the DCT's normalisers,
+ * and the lifter (integer lifter_val / 2, as there; 1 when it is off) */
+static void
+fe_melcosine(int nfilt, int ncep, int lifter_val, float *mel_cosine, float *lifter,
+             float *sqrt_inv_n, float *sqrt_inv_2n)
+{
+    double freqstep = M_PI / nfilt;
+    int i, j;
+    for (i = 0; i < ncep; ++i)
+        for (j = 0; j < nfilt; ++j)
+            mel_cosine[i * nfilt + j] = (float)cos(freqstep * i * (j + 0.5));
+    *sqrt_inv_n = (float)sqrt(1.0 / nfilt);
+    *sqrt_inv_2n = (float)sqrt(2.0 / nfilt);
+    for (i = 0; i < ncep; ++i)
+        lifter[i] = lifter_val ? (float)(1 + lifter_val / 2 * sin(i * M_PI / lifter_val)) : 1.0f;
 }
 
 /* the settings are checked (ssw_fe_config_check or _ex) before */
 int
 ssw_fe_tables_build(const ssw_fe_config_t *c, ssw_fe_tables_t *t)
 {
-    int i, j;
     memset(t, 0, sizeof(*t));
     t->nfilt = c->nfilt;
     t->ncep = c->ncep;
@@ -493,35 +627,59 @@ ssw_fe_tables_build(const ssw_fe_config_t *c, ssw_fe_tables_t *t)
     t->remove_noise = c->remove_noise;
     t->lifter_val = c->lifter;
     t->alpha = (float)c->alpha;
-    /* fe_compute_melcosine, src/fe_sigproc.c:184-217 */
-    {
-        double freqstep = M_PI / t->nfilt;
-        for (i = 0; i < t->ncep; ++i)
-            for (j = 0; j < t->nfilt; ++j)
-                t->mel_cosine[i * t->nfilt + j] = (float)cos(freqstep * i * (j + 0.5));
-        t->sqrt_inv_n = (float)sqrt(1.0 / t->nfilt);
-        t->sqrt_inv_2n = (float)sqrt(2.0 / t->nfilt);
-    }
-    /* the lifter, src/fe_sigproc.c:228-232 (integer lifter_val / 2, as there) */
-    for (i = 0; i < t->ncep; ++i)
-        t->lifter[i] = t->lifter_val
-            ? (float)(1 + t->lifter_val / 2 * sin(i * M_PI / t->lifter_val)) : 1.0f;
+    fe_melcosine(t->nfilt, t->ncep, t->lifter_val, t->mel_cosine, t->lifter, &t->sqrt_inv_n,
+                 &t->sqrt_inv_2n);
     return 0;
 }
 
-ssw_fe_rate_t *
-ssw_fe_rate_build(const ssw_fe_config_t *c, const ssw_fe_framing_t *f, int finite)
+/* ssw_fe_tables_build for a resolved configuration: any ncep, and what the cepstrum kernel of
+ * ssw_k8_fe_any.inc needs to know besides */
+void
+ssw_fe_any_tables_build(const struct ssw_fe_s *fe, ssw_fe_any_tables_t *t)
+{
+    const ssw_fe_config_t *c = &fe->cfg;
+    memset(t, 0, sizeof(*t));
+    t->nfilt = c->nfilt;
+    t->ncep = c->ncep;
+    t->transform = c->transform;
+    t->remove_noise = c->remove_noise;
+    t->lifter_val = c->lifter;
+    t->alpha = (float)c->alpha;
+    t->log_spec = fe->log_spec;
+    t->remove_dc = c->remove_dc;
+    t->out_dim = fe->out_dim;
+    fe_melcosine(t->nfilt, t->ncep, t->lifter_val, t->mel_cosine, t->lifter, &t->sqrt_inv_n,
+                 &t->sqrt_inv_2n);
+}
+
+/* fe: NULL for ssw_fe_batch(_ex, _f32)'s family of settings (no warping, single bandwidth) */
+static ssw_fe_rate_t *
+fe_rate_build(const ssw_fe_config_t *c, const ssw_fe_framing_t *f, int finite,
+              const struct ssw_fe_s *fe)
 {
     const float samprate = (float)f->samprate;
     const float lowerf = (float)c->lowerf, upperf = (float)c->upperf;
+    const int doublewide = fe != NULL && c->doublebw;
+    fe_warp_t warp;
+    const fe_warp_t *w = fe_warp_at(fe, samprate, &warp);
     ssw_fe_rate_t h, *t;
     double *ham, *ccc, *sss;
     float *coeffs;
     int i, j, n_coeffs = 0;
-    float melmin = fe_mel(lowerf), melmax = fe_mel(upperf);
+    float melmin = fe_mel(w, lowerf), melmax = fe_mel(w, upperf);
     float melbw = (melmax - melmin) / (c->nfilt + 1);
     float fftfreq = samprate / (float)f->fft_size;
 
+    if (doublewide) { /* src/fe_sigproc.c:103-113 */
+        melmin -= melbw;
+        melmax += melbw;
+        if (fe_melinv(w, melmin) < 0 || fe_melinv(w, melmax) > samprate / 2) {
+            ssw_set_error("front end: doublebw: the outer filter edges %g and %g Hz are outside "
+                          "0 .. %g (samprate %d / 2)", (double)fe_melinv(w, melmin),
+                          (double)fe_melinv(w, melmax), (double)(samprate / 2), f->samprate);
+            return NULL;
+        }
+    }
     memset(&h, 0, sizeof(h));
     h.samprate = f->samprate;
     h.frame_shift = f->frame_shift;
@@ -532,7 +690,7 @@ ssw_fe_rate_build(const ssw_fe_config_t *c, const ssw_fe_framing_t *f, int finit
     /* fe_build_melfilters, src/fe_sigproc.c:85-182: the widths first */
     for (i = 0; i < c->nfilt; ++i) {
         float fr[3];
-        filter_edges(i, melbw, melmin, fftfreq, c->round_filters, fr);
+        filter_edges(w, i, melbw, melmin, fftfreq, doublewide, c->round_filters, fr);
         h.spec_start[i] = -1;
         h.filt_width[i] = 0;
         for (j = 0; j < f->fft_size / 2 + 1; ++j) {
@@ -582,7 +740,7 @@ ssw_fe_rate_build(const ssw_fe_config_t *c, const ssw_fe_framing_t *f, int finit
     n_coeffs = 0;
     for (i = 0; i < c->nfilt; ++i) {
         float fr[3];
-        filter_edges(i, melbw, melmin, fftfreq, c->round_filters, fr);
+        filter_edges(w, i, melbw, melmin, fftfreq, doublewide, c->round_filters, fr);
         for (j = 0; j < h.filt_width[i]; ++j) {
             float hz = (h.spec_start[i] + j) * fftfreq;
             float loslope = (hz - fr[0]) / (fr[1] - fr[0]);
@@ -604,6 +762,123 @@ ssw_fe_rate_build(const ssw_fe_config_t *c, const ssw_fe_framing_t *f, int finit
             }
     }
     return t;
+}
+
+ssw_fe_rate_t *
+ssw_fe_rate_build(const ssw_fe_config_t *c, const ssw_fe_framing_t *f, int finite)
+{
+    return fe_rate_build(c, f, finite, NULL);
+}
+
+ssw_fe_rate_t *
+ssw_fe_any_rate_build(const struct ssw_fe_s *fe, const ssw_fe_framing_t *f)
+{
+    return fe_rate_build(&fe->cfg, f, 1, fe);
+}
+
+/* fe_parse_general_params, fe_parse_melfb_params and fe_warp_set (src/fe_interface.c:84-210,
+ * src/fe_warp.c:99-131) for everything that does not depend on the rate */
+int
+ssw_fe_resolve(const ssw_fe_config_t *cfg, const char *warp_type, const char *warp_params,
+               struct ssw_fe_s *fe)
+{
+    static const char *const names[] = {"inverse_linear", "affine", "piecewise_linear"};
+    static const char *const aliases[] = {"inverse", "linear", "piecewise"};
+    const ssw_fe_config_t *c = &fe->cfg;
+    const char *p;
+    int i, n_param, given = warp_params != NULL && warp_params[0] != '\0';
+
+    memset(fe, 0, sizeof(*fe));
+    fe->cfg = *cfg;
+    if (warp_type == NULL)
+        warp_type = names[0];
+    if (c->transform != SSW_FE_LEGACY && c->transform != SSW_FE_DCT && c->transform != SSW_FE_HTK) {
+        ssw_set_error("front end: unknown transform %d", c->transform);
+        return -1;
+    }
+    if (c->dither) {
+        ssw_set_error("front end: dither is not supported: its random stream belongs to a "
+                      "process's lifetime");
+        return -1;
+    }
+    if (c->ncep < 1 || c->ncep > SSW_FE_MAX_CEP || c->nfilt < 1 || c->nfilt > SSW_FE_MAX_FILT) {
+        ssw_set_error("front end: ncep must be 1..%d and nfilt 1..%d (got %d, %d)", SSW_FE_MAX_CEP,
+                      SSW_FE_MAX_FILT, c->ncep, c->nfilt);
+        return -1;
+    }
+    if (c->lifter < 0) {
+        ssw_set_error("front end: lifter must be >= 0 (got %d)", c->lifter);
+        return -1;
+    }
+    if (!isfinite((float)c->alpha)) {
+        ssw_set_error("front end: alpha %g is not a finite float32", c->alpha);
+        return -1;
+    }
+    if (!(c->lowerf >= 0) || !(c->lowerf < c->upperf)) {
+        ssw_set_error("front end: need 0 <= lowerf < upperf (got %g, %g)", c->lowerf, c->upperf);
+        return -1;
+    }
+    for (i = 0; i < 3 && strcmp(warp_type, names[i]) != 0 && strcmp(warp_type, aliases[i]) != 0; ++i)
+        ;
+    if (i == 3) {
+        ssw_set_error("front end: Unimplemented warping function %s", warp_type);
+        return -1;
+    }
+    fe->warp_id = i;
+    if (c->warp && !given) {
+        ssw_set_error("front end: warp is set but no warp_params are given");
+        return -1;
+    }
+    if (given && strlen(warp_params) >= sizeof(fe->warp_params)) {
+        ssw_set_error("front end: warp_params is longer than %d characters",
+                      (int)sizeof(fe->warp_params) - 1);
+        return -1;
+    }
+    snprintf(fe->warp_type, sizeof(fe->warp_type), "%s", names[i]);
+    snprintf(fe->warp_params, sizeof(fe->warp_params), "%s", given ? warp_params : "");
+    fe->cfg.warp = given;
+    /* set_parameters: atof of up to N_PARAM blank-separated tokens, the rest ignored; slope 0 is
+     * neutral */
+    n_param = fe->warp_id == SSW_FE_WARP_INVERSE_LINEAR ? 1 : 2;
+    for (p = fe->warp_params, i = 0; given && i < n_param; ++i) {
+        p += strspn(p, " \t");
+        if (*p == '\0')
+            break;
+        fe->warp_p[i] = (float)atof(p);
+        p += strcspn(p, " \t");
+    }
+    fe->warp_on = given && fe->warp_p[0] != 0;
+    fe->log_spec = c->smoothspec ? SSW_FE_SMOOTH_LOG_SPEC : c->logspec ? SSW_FE_RAW_LOG_SPEC
+                                                                       : SSW_FE_CEPSTRA;
+    fe->out_dim = fe->log_spec ? c->nfilt : c->ncep; /* fe_get_output_size */
+    fe->plain = !given && ssw_fe_config_check_ex(c) == 0;
+    return 0;
+}
+
+/* Frame sample i after pre-emphasis is x[i] - x[i - 1] alpha with |x| <= 2^15 whole numbers and
+ * alpha = k 2^q (k odd): a multiple of 2^g, g = min(q, 0), of size at most 2^15 (1 + |alpha|).
+ * Every sum of some of a frame's n samples is then a multiple of 2^g of size at most
+ * B = n 2^15 (1 + |alpha|); where B < 2^(53 + g) a double holds each of them exactly, so no
+ * addition in any order rounds and every order gives the reference's sum.  float32 samples have
+ * no such grid. */
+int
+ssw_fe_dc_sum_exact(float alpha, int32_t frame_size, int f32)
+{
+    int e, g = 0;
+    double m;
+    if (f32 || !isfinite(alpha))
+        return 0;
+    if (alpha != 0) {
+        m = frexp(fabs((double)alpha), &e); /* |alpha| = m 2^e, m in [0.5, 1) */
+        while (m != floor(m)) {              /* -> k 2^q */
+            m *= 2;
+            --e;
+        }
+        g = e < 0 ? e : 0;
+    }
+    if (53 + g < 0)
+        return 0;
+    return (double)frame_size * 32768.0 * (1.0 + fabs((double)alpha)) < ldexp(1.0, 53 + g);
 }
 
 int64_t
@@ -3006,8 +3281,10 @@ ssw_host_model_load(const char *mdef, const char *means, const char *variances,
         }
         memcpy(path, means, dir);
         strcpy(path + dir, "feat_params.json");
-        if (ssw_fe_config_read(path, &h->fe, h->fe_err, sizeof(h->fe_err)) < 0) {
+        ssw_fe_strings_defaults(&h->fe_str);
+        if (ssw_fe_config_read_strings(path, &h->fe, &h->fe_str, h->fe_err, sizeof(h->fe_err)) < 0) {
             ssw_fe_config_defaults(&h->fe);
+            ssw_fe_strings_defaults(&h->fe_str);
             h->fe.from_file = 0;
         }
         /* the feature stage's keys of the same file; `lda` unset = the directory's
