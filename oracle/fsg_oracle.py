@@ -325,7 +325,7 @@ def first_pass(model, lex, words, senscr, cfg=Config, trace=None, n_frames=None)
     or None when the final state is not reached in the last frame that has word exits.  senscr:
     int16 [T][n_sen], or a function (frame, senone ids [n_active][3]) -> int16 [n_sen] row with
     n_frames given (scoring interleaved with the search, as with compallsen=no)."""
-    lmath = O.Logmath(1.0001, 0)
+    lmath = O.Logmath(model.logbase, 0)  # the decoder's logmath: the model's base, no shift
     lw = np.float32(cfg.lw)
     beam = int(lmath.log(cfg.beam)) >> SENSCR_SHIFT
     pbeam = int(lmath.log(cfg.pbeam)) >> SENSCR_SHIFT

@@ -219,6 +219,7 @@ class Model:
     phone_tmat = property(lambda s: _view(s._l.orc_model_phone_tmat(s._m), (s.n_phone,), np.int32))
     logadd_table = property(lambda s: _table_of(s._l.orc_model_lmath(s._m)))
     logadd_table_8b = property(lambda s: _table_of(s._l.orc_model_lmath_8b(s._m)))
+    logbase = property(lambda s: float(s._l.orc_model_lmath(s._m).contents.base))
 
     def mean4(self):
         """means as [cb][feat][density][veclen] (equal stream lengths only)."""

@@ -69,6 +69,14 @@ check_scorer_shape(const ssw_model_s *m, int scorer)
         ssw_set_error("unknown scorer %d", scorer);
         return -1;
     }
+    /* the reference's add table has more than 256 entries below a base of about 1.000018, and
+     * its fast_logmath_add reads them all (tied_mgau_common.h:100-117); the kernels hold 256 and
+     * take 0 beyond */
+    if (h->logadd8_size != 256) {
+        ssw_set_error("PTM scorer: unsupported log-add table (%d entries, the kernels hold 256)",
+                      h->logadd8_size);
+        return -1;
+    }
     if (h->n_density != 128 || h->cfg.topn != 4 || h->n_cb > 255) {
         ssw_set_error("PTM kernels are built for 128 densities, top-4, <= 255 codebooks "
                       "(model: %d densities, topn %d, %d codebooks)",

@@ -23,6 +23,11 @@ semi_check_shape(const ssw_model_s *m, int scorer)
         ssw_set_error("s2_semi scorer: the model has no 8-bit mixture weights (sendump / mixw)");
         return -1;
     }
+    if (h->logadd8_size != 256) { /* (as for PTM: the reference reads its whole table) */
+        ssw_set_error("s2_semi scorer: unsupported log-add table (%d entries, the kernels hold 256)",
+                      h->logadd8_size);
+        return -1;
+    }
     if (h->cfg.topn < 1 || h->cfg.topn > SSW_SC_MAX_TOPN) {
         ssw_set_error("s2_semi scorer: topn %d, 1 to %d are supported", h->cfg.topn, SSW_SC_MAX_TOPN);
         return -1;
