@@ -1411,6 +1411,105 @@ void *ssw_stream_create(void);
 void ssw_stream_destroy(void *stream);
 int ssw_stream_synchronize(void *stream);
 
+/* ------------------------------------------------------------------------------------ */
+/* Voice activity detection and endpointing for batches of audio streams (vad.h,          */
+/* endpointer.h: src/ps_vad.c, src/ps_endpointer.c over src/common_audio/vad/ and          */
+/* src/common_audio/signal_processing/).  All of it is integer arithmetic, so the           */
+/* decisions EQUAL the reference's.  No model is involved: the object owns its workspace.  */
+/* ------------------------------------------------------------------------------------ */
+typedef struct ssw_vad_s ssw_vad_t;
+/* vad_init + vad_set_input_params (src/ps_vad.c:49-128).  mode 0..3 (vad_mode_t; another is
+ * refused: "Invalid VAD mode %d").  sample_rate 0 = 16000, frame_length 0 = 0.03 s.  The
+ * detector works at the rate r of 8000, 16000, 32000, 48000 with the smallest |1 - r /
+ * sample_rate| below 0.5 ("No suitable sampling rate found for %d" when there is none), on
+ * frames of (size_t)(r * frame_length) samples OF THE CALLER'S AUDIO, which must be 10, 20 or
+ * 30 ms at r ("Unsupported frame length %f", WebRtcVad_ValidRateAndFrameLength,
+ * src/common_audio/vad/webrtc_vad.c:92-115).  NULL on refusal (ssw_last_error). */
+ssw_vad_t *ssw_vad_create(int32_t mode, int32_t sample_rate, double frame_length);
+void ssw_vad_free(ssw_vad_t *v);
+int32_t ssw_vad_frame_size(const ssw_vad_t *v);    /* vad_frame_size, samples; -1 on NULL */
+double ssw_vad_frame_length(const ssw_vad_t *v);   /* vad_frame_length: frame_size / sample_rate */
+int32_t ssw_vad_sample_rate(const ssw_vad_t *v);   /* vad_sample_rate: the caller's rate */
+int32_t ssw_vad_closest_rate(const ssw_vad_t *v);  /* the rate the detector works at */
+/* whole frames in n_samples samples: n_samples / frame_size; -1 on error */
+int64_t ssw_vad_frame_count(const ssw_vad_t *v, int64_t n_samples);
+
+/* What VadInstT (src/common_audio/vad/vad_core.h:25-51) carries from frame to frame, mode
+ * thresholds apart (they belong to the ssw_vad_t).  Plain data: copy it, keep it, hand it back. */
+typedef struct ssw_vad_state_s {
+    int32_t downsampling_filter_states[4]; /* WebRtcVad_Downsampling: [0..1] 16 -> 8, [2..3] 32 -> 16 */
+    int32_t s_48_24[8], s_24_24[16], s_24_16[8], s_16_8[8]; /* WebRtcSpl_State48khzTo8khz */
+    int32_t frame_counter;
+    int16_t noise_means[12], speech_means[12], noise_stds[12], speech_stds[12];
+    int16_t over_hang, num_of_speech;
+    int16_t index_vector[96], low_value_vector[96]; /* the minimum tracker's ages and values */
+    int16_t mean_value[6];                          /* its smoothed medians */
+    int16_t upper_state[5], lower_state[5], hp_filter_state[4];
+    int16_t initialised; /* 42 (kInitCheck) once set up; anything else: the batch call starts afresh */
+    int16_t reserved;
+} ssw_vad_state_t;
+/* the state after WebRtcVad_InitCore (src/common_audio/vad/vad_core.c:491-545) */
+void ssw_vad_state_init(ssw_vad_state_t *s);
+
+/* vad_classify (src/ps_vad.c:154-160) over every whole frame of every stream: d_pcm int16 in
+ * HBM, stream u = samples samp_off[u] .. samp_off[u + 1] (host int64 [n_streams + 1]); frames
+ * are ssw_vad_frame_size samples, the samples left after the last whole frame are not read.
+ * d_is_speech int8 [total frames] in HBM holds vad_classify's return value per frame: 1 speech,
+ * 0 not.  (GmmProbability's own value, 2 + over_hang during the hang-over, never leaves
+ * WebRtcVad_Process: src/common_audio/vad/webrtc_vad.c:86-88 makes it 1.)  frame_off_out host
+ * int32 [n_streams + 1].  state NULL: every stream starts afresh; else host [n_streams], read
+ * where .initialised is 42 (else started afresh) and written with the state after the stream's
+ * last frame, so a stream may arrive in pieces of whole frames.  Kept as the reference has it:
+ * at 48 kHz WebRtcVad_CalcVad48khz (vad_core.c:607-630) resamples the frame's FIRST 10 ms once
+ * per 10 ms of frame and never reads the rest; the model update's multiply wraps
+ * (vad_core.c:117-120); a frame of digital silence takes LogOfEnergy's energy == 0 branch and
+ * one whose total energy stays at or below kMinEnergy skips the Gaussians and the update.
+ * Synchronous on `stream`; 0, or -1 (ssw_last_error). */
+int ssw_vad_batch(ssw_vad_t *v, const int16_t *d_pcm, const int64_t *samp_off, int32_t n_streams,
+                  int8_t *d_is_speech, int32_t *frame_off_out, ssw_vad_state_t *state,
+                  void *stream);
+/* How many of a workgroup's 64 lanes ssw_vad_batch gives streams: 8, 16, 32 or 64, or 0 (the
+ * default) for the rule that spreads a batch over the device's compute units first -- 8 until
+ * 8 per unit no longer covers the batch, then 16, 32, 64.  The results do not depend on it.
+ * 0, or -1 on another value. */
+int ssw_vad_set_streams_per_workgroup(ssw_vad_t *v, int32_t streams);
+/* the same over host pointers with no device call, from the same arithmetic source */
+int ssw_vad_batch_host(const ssw_vad_t *v, const int16_t *pcm, const int64_t *samp_off,
+                       int32_t n_streams, int8_t *is_speech, int32_t *frame_off_out,
+                       ssw_vad_state_t *state, int16_t *features);
+/* parity view: the last ssw_vad_batch call's int16 [total frames][7] -- the six band
+ * log-energies WebRtcVad_CalculateFeatures made and its total_energy -- copied to the host
+ * buffer `out` of n_frames rows.  (ssw_vad_batch_host writes the same rows to `features` when
+ * that is not NULL.)  0, or -1 when there was no call or n_frames is not its frame count. */
+int ssw_vad_debug_features(ssw_vad_t *v, int16_t *out, int64_t n_frames);
+
+/* one utterance the endpointer cut out of a stream */
+typedef struct ssw_endpoint_seg_s {
+    int64_t first_sample; /* in the stream: the first frame endpointer_process handed back */
+    int64_t n_samples;    /* frames handed back x frame size + endpointer_end_stream's out_nsamp */
+    double speech_start;  /* endpointer_speech_start, seconds */
+    double speech_end;    /* endpointer_speech_end */
+} ssw_endpoint_seg_t;
+typedef struct ssw_endpoints_s ssw_endpoints_t;
+/* Host only.  endpointer_init's window arithmetic (src/ps_endpointer.c:53-94; window 0 = 0.3,
+ * ratio 0 = 0.9; "Ratio %.2f makes start-pointing stupid or impossible (%d frames of %d)" and
+ * the end-pointing twin refuse) and endpointer_process over is_speech[0 .. n_frames) followed
+ * by one endpointer_end_stream with tail_samples samples (0 .. frame_size), replayed without
+ * the audio (:129-322).  Times are accumulated as there, by repeated addition of the frame
+ * length.  The result holds one stream (index 0).  NULL on refusal (ssw_last_error). */
+ssw_endpoints_t *ssw_endpoints_from_decisions(const ssw_vad_t *v, double window, double ratio,
+                                              const int8_t *is_speech, int64_t n_frames,
+                                              int64_t tail_samples);
+/* ssw_vad_batch (every stream afresh), the decisions brought to the host, and the replay per
+ * stream with the samples left after its last whole frame as the tail (zero of them included) */
+ssw_endpoints_t *ssw_endpoint_batch(ssw_vad_t *v, double window, double ratio,
+                                    const int16_t *d_pcm, const int64_t *samp_off,
+                                    int32_t n_streams, void *stream);
+int32_t ssw_endpoints_streams(const ssw_endpoints_t *e);
+int32_t ssw_endpoints_count(const ssw_endpoints_t *e, int32_t stream); /* segments; -1 on error */
+int ssw_endpoints_get(const ssw_endpoints_t *e, int32_t stream, int32_t k, ssw_endpoint_seg_t *out);
+void ssw_endpoints_free(ssw_endpoints_t *e);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,26 @@ class SswAlignEntry(C.Structure):
     _fields_ = [("start", C.c_int32), ("duration", C.c_int32), ("score", C.c_int32)]
 
 
+class SswVadState(C.Structure):
+    """ssw_vad_state_t: what the voice activity detector carries from frame to frame"""
+    _fields_ = [("downsampling_filter_states", C.c_int32 * 4), ("s_48_24", C.c_int32 * 8),
+                ("s_24_24", C.c_int32 * 16), ("s_24_16", C.c_int32 * 8), ("s_16_8", C.c_int32 * 8),
+                ("frame_counter", C.c_int32), ("noise_means", C.c_int16 * 12),
+                ("speech_means", C.c_int16 * 12), ("noise_stds", C.c_int16 * 12),
+                ("speech_stds", C.c_int16 * 12), ("over_hang", C.c_int16),
+                ("num_of_speech", C.c_int16), ("index_vector", C.c_int16 * 96),
+                ("low_value_vector", C.c_int16 * 96), ("mean_value", C.c_int16 * 6),
+                ("upper_state", C.c_int16 * 5), ("lower_state", C.c_int16 * 5),
+                ("hp_filter_state", C.c_int16 * 4), ("initialised", C.c_int16),
+                ("reserved", C.c_int16)]
+
+
+class SswEndpointSeg(C.Structure):
+    """ssw_endpoint_seg_t: one utterance the endpointer cut out of a stream"""
+    _fields_ = [("first_sample", C.c_int64), ("n_samples", C.c_int64),
+                ("speech_start", C.c_double), ("speech_end", C.c_double)]
+
+
 FRAME_EVAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                             C.POINTER(C.POINTER(C.c_float)), C.c_int32, C.c_int32)
 TRANSFORM_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
@@ -406,6 +426,36 @@ def lib() -> C.CDLL:
     L.ssw_device_mem_info.argtypes = [vp, vp]
     L.ssw_memcpy_h2d.argtypes = [vp, vp, sz]
     L.ssw_memcpy_d2h.argtypes = [vp, vp, sz]
+    if hasattr(L, "ssw_vad_create"):     # (an older build has no voice activity detector)
+        L.ssw_vad_create.restype = vp
+        L.ssw_vad_create.argtypes = [i32, i32, C.c_double]
+        L.ssw_vad_free.argtypes = [vp]
+        L.ssw_vad_free.restype = None
+        for name in ("ssw_vad_frame_size", "ssw_vad_sample_rate", "ssw_vad_closest_rate"):
+            getattr(L, name).argtypes = [vp]
+            getattr(L, name).restype = i32
+        L.ssw_vad_frame_length.argtypes = [vp]
+        L.ssw_vad_frame_length.restype = C.c_double
+        L.ssw_vad_frame_count.argtypes = [vp, C.c_int64]
+        L.ssw_vad_frame_count.restype = C.c_int64
+        L.ssw_vad_set_streams_per_workgroup.argtypes = [vp, i32]
+        L.ssw_vad_state_init.argtypes = [vp]
+        L.ssw_vad_state_init.restype = None
+        L.ssw_vad_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+        L.ssw_vad_batch_host.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+        L.ssw_vad_debug_features.argtypes = [vp, vp, C.c_int64]
+        L.ssw_endpoints_from_decisions.restype = vp
+        L.ssw_endpoints_from_decisions.argtypes = [vp, C.c_double, C.c_double, vp, C.c_int64,
+                                                   C.c_int64]
+        L.ssw_endpoint_batch.restype = vp
+        L.ssw_endpoint_batch.argtypes = [vp, C.c_double, C.c_double, vp, vp, i32, vp]
+        L.ssw_endpoints_streams.argtypes = [vp]
+        L.ssw_endpoints_streams.restype = i32
+        L.ssw_endpoints_count.argtypes = [vp, i32]
+        L.ssw_endpoints_count.restype = i32
+        L.ssw_endpoints_get.argtypes = [vp, i32, i32, C.POINTER(SswEndpointSeg)]
+        L.ssw_endpoints_free.argtypes = [vp]
+        L.ssw_endpoints_free.restype = None
     _lib = L
     return L
 

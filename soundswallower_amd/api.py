@@ -2209,3 +2209,209 @@ def recognize_align_audio_batch(model: Model, lex: Lexicon, pcm, samp_off, plan:
         for p in (d_cep, d_feat):
             if p:
                 model.device_free(p)
+
+
+# ---- voice activity detection and endpointing (vad.h, endpointer.h) ------------------------
+
+VAD_STATE_DTYPE = np.dtype(_lib.SswVadState)
+ENDPOINT_SEG_DTYPE = np.dtype(_lib.SswEndpointSeg)
+
+
+def _vad_pcm_check(pcm, who):
+    """int16 audio only: the reference's detector has no float entry, and what 1.0 should stand
+    for is the caller's to say"""
+    dt = str(pcm.dtype) if hasattr(pcm, "data_ptr") else np.asarray(pcm).dtype
+    name = str(dt).replace("torch.", "")
+    if "float" in name or "double" in name or name in ("half", "bfloat16"):
+        raise SswError(f"{who}: audio of dtype {name}; the detector takes int16 samples, so "
+                       "scale float audio yourself (e.g. x * 32768) and convert")
+    if name != "int16":
+        raise SswError(f"{who}: audio of dtype {name} (int16)")
+
+
+def _vad_device_pcm(pcm, who):
+    """the audio as a contiguous int16 device tensor (a host array is uploaded)"""
+    import torch
+    _vad_pcm_check(pcm, who)
+    if _is_device_tensor(pcm):
+        return pcm.contiguous().reshape(-1)
+    host = pcm.numpy() if hasattr(pcm, "data_ptr") else np.asarray(pcm)
+    return torch.from_numpy(np.ascontiguousarray(host, np.int16).reshape(-1)).to("cuda")
+
+
+class Vad:
+    """vad_t for batches of streams: vad_init + vad_set_input_params (src/ps_vad.c:49-128), with
+    vad_classify over every whole frame of every stream as one call.  mode 0..3 (loose to
+    strict); sample_rate 0 = 16000; frame_length 0 = 0.03."""
+
+    def __init__(self, mode=0, sample_rate=16000, frame_length=0.03):
+        self._L = _lib.lib()
+        self._h = self._L.ssw_vad_create(int(mode), int(sample_rate), float(frame_length))
+        if not self._h:
+            raise SswError("ssw_vad_create: " + _lib.last_error())
+        self.mode = int(mode)
+        self.frame_size = int(self._L.ssw_vad_frame_size(self._h))
+        self.frame_length = float(self._L.ssw_vad_frame_length(self._h))
+        self.sample_rate = int(self._L.ssw_vad_sample_rate(self._h))
+        self.closest_rate = int(self._L.ssw_vad_closest_rate(self._h))
+
+    def frame_count(self, n_samples) -> int:
+        return int(_check(int(self._L.ssw_vad_frame_count(self._h, int(n_samples))),
+                          "ssw_vad_frame_count"))
+
+    def set_streams_per_workgroup(self, streams=0):
+        """ssw_vad_set_streams_per_workgroup: 8, 16, 32 or 64 of a workgroup's lanes take streams;
+        0 = by the batch's size.  The results do not depend on it."""
+        _check(self._L.ssw_vad_set_streams_per_workgroup(self._h, int(streams)),
+               "ssw_vad_set_streams_per_workgroup")
+
+    def new_states(self, n) -> np.ndarray:
+        """n states as WebRtcVad_InitCore leaves them (VAD_STATE_DTYPE); np.zeros of that dtype
+        is n states not yet set up, which a batch call starts afresh too"""
+        s = np.zeros(int(n), VAD_STATE_DTYPE)
+        for i in range(len(s)):
+            self._L.ssw_vad_state_init(C.c_void_p(s[i:i + 1].ctypes.data))
+        return s
+
+    @staticmethod
+    def _state_arg(state, n):
+        if state is None:
+            return None
+        if not (isinstance(state, np.ndarray) and state.dtype == VAD_STATE_DTYPE
+                and state.shape == (n,) and state.flags.c_contiguous):
+            raise SswError("state: a contiguous numpy array [n_streams] of VAD_STATE_DTYPE")
+        return state
+
+    def classify_batch(self, pcm, samp_off, state=None, stream=None):
+        """ssw_vad_batch: int16 audio (numpy array or device tensor), stream u = samples
+        samp_off[u] .. samp_off[u + 1] -> (is_speech int8 [total frames] on the host, frame_off
+        int32 [n + 1]).  state: None, or Vad.new_states(n), updated in place."""
+        off = np.ascontiguousarray(samp_off, np.int64)
+        n = len(off) - 1
+        import torch
+        d_pcm = _vad_device_pcm(pcm, "Vad.classify_batch")
+        if n >= 0 and len(off) and int(off[-1]) > d_pcm.numel():
+            raise SswError("Vad.classify_batch: samp_off runs past the audio")
+        frame_off = np.zeros(n + 1, np.int32)
+        total = int((np.diff(off) // self.frame_size).sum()) if n > 0 else 0
+        d_out = torch.empty(max(total, 1), dtype=torch.int8, device=d_pcm.device)
+        st = self._state_arg(state, n)
+        _check(self._L.ssw_vad_batch(self._h, _ptr(d_pcm), _ptr(off), n, _ptr(d_out),
+                                     _ptr(frame_off), _ptr(st), _ptr(stream)), "ssw_vad_batch")
+        return d_out[:total].cpu().numpy(), frame_off
+
+    def classify_batch_host(self, pcm, samp_off, state=None, features=False):
+        """ssw_vad_batch_host: the same on the host, from the same arithmetic source; with
+        features=True also the int16 [frames][7] rows ssw_vad_debug_features shows"""
+        _vad_pcm_check(pcm, "Vad.classify_batch_host")
+        host = np.ascontiguousarray(pcm.cpu().numpy() if hasattr(pcm, "data_ptr") else pcm,
+                                    np.int16).reshape(-1)
+        off = np.ascontiguousarray(samp_off, np.int64)
+        n = len(off) - 1
+        if len(off) and int(off[-1]) > len(host):
+            raise SswError("Vad.classify_batch_host: samp_off runs past the audio")
+        frame_off = np.zeros(n + 1, np.int32)
+        total = int((np.diff(off) // self.frame_size).sum()) if n > 0 else 0
+        out = np.zeros(max(total, 1), np.int8)
+        feat = np.zeros((max(total, 1), 7), np.int16) if features else None
+        st = self._state_arg(state, n)
+        _check(self._L.ssw_vad_batch_host(self._h, _ptr(host), _ptr(off), n, _ptr(out),
+                                          _ptr(frame_off), _ptr(st), _ptr(feat)),
+               "ssw_vad_batch_host")
+        return (out[:total], frame_off, feat[:total]) if features else (out[:total], frame_off)
+
+    def debug_features(self, n_frames) -> np.ndarray:
+        """ssw_vad_debug_features of the last classify_batch: int16 [n_frames][7]"""
+        out = np.zeros((max(int(n_frames), 1), 7), np.int16)
+        _check(self._L.ssw_vad_debug_features(self._h, _ptr(out), int(n_frames)),
+               "ssw_vad_debug_features")
+        return out[:int(n_frames)]
+
+    def endpoints_from_decisions(self, is_speech, tail_samples=0, window=0.3, ratio=0.9):
+        """ssw_endpoints_from_decisions: the segments (ENDPOINT_SEG_DTYPE) of one stream"""
+        dec = np.ascontiguousarray(is_speech, np.int8)
+        h = self._L.ssw_endpoints_from_decisions(self._h, float(window), float(ratio), _ptr(dec),
+                                                 len(dec), int(tail_samples))
+        if not h:
+            raise SswError("ssw_endpoints_from_decisions: " + _lib.last_error())
+        try:
+            return _endpoint_segments(self._L, h, 0)
+        finally:
+            self._L.ssw_endpoints_free(h)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.ssw_vad_free(self._h)
+            self._h = None
+
+
+def _endpoint_segments(L, h, u) -> np.ndarray:
+    n = L.ssw_endpoints_count(h, u)
+    if n < 0:
+        raise SswError("ssw_endpoints_count: no such stream")
+    segs = np.zeros(n, ENDPOINT_SEG_DTYPE)
+    for k in range(n):
+        _check(L.ssw_endpoints_get(h, u, k, C.cast(C.c_void_p(segs[k:k + 1].ctypes.data),
+                                                   C.POINTER(_lib.SswEndpointSeg))),
+               "ssw_endpoints_get")
+    return segs
+
+
+class Endpoints:
+    """What endpoint_audio_batch found: per stream the utterances endpointer_process and
+    endpointer_end_stream hand back (src/ps_endpointer.c:233-322)."""
+
+    def __init__(self, vad: Vad, d_pcm, samp_off, segments):
+        self.vad = vad
+        self._d_pcm = d_pcm
+        self._off = samp_off
+        self._segs = segments
+
+    def __len__(self):
+        return len(self._segs)
+
+    def segments(self, u) -> np.ndarray:
+        """stream u's segments, ENDPOINT_SEG_DTYPE: first_sample (in the stream), n_samples,
+        speech_start, speech_end (seconds)"""
+        return self._segs[u]
+
+    def utterances(self):
+        """(pcm, samp_off, stream_of_utt, start_time): every segment's samples gathered into one
+        int16 device tensor, ready for align_audio_batch / recognize_audio_batch"""
+        import torch
+        stream_of = np.concatenate([np.full(len(s), u, np.int32) for u, s in enumerate(self._segs)]
+                                   + [np.zeros(0, np.int32)])
+        first = np.concatenate([self._off[u] + s["first_sample"] for u, s in enumerate(self._segs)]
+                               + [np.zeros(0, np.int64)]).astype(np.int64)
+        lens = np.concatenate([s["n_samples"] for s in self._segs]
+                              + [np.zeros(0, np.int64)]).astype(np.int64)
+        start = np.concatenate([s["speech_start"] for s in self._segs] + [np.zeros(0)])
+        off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        dev = self._d_pcm.device
+        shift = torch.from_numpy(first - off[:-1]).to(dev)
+        idx = torch.arange(int(off[-1]), device=dev) + torch.repeat_interleave(
+            shift, torch.from_numpy(lens).to(dev))
+        return self._d_pcm[idx], off, stream_of, start
+
+
+def endpoint_audio_batch(pcm, samp_off, samprate=16000, mode=0, window=0.3, ratio=0.9,
+                         frame_length=0.03, stream=None) -> Endpoints:
+    """ssw_endpoint_batch: a fresh endpointer_init(window, ratio, mode, samprate, frame_length)
+    per stream over all of its audio -- endpointer_process on every whole frame, then
+    endpointer_end_stream with the samples left over.  int16 audio, numpy array or device
+    tensor; stream u = samples samp_off[u] .. samp_off[u + 1]."""
+    vad = Vad(mode, samprate, frame_length)
+    L = vad._L
+    off = np.ascontiguousarray(samp_off, np.int64)
+    d_pcm = _vad_device_pcm(pcm, "endpoint_audio_batch")
+    if len(off) and int(off[-1]) > d_pcm.numel():
+        raise SswError("endpoint_audio_batch: samp_off runs past the audio")
+    h = L.ssw_endpoint_batch(vad._h, float(window), float(ratio), _ptr(d_pcm), _ptr(off),
+                             len(off) - 1, _ptr(stream))
+    if not h:
+        raise SswError("ssw_endpoint_batch: " + _lib.last_error())
+    try:
+        segs = [_endpoint_segments(L, h, u) for u in range(len(off) - 1)]
+    finally:
+        L.ssw_endpoints_free(h)
+    return Endpoints(vad, d_pcm, off, segs)

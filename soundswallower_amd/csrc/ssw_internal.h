@@ -387,6 +387,35 @@ ssw_fp_graphs_t *ssw_fp_graphs_build(const ssw_model_t *m, const struct ssw_dict
                                      const ssw_first_pass_config_t *cfg, int32_t n_utts,
                                      const int32_t *word_off, const char *const *words);
 void ssw_fp_graphs_free(ssw_fp_graphs_t *g);
+/* Voice activity detection (ssw_vad.c: the object, the host path, the endpointer's replay;
+ * ssw_host_vad.inc: the device calls).  The device workspace is the HIP side's: ssw_vad.c frees
+ * it through dev_free, which the first device call sets. */
+struct ssw_vad_s {
+    int32_t mode, sample_rate, closest_rate, frame_size;
+    int32_t nb_len;                                    /* the frame at 8 kHz: 80, 160 or 240 */
+    int16_t overhead1, overhead2, individual, total;   /* the mode's thresholds at nb_len */
+    void *d_state, *d_feat, *d_off;                    /* grow-only device buffers */
+    size_t d_state_cap, d_feat_cap, d_off_cap;
+    int64_t feat_frames;                               /* rows of d_feat the last call wrote; -1 none */
+    int32_t spw;                                       /* streams per workgroup; 0 = by the batch's size */
+    int32_t n_cus;                                     /* the device's compute units, asked once; 0 = not yet */
+    void (*dev_free)(struct ssw_vad_s *);
+};
+struct ssw_endpoints_s {
+    int32_t n_streams;
+    int32_t *seg_off; /* [n_streams + 1] */
+    ssw_endpoint_seg_t *segs;
+};
+/* the replay of ssw_endpoints_from_decisions per stream: decisions of stream u at
+ * is_speech[frame_off[u] .. frame_off[u + 1]), its tail (samp_off[u + 1] - samp_off[u]) %
+ * frame_size samples.  NULL and ssw_set_error. */
+ssw_endpoints_t *ssw_endpoints_replay(const ssw_vad_t *v, double window, double ratio,
+                                      const int8_t *is_speech, const int32_t *frame_off,
+                                      const int64_t *tail, int32_t n_streams);
+/* frame_off_out [n_streams + 1] of a batch, or -1 and ssw_set_error (bad offsets, too many frames) */
+int ssw_vad_frame_offsets(const ssw_vad_t *v, const int64_t *samp_off, int32_t n_streams,
+                          int32_t *frame_off_out);
+
 int ssw_host_threads(void);
 /* fn(arg, k) for k in [0, n_chunks) on a persistent pool of host threads + the caller */
 void ssw_parallel_for(int n_chunks, void (*fn)(void *arg, int chunk), void *arg);

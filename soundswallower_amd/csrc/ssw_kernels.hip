@@ -89,6 +89,12 @@
  *                        feat_chain_kernel (the utterances' means and scales, live CMN's state)
  *                        and feat_tile_kernel (frame-parallel), src/feat.c:437-712, :977-1008,
  *                        src/cmn.c:159-224, src/cmn_live.c:60-134, src/lda.c:124-144
+ *   ssw_vad_core.inc     the reference's voice activity detector, each step once, for this file
+ *                        and for ssw_vad.c's host path alike: the resamplers to 8 kHz, the band
+ *                        splits, LogOfEnergy, the Gaussians, the minimum tracker, GmmProbability
+ *                        (src/common_audio/vad/, src/common_audio/signal_processing/)
+ *   ssw_k13_vad.inc      vad_batch_kernel: vad_classify over a batch of streams, a lane per
+ *                        stream, audio staged through LDS, every per-sample buffer in LDS
  *   ssw_feat_tiles.inc   host, no HIP: the tile table and tile size of ssw_feat_batch_ex
  *   ssw_ws_layout.inc    host, no HIP: align256 and WsLayout, the one layout of a device
  *                        workspace (256-byte-aligned offsets in call order, the uploaded pieces
@@ -184,6 +190,7 @@ namespace {
 #include "ssw_k10_semi.inc"
 #include "ssw_k11_cont.inc"
 #include "ssw_k12_feat.inc"
+#include "ssw_k13_vad.inc"
 
 } // namespace
 
@@ -243,3 +250,5 @@ static int cont_align_active(ssw_model_t *m, const float *d_feats, int32_t n_utt
 #include "ssw_host_featex.inc"
 /* ... and the listed-senone kernel of continuous models behind those */
 #include "ssw_host_cont_listed.inc"
+/* ... and the voice activity detector's behind those */
+#include "ssw_host_vad.inc"
